@@ -13,6 +13,11 @@ N>1 ranks: one RCCL all-gather of the per-shard partial top-k + certificate flag
 The corpus and the query batch are resident in HBM before the timed region starts; every step ends with its
 ids + float8 distances copied to (pinned) host memory inside the timed region (SURVEY 8d's protocol).
 
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes the
+last timed step's ids and distances there (ids.npy, distances.npy, float64). Everything else below
+(telemetry, cpu_baseline, verified, pcie_inclusive, the vendor-stack, side-config and embed legs) runs
+only with --full.
+
 The JSON line carries
   roofline     : the scan kernel (k_scan) against the bf16 MFMA peak (Q >= 320) or HBM peak,
                  achieved = algorithmic flops|bytes per launch / mean launch duration measured
@@ -25,6 +30,7 @@ The JSON line carries
   pcie_inclusive / step_ms_hip_events : SURVEY 8d's protocol fields (never `value`).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -77,10 +83,18 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline budget")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the in-run result verification (outside the timed region; on by default): sampled queries "
+                    help="skip the in-run result verification of --full (outside the timed region; on by default there): sampled queries "
                          "re-scored by the oracle, compared with the exact HIP path and with the oracle's scan of a row "
                          "slice; with N > 1 ranks, rank 0 also builds the WHOLE corpus as one index and checks that the "
                          "sharded result (all-gather + merge) is identical")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: GPU telemetry, the vendor-stack and CPU baselines, the "
+                         "in-run verification, the PCIe-inclusive, replicated-corpus, HBM-bound-config and query-latency legs "
+                         "and the embed legs (the --no-* switches above trim this set). Off: set up, warm up, time the "
+                         "--steps steps, write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/ids.npy and DIR/distances.npy "
+                         "([queries, k] float64; ids are exact in float64)")
     return ap.parse_args()
 
 
@@ -1015,6 +1029,14 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    def emit(out):
+        if world > 1:
+            dist.destroy_process_group()
+        sys.stdout.flush()
+        if rank == 0:
+            os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        os.close(real_stdout)
+
     for _ in range(args.warmup):
         ids, dd = searcher.search(q_dev, args.k)
     sync_all()
@@ -1025,7 +1047,8 @@ def main():
     # the timed region (pinned buffers, the search's stream; 164 KB per 1024-query step), behind the step's closing event
     ids_host = torch.empty((args.queries, args.k), dtype=torch.int64).pin_memory()
     dd_host = torch.empty((args.queries, args.k), dtype=torch.float64).pin_memory()
-    with GpuTelemetry(local_rank) as tele:
+    tele = GpuTelemetry(local_rank) if args.full else None
+    with tele or contextlib.nullcontext():
         t0 = time.perf_counter()
         for i in range(args.steps):
             ev[i][0].record()                    # the stream the search is launched on (torch's current stream)
@@ -1034,7 +1057,7 @@ def main():
             ev[i][1].record()
         sync_all()
         elapsed = time.perf_counter() - t0
-        if world == 1 and elapsed < 1.0:         # the timed region is a fraction of a second: keep the same load on, UNTIMED, until
+        if tele and world == 1 and elapsed < 1.0:  # the timed region is a fraction of a second: keep the same load on, UNTIMED, until
             t_end = time.perf_counter() + 1.0    # the sampler has seen a steady state (these searches are not part of `value`)
             while time.perf_counter() < t_end:
                 searcher.search(q_dev, args.k)
@@ -1071,10 +1094,11 @@ def main():
     roof["launch_ms"] = mean_scan_ms
     roof["launch_ms_median"] = float(np.median(scan_ms)) if scan_ms.size else None
     roof["launches_timed"] = int(scan_ms.size)
-    roof.update(tele.summary())                              # scalars: a slow box shows here, slow code does not
+    if tele:
+        roof.update(tele.summary())                          # scalars: a slow box shows here, slow code does not
     add_clock_adjusted(roof)
     roof["vendor_gemm_tflops"] = roof["achieved_over_vendor_gemm"] = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             ref = vendor_gemm_tflops()
             roof["vendor_gemm_tflops"] = ref                 # torch.matmul bf16 8192^3 (hipBLASLt) on this GPU, same run
@@ -1120,6 +1144,13 @@ def main():
         "roofline": roof,
     }
     ids_h, dd_h = ids.cpu().numpy(), dd.cpu().numpy()
+    if args.dump_outputs and rank == 0:                      # every rank holds the same merged result
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), ids_h.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "distances.npy"), dd_h.astype(np.float64))
+    if not args.full:
+        ix.close()
+        return emit(out)
     if not args.no_verify:
         full = ix
         ok = True
@@ -1215,12 +1246,7 @@ def main():
             if world > 1:
                 raise                               # (ranks must not diverge around the leg's barriers)
             out["embed"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if world > 1:
-        dist.destroy_process_group()
-    sys.stdout.flush()
-    if rank == 0:
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
-    os.close(real_stdout)
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@ def test_bench_multirank_path(world):
                    MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "bench_rehearsal.py"), "--gpus", str(world),
                                        "--rows", "300000", "--queries", "300", "--steps", "3", "--warmup", "1",
-                                       "--no-embed", "--no-cpu-baseline"], env=env,
+                                       "--full", "--no-embed", "--no-cpu-baseline"], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = []
     for p in procs:
@@ -52,7 +52,7 @@ def test_plain_bench_gpus_2_starts_its_own_ranks():
     print ONE JSON line with n_gpus == 2 (through the rehearsal shim: the test box has one GPU)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(HERE, "bench_rehearsal.py"), "--gpus", "2", "--rows", "200000",
-                        "--queries", "300", "--steps", "2", "--warmup", "1", "--no-embed", "--no-cpu-baseline"],
+                        "--queries", "300", "--steps", "2", "--warmup", "1", "--full", "--no-embed", "--no-cpu-baseline"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode("utf-8", "replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
