@@ -31,7 +31,7 @@ class StaleFilterError(HipBackendError):
 
 ERR_STALE_FILTER = -11
 ERR_COMM_BROKEN = -13
-ABI_VERSION = 4          # AK_ABI_VERSION of include/archi_knn.h this binding was written against
+ABI_VERSION = 5          # AK_ABI_VERSION of include/archi_knn.h this binding was written against
 
 # switches that exist only in libarchi_hip_dbg.so (`make -C archi_amd/csrc dbg`): instrumented kernels, stage-skipping
 # ablations (WRONG RESULTS) and the superseded kernel generations kept as A/B references. One of them in the environment --
@@ -52,6 +52,21 @@ class AkBertConfig(ctypes.Structure):
         ("ln_eps", ctypes.c_float),
         ("residual_bf16", ctypes.c_int),
         ("precision", ctypes.c_int),
+    ]
+
+
+class AkDecoderConfig(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("q_heads", ctypes.c_int),
+        ("kv_heads", ctypes.c_int),
+        ("head_dim", ctypes.c_int),
+        ("intermediate", ctypes.c_int),
+        ("max_position", ctypes.c_int),
+        ("rms_eps", ctypes.c_float),
+        ("rope_theta", ctypes.c_float),
     ]
 
 
@@ -103,6 +118,10 @@ SYMBOLS = [
     ("ak_encoder_forward", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     ("ak_encoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_encoder_gelu_table", _I, [_P]),
+    ("ak_decoder_create", _I, [ctypes.POINTER(AkDecoderConfig), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_decoder_destroy", _I, [_P]),
+    ("ak_decoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    ("ak_decoder_rope_table", _I, [ctypes.c_float, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_destroy", _I, [_P]),
     ("ak_wordpiece_encode", _I, [_P, _P, _P, _I64, _I, _I, _P, _P]),

@@ -18,6 +18,9 @@ EMBEDDING_DIMENSIONS = {
     "all-MiniLM-L6-v2": 384,
     "BAAI/bge-base-en": 768,
     "BAAI/bge-base-en-v1.5": 768,
+    "Qwen/Qwen3-Embedding-0.6B": 1024,
+    "Qwen/Qwen3-Embedding-4B": 2560,
+    "Qwen/Qwen3-Embedding-8B": 4096,
 }
 
 

@@ -141,6 +141,16 @@ struct QfArgs {
 };
 bool query_forward_supported(int H, int I, int heads, int64_t T, int S);
 int launch_query_forward(const QfArgs &a, hipStream_t st);
+// causal grouped-query attention at head dim 128 (attn_causal.hip; the decoder, decoder.hip): q [B][nq][S][128] pre-scaled by
+// log2(e) / sqrt(128), k / v [B][nkv][S][128], ctx [B * S][nq * 128]; lens [B] already clamped to [0, S]
+struct CausalAttnArgs {
+    const uint16_t *q, *k, *v;
+    const int *lens;
+    uint16_t *ctx;
+    int B, S, nq, nkv;
+};
+bool attn_causal_supported(int nq, int nkv, int head_dim, int S);
+int launch_attn_causal(const CausalAttnArgs &a, hipStream_t st);
 bool gemm_skinny_supported(int N, int K);
 int launch_gemm_skinny(const uint16_t *X, const uint16_t *W, const float *bias, int rows, int N, int K, float *out_f32,
                        uint16_t *out_bf16, int ldo, hipStream_t st);

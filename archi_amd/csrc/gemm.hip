@@ -15,6 +15,9 @@
 //           the other -- and normalises the rows it has just stored, from L2, instead of a LayerNorm launch: bge-base 128 x 512
 //           17.1 ms against 15.6 with one row per wave at a time, 20.2 with eight rows in flight -- the tail's registers spill
 //           into a kernel that has none to spare, and its loads run with two waves per SIMD to hide them.) (what the LayerNorm of the hidden != 384 path reads: one array instead of two)
+//   MODE 7  SwiGLU (the decoder's gate / up projection, decoder.hip): W holds the gate and up rows INTERLEAVED (row 2 j = gate j,
+//           row 2 j + 1 = up j), so each lane's four consecutive features are (g_j, u_j, g_j+1, u_j+1); it stores silu(g) u as bf16,
+//           N / 2 columns wide (a.ldo = N / 2) -- the 2I-wide product never reaches memory
 // Replaces the torch CPU GEMMs behind SentenceTransformer.encode as called at
 // /root/reference/src/data_manager/vectorstore/manager.py:373.
 //
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
     const int ntn = a.N / G_BN, ntt = a.T / G_BT, ntiles = ntn * ntt;
     const int KS = a.K / 64;
     // split operands (MODE 5 / 6): rows of 2 K' elements [hi | lo]; KS3 = k-tiles per half
-    constexpr bool X3 = MODE >= 5;
+    constexpr bool X3 = MODE == 5 || MODE == 6;
     const int ldk = X3 ? a.K / 3 * 2 : a.K, KS3 = KS / 3;
     // step kk of the walk = term kk % 3 of k-tile kk / 3: (X hi, W hi), (X lo, W hi), (X hi, W lo) -- the two uses of a half are at most
     // two steps apart, so the second comes from L2 (walking the three terms as three passes over K fetched every hi half twice from
@@ -278,6 +281,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
             *(uint2 *)(a.out_bf16 + (int64_t)t * a.ldo + n) = GTAB ? f_gelu_tab4(o) : cvt_bf16x4(gelu_erf4(o));
         } else if constexpr (MODE == 2 || MODE == 5) {
             *(f32x4 *)(a.out_f32 + (int64_t)t * a.N + n) = o;   // the residual is added by the LayerNorm kernel that follows
+        } else if constexpr (MODE == 7) {
+            // (g_j, u_j, g_j+1, u_j+1), j = n / 2: silu(g) u = g u / (1 + exp(-g)), two bf16 values in one 4-byte store
+            const float s0 = o.x * o.y / (1.0f + __expf(-o.x)), s1 = o.z * o.w / (1.0f + __expf(-o.z));
+            *(uint32_t *)(a.out_bf16 + (int64_t)t * a.ldo + (n >> 1)) = pack_bf16x2(s0, s1);
         } else {
             *(uint2 *)(a.out_bf16 + (int64_t)t * a.ldo + n) = cvt_bf16x4(o);
         }
@@ -564,6 +571,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
     auto tile_out = [&](char *scr, int tn) {
         if constexpr (MODE == 1 || MODE == 3 || MODE == 4) rows_out(scr, a.out_bf16, a.ldo, tn * G_BN, 1.0f);
         else if constexpr (MODE == 6) rows_out_split(scr, tn * G_BN);
+        else if constexpr (MODE == 7) all_pieces();
         else if constexpr (MODE == 0 && G_BN == 256) {     // H % 256 == 0: a tile is all Q, all K or all V
             if (tn * G_BN >= 2 * a.H) v_out(scr);
             else {
@@ -843,6 +851,7 @@ static int launch_gemm_bn(int mode, const GemmArgs &a, hipStream_t st) {
         AK_HIP(hipFuncSetAttribute((const void *)k_gemm<2, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
         AK_HIP(hipFuncSetAttribute((const void *)k_gemm<3, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
         AK_HIP(hipFuncSetAttribute((const void *)k_gemm<4, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
+        AK_HIP(hipFuncSetAttribute((const void *)k_gemm<7, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
         attr = true;
     }
     const int ntiles = (a.T / G_BT) * (a.N / BN);
@@ -852,6 +861,7 @@ static int launch_gemm_bn(int mode, const GemmArgs &a, hipStream_t st) {
         case 1: k_gemm<1, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS + (BN == 256 ? GELU_TAB_BYTES : 0), st>>>(a); break;
         case 2: k_gemm<2, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a); break;
         case 4: k_gemm<4, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a); break;
+        case 7: k_gemm<7, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a); break;
         default: k_gemm<3, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a); break;
     }
     AK_HIP(hipGetLastError());

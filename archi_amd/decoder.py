@@ -1,0 +1,284 @@
+"""HipDecoder -- Python handle of the HIP Qwen3 decoder (ak_decoder_*): the Qwen3-Embedding models the reference's retrievers
+name as instruction-aware embedders (src/data_manager/vectorstore/retrievers/utils.py:7-11).
+
+PyTorch-ROCm only HOLDS the weights in HBM (bf16 matrices, fp32 vectors) and hands raw device pointers to the C ABI; every
+arithmetic step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/decoder.hip, attn_causal.hip, gemm.hip).
+Also here: the checkpoint loader (load_qwen3_weights), seeded random weights of the named shapes, the sentence-transformers
+configuration of a decoder checkpoint and the byte-level BPE tokenizer wrapper.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import os
+import threading
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from . import _lib
+from ._lib import AkDecoderConfig, HipBackendError, check
+
+MAX_SEQ = 8192          # longest sequence the decoder kernels take (attn_causal.hip)
+HEAD_DIM = 128
+
+# name -> config.json numbers (vocab, hidden, layers, q_heads, kv_heads, intermediate, max_position, rope_theta, rms_eps)
+QWEN3_SHAPES = {
+    "Qwen/Qwen3-Embedding-0.6B": (151669, 1024, 28, 16, 8, 3072, 32768, 1e6, 1e-6),
+    "Qwen/Qwen3-Embedding-4B": (151669, 2560, 36, 32, 8, 9728, 40960, 1e6, 1e-6),
+    "Qwen/Qwen3-Embedding-8B": (151669, 4096, 36, 32, 8, 12288, 40960, 1e6, 1e-6),
+    # small shapes of the test fixtures (tests/golden/make_decoder_fixtures.py): GQA ratios 1, 2 and 4 at head dim 128
+    "qwen3-tiny-g1": (1000, 256, 2, 2, 2, 512, 8192, 1e6, 1e-6),
+    "qwen3-tiny-g2": (1000, 256, 3, 4, 2, 768, 8192, 1e6, 1e-6),
+    "qwen3-tiny-g4": (1000, 256, 4, 8, 2, 512, 8192, 1e4, 1e-6),
+}
+
+LAYER_KEYS = ("wq", "wk", "wv", "q_norm", "k_norm", "wo", "ln_in", "ln_post", "w_gate", "w_up", "w_down")
+MATRIX_KEYS = {"wq", "wk", "wv", "wo", "w_gate", "w_up", "w_down"}
+# our name -> HF Qwen3Model state-dict name (layer keys under "layers.{l}.")
+HF_LAYER_NAMES = {"wq": "self_attn.q_proj.weight", "wk": "self_attn.k_proj.weight", "wv": "self_attn.v_proj.weight",
+                  "q_norm": "self_attn.q_norm.weight", "k_norm": "self_attn.k_norm.weight", "wo": "self_attn.o_proj.weight",
+                  "ln_in": "input_layernorm.weight", "ln_post": "post_attention_layernorm.weight",
+                  "w_gate": "mlp.gate_proj.weight", "w_up": "mlp.up_proj.weight", "w_down": "mlp.down_proj.weight"}
+
+
+def weight_order(layers: int) -> List[str]:
+    """The header's weight order: embed_tokens, final norm, then per layer wq wk wv q_norm k_norm wo ln_in ln_post w_gate w_up w_down."""
+    names = ["embed_tokens", "norm"]
+    for l in range(layers):
+        names += [f"l{l}.{k}" for k in LAYER_KEYS]
+    return names
+
+
+def hf_state_dict(weights: Dict[str, "np.ndarray"], layers: int) -> Dict[str, "np.ndarray"]:
+    """Our weight names -> HF Qwen3Model's (no "model." prefix)."""
+    sd = {"embed_tokens.weight": weights["embed_tokens"], "norm.weight": weights["norm"]}
+    for l in range(layers):
+        for k, hf in HF_LAYER_NAMES.items():
+            sd[f"layers.{l}.{hf}"] = weights[f"l{l}.{k}"]
+    return sd
+
+
+def random_qwen3_weights(shape, seed: int = 0) -> Dict[str, "np.ndarray"]:
+    """Seeded random weights of a Qwen3 shape (a QWEN3_SHAPES tuple or name). Matrices are drawn with std 0.02 and ROUNDED TO
+    bf16 (kept as float32 values): the released checkpoints are bf16, and a float32 reference on the same values measures the
+    kernels' activation rounding alone. Norm weights are drawn around 1, not set to it."""
+    import torch
+    if isinstance(shape, str):
+        shape = QWEN3_SHAPES[shape]
+    vocab, H, L, nq, nkv, I = shape[:6]
+    g = torch.Generator().manual_seed(seed)
+
+    def mat(r, c):
+        return (torch.randn(r, c, generator=g) * 0.02).to(torch.bfloat16).float().numpy()
+
+    def vec(n):
+        return (1.0 + 0.1 * torch.randn(n, generator=g)).numpy().astype(np.float32)
+
+    w = {"embed_tokens": mat(vocab, H), "norm": vec(H)}
+    for l in range(L):
+        p = f"l{l}."
+        w[p + "wq"], w[p + "wk"], w[p + "wv"] = mat(nq * HEAD_DIM, H), mat(nkv * HEAD_DIM, H), mat(nkv * HEAD_DIM, H)
+        w[p + "q_norm"], w[p + "k_norm"] = vec(HEAD_DIM), vec(HEAD_DIM)
+        w[p + "wo"] = mat(H, nq * HEAD_DIM)
+        w[p + "ln_in"], w[p + "ln_post"] = vec(H), vec(H)
+        w[p + "w_gate"], w[p + "w_up"], w[p + "w_down"] = mat(I, H), mat(I, H), mat(H, I)
+    return w
+
+
+def _rope_theta(cfg: dict) -> float:
+    """rope_theta at the top level (transformers 4) or inside rope_parameters (transformers 5); default RoPE only."""
+    rp = cfg.get("rope_parameters") or {}
+    rs = cfg.get("rope_scaling")
+    for what in (rs, rp):
+        if what and what.get("rope_type", what.get("type", "default")) not in ("default", None):
+            raise ValueError(f"rope type {what.get('rope_type', what.get('type'))!r} is not supported (default RoPE only)")
+    theta = cfg.get("rope_theta", rp.get("rope_theta"))
+    if theta is None:
+        raise ValueError("config.json has no rope_theta")
+    return float(theta)
+
+
+def qwen3_config_shape(cfg: dict, where: str = "config.json"):
+    """config.json of a Qwen3 checkpoint -> QWEN3_SHAPES-style tuple; everything the kernels do not implement is refused."""
+    if cfg.get("model_type") != "qwen3":
+        raise ValueError(f"{where}: model_type {cfg.get('model_type')!r} is not qwen3")
+    if cfg.get("hidden_act", "silu") != "silu":
+        raise ValueError(f"{where}: hidden_act {cfg.get('hidden_act')!r} (the HIP decoder implements SiLU / SwiGLU)")
+    if cfg.get("attention_bias", False):
+        raise ValueError(f"{where}: attention_bias is not supported")
+    if cfg.get("use_sliding_window", False) or any(t == "sliding_attention" for t in (cfg.get("layer_types") or [])):
+        raise ValueError(f"{where}: sliding-window attention is not supported")
+    H, nq = cfg["hidden_size"], cfg["num_attention_heads"]
+    hd = cfg.get("head_dim") or H // nq
+    if hd != HEAD_DIM:
+        raise ValueError(f"{where}: head_dim {hd} (the HIP decoder implements 128)")
+    try:
+        theta = _rope_theta(cfg)
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return (cfg["vocab_size"], H, cfg["num_hidden_layers"], nq, cfg.get("num_key_value_heads", nq), cfg["intermediate_size"],
+            cfg.get("max_position_embeddings", 32768), theta, float(cfg.get("rms_norm_eps", 1e-6)))
+
+
+def load_qwen3_weights(model_dir: str):
+    """Local Qwen3 checkpoint directory (config.json + model.safetensors or sharded model-*.safetensors) -> (shape, weights in
+    the header's names). A "model." prefix on the tensor names is stripped. No network."""
+    cfg = json.load(open(os.path.join(model_dir, "config.json")))
+    shape = qwen3_config_shape(cfg, os.path.join(model_dir, "config.json"))
+    from safetensors.torch import load_file     # torch loader: bf16 checkpoints load too
+    files = sorted(f for f in os.listdir(model_dir) if f.endswith(".safetensors"))
+    if not files:
+        raise FileNotFoundError(f"{model_dir}: no *.safetensors file")
+    sd = {}
+    for f in files:
+        sd.update(load_file(os.path.join(model_dir, f)))
+    sd = {(k[6:] if k.startswith("model.") else k): v for k, v in sd.items()}
+    L = shape[2]
+    w = {"embed_tokens": sd["embed_tokens.weight"], "norm": sd["norm.weight"]}
+    for l in range(L):
+        for k, hf in HF_LAYER_NAMES.items():
+            w[f"l{l}.{k}"] = sd[f"layers.{l}.{hf}"]
+    return shape, w
+
+
+def read_decoder_st_config(model_dir: str):
+    """sentence-transformers files of a decoder checkpoint: `modules.json` (Normalize module?), the Pooling module's config (must be
+    lasttoken) and `sentence_bert_config.json` (max_seq_length). Returns (max_seq_length | None, always_normalise)."""
+    max_len, norm, pool_dir = None, False, "1_Pooling"
+    mj = os.path.join(model_dir, "modules.json")
+    if os.path.exists(mj):
+        for m in json.load(open(mj)):
+            kind = m.get("type", "")
+            if kind.endswith("Normalize"):
+                norm = True
+            elif kind.endswith("Pooling"):
+                pool_dir = m.get("path", pool_dir)
+    pj = os.path.join(model_dir, pool_dir, "config.json")
+    if not os.path.exists(pj):
+        raise ValueError(f"{model_dir}: no {pool_dir}/config.json (a decoder embedder needs lasttoken pooling)")
+    pc = json.load(open(pj))
+    modes = [k for k in ("cls_token", "mean_tokens", "max_tokens", "mean_sqrt_len_tokens", "weightedmean_tokens", "lasttoken")
+             if pc.get("pooling_mode_" + k)]
+    if modes != ["lasttoken"]:
+        raise ValueError(f"{model_dir}: pooling modes {modes} (the HIP decoder implements lasttoken)")
+    sj = os.path.join(model_dir, "sentence_bert_config.json")
+    if os.path.exists(sj):
+        max_len = json.load(open(sj)).get("max_seq_length")
+    return max_len, norm
+
+
+class BpeTokenizer:
+    """The checkpoint's own tokenizer.json (byte-level BPE for Qwen3) through the `tokenizers` wheel. Special tokens are whatever
+    the file's post-processor adds (Qwen3-Embedding appends <|endoftext|>, the token the last-token pool reads); truncation at
+    max_len happens before the post-processor, as PreTrainedTokenizerFast(truncation=True, max_length=max_len) does."""
+
+    def __init__(self, tokenizer_file: str):
+        from tokenizers import Tokenizer
+        self._tok = Tokenizer.from_file(tokenizer_file)
+        self._tok.no_padding()
+        self._max = None
+        self._lock = threading.Lock()
+
+    def encode_batch(self, texts: List[str], max_len: int) -> List[List[int]]:
+        with self._lock:
+            if self._max != max_len:
+                self._tok.enable_truncation(max_len)
+                self._max = max_len
+            return [e.ids for e in self._tok.encode_batch(list(texts))]
+
+    def encode(self, text: str, max_len: int) -> List[int]:
+        return self.encode_batch([text], max_len)[0]
+
+    def encode_batch_array(self, texts: List[str], max_len: int):
+        """-> (ids [n, max_len] int32 zero padded, lens [n] int32)."""
+        rows = self.encode_batch(texts, max_len)
+        ids = np.zeros((len(rows), max_len), np.int32)
+        lens = np.empty(len(rows), np.int32)
+        for i, r in enumerate(rows):
+            ids[i, : len(r)] = r
+            lens[i] = len(r)
+        return ids, lens
+
+
+class HipDecoder:
+    def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
+        """shape: a QWEN3_SHAPES tuple (vocab, hidden, layers, q_heads, kv_heads, intermediate, max_position, rope_theta, rms_eps);
+        weights: the header's names (weight_order), numpy arrays or torch tensors."""
+        import torch
+        vocab, H, L, nq, nkv, I, max_pos, theta, eps = shape
+        self._lib = _lib.init(device)
+        self.shape = tuple(shape)
+        self.hidden, self.layers, self.vocab = H, L, vocab
+        self.max_seq = min(int(max_pos), MAX_SEQ)
+        dev = torch.device("cuda", _lib.bound_device())
+        self._tensors = []
+        ptrs = []
+        for name in weight_order(L):
+            if name not in weights:
+                raise HipBackendError(f"decoder weight {name!r} missing")
+            arr = weights[name]
+            t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
+            is_matrix = name == "embed_tokens" or name.split(".")[-1] in MATRIX_KEYS
+            t = t.to(device=dev, dtype=torch.bfloat16 if is_matrix else torch.float32).contiguous()
+            self._tensors.append(t)
+            ptrs.append(t.data_ptr())
+        cfg = AkDecoderConfig(vocab, H, L, nq, nkv, HEAD_DIM, I, max_pos, eps, theta)
+        arr_t = ctypes.c_void_p * len(ptrs)
+        h = ctypes.c_void_p()
+        torch.cuda.synchronize(dev)
+        check(self._lib.ak_decoder_create(ctypes.byref(cfg), arr_t(*ptrs), len(ptrs), ctypes.byref(h)), "ak_decoder_create")
+        self._h = h
+        self._dev = dev
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.ak_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def forward_lens(self, stage, n_rows: int, S: int, out, pooling: str = "last", normalise: bool = True) -> None:
+        """The provider's tile layout, as HipEncoder.forward_lens: `stage` an int32 CUDA tensor [n_rows, S + 1] (S ids per row,
+        the length in column S), `out` a float32 CUDA tensor view [n_rows, hidden]. Decoder models pool the last token only."""
+        import torch
+        if pooling != "last":
+            raise ValueError(f"pooling {pooling!r}: the decoder implements last-token pooling only")
+        if stage.dtype != torch.int32 or not stage.is_cuda or not stage.is_contiguous() or tuple(stage.shape) != (n_rows, S + 1):
+            raise ValueError("forward_lens: stage must be a contiguous int32 CUDA tensor [n_rows, S + 1]")
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n_rows, self.hidden):
+            raise ValueError("forward_lens: out must be a contiguous float32 CUDA tensor [n_rows, hidden]")
+        if S % 32 or S > self.max_seq:
+            raise ValueError(f"sequence length {S} must be a multiple of 32, <= {self.max_seq}")
+        base = stage.data_ptr()
+        check(self._lib.ak_decoder_forward_lens(self._h, ctypes.c_void_p(base), S + 1, ctypes.c_void_p(base + 4 * S), S + 1, n_rows, S,
+                                                int(normalise), ctypes.c_void_p(out.data_ptr()),
+                                                ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)),
+              "ak_decoder_forward_lens")
+
+    def forward(self, ids, lens, normalise: bool = True):
+        """ids [B, W] (row i holds lens[i] ids), lens [B] -> [B, hidden] float32 CUDA tensor (one tile, S = W rounded up to 32)."""
+        import torch
+        ids = np.asarray(ids, np.int32)
+        B, W = ids.shape
+        S = max(32, (W + 31) // 32 * 32)
+        stage = np.zeros((B, S + 1), np.int32)
+        stage[:, :W] = ids
+        stage[:, S] = np.asarray(lens, np.int32)
+        st = torch.from_numpy(stage).to(self._dev)
+        out = torch.empty((B, self.hidden), dtype=torch.float32, device=self._dev)
+        self.forward_lens(st, B, S, out, pooling="last", normalise=normalise)
+        return out
+
+
+def rope_table(theta: float, n_pos: int, head_dim: int = HEAD_DIM):
+    """ak_decoder_rope_table (host only): cos, sin [n_pos][head_dim / 2] float32."""
+    lib = _lib.load()
+    c = np.empty((n_pos, head_dim // 2), np.float32)
+    s = np.empty((n_pos, head_dim // 2), np.float32)
+    check(lib.ak_decoder_rope_table(ctypes.c_float(theta), head_dim, n_pos, c.ctypes.data, s.ctypes.data), "ak_decoder_rope_table")
+    return c, s

@@ -13,6 +13,8 @@ Errors are RAISED (never partial results): the manager records a failed file per
 
 Host side (this file): text normalisation, WordPiece tokenisation, length-sorted batching.
 Device side: archi_amd.encoder.HipEncoder (hand-written HIP). No CPU fallback.
+Qwen3-Embedding checkpoints (config.json model_type "qwen3") run on archi_amd.decoder.HipDecoder instead, tokenised by the
+checkpoint's own tokenizer.json, pooled on the last token; the same batching harness drives both.
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ from . import _lib
 from ._lib import check
 from .encoder import (MODEL_SHAPES, HipEncoder, load_hf_weights, random_init_weights,
                       read_sentence_transformers_config)
+from .decoder import MAX_SEQ, QWEN3_SHAPES, BpeTokenizer, HipDecoder, load_qwen3_weights, random_qwen3_weights, read_decoder_st_config
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
 
@@ -144,6 +147,15 @@ class NativeWordPiece:
         return self.encode_batch([text], max_len)[0]
 
 
+def _is_qwen3(model_name: str) -> bool:
+    """A Qwen3 checkpoint directory (config.json model_type "qwen3") or one of the named Qwen3-Embedding shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "qwen3"
+    return model_name in QWEN3_SHAPES
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -163,6 +175,11 @@ class ArchiHipEmbeddings:
         self.batch_tokens = int(self.encode_kwargs.get("batch_tokens", 65536))
         dev = str(self.model_kwargs.get("device", "cuda"))
         device = int(dev.split(":")[1]) if ":" in dev else None
+        self._stage = self._stage_out = None
+        self._stage_lock = threading.Lock()
+        if _is_qwen3(model_name):
+            self._init_decoder(model_name, device)
+            return
         if os.path.isdir(model_name):
             shape, weights, eps = load_hf_weights(model_name)
             vocab, H, L, heads, I, max_pos = shape
@@ -189,11 +206,39 @@ class ArchiHipEmbeddings:
                 f"{model_name!r}: no local checkpoint directory (offline image). Pass a directory with config.json + "
                 "model.safetensors (+ vocab.txt), or model_kwargs={'synthetic_seed': N} for seeded random weights")
         self.dimensions = H
-        self._stage = self._stage_out = None
-        self._stage_lock = threading.Lock()
         self.encoder = HipEncoder(vocab, H, L, heads, I, max_pos, weights, ln_eps=eps, device=device,
                                   residual=str(self.model_kwargs.get("residual", "bf16")),
                                   precision=str(self.model_kwargs.get("precision", "bf16")))
+
+    def _init_decoder(self, model_name: str, device: Optional[int]) -> None:
+        """Qwen3-Embedding: a local checkpoint directory (config.json model_type qwen3, safetensors, tokenizer.json, the
+        sentence-transformers files with lasttoken pooling) or a named shape with synthetic_seed. bf16 only."""
+        precision = str(self.model_kwargs.get("precision", "bf16"))
+        if precision != "bf16":
+            raise ValueError(f"precision {precision!r}: decoder models (Qwen3) run in bf16 only")
+        self.pooling = "last"
+        if os.path.isdir(model_name):
+            shape, weights = load_qwen3_weights(model_name)
+            st_len, st_norm = read_decoder_st_config(model_name)
+            tf = os.path.join(model_name, "tokenizer.json")
+            if not os.path.exists(tf):
+                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- a Qwen3 checkpoint needs its byte-level BPE tokenizer")
+            self.tokenizer = BpeTokenizer(tf)
+            self.normalize = self.normalize or st_norm
+        else:
+            if "synthetic_seed" not in self.model_kwargs:
+                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass a Qwen3 checkpoint "
+                                        "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
+            shape = QWEN3_SHAPES[model_name]
+            weights = random_qwen3_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]))
+            st_len = None
+            self.normalize = True                      # the released models carry a Normalize module
+            tf = self.model_kwargs.get("tokenizer_file")
+            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
+        max_pos = int(shape[6])
+        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, MAX_SEQ)
+        self.dimensions = int(shape[1])
+        self.encoder = HipDecoder(shape, weights, device=device)
 
     # -- LangChain Embeddings duck type -------------------------------------
     def embed_documents(self, texts: List[str]) -> List[List[float]]:

@@ -66,10 +66,10 @@ typedef void *ak_encoder_t;
 /* ABI version: bumped whenever a signature in this header changes (3: filter_len / filter_epoch on the search entry points,
  * a fourth out-pointer on ak_index_slots -- round 4; ak_abi_version / ak_debug_set / ak_encoder_forward_lens -- round 5;
  * 4: the sharded exchange's payload carries a status word per rank (wire format of ak_index_search_sharded_dev / ak_merge_shards_dev
- * callers), AK_ERR_COMM_BROKEN and the ak_shard_* helpers, AkBertConfig.precision 2 -- round 6).
+ * callers), AK_ERR_COMM_BROKEN and the ak_shard_* helpers, AkBertConfig.precision 2 -- round 6; 5: the ak_decoder_* entry points).
  * A binding checks ak_abi_version() == AK_ABI_VERSION right after loading the library (archi_amd/_lib.py does) instead of
  * passing arguments to a function whose parameter list has moved. */
-#define AK_ABI_VERSION 4
+#define AK_ABI_VERSION 5
 
 /* ---- library ---------------------------------------------------------- */
 const char *ak_last_error(void);
@@ -328,6 +328,44 @@ int ak_encoder_forward_lens(ak_encoder_t h, const int32_t *ids_dev, int ld_ids, 
  * (the activation of the reference's default embedder, all-MiniLM-L6-v2, inside Embeddings.embed_documents, manager.py:373).
  * Host only -- no GPU work; exported so that the CPU suite can hold the table to the exact function. */
 int ak_encoder_gelu_table(uint16_t *out8192);
+
+/* ---- decoder: Qwen3-Embedding (0.6B / 4B / 8B), the instruction-aware embedders of the reference's retrievers -------- */
+/* retrievers/utils.py:7-11, semantic_retriever.py:31-38. The forward pass of HF Qwen3Model (RMSNorm, per-head q / k RMSNorm, rotate_half
+ * RoPE, grouped-query causal attention at head dim 128, SwiGLU MLP), then the final norm of each row's LAST valid token and L2
+ * normalisation (sentence-transformers' lasttoken Pooling + Normalize). bf16 MFMA GEMMs, float32 residual stream. */
+typedef void *ak_decoder_t;
+typedef struct AkDecoderConfig {
+    int vocab_size;     /* 151669 */
+    int hidden;         /* 1024 / 2560 / 4096; a multiple of 128 */
+    int layers;         /* 28 / 36 / 36 */
+    int q_heads;        /* 16 / 32 / 32 */
+    int kv_heads;       /* 8; q_heads % kv_heads == 0, at most 4 query heads per kv head */
+    int head_dim;       /* 128 (the only head size implemented) */
+    int intermediate;   /* 3072 / 9728 / 12288; a multiple of 64 */
+    int max_position;   /* 32768 (sequences are limited to min(max_position, 8192) tokens) */
+    float rms_eps;      /* 1e-6 */
+    float rope_theta;   /* 1e6 (default RoPE only: no rope scaling) */
+} AkDecoderConfig;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] exactly as torch.nn.Linear.weight, vectors float32):
+ *   0 embed_tokens [vocab][H] bf16, 1 final norm [H],
+ *   per layer l (base 2 + 11 * l):
+ *     +0 wq [q_heads 128][H] +1 wk [kv_heads 128][H] +2 wv [kv_heads 128][H] +3 q_norm [128] +4 k_norm [128]
+ *     +5 wo [H][q_heads 128] +6 ln_in [H] (input_layernorm) +7 ln_post [H] (post_attention_layernorm)
+ *     +8 w_gate [I][H] +9 w_up [I][H] +10 w_down [H][I]
+ * The library copies wq | wk | wv into one matrix and interleaves the gate and up rows at create; the other pointers must stay valid
+ * until ak_decoder_destroy. */
+int ak_decoder_create(const AkDecoderConfig *cfg, const void *const *weights_dev, int n_weights, ak_decoder_t *out);
+int ak_decoder_destroy(ak_decoder_t h);
+/* The tile layout of ak_encoder_forward_lens: B right-padded rows of S token ids `ld_ids` int32 apart, lengths `lens_stride` apart
+ * (clamped to [0, S]; ids past a row's length are ignored; a row of length 0 embeds to zeros); out_dev [B][H] float32, the final norm
+ * of token len - 1 of each row, L2-normalised when `normalise` != 0. S a multiple of 32, <= 8192 and <= max_position. Positions are
+ * 0 .. len - 1 (RoPE is relative, so this equals a left-padded batch up to rounding). Asynchronous on `stream`. */
+int ak_decoder_forward_lens(ak_decoder_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                            int normalise, float *out_dev, void *stream);
+/* The RoPE table the decoder uploads at create: cos_out / sin_out [n_pos][head_dim / 2] float32, angle = float(pos) * inv_freq[i],
+ * inv_freq[i] = 1 / theta^(2 i / head_dim) (HF's default rotary embedding; its cos / sin are these rows twice). Host only -- no GPU
+ * work; exported so that the CPU suite can hold the table to HF's. */
+int ak_decoder_rope_table(float theta, int head_dim, int n_pos, float *cos_out, float *sin_out);
 
 /* ---- host tokenizer: the tokenisation step inside Embeddings.embed_documents -------- */
 /* manager.py:373 -> HuggingFaceEmbeddings -> sentence-transformers' BERT WordPiece tokenizer [upstream]. Pure host
