@@ -118,11 +118,14 @@ SYMBOLS = [
     ("ak_encoder_forward", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     ("ak_encoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_encoder_gelu_table", _I, [_P]),
+    ("ak_encoder_set_rel_bias", _I, [_P, _P, _I, _I]),
     ("ak_decoder_create", _I, [ctypes.POINTER(AkDecoderConfig), _P, _I, ctypes.POINTER(_P)]),
     ("ak_decoder_destroy", _I, [_P]),
     ("ak_decoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     ("ak_decoder_rope_table", _I, [ctypes.c_float, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
+    ("ak_wordpiece_create_ex", _I, [ctypes.c_char_p, _I, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                    ctypes.POINTER(ctypes.c_char_p), _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_destroy", _I, [_P]),
     ("ak_wordpiece_encode", _I, [_P, _P, _P, _I64, _I, _I, _P, _P]),
 ]

@@ -18,6 +18,10 @@ EMBEDDING_DIMENSIONS = {
     "all-MiniLM-L6-v2": 384,
     "BAAI/bge-base-en": 768,
     "BAAI/bge-base-en-v1.5": 768,
+    "sentence-transformers/all-mpnet-base-v2": 768,
+    "all-mpnet-base-v2": 768,
+    "sentence-transformers/multi-qa-mpnet-base-dot-v1": 768,
+    "sentence-transformers/paraphrase-mpnet-base-v2": 768,
     "Qwen/Qwen3-Embedding-0.6B": 1024,
     "Qwen/Qwen3-Embedding-4B": 2560,
     "Qwen/Qwen3-Embedding-8B": 4096,

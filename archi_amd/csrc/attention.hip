@@ -22,7 +22,8 @@ using namespace mt;
 
 // (An inline-asm v_max3_f32 on MFMA outputs, tried to avoid hipcc's canonicalising v_max, read the accumulators BEFORE the MFMA
 // had written them: the hazard recogniser does not cover inline-asm operands. Results differed from run to run.)
-template <int HD, int NW, int CB = 4>   // CB: 32-key blocks per online-softmax chunk
+// BIAS: add the relative-position bias a.rel (a separate instantiation: the kernels without it are the code they were before)
+template <int HD, int NW, int CB = 4, bool BIAS = false>   // CB: 32-key blocks per online-softmax chunk
 __global__ __launch_bounds__(NW * 64, (HD == 32 && NW <= 8 && CB == 2) ? 6 : ((HD == 32 || NW == 16) ? 4 : 2)) void k_attn(AttnArgs a) {
     constexpr int NT = NW * 64;
     constexpr int DB = HD / 32, KSTEPS = HD / 16;
@@ -33,6 +34,7 @@ __global__ __launch_bounds__(NW * 64, (HD == 32 && NW <= 8 && CB == 2) ? 6 : ((H
     char *sK = smem;
     char *sV = sK + S * KSTRIDE;
     float *sM = (float *)(sV + HD * VSTRIDE);
+    float *sB = sM + S;                              // relative-position bias band (a.rel): distances -qs - 32 NW + i, i < S + 32 NW
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, h = blockIdx.y;
     const int q0 = blockIdx.x * (NW * 32) + wave * 32;
@@ -91,9 +93,14 @@ __global__ __launch_bounds__(NW * 64, (HD == 32 && NW <= 8 && CB == 2) ? 6 : ((H
         asm volatile("" : "+v"(mraw));
         if (tid < S) sM[tid] = mraw ? 0.f : -__builtin_inff();
         for (int i = tid + NT; i < S; i += NT) sM[i] = a.mask[b * S + i] ? 0.f : -__builtin_inff();
+        if (BIAS) {
+            const float *rg = a.rel + (int64_t)h * REL_ROW + REL_MID - blockIdx.x * (NW * 32) - NW * 32;
+            for (int i = tid; i < S + NW * 32; i += NT) sB[i] = rg[i];
+        }
     }
     __syncthreads();
     if (q0 >= S) return;
+    const float *bB = sB + (NW * 32 - wave * 32 - r);   // this lane's diagonal: key s at bB[s]
 
     f32x16 o[DB];
 #pragma unroll
@@ -117,7 +124,11 @@ __global__ __launch_bounds__(NW * 64, (HD == 32 && NW <= 8 && CB == 2) ? 6 : ((H
                 f32x16 acc;
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
-                    const float4 mk = *(const float4 *)&sM[kc0 + blk * 32 + 8 * g + 4 * kh];
+                    float4 mk = *(const float4 *)&sM[kc0 + blk * 32 + 8 * g + 4 * kh];
+                    if (BIAS) {
+                        const float *bp = bB + kc0 + blk * 32 + 8 * g + 4 * kh;
+                        mk.x += bp[0]; mk.y += bp[1]; mk.z += bp[2]; mk.w += bp[3];
+                    }
                     acc[4 * g + 0] = mk.x; acc[4 * g + 1] = mk.y; acc[4 * g + 2] = mk.z; acc[4 * g + 3] = mk.w;
                 }
                 const char *kr = sK + (kc0 + blk * 32 + r) * KSTRIDE + kh * 16;
@@ -225,15 +236,18 @@ __global__ __launch_bounds__(512) void k_attn_prepare(const int *__restrict__ ma
     if (t == 0) blkmask[b] = bits;
 }
 
-template <int HD, int NW>
+template <int HD, int NW, bool BIAS = false>
 __global__ __launch_bounds__(NW * 64, 4) void k_attn_s(AttnArgs a, int nitems, int ktm) {
     constexpr int DB = HD / 32, KSTEPS = HD / 16, KROW = HD * 2, CRK = HD / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = a.S, H = a.H, heads = a.heads;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, kh = lane >> 5;
-    // ring slot: K tile [kt][HD] | V^T tile [HD][kt] | additive mask [kt] f32, sized for the largest tile of this S
-    const int slot_k = ktm * KROW, slot_v = HD * ktm * 2, slot = slot_k + slot_v + ktm * 4;
+    // ring slot: K tile [kt][HD] | V^T tile [HD][kt] | additive mask [kt] f32 | with a relative-position bias, its band for the
+    // item's queries [qs, qs + 32 NW) and the tile's keys: distances k0 - qs - 32 NW + 1 + i, i < kt + 32 NW - 1 (f32), sized for
+    // the largest tile of this S
+    constexpr bool hasb = BIAS;
+    const int slot_k = ktm * KROW, slot_v = HD * ktm * 2, slot = slot_k + slot_v + ktm * 4 + (hasb ? (ktm + NW * 32) * 4 : 0);
     const uint32_t lds0 = lds_addr(smem);
     const int nqb = (S + NW * 32 - 1) / (NW * 32);
     const int n256 = S >> 8, rem = S & 255;
@@ -261,7 +275,9 @@ __global__ __launch_bounds__(NW * 64, 4) void k_attn_s(AttnArgs a, int nitems, i
         const char *vg = (const char *)(a.vt + ((int64_t)b * H + h * HD) * S + k0);
         const int lcr = 31 - __clz(kt >> 3);           // log2(16-B chunks per V^T tile row)
         const int vsh = lcr >= 4 ? 0 : 4 - lcr, vmsk = (lcr >= 4 ? 16 : (1 << lcr)) - 1;
-        for (int p = wave; p < 2 * nkp + 1; p += NW) {
+        // bias band: 1 KiB pieces of 256 distances, starting 128-byte aligned (k0, qs and 32 NW are multiples of 32)
+        const int nbp = hasb ? (kt + NW * 32 + 255) >> 8 : 0;
+        for (int p = wave; p < 2 * nkp + 1 + nbp; p += NW) {
             if (p < nkp) {
                 const int g = p * 64 + lane, row = g / CRK, c = g % CRK;
                 const int swz = HD == 64 ? (row >> 1) & 7 : (row >> 2) & 3;
@@ -270,8 +286,13 @@ __global__ __launch_bounds__(NW * 64, 4) void k_attn_s(AttnArgs a, int nitems, i
                 const int g = (p - nkp) * 64 + lane, row = g >> lcr, c = g & ((1 << lcr) - 1);
                 const int swz = (row >> vsh) & vmsk;
                 glds16(vg + (int64_t)row * S * 2 + ((c ^ swz) << 4), sb + slot_k + (p - nkp) * 1024);
-            } else if (lane * 4 < kt) {
-                glds16(a.maskf + (int64_t)b * S + k0 + lane * 4, sb + slot_k + slot_v);
+            } else if (!hasb || p == 2 * nkp) {
+                if (lane * 4 < kt) glds16(a.maskf + (int64_t)b * S + k0 + lane * 4, sb + slot_k + slot_v);
+            } else {
+                const int pb = p - 2 * nkp - 1, i = pb * 256 + lane * 4;
+                const int qs = (it - (it / nqb) * nqb) * (NW * 32);
+                if (i < kt + NW * 32)
+                    glds16(a.rel + (int64_t)h * REL_ROW + REL_MID + k0 - qs - NW * 32 + i, sb + slot_k + slot_v + kt * 4 + pb * 1024);
             }
         }
     };
@@ -326,19 +347,27 @@ __global__ __launch_bounds__(NW * 64, 4) void k_attn_s(AttnArgs a, int nitems, i
             const uint32_t flags = flags_all >> (k0 >> 5), fullf = full_all >> (k0 >> 5);
             const char *krow = sb + r * KROW;
             const char *vrow = sV + r * (kt * 2);
+            // this lane's diagonal of the bias band: key t of the tile (accumulator row) at bB[t]
+            const float *bB = (const float *)(sb + slot_k + slot_v + kt * 4) + (NW * 32 - wave * 32) + 4 * kh - r;
             for (int blk = 0; blk < (kt >> 5); blk++) {
                 if (!((flags >> blk) & 1)) continue;    // padding only: contributes exp2(-inf) = 0 to every sum
                 // the additive mask (0 / -inf per key = per accumulator row) is the MFMA's initial accumulator; a block of 32 real
-                // keys (wave-uniform flag) starts from the zero constant instead
+                // keys (wave-uniform flag) starts from the zero constant instead. With a bias: mask + bias
                 f32x16 acc;
                 const char *kr = krow + blk * 32 * KROW;
-                if ((fullf >> blk) & 1) {
+                const bool full = (fullf >> blk) & 1;
+                if (full && !hasb) {
                     const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     acc = mfma_bf16(*(const uint4 *)(kr + kx), qf[0], z);
                 } else {
 #pragma unroll
                     for (int g = 0; g < 4; g++) {
-                        const float4 mk = *(const float4 *)&sM[blk * 32 + 8 * g + 4 * kh];
+                        float4 mk = {0.f, 0.f, 0.f, 0.f};
+                        if (!full) mk = *(const float4 *)&sM[blk * 32 + 8 * g + 4 * kh];
+                        if (hasb) {
+                            const float *bp = bB + blk * 32 + 8 * g;
+                            mk.x += bp[0]; mk.y += bp[1]; mk.z += bp[2]; mk.w += bp[3];
+                        }
                         acc[4 * g + 0] = mk.x; acc[4 * g + 1] = mk.y; acc[4 * g + 2] = mk.z; acc[4 * g + 3] = mk.w;
                     }
                     acc = mfma_bf16(*(const uint4 *)(kr + kx), qf[0], acc);
@@ -438,10 +467,10 @@ __global__ __launch_bounds__(NW * 64, 4) void k_attn_s(AttnArgs a, int nitems, i
 // cap, 162 us); key tiles of 128 / 64 keys, each with its own counted vmcnt wait and barrier so that the first blocks run
 // while the rest of the item is in flight: 60.0 / 64.3 against 57.5 -- the workgroups of a CU are already out of step, a
 // barrier per tile costs more than the exposed part of one item's staging.
-template <int HD, int NW>
+template <int HD, int NW, bool BIAS = false>
 __global__ __launch_bounds__(NW * 64, (HD == 32 && NW <= 8) ? 6 : 4) void k_attn_d(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_d_body<HD, NW, LdPlain>(a, blockIdx.x, smem);
+    attn_d_body<HD, NW, LdPlain, BIAS>(a, blockIdx.x, smem);
 }
 
 // =====================================================================================================================
@@ -1209,6 +1238,7 @@ int launch_attn(const AttnArgs &a0, hipStream_t st) {
     if (hd != 32 && hd != 64) AK_FAIL(-1, "attention: head size must be 32 or 64");
     if (a.S % 32 || a.S > 512) AK_FAIL(-1, "attention: S must be a multiple of 32 and <= 512");
     size_t lds = (size_t)a.S * (hd * 2 + 16) + (size_t)hd * (a.S * 2 + 16) + (size_t)a.S * 4;
+    const bool hasb = a.rel != nullptr;
     static std::atomic<bool> attr{false};      // (set twice by two first callers at worst: idempotent)
     if (!attr) {
         AK_HIP(hipFuncSetAttribute((const void *)k_attn<32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1228,29 +1258,34 @@ int launch_attn(const AttnArgs &a0, hipStream_t st) {
     // blocks that hold only padding: MiniLM 2.09 vs 2.13 ms, bge-base 15.45 vs 16.05 ms.
     static const int force_stream = env_get("AK_ATTN_STREAM") ? atoi(env_get("AK_ATTN_STREAM")) : (env_get("AK_ATTN_OLD") ? 0 : -1);
     const int variant = force_stream >= 0 ? force_stream : (hd == 64 ? 1 : 2);
+    // the relative-position bias is added by k_attn, k_attn_s and k_attn_d only
+    if (hasb && variant > 2) AK_FAIL(-1, "attention: AK_ATTN_STREAM selects a kernel without the relative-position bias");
     if (variant == 2 && a.maskf && a.blkmask) {
         static std::atomic<bool> attr_d{false};
         if (!attr_d) {
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<32, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<32, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<64, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define AK_ATTN_D_ATTR(HDV, NWV) \
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<HDV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn_d<HDV, NWV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+            AK_ATTN_D_ATTR(32, 4); AK_ATTN_D_ATTR(32, 8); AK_ATTN_D_ATTR(32, 16);
+            AK_ATTN_D_ATTR(64, 4); AK_ATTN_D_ATTR(64, 8); AK_ATTN_D_ATTR(64, 16);
+#undef AK_ATTN_D_ATTR
             attr_d = true;
         }
         const int nw = force_nw ? force_nw : (a.S >= 512 ? 16 : (a.S >= 256 ? 8 : 4));
-        const size_t ldsd = (size_t)a.S * (hd * 2 + 2 * hd + 4);
+        const size_t ldsd = (size_t)a.S * (hd * 2 + 2 * hd + 4) + (hasb ? (size_t)(a.S + nw * 32) * 4 : 0);
         const int nitems = a.B * a.heads * ((a.S + nw * 32 - 1) / (nw * 32));
+#define AK_ATTN_D(HDV, NWV) do { if (hasb) k_attn_d<HDV, NWV, true><<<nitems, NWV * 64, ldsd, st>>>(a); \
+                                 else k_attn_d<HDV, NWV><<<nitems, NWV * 64, ldsd, st>>>(a); } while (0)
         if (hd == 32) {
-            if (nw == 16) k_attn_d<32, 16><<<nitems, 1024, ldsd, st>>>(a);
-            else if (nw == 8) k_attn_d<32, 8><<<nitems, 512, ldsd, st>>>(a);
-            else k_attn_d<32, 4><<<nitems, 256, ldsd, st>>>(a);
+            if (nw == 16) AK_ATTN_D(32, 16);
+            else if (nw == 8) AK_ATTN_D(32, 8);
+            else AK_ATTN_D(32, 4);
         } else {
-            if (nw == 16) k_attn_d<64, 16><<<nitems, 1024, ldsd, st>>>(a);
-            else if (nw == 8) k_attn_d<64, 8><<<nitems, 512, ldsd, st>>>(a);
-            else k_attn_d<64, 4><<<nitems, 256, ldsd, st>>>(a);
+            if (nw == 16) AK_ATTN_D(64, 16);
+            else if (nw == 8) AK_ATTN_D(64, 8);
+            else AK_ATTN_D(64, 4);
         }
+#undef AK_ATTN_D
         AK_HIP(hipGetLastError());
         return 0;
     }
@@ -1351,37 +1386,65 @@ int launch_attn(const AttnArgs &a0, hipStream_t st) {
         if (!cus) {
             int dev = 0; hipDeviceProp_t pr;
             AK_HIP(hipGetDevice(&dev)); AK_HIP(hipGetDeviceProperties(&pr, dev));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<32, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<32, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<64, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define AK_ATTN_S_ATTR(HDV, NWV) \
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<HDV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn_s<HDV, NWV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+            AK_ATTN_S_ATTR(32, 4); AK_ATTN_S_ATTR(32, 8); AK_ATTN_S_ATTR(32, 16);
+            AK_ATTN_S_ATTR(64, 4); AK_ATTN_S_ATTR(64, 8); AK_ATTN_S_ATTR(64, 16);
+#undef AK_ATTN_S_ATTR
             cus = pr.multiProcessorCount;      // last: a second thread that sees it set may launch at once
         }
         const int nw = force_nw ? force_nw : (a.S >= 512 ? 16 : (a.S >= 256 ? 8 : 4));
         int ktm = a.S >= 256 ? 256 : 32;
         if (a.S < 256) while (ktm * 2 <= a.S) ktm *= 2;       // largest power-of-two tile of this S
-        const size_t slot = (size_t)ktm * hd * 2 * 2 + (size_t)ktm * 4;
+        const size_t slot = (size_t)ktm * hd * 2 * 2 + (size_t)ktm * 4 + (hasb ? (size_t)(ktm + nw * 32) * 4 : 0);    // k_attn_s' slot
         const size_t ring = 2 * slot;
         const int nqb = (a.S + nw * 32 - 1) / (nw * 32);
         const int nitems = a.B * a.heads * nqb;
         int per_cu = 16 / nw;                                 // 16 waves per CU: four per SIMD at <= 128 registers
         while (per_cu > 1 && per_cu * ring > 160 * 1024) per_cu--;
         const int grid = nitems < cus * per_cu ? nitems : cus * per_cu;
+#define AK_ATTN_S(HDV, NWV) do { if (hasb) k_attn_s<HDV, NWV, true><<<grid, NWV * 64, ring, st>>>(a, nitems, ktm); \
+                                 else k_attn_s<HDV, NWV><<<grid, NWV * 64, ring, st>>>(a, nitems, ktm); } while (0)
         if (hd == 32) {
-            if (nw == 16) k_attn_s<32, 16><<<grid, 1024, ring, st>>>(a, nitems, ktm);
-            else if (nw == 8) k_attn_s<32, 8><<<grid, 512, ring, st>>>(a, nitems, ktm);
-            else k_attn_s<32, 4><<<grid, 256, ring, st>>>(a, nitems, ktm);
+            if (nw == 16) AK_ATTN_S(32, 16);
+            else if (nw == 8) AK_ATTN_S(32, 8);
+            else AK_ATTN_S(32, 4);
         } else {
-            if (nw == 16) k_attn_s<64, 16><<<grid, 1024, ring, st>>>(a, nitems, ktm);
-            else if (nw == 8) k_attn_s<64, 8><<<grid, 512, ring, st>>>(a, nitems, ktm);
-            else k_attn_s<64, 4><<<grid, 256, ring, st>>>(a, nitems, ktm);
+            if (nw == 16) AK_ATTN_S(64, 16);
+            else if (nw == 8) AK_ATTN_S(64, 8);
+            else AK_ATTN_S(64, 4);
         }
+#undef AK_ATTN_S
         AK_HIP(hipGetLastError());
         return 0;
     }
     const int nw = force_nw ? force_nw : (a.S >= 512 ? 16 : (a.S >= 256 ? 8 : 4));
+    if (hasb) {                                               // k_attn with the bias band: 64-key chunks at hd 64, 128 at hd 32
+        static std::atomic<bool> attr_b{false};
+        if (!attr_b) {
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn<32, 4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn<32, 8, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn<32, 16, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn<64, 4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn<64, 8, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            AK_HIP(hipFuncSetAttribute((const void *)k_attn<64, 16, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_b = true;
+        }
+        lds += (size_t)(a.S + nw * 32) * 4;
+        dim3 grid((a.S + nw * 32 - 1) / (nw * 32), a.heads, a.B);
+        if (hd == 32) {
+            if (nw == 16) k_attn<32, 16, 4, true><<<grid, 1024, lds, st>>>(a);
+            else if (nw == 8) k_attn<32, 8, 4, true><<<grid, 512, lds, st>>>(a);
+            else k_attn<32, 4, 4, true><<<grid, 256, lds, st>>>(a);
+        } else {
+            if (nw == 16) k_attn<64, 16, 2, true><<<grid, 1024, lds, st>>>(a);
+            else if (nw == 8) k_attn<64, 8, 2, true><<<grid, 512, lds, st>>>(a);
+            else k_attn<64, 4, 2, true><<<grid, 256, lds, st>>>(a);
+        }
+        AK_HIP(hipGetLastError());
+        return 0;
+    }
     dim3 grid((a.S + nw * 32 - 1) / (nw * 32), a.heads, a.B);
     if (hd == 32) {
         if (nw == 16) k_attn<32, 16><<<grid, 1024, lds, st>>>(a);

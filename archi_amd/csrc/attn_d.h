@@ -113,7 +113,8 @@ __device__ inline void glds16(const void *g, uint32_t lds_wave_base) {
 }
 
 
-template <int HD, int NW, class LD>
+// BIAS: add the relative-position bias a.rel (k_attn_d<.., true>; the query forward never sets it)
+template <int HD, int NW, class LD, bool BIAS = false>
 __device__ __forceinline__ void attn_d_body(const AttnArgs &a, const int it_, char *smem) {
     constexpr int DB = HD / 32, KSTEPS = HD / 16, KROW = HD * 2, CRK = HD / 8, PERKEY = KROW + 2 * HD + 4;
     const int S = a.S, H = a.H, heads = a.heads;
@@ -157,9 +158,18 @@ __device__ __forceinline__ void attn_d_body(const AttnArgs &a, const int it_, ch
         }
         k0 += kt;
     }
+    // relative-position bias band behind the tiles (a.rel): distances -qs - 32 NW + i, i < S + 32 NW, in 1 KiB pieces of 256
+    // (qs = the item's first query; the source starts 128-byte aligned)
+    constexpr bool hasb = BIAS;
+    if (hasb) {
+        const float *rg = a.rel + (int64_t)h * REL_ROW + REL_MID - qb * (NW * 32) - NW * 32;
+        for (int p = wave; p < (S + NW * 32 + 255) >> 8; p += NW)
+            if (p * 256 + lane * 4 < S + NW * 32) LD::glds16(rg + p * 256 + lane * 4, lds0 + S * PERKEY + p * 1024);
+    }
     wait_vm<0>();
     __syncthreads();
     if (q0 >= S) return;
+    const float *bB = (const float *)(smem + S * PERKEY) + (NW * 32 - wave * 32 - r);    // this lane's diagonal: key s at bB[s]
 
     f32x16 o[DB];
     float m = 0.f;
@@ -174,15 +184,20 @@ __device__ __forceinline__ void attn_d_body(const AttnArgs &a, const int it_, ch
     // selects are scalar, and every other block only checks whether a score exceeds the current reference by more than 2^8
     // (one compare + a scalar branch, rarely taken). The two halves of a query's column (lanes r, r + 32) meet in one
     // v_permlane32_swap, not an LDS permute.
-    auto block = [&](const char *kr, const float *mrow, const char *vr, int voff, int kt2, int vx, bool first, bool full) {
+    auto block = [&](const char *kr, const float *mrow, const float *brow, const char *vr, int voff, int kt2, int vx, bool first, bool full) {
         f32x16 acc;
-        if (full) {                                       // 32 real keys (wave-uniform): zero constant instead of the mask's four LDS reads
+        if (full && !hasb) {                              // 32 real keys (wave-uniform): zero constant instead of the mask's four LDS reads
             const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             acc = mfma_bf16(*(const uint4 *)(kr + kx), qf[0], z);
         } else {
 #pragma unroll
             for (int g = 0; g < 4; g++) {
-                const float4 mk = *(const float4 *)&mrow[8 * g + 4 * kh];
+                float4 mk = {0.f, 0.f, 0.f, 0.f};
+                if (!full) mk = *(const float4 *)&mrow[8 * g + 4 * kh];
+                if (hasb) {                               // + the bias of this lane's query and the block's keys
+                    const float *bp = brow + 8 * g + 4 * kh;
+                    mk.x += bp[0]; mk.y += bp[1]; mk.z += bp[2]; mk.w += bp[3];
+                }
                 acc[4 * g + 0] = mk.x; acc[4 * g + 1] = mk.y; acc[4 * g + 2] = mk.z; acc[4 * g + 3] = mk.w;
             }
             acc = mfma_bf16(*(const uint4 *)(kr + kx), qf[0], acc);
@@ -254,7 +269,7 @@ __device__ __forceinline__ void attn_d_body(const AttnArgs &a, const int it_, ch
         const uint32_t flags = flags_all >> b0, fullf = full_all >> b0;
         for (int blk = 0; blk < (kt >> 5); blk++) {
             if (!((flags >> blk) & 1)) continue;        // padding only: exp2(-inf) = 0 in every sum
-            block(krow + blk * 32 * KROW, sM + blk * 32, vrow, blk * 64, kt * 2, vx, b0 + blk == fb, (fullf >> blk) & 1);
+            block(krow + blk * 32 * KROW, sM + blk * 32, bB + k0 + blk * 32, vrow, blk * 64, kt * 2, vx, b0 + blk == fb, (fullf >> blk) & 1);
         }
         k0 += kt;
     }

@@ -528,6 +528,9 @@ struct Encoder {
     float *maskf = nullptr;       // additive key mask [tokens] + per-sequence block bitmap behind it (attention.hip)
     float *st1 = nullptr, *st2 = nullptr;   // lazy LayerNorm: per-token (mean, 1 / std) [tokens][2] behind the two sub-layers
     float *stp = nullptr;                   // ... and the partial sums [H / 128][tokens][2] they are made of
+    // relative-position bias (ak_encoder_set_rel_bias): per-distance tables [heads][REL_ROW] (encoder_kernels.h), natural domain
+    // (float32 attention) and scaled by log2(e) (the base-2 kernels); NULL: none. rel_n: distances |d| < rel_n are covered
+    float *rel = nullptr, *rel2 = nullptr; int rel_n = 0;
     std::mutex mu;
 };
 
@@ -572,7 +575,7 @@ constexpr int X3_PADN_DEFAULT = 1;      // MiniLM 256 x 256, ms per forward: non
 // x3: nullptr = exact float32 GEMMs (precision 1); else the layer matrices split into bf16 hi / lo (precision 2: every GEMM as
 // hi.hi + lo.hi + hi.lo on the bf16 matrix cores, encoder_f32.hip k3_gemm). Everything else is the same float32 code.
 static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16_t *const *x3, const int *ids, const int *mask, int B, int S, int pooling,
-                       int normalise, float *out, float **ws, size_t *ws_bytes, hipStream_t st) {
+                       int normalise, float *out, float **ws, size_t *ws_bytes, hipStream_t st, const float *rel = nullptr, const float *rel2 = nullptr) {
     const int H = c.hidden, I = c.intermediate, L = c.layers;
     const int64_t T = (int64_t)B * S;
     // Split mode on gemm.hip's tiles (x3_tiles below): whole 256-token tiles, so the rows are padded to one (rows past T: zeros in,
@@ -628,7 +631,7 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
                 return launch_gemm_x3w(mode, g, st);
             };
             if (gemm(5, xs, s3[12], (const float *)s3[16], Qn, H, qkv2, nullptr, 3 * H)) return -10;
-            if (launch_attn_x3_split(qkv2, Qn, mask, B, S, H, c.heads, cs, st)) return -10;
+            if (launch_attn_x3_split(qkv2, Qn, mask, B, S, H, c.heads, cs, st, rel2)) return -10;
             // hidden 384: out-projection / FFN-down with the residual add and the LayerNorm in the epilogue (gemm_ln.hip, X3): the
             // float32 sub-layer output never goes to HBM (AK_X3_GEMMLN=0: MODE 5 + k3_add_ln, as the other widths)
             static const bool x3_gemmln = !(env_get("AK_X3_GEMMLN") && atoi(env_get("AK_X3_GEMMLN")) == 0);
@@ -673,8 +676,8 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
                     if (gemm(0, x, j, 2 * j, (const float *)p[2 * j + 1], nullptr, H, H, qkv, 3 * H, j * H)) return -10;
             }
             static const bool x3_attn_f32 = env_get("AK_X3_ATTN_F32") != nullptr;        // A/B: the float32 attention kernel under the split GEMMs
-            if (s3 && !x3_attn_f32) { if (launch_attn_x3(qkv, mask, B, S, H, c.heads, ctx, st)) return -10; }
-            else if (launch_attn_f32(qkv, mask, B, S, H, c.heads, ctx, st)) return -10;
+            if (s3 && !x3_attn_f32) { if (launch_attn_x3(qkv, mask, B, S, H, c.heads, ctx, st, rel2)) return -10; }
+            else if (launch_attn_f32(qkv, mask, B, S, H, c.heads, ctx, st, rel)) return -10;
             if (gemm(2, ctx, 3, 6, (const float *)p[7], x, H, H, y, H, 0)) return -10;      // + residual
             k32_add_ln<<<rows4, 256, 0, st>>>(y, nullptr, (int)T, H, (const float *)p[8], (const float *)p[9], c.ln_eps, x);
             AK_HIP(hipGetLastError());
@@ -688,6 +691,7 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
         return 0;
     }
 #if AK_DBG_KERNELS
+    if (rel) AK_FAIL(-1, "ak_encoder_forward (precision f32): the scalar attention kernel has no relative-position bias");
     const dim3 gt((unsigned)((T + 63) / 64));
     for (int l = 0; l < L; l++) {
         const void *const *p = w + 5 + 16 * l;
@@ -871,8 +875,44 @@ extern "C" int ak_encoder_destroy(ak_encoder_t h) {
     if (e->qf_ctl) hipFree(e->qf_ctl);
     if (e->qf_layers) hipFree(e->qf_layers);
     if (e->qf_fail) hipHostFree(e->qf_fail);
+    if (e->rel) hipFree(e->rel);
+    if (e->rel2) hipFree(e->rel2);
     for (void *p : e->owned) hipFree(p);
     delete e;
+    return 0;
+}
+
+namespace ak {
+// the caller's [heads][2 n_rel - 1] table -> the per-distance rows [heads][REL_ROW] (distance d at REL_MID + d, zero for |d| >= n_rel),
+// once as given (rel) and once times log2(e) (rel2: the base-2 kernels); one thread per output element
+__global__ void k_rel_table(const float *__restrict__ src, int heads, int n_rel, float *__restrict__ rel, float *__restrict__ rel2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= heads * REL_ROW) return;
+    const int h = i / REL_ROW, d = i - h * REL_ROW - REL_MID;
+    const float v = (d > -n_rel && d < n_rel) ? src[(int64_t)h * (2 * n_rel - 1) + d + n_rel - 1] : 0.f;
+    rel[i] = v;
+    rel2[i] = v * 1.4426950408889634f;
+}
+}  // namespace ak
+
+extern "C" int ak_encoder_set_rel_bias(ak_encoder_t h, const float *bias_dev, int heads, int n_rel) {
+    AK_BIND();
+    if (!h || !bias_dev) AK_FAIL(-1, "ak_encoder_set_rel_bias: NULL argument");
+    Encoder &e = *(Encoder *)h;
+    if (heads != e.cfg.heads) AK_FAIL(-1, "ak_encoder_set_rel_bias: heads must equal the encoder's attention heads");
+    if (n_rel < 1 || n_rel > REL_MID - 1) AK_FAIL(-1, "ak_encoder_set_rel_bias: n_rel must be in [1, 1023]");
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (e.rel) AK_FAIL(-1, "ak_encoder_set_rel_bias: the encoder already has a relative-position bias");
+    float *rel = nullptr, *rel2 = nullptr;
+    const size_t bytes = (size_t)heads * REL_ROW * 4;
+    if (hipMalloc((void **)&rel, bytes) != hipSuccess) AK_FAIL(-10, "ak_encoder_set_rel_bias: hipMalloc failed");
+    if (hipMalloc((void **)&rel2, bytes) != hipSuccess) { hipFree(rel); AK_FAIL(-10, "ak_encoder_set_rel_bias: hipMalloc failed"); }
+    k_rel_table<<<(unsigned)((heads * REL_ROW + 255) / 256), 256>>>(bias_dev, heads, n_rel, rel, rel2);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        hipFree(rel); hipFree(rel2);
+        AK_FAIL(-10, "ak_encoder_set_rel_bias: table launch failed");
+    }
+    e.rel = rel; e.rel2 = rel2; e.rel_n = n_rel;
     return 0;
 }
 
@@ -891,6 +931,7 @@ extern "C" int ak_encoder_forward(ak_encoder_t h, const int32_t *ids, const int3
     if (B <= 0) return 0;
     if (S % 32 || S > 512 || S > e.cfg.max_position) AK_FAIL(-1, "ak_encoder_forward: S must be a multiple of 32, <= 512 and <= max_position (pad with mask 0)");
     std::lock_guard<std::mutex> lk(e.mu);
+    if (e.rel && S > e.rel_n) AK_FAIL(-1, "ak_encoder_forward: S exceeds the n_rel of the relative-position bias table");
     return forward_locked(e, ids, mask, B, S, pooling, normalise, out, (hipStream_t)stream);
 }
 
@@ -919,6 +960,7 @@ extern "C" int ak_encoder_forward_lens(ak_encoder_t h, const int32_t *ids, int l
     if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, "ak_encoder_forward_lens: bad arguments");
     if (S % 32 || S > 512 || S > e.cfg.max_position) AK_FAIL(-1, "ak_encoder_forward_lens: S must be a multiple of 32, <= 512 and <= max_position");
     std::lock_guard<std::mutex> lk(e.mu);
+    if (e.rel && S > e.rel_n) AK_FAIL(-1, "ak_encoder_forward_lens: S exceeds the n_rel of the relative-position bias table");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)B * S;
     if (n > e.lens_cap) {
@@ -990,7 +1032,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
     if (e.cfg.precision == 1 || e.cfg.precision == 2) {
         if (lens_to_mask()) return -10;
         return forward_f32(e.cfg, e.raw.data(), e.cfg.precision == 2 ? e.x3.data() : nullptr, ids, mask, B, S, pooling, normalise, out,
-                           &e.ws32, &e.ws32_bytes, st);
+                           &e.ws32, &e.ws32_bytes, st, e.rel, e.rel2);
     }
     const int H = e.cfg.hidden, I = e.cfg.intermediate, heads = e.cfg.heads;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
@@ -998,7 +1040,8 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
     // <= 64 token rows (embed_query): the whole forward pass as ONE launch on one XCD (query_forward.hip), bit-identical to the
     // launches below; 1 = not taken / gave up safely
     const int qf_mode = switches().query_fused.load(std::memory_order_relaxed);      // 0 off (default), 1 when it applies, 2 required (tests)
-    if (!e.qf_off && query_forward_supported(H, I, heads, T, S) && (lens_in == nullptr || e.lens_ids != nullptr)) {
+    // (the single launch has no relative-position bias: an encoder with one always takes the launches below)
+    if (!e.qf_off && !e.rel2 && query_forward_supported(H, I, heads, T, S) && (lens_in == nullptr || e.lens_ids != nullptr)) {
         const int rc = run_query_forward(e, lens_in, ids, mask, B, S, pooling, normalise, out, tpad, st);
         if (rc <= 0) return rc;
         if (qf_mode == 2) AK_FAIL(-10, "ak_encoder_forward: the single-launch query forward gave up (a bounded wait ran out) and AK_QUERY_FUSED=2 requires it");
@@ -1045,7 +1088,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
             g.nslot = H / 128; g.inv_h = 1.0f / (float)H; g.eps = eps;
             if (l == 0) { g.W = ly.wqkv; g.bias = ly.bqkv; if (launch_gemm(0, g, st)) return -10; }
             else { g.W = ly.wqkv; g.bias = ly.bqkv_f; g.fold_c = ly.cqkv; g.a_stats = e.st2; if (launch_gemm_lazy(0, g, st)) return -10; }
-            AttnArgs a{e.q, e.k, e.vt, mask, e.ctx, B, S, H, heads, e.maskf, (const uint32_t *)(e.maskf + tpad), 0, 0};
+            AttnArgs a{e.q, e.k, e.vt, mask, e.ctx, B, S, H, heads, e.maskf, (const uint32_t *)(e.maskf + tpad), 0, 0, e.rel2};
             if (launch_attn(a, st)) return -10;
             GemmArgs o{};                         // r1 = ctx Wo^T + bo + LN2_prev(r2) -> e.q, st1
             o.X = e.ctx; o.W = ly.wo; o.bias = ly.bo; o.T = (int)tpad; o.N = H; o.K = H; o.out_bf16 = e.q; o.ldo = H; o.res16 = e.x16;
@@ -1086,7 +1129,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
             qk_head_major = head_major;
         } else if (launch_gemm(0, g, st)) return -10;
         AttnArgs a{e.q, e.k, e.vt, mask, e.ctx, B, S, H, heads, e.maskf, (const uint32_t *)(e.maskf + tpad),
-                   qk_head_major ? H / heads : 0, qk_head_major ? S * (H / heads) : 0};
+                   qk_head_major ? H / heads : 0, qk_head_major ? S * (H / heads) : 0, e.rel2};
         if (launch_attn(a, st)) return -10;
         static const bool noffn = dbg_env_int("AK_ENC_NOFFN", 0) != 0;
         const bool ffn_fused = !skinny && fuse && r16 && ly.wf && !noffn && ffn_fused_supported(H, I, tpad);

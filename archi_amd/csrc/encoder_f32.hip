@@ -164,13 +164,25 @@ __global__ __launch_bounds__(256, 2) void k32m_gemm(const float *__restrict__ X,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Relative-position bias of the two parity-mode attention kernels (rel != NULL: the library's per-distance table, encoder_kernels.h
+// REL_ROW layout): the band of head h for the workgroup's 128 queries [128 qb, 128 qb + 128) and all S keys -- distances
+// -128 qb - 128 + i, i < S + 128 -- is copied to LDS before the kernel's first barrier. Returns this lane's diagonal (query
+// 128 qb + 32 wave + li): key s at [s]. NULL when there is no bias.
+__device__ __forceinline__ const float *attn_bias_band(const float *rel, float *band, int h, int qb, int S, int wave, int li, int tid) {
+    if (!rel) return nullptr;
+    const float *rg = rel + (int64_t)h * REL_ROW + REL_MID - qb * 128 - 128;
+    for (int i = tid; i < S + 128; i += 256) band[i] = rg[i];
+    return band + (128 - wave * 32 - li);
+}
+
 // attention: one workgroup = 4 waves = 128 queries of one (sequence, head); qkv [T][3H] (q | k | v) float32
 template <int HD>
 __global__ __launch_bounds__(256, 2) void k32m_attn(const float *__restrict__ qkv, const int *__restrict__ mask, int B, int S, int H, int heads,
-                                                    float *__restrict__ ctx) {
+                                                    float *__restrict__ ctx, const float *__restrict__ rel) {
     constexpr int LD = HD + 1, DB = HD / 32, KB = 32;                       // key block
     __shared__ float sK[2][KB][LD], sV[2][KB][LD];
     __shared__ float sMask[2][KB];
+    __shared__ float sBias[512 + 128];                                      // relative-position bias band (rel != NULL; attn_bias_band)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lk = lane >> 5;
     const int nqb = (S + 127) / 128;
@@ -184,6 +196,7 @@ __global__ __launch_bounds__(256, 2) void k32m_attn(const float *__restrict__ qk
     const int q0 = qb * 128 + wave * 32;
     const float scale = 1.0f / sqrtf((float)HD);
     const int64_t row0 = (int64_t)b * S;
+    const float *bB = attn_bias_band(rel, sBias, h, qb, S, wave, li, tid);
     // this lane's query operand: Q[q0 + li][2 kk + lk], kk = 0 .. HD / 2 - 1 (B operand of the score MFMAs)
     float qreg[HD / 2];
     {
@@ -245,6 +258,7 @@ __global__ __launch_bounds__(256, 2) void k32m_attn(const float *__restrict__ qk
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             sc[r] = sc[r] * scale + sMask[slot][(r & 3) + 8 * (r >> 2) + 4 * lk];
+            if (rel) sc[r] += bB[blk * KB + (r & 3) + 8 * (r >> 2) + 4 * lk];
             mx = fmaxf(mx, sc[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -479,12 +493,13 @@ int launch_gemm_x3(int epi, const float *X, const uint16_t *Whi, const uint16_t 
 // the 16 lanes of a ds_read_b128 group cover all 64 banks.
 template <int HD>
 __global__ __launch_bounds__(256, 2) void k3_attn(const float *__restrict__ qkv, const int *__restrict__ mask, int B, int S, int H, int heads,
-                                                  float *__restrict__ ctx, uint16_t *__restrict__ ctx2, int ldq) {
+                                                  float *__restrict__ ctx, uint16_t *__restrict__ ctx2, int ldq, const float *__restrict__ rel) {
     constexpr int KB = 32, DB = HD / 32, KC = HD / 16;                       // key block; 32-feature tiles; 16-wide chunks of the head dimension
     constexpr int KROW = HD * 2 + 16, VROW = KB * 2 + 16;                   // padded LDS rows (bytes): K [key][HD], V^T [feature][KB]
     constexpr int K_BYTES = KB * KROW, V_BYTES = HD * VROW, SLOT = 2 * K_BYTES + 2 * V_BYTES + KB * 4;
     constexpr int LD = HD + 1;
     __shared__ __attribute__((aligned(16))) char ring[2 * SLOT];
+    __shared__ float sBias[512 + 128];                                      // relative-position bias band, base 2 (rel != NULL; attn_bias_band)
     static_assert(2 * SLOT >= 4 * 32 * LD * 4, "the ring also carries the context rows out");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lk = lane >> 5;
@@ -502,6 +517,7 @@ __global__ __launch_bounds__(256, 2) void k3_attn(const float *__restrict__ qkv,
     // time is its VALU stream (r6z trace: 219 / 585 us per layer with expf, 12 MFMAs against ~420 vector instructions per key block)
     const float scale = 1.4426950408889634f / sqrtf((float)HD);
     const int64_t row0 = (int64_t)b * S;
+    const float *bB = attn_bias_band(rel, sBias, h, qb, S, wave, li, tid);
     auto split8 = [](const float (&x)[8], uint4 &hi, uint4 &lo) {
         uint32_t hw[4], lw[4];
 #pragma unroll
@@ -590,6 +606,10 @@ __global__ __launch_bounds__(256, 2) void k3_attn(const float *__restrict__ qkv,
         f32x16 sc;
 #pragma unroll
         for (int r = 0; r < 16; r++) sc[r] = sm[(r & 3) + 8 * (r >> 2) + 4 * lk];
+        if (rel) {                                                          // + the bias: still the accumulator's starting value
+#pragma unroll
+            for (int r = 0; r < 16; r++) sc[r] += bB[blk * KB + (r & 3) + 8 * (r >> 2) + 4 * lk];
+        }
 #pragma unroll
         for (int c = 0; c < KC; c++) {
             const uint4 kh = *(const uint4 *)(sk + li * KROW + c * 32 + lk * 16), kl = *(const uint4 *)(sk + K_BYTES + li * KROW + c * 32 + lk * 16);
@@ -832,33 +852,34 @@ int launch_gemm_f32(int epi, const float *X, const float *W, const float *bias, 
     return 0;
 }
 
-int launch_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st) {
+int launch_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel) {
     const int hd = H / heads;
     const int nqb = (S + 127) / 128;
     const unsigned grid = attn_grid(B, heads, nqb);
-    if (hd == 64) k3_attn<64><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx, nullptr, 3 * H);
-    else if (hd == 32) k3_attn<32><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx, nullptr, 3 * H);
+    if (hd == 64) k3_attn<64><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx, nullptr, 3 * H, rel);
+    else if (hd == 32) k3_attn<32><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx, nullptr, 3 * H, rel);
     else AK_FAIL(-1, "launch_attn_x3: head size must be 32 or 64");
     AK_HIP(hipGetLastError());
     return 0;
 }
-int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, hipStream_t st) {
+int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, hipStream_t st,
+                         const float *rel) {
     const int hd = H / heads;
     const int nqb = (S + 127) / 128;
     const unsigned grid = attn_grid(B, heads, nqb);
-    if (hd == 64) k3_attn<64><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, nullptr, ctx2, ldq);
-    else if (hd == 32) k3_attn<32><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, nullptr, ctx2, ldq);
+    if (hd == 64) k3_attn<64><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, nullptr, ctx2, ldq, rel);
+    else if (hd == 32) k3_attn<32><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, nullptr, ctx2, ldq, rel);
     else AK_FAIL(-1, "launch_attn_x3_split: head size must be 32 or 64");
     AK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st) {
+int launch_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel) {
     const int hd = H / heads;
     const int nqb = (S + 127) / 128;
     const unsigned grid = attn_grid(B, heads, nqb);
-    if (hd == 64) k32m_attn<64><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx);
-    else if (hd == 32) k32m_attn<32><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx);
+    if (hd == 64) k32m_attn<64><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx, rel);
+    else if (hd == 32) k32m_attn<32><<<grid, 256, 0, st>>>(qkv, mask, B, S, H, heads, ctx, rel);
     else AK_FAIL(-1, "launch_attn_f32: head size must be 32 or 64");
     AK_HIP(hipGetLastError());
     return 0;

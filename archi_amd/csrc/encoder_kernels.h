@@ -39,7 +39,13 @@ struct AttnArgs {
     // layout of q and k inside a sequence's S * H elements: row (token) stride and head stride in elements.
     // 0 / 0 = token-major [S][H] (ld = H, hs = H / heads); head-major [heads][S][hd] (k_qkv384): ld = hd, hs = S * hd
     int qk_ld, qk_hs;
+    // additive relative-position bias (MPNet): rel[h * REL_ROW + REL_MID + (key - query)], base-2 domain (scaled by log2(e) like q);
+    // zero outside |key - query| < n_rel. NULL: no bias (the kernels run the code they ran before it existed)
+    const float *rel = nullptr;
 };
+// layout of the library's per-distance bias tables (ak_encoder_set_rel_bias): one row of REL_ROW floats per head, distance d at
+// REL_MID + d. Any (key, query) pair of a 32-query block of a wave / workgroup, S <= 512, lands inside the row.
+constexpr int REL_ROW = 2048, REL_MID = 1024;
 struct GemmLnArgs {
     const uint16_t *X; const uint16_t *W; const float *bias; const float *gamma; const float *beta;
     float *x32; uint16_t *x16;     // residual in / LayerNorm out (fp32, in place) and its bf16 copy; x32 == NULL: the
@@ -101,11 +107,12 @@ int launch_gemm_ln_x3(const GemmLnArgs &a, hipStream_t st);   // split-bf16 oper
 bool f32_mfma_supported(int H, int I, int heads);
 int launch_gemm_f32(int epi, const float *X, const float *W, const float *bias, const float *R, int T, int N, int K, float *Y, int ldc,
                     int col0, hipStream_t st);
-int launch_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st);
+// rel (launch_attn_f32: natural domain; launch_attn_x3 / _split: base 2): the per-distance bias table (AttnArgs::rel), or NULL
+int launch_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel = nullptr);
 // split-bf16 parity mode (precision 2): W as bf16 hi + lo (split_hilo, once), X float32 split on its way into LDS; three bf16
 // MFMAs per product into one float32 accumulator (encoder_f32.hip k3_gemm); epilogues as launch_gemm_f32
 int split_hilo(const float *w, int64_t n, uint16_t *hi, uint16_t *lo, hipStream_t st);
-int launch_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st);   // k3_attn: both products as three bf16 MFMAs
+int launch_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel = nullptr);   // k3_attn: both products as three bf16 MFMAs
 int launch_gemm_x3(int epi, const float *X, const uint16_t *Whi, const uint16_t *Wlo, const float *bias, const float *R, int T, int N, int K,
                    float *Y, int ldc, int col0, hipStream_t st);
 // ... and on gemm.hip's LDS-DMA tiles for batches of whole 256-token tiles (MODE 5 / 6 there): the activations travel as bf16
@@ -119,7 +126,8 @@ int launch_add_ln_split(const float *y, int ldy, const float *r, int64_t T, int 
 int launch_embed_split(const int *ids, int64_t T, int S, int H, int vocab, const float *word, const float *pos, const float *type, const float *g,
                        const float *b, float eps, float *out, uint16_t *out2, hipStream_t st);       // embeddings + LayerNorm: float32 rows and [hi | lo] rows
 // k3_attn over qkv rows of ldq floats (q | k | v in the first 3 H), context as [hi | lo] rows
-int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, hipStream_t st);
+int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, hipStream_t st,
+                         const float *rel = nullptr);
 // the whole forward pass of <= 64 token rows in ONE launch confined to one XCD (query_forward.hip)
 struct QfCtlSlot { unsigned long long arrived_tickets; unsigned int target; unsigned int count; unsigned int pad[4]; };   // 32 bytes
 struct QfCtl { QfCtlSlot slot[64]; };                     // one slot per launch, by launch number mod 64; zeroed 32 launches ahead

@@ -77,19 +77,21 @@ struct WordPiece {
     bool lowercase = true;
     uint8_t cls_of[128];         // per ASCII byte: 0 keep, 1 whitespace, 2 punctuation, 3 removed
     uint64_t pw[MAX_WORD + 1];   // HASH_P powers for substring hashes
+    std::vector<std::string> specials;   // the model's special tokens as they may appear in raw text
+    bool special_first[256] = {};        // bytes a special token starts with
 };
 
 const char *const SPECIALS[] = {"[CLS]", "[SEP]", "[UNK]", "[PAD]", "[MASK]"};
 
 // true when the text must go through the full tokenizer
-bool needs_full_tokenizer(const char *s, int64_t n) {
+bool needs_full_tokenizer(const WordPiece &wp, const char *s, int64_t n) {
     for (int64_t i = 0; i < n; i++) {
         const uint8_t c = (uint8_t)s[i];
         if (c >= 0x80) return true;
-        if (c == '[' && n - i >= 5)
-            for (const char *sp : SPECIALS) {
-                const size_t l = strlen(sp);
-                if ((size_t)(n - i) >= l && memcmp(s + i, sp, l) == 0) return true;
+        if (wp.special_first[c])
+            for (const std::string &sp : wp.specials) {
+                const size_t l = sp.size();
+                if ((size_t)(n - i) >= l && memcmp(s + i, sp.data(), l) == 0) return true;
             }
     }
     return false;
@@ -156,14 +158,15 @@ int encode_one(const WordPiece &wp, const char *s, int64_t n, int max_len, int32
     return cnt;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ak_wordpiece_create(const char *vocab_path, int lowercase, ak_wordpiece_t *out) {
-    if (!vocab_path || !out) { ak::set_error("ak_wordpiece_create: null argument"); return -1; }
+// the vocabulary, the three tokens the encoder emits by name and the special tokens that send a text to the full tokenizer
+int create(const char *who, const char *vocab_path, int lowercase, const char *cls, const char *sep, const char *unk,
+           const char *const *specials, int n_specials, ak_wordpiece_t *out) {
+    const std::string w(who);
+    if (!vocab_path || !out || !cls || !sep || !unk || n_specials < 0 || (n_specials > 0 && !specials)) { ak::set_error(w + ": null argument"); return -1; }
+    for (int i = 0; i < n_specials; i++)
+        if (!specials[i] || !specials[i][0]) { ak::set_error(w + ": empty special token"); return -1; }
     std::ifstream f(vocab_path, std::ios::binary);
-    if (!f) { ak::set_error(std::string("ak_wordpiece_create: cannot open ") + vocab_path); return -2; }
+    if (!f) { ak::set_error(w + ": cannot open " + vocab_path); return -2; }
     std::unordered_map<std::string, int32_t> first, cont;
     auto *wp = new WordPiece();
     std::string line;
@@ -171,9 +174,9 @@ int ak_wordpiece_create(const char *vocab_path, int lowercase, ak_wordpiece_t *o
     while (std::getline(f, line)) {
         while (!line.empty() && (line.back() == '\r' || line.back() == '\n' || line.back() == ' ' || line.back() == '\t'))
             line.pop_back();
-        if (line == "[CLS]") wp->cls = idx;
-        else if (line == "[SEP]") wp->sep = idx;
-        else if (line == "[UNK]") wp->unk = idx;
+        if (line == cls) wp->cls = idx;
+        else if (line == sep) wp->sep = idx;
+        else if (line == unk) wp->unk = idx;
         bool ascii = true;
         for (char ch : line) ascii &= (uint8_t)ch < 0x80;
         if (ascii && !line.empty() && line.size() <= (size_t)MAX_WORD) {     // later duplicates win, like the reference's map
@@ -184,8 +187,12 @@ int ak_wordpiece_create(const char *vocab_path, int lowercase, ak_wordpiece_t *o
     }
     if (wp->cls < 0 || wp->sep < 0 || wp->unk < 0) {
         delete wp;
-        ak::set_error("ak_wordpiece_create: vocabulary lacks [CLS], [SEP] or [UNK]");
+        ak::set_error(w + ": vocabulary lacks " + cls + ", " + sep + " or " + unk);
         return -3;
+    }
+    for (int i = 0; i < n_specials; i++) {
+        wp->specials.emplace_back(specials[i]);
+        wp->special_first[(uint8_t)specials[i][0]] = true;
     }
     wp->first.build(first);
     wp->cont.build(cont);
@@ -201,6 +208,19 @@ int ak_wordpiece_create(const char *vocab_path, int lowercase, ak_wordpiece_t *o
     for (int i = 1; i <= MAX_WORD; i++) wp->pw[i] = wp->pw[i - 1] * HASH_P;
     *out = wp;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ak_wordpiece_create(const char *vocab_path, int lowercase, ak_wordpiece_t *out) {
+    return create("ak_wordpiece_create", vocab_path, lowercase, "[CLS]", "[SEP]", "[UNK]", SPECIALS, 5, out);
+}
+
+int ak_wordpiece_create_ex(const char *vocab_path, int lowercase, const char *cls, const char *sep, const char *unk,
+                           const char *const *specials, int n_specials, ak_wordpiece_t *out) {
+    return create("ak_wordpiece_create_ex", vocab_path, lowercase, cls, sep, unk, specials, n_specials, out);
 }
 
 int ak_wordpiece_destroy(ak_wordpiece_t h) {
@@ -231,7 +251,7 @@ int ak_wordpiece_encode(ak_wordpiece_t h, const char *blob, const int64_t *offse
                 const char *s = blob + offsets[i];
                 const int64_t len = offsets[i + 1] - offsets[i];
                 int32_t *row = out_ids + i * (int64_t)max_len;
-                if (len < 0 || needs_full_tokenizer(s, len)) {
+                if (len < 0 || needs_full_tokenizer(wp, s, len)) {
                     for (int j = 0; j < max_len; j++) row[j] = 0;
                     out_len[i] = -1;
                 } else {

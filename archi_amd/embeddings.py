@@ -29,11 +29,14 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .encoder import (MODEL_SHAPES, HipEncoder, load_hf_weights, random_init_weights,
-                      read_sentence_transformers_config)
+from .encoder import (MODEL_SHAPES, MPNET_SHAPES, HipEncoder, load_hf_weights, load_mpnet_weights, mpnet_rel_bias_table,
+                      random_init_weights, random_mpnet_weights, read_sentence_transformers_config)
 from .decoder import MAX_SEQ, QWEN3_SHAPES, BpeTokenizer, HipDecoder, load_qwen3_weights, random_qwen3_weights, read_decoder_st_config
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
+# special tokens by name: (cls, sep, unk, the strings the full tokenizer matches in raw text)
+BERT_SPECIALS = ("[CLS]", "[SEP]", "[UNK]", ("[CLS]", "[SEP]", "[UNK]", "[PAD]", "[MASK]"))
+MPNET_SPECIALS = ("<s>", "</s>", "[UNK]", ("<s>", "</s>", "<pad>", "<mask>", "[UNK]"))      # transformers' MPNetTokenizer(Fast)
 
 
 def _do_lower_case(model_dir: str) -> bool:
@@ -67,13 +70,23 @@ class HashWordPiece:
 
 
 class VocabWordPiece:
-    """BERT WordPiece through the `tokenizers` wheel, from a local vocab.txt."""
+    """BERT WordPiece through the `tokenizers` wheel, from a local vocab.txt. specials: BERT_SPECIALS, or MPNET_SPECIALS for
+    MPNet's <s> $A </s> post-processing with its own special tokens (as transformers' MPNetTokenizerFast builds it)."""
 
-    def __init__(self, vocab_file: str, lowercase: bool = True):
+    def __init__(self, vocab_file: str, lowercase: bool = True, specials=BERT_SPECIALS):
         from tokenizers import BertWordPieceTokenizer
-        self._tok = BertWordPieceTokenizer(vocab_file, lowercase=lowercase)
-        sep = self._tok.token_to_id("[SEP]")
-        self._sep = SEP if sep is None else sep
+        cls, sep, unk, added = specials
+        if specials == BERT_SPECIALS:
+            self._tok = BertWordPieceTokenizer(vocab_file, lowercase=lowercase)
+        else:
+            from tokenizers.processors import TemplateProcessing
+            self._tok = BertWordPieceTokenizer(vocab_file, lowercase=lowercase, unk_token=unk, sep_token=sep, cls_token=cls,
+                                               pad_token=added[2], mask_token=added[3])
+            self._tok.add_special_tokens(list(added))
+            ci, si = self._tok.token_to_id(cls), self._tok.token_to_id(sep)
+            self._tok.post_processor = TemplateProcessing(single=f"{cls} $A {sep}", special_tokens=[(cls, ci), (sep, si)])
+        sep_id = self._tok.token_to_id(sep)
+        self._sep = SEP if sep_id is None else sep_id
 
     def encode(self, text: str, max_len: int) -> List[int]:
         ids = self._tok.encode(text).ids
@@ -97,13 +110,19 @@ class NativeWordPiece:
     special token come back flagged and go through the `tokenizers` wheel (VocabWordPiece), so the ids are always the
     reference tokenizer's."""
 
-    def __init__(self, vocab_file: str, lowercase: bool = True, threads: int = 0):
+    def __init__(self, vocab_file: str, lowercase: bool = True, threads: int = 0, specials=BERT_SPECIALS):
         self._lib = _lib.load()
         h = ctypes.c_void_p()
-        check(self._lib.ak_wordpiece_create(vocab_file.encode(), int(lowercase), ctypes.byref(h)), "ak_wordpiece_create")
+        if specials == BERT_SPECIALS:
+            check(self._lib.ak_wordpiece_create(vocab_file.encode(), int(lowercase), ctypes.byref(h)), "ak_wordpiece_create")
+        else:                                # the model's own special tokens (MPNet): emitted and matched by name
+            cls, sep, unk, added = specials
+            arr = (ctypes.c_char_p * len(added))(*[a.encode() for a in added])
+            check(self._lib.ak_wordpiece_create_ex(vocab_file.encode(), int(lowercase), cls.encode(), sep.encode(), unk.encode(),
+                                                   arr, len(added), ctypes.byref(h)), "ak_wordpiece_create_ex")
         self._h = h
         self._threads = int(os.environ.get("ARCHI_TOKENIZER_THREADS", threads))
-        self._vocab_file, self._lowercase, self._full = vocab_file, lowercase, None
+        self._vocab_file, self._lowercase, self._full, self._specials = vocab_file, lowercase, None, specials
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -118,7 +137,7 @@ class NativeWordPiece:
 
     def _fallback(self) -> "VocabWordPiece":
         if self._full is None:
-            self._full = VocabWordPiece(self._vocab_file, lowercase=self._lowercase)
+            self._full = VocabWordPiece(self._vocab_file, lowercase=self._lowercase, specials=self._specials)
         return self._full
 
     def encode_batch_array(self, texts: List[str], max_len: int):
@@ -156,6 +175,15 @@ def _is_qwen3(model_name: str) -> bool:
     return model_name in QWEN3_SHAPES
 
 
+def _is_mpnet(model_name: str) -> bool:
+    """An MPNet checkpoint directory (config.json model_type "mpnet") or one of the named MPNet shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "mpnet"
+    return model_name in MPNET_SHAPES
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -180,7 +208,10 @@ class ArchiHipEmbeddings:
         if _is_qwen3(model_name):
             self._init_decoder(model_name, device)
             return
-        if os.path.isdir(model_name):
+        rel_bias = None
+        if _is_mpnet(model_name):
+            vocab, H, L, heads, I, max_pos, weights, eps, rel_bias = self._init_mpnet(model_name)
+        elif os.path.isdir(model_name):
             shape, weights, eps = load_hf_weights(model_name)
             vocab, H, L, heads, I, max_pos = shape
             st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
@@ -208,7 +239,38 @@ class ArchiHipEmbeddings:
         self.dimensions = H
         self.encoder = HipEncoder(vocab, H, L, heads, I, max_pos, weights, ln_eps=eps, device=device,
                                   residual=str(self.model_kwargs.get("residual", "bf16")),
-                                  precision=str(self.model_kwargs.get("precision", "bf16")))
+                                  precision=str(self.model_kwargs.get("precision", "bf16")), rel_bias=rel_bias)
+
+    def _init_mpnet(self, model_name: str):
+        """MPNet (all-mpnet-base-v2 and its family): a local checkpoint directory (config.json model_type mpnet, safetensors,
+        vocab.txt, the sentence-transformers files) or a named shape with synthetic_seed. The BERT encoder with MPNet's
+        relative-position bias, its offset positions and its <s> ... </s> tokenizer; every precision."""
+        if os.path.isdir(model_name):
+            shape, weights, rel_w, eps = load_mpnet_weights(model_name)
+            vocab, H, L, heads, I, max_pos = shape
+            st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
+            self.pooling = self.model_kwargs.get("pooling", st_pool)
+            self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, 512)
+            self.normalize = self.normalize or st_norm
+            vf = os.path.join(model_name, "vocab.txt")
+            if not os.path.exists(vf):
+                raise FileNotFoundError(f"{model_name}: vocab.txt not found -- an MPNet checkpoint directory needs its WordPiece "
+                                        "vocabulary (the hashing stand-in tokenizer is only used with synthetic_seed)")
+            self.tokenizer = NativeWordPiece(vf, lowercase=_do_lower_case(model_name), specials=MPNET_SPECIALS)
+        elif "synthetic_seed" in self.model_kwargs:
+            shape = MPNET_SHAPES[model_name]
+            vocab, H, L, heads, I = shape[:5]
+            max_pos = min(shape[5] - 2, 512)
+            self.pooling, self.max_seq_length = shape[6], min(shape[7], max_pos)
+            weights, rel_w, _ = random_mpnet_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]))
+            eps = 1e-5
+            self.normalize = True                      # the released sentence-transformers models carry a Normalize module
+            vf = self.model_kwargs.get("vocab_file")
+            self.tokenizer = NativeWordPiece(vf, specials=MPNET_SPECIALS) if vf else HashWordPiece(vocab)
+        else:
+            raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass an MPNet checkpoint "
+                                    "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
+        return vocab, H, L, heads, I, max_pos, weights, eps, mpnet_rel_bias_table(rel_w, max_pos)
 
     def _init_decoder(self, model_name: str, device: Optional[int]) -> None:
         """Qwen3-Embedding: a local checkpoint directory (config.json model_type qwen3, safetensors, tokenizer.json, the

@@ -22,6 +22,22 @@ MODEL_SHAPES = {
     "BAAI/bge-base-en-v1.5": (30522, 768, 12, 12, 3072, 512, "cls", 512),
 }
 
+# MPNet (sentence-transformers/all-mpnet-base-v2 and its family): name -> (vocab, hidden, layers, heads, intermediate,
+# max_position_embeddings, pooling, max_seq_length) as in their config.json / sentence-transformers files. Not in MODEL_SHAPES:
+# other code indexes that table as BERT.
+MPNET_SHAPES = {
+    "sentence-transformers/all-mpnet-base-v2": (30527, 768, 12, 12, 3072, 514, "mean", 384),
+    "all-mpnet-base-v2": (30527, 768, 12, 12, 3072, 514, "mean", 384),
+    "sentence-transformers/multi-qa-mpnet-base-dot-v1": (30527, 768, 12, 12, 3072, 514, "cls", 512),
+    "sentence-transformers/paraphrase-mpnet-base-v2": (30527, 768, 12, 12, 3072, 514, "mean", 512),
+    # small shapes of the test fixtures (tests/golden/make_mpnet_fixtures.py): head size 64 (a 2-layer cut of the 768 shape) and 32
+    "mpnet-cut2": (30527, 768, 2, 12, 3072, 514, "mean", 512),
+    "mpnet-tiny-hd32": (1000, 256, 2, 8, 512, 514, "mean", 512),
+}
+MPNET_PADDING_IDX = 1           # MPNetEmbeddings.padding_idx: token p of a row sits at position padding_idx + 1 + p
+MPNET_NUM_BUCKETS = 32          # MPNetEncoder.compute_position_bias buckets with its default, whatever the config holds
+MPNET_MAX_DISTANCE = 128
+
 LAYER_KEYS = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b", "w1", "b1", "w2", "b2", "ln2_g", "ln2_b")
 MATRIX_KEYS = {"wq", "wk", "wv", "wo", "w1", "w2"}
 
@@ -39,7 +55,7 @@ PRECISIONS = {"bf16": 0, "f32": 1, "bf16x3": 2}        # AkBertConfig.precision
 class HipEncoder:
     def __init__(self, vocab: int, hidden: int, layers: int, heads: int, intermediate: int, max_position: int,
                  weights: Dict[str, np.ndarray], ln_eps: float = 1e-12, device: Optional[int] = None,
-                 residual: str = "bf16", precision: str = "bf16"):
+                 residual: str = "bf16", precision: str = "bf16", rel_bias=None):
         """residual: "bf16" keeps the residual stream between layers in bf16 only (hidden size 384: 60% less epilogue
         traffic; adds ~1e-6 of cosine deviation from the fp32 reference to the ~2e-6 the bf16 GEMM inputs already
         cost); "f32" keeps it in fp32 like the reference's CPU path. ARCHI_ENCODER_RESIDUAL overrides.
@@ -47,7 +63,10 @@ class HipEncoder:
         v_mfma_f32_32x32x2_f32 (~1e-6 from the reference's torch-fp32 CPU embedder, ~1/9 of the bf16 rate); "bf16x3" = split-bf16
         parity mode: float32 weights, every GEMM operand split x = hi + lo into two bf16 values and every product run as
         hi.hi + lo.hi + hi.lo on the bf16 matrix cores with one float32 accumulator, everything between the GEMMs in float32
-        (~1e-6 per component from float64, scores within 1e-5 of the CPU path, ~3x the "f32" mode's rate)."""
+        (~1e-6 per component from float64, scores within 1e-5 of the CPU path, ~3x the "f32" mode's rate).
+        rel_bias: an additive relative-position bias [heads][2 n_rel - 1] (distance key - query at column d + n_rel - 1, natural-log
+        domain; MPNet: mpnet_rel_bias_table) added to every attention score (ak_encoder_set_rel_bias); sequences are then limited
+        to n_rel tokens. None: no bias."""
         import os
         import torch
         residual = os.environ.get("ARCHI_ENCODER_RESIDUAL", residual)
@@ -71,7 +90,8 @@ class HipEncoder:
             t = t.to(device=dev, dtype=torch.bfloat16 if (is_matrix and precision == "bf16") else torch.float32).contiguous()
             self._tensors.append(t)
             ptrs.append(t.data_ptr())
-        cfg = AkBertConfig(vocab, hidden, layers, heads, intermediate, max_position, 2, ln_eps, int(residual == "bf16"),
+        type_vocab = int(weights["type_emb"].shape[0]) if weights["type_emb"].ndim == 2 else 2     # MPNet: one zero row
+        cfg = AkBertConfig(vocab, hidden, layers, heads, intermediate, max_position, type_vocab, ln_eps, int(residual == "bf16"),
                            PRECISIONS[precision])
         arr_t = ctypes.c_void_p * len(ptrs)
         h = ctypes.c_void_p()
@@ -80,6 +100,17 @@ class HipEncoder:
               "ak_encoder_create")
         self._h = h
         self._dev = dev
+        if rel_bias is not None:
+            # [heads][2 n_rel - 1] float32 per-distance table (mpnet_rel_bias_table): the library copies it
+            rb = rel_bias if isinstance(rel_bias, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rel_bias))
+            rb = rb.to(device=dev, dtype=torch.float32).contiguous()
+            if rb.dim() != 2 or rb.shape[0] != heads or rb.shape[1] % 2 == 0:
+                self.close()
+                raise ValueError("rel_bias must be [heads][2 n_rel - 1]")
+            torch.cuda.synchronize(dev)
+            check(self._lib.ak_encoder_set_rel_bias(self._h, ctypes.c_void_p(rb.data_ptr()), heads, (rb.shape[1] + 1) // 2),
+                  "ak_encoder_set_rel_bias")
+        self.rel_bias = rel_bias is not None
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -232,3 +263,132 @@ def read_sentence_transformers_config(model_dir: str):
     if os.path.exists(sj):
         max_len = json.load(open(sj)).get("max_seq_length")
     return pooling, max_len, norm
+
+
+def mpnet_relative_position_bucket(relative_position, num_buckets: int = MPNET_NUM_BUCKETS, max_distance: int = MPNET_MAX_DISTANCE):
+    """MPNetEncoder.relative_position_bucket restated with the same torch ops (T5-style, bidirectional; the float32 log decides
+    the large buckets, so the ops are kept as they are)."""
+    import math
+    import torch
+    ret = 0
+    n = -relative_position
+    num_buckets //= 2
+    ret += (n < 0).to(torch.long) * num_buckets
+    n = torch.abs(n)
+    max_exact = num_buckets // 2
+    is_small = n < max_exact
+    val_if_large = max_exact + (
+        torch.log(n.float() / max_exact) / math.log(max_distance / max_exact) * (num_buckets - max_exact)).to(torch.long)
+    val_if_large = torch.min(val_if_large, torch.full_like(val_if_large, num_buckets - 1))
+    ret += torch.where(is_small, n, val_if_large)
+    return ret
+
+
+def mpnet_rel_bias_table(weight, n_rel: int) -> "np.ndarray":
+    """encoder.relative_attention_bias.weight [buckets][heads] -> the per-distance table [heads][2 n_rel - 1] float32 that
+    ak_encoder_set_rel_bias takes: column d + n_rel - 1 holds the bias HF adds for key - query = d."""
+    import torch
+    w = weight if isinstance(weight, torch.Tensor) else torch.from_numpy(np.asarray(weight))
+    d = torch.arange(-(n_rel - 1), n_rel, dtype=torch.long)
+    bucket = mpnet_relative_position_bucket(d)
+    return w.float()[bucket].t().contiguous().numpy()
+
+
+def random_mpnet_weights(shape, seed: int = 0):
+    """Seeded random weights of an MPNet shape (an MPNET_SHAPES name or tuple) -> (encoder weight dict in the header's order with
+    MPNet's positions already offset, relative_attention_bias [32][heads], the raw position table [max_position_embeddings][H]).
+    Matrices are ROUNDED TO bf16 (kept as float32): a float32 reference on the same values then measures the kernels' activation
+    rounding alone. The relative-bias weights are drawn with std 1, not HF's 0.02, and the attention projections with std 0.06
+    (three times the rest): the bias must visibly move the output, or a kernel that dropped it would pass -- with every matrix at
+    0.02 the attention sub-layer is a small share of the residual stream and the bias moves the embeddings by ~1.5x the bf16 bar."""
+    import torch
+    if isinstance(shape, str):
+        shape = MPNET_SHAPES[shape]
+    vocab, H, L, heads, I, max_pos = shape[:6]
+    w = random_init_weights(vocab, H, L, I, max_pos, seed=seed)
+    g = torch.Generator().manual_seed(seed + 7919)
+    for k, v in list(w.items()):
+        if k.split(".")[-1] in ("wq", "wk", "wv", "wo"):
+            v = v * 3.0
+        if k in ("word_emb", "pos_emb") or k.split(".")[-1] in MATRIX_KEYS:
+            w[k] = torch.from_numpy(v).to(torch.bfloat16).float().numpy()
+    pos_full = w["pos_emb"]
+    rel = torch.randn(MPNET_NUM_BUCKETS, heads, generator=g).numpy().astype(np.float32)
+    return mpnet_encoder_weights(w, pos_full), rel, pos_full
+
+
+def mpnet_encoder_weights(w, pos_full):
+    """MPNet's embeddings as the BERT encoder takes them: positions offset by padding_idx + 1 rows, one zero token-type row."""
+    w = dict(w)
+    w["pos_emb"] = pos_full[MPNET_PADDING_IDX + 1:]
+    w["type_emb"] = np.zeros((1, pos_full.shape[1]), np.float32)
+    return w
+
+
+def mpnet_hf_state_dict(w, rel, pos_full, layers: int):
+    """Our weight names (mpnet_encoder_weights form) -> HF MPNetModel's state dict (no "mpnet." prefix)."""
+    import torch
+    t = lambda x: torch.as_tensor(np.asarray(x, np.float32))
+    sd = {"embeddings.word_embeddings.weight": t(w["word_emb"]), "embeddings.position_embeddings.weight": t(pos_full),
+          "embeddings.LayerNorm.weight": t(w["emb_ln_g"]), "embeddings.LayerNorm.bias": t(w["emb_ln_b"]),
+          "encoder.relative_attention_bias.weight": t(rel)}
+    for l in range(layers):
+        p, q = f"encoder.layer.{l}.", f"l{l}."
+        for hf, m in MPNET_LAYER_NAMES:
+            sd[p + hf] = t(w[q + m])
+    return sd
+
+
+# HF MPNetLayer names (under encoder.layer.{l}.) -> ours
+MPNET_LAYER_NAMES = (("attention.attn.q.weight", "wq"), ("attention.attn.q.bias", "bq"), ("attention.attn.k.weight", "wk"),
+                     ("attention.attn.k.bias", "bk"), ("attention.attn.v.weight", "wv"), ("attention.attn.v.bias", "bv"),
+                     ("attention.attn.o.weight", "wo"), ("attention.attn.o.bias", "bo"),
+                     ("attention.LayerNorm.weight", "ln1_g"), ("attention.LayerNorm.bias", "ln1_b"),
+                     ("intermediate.dense.weight", "w1"), ("intermediate.dense.bias", "b1"),
+                     ("output.dense.weight", "w2"), ("output.dense.bias", "b2"),
+                     ("output.LayerNorm.weight", "ln2_g"), ("output.LayerNorm.bias", "ln2_b"))
+
+
+def load_mpnet_weights(model_dir: str):
+    """Load a local HF MPNet checkpoint directory (config.json model_type "mpnet" + model.safetensors | pytorch_model.bin; an
+    "mpnet." prefix on the names is stripped). No network. Returns (shape, weights, rel_weight, eps): shape as load_hf_weights'
+    with max_position the positions a row may use (max_position_embeddings - padding_idx - 1), weights in the encoder's order with
+    the positions offset and one zero token-type row, rel_weight encoder.relative_attention_bias.weight [buckets][heads]. What the
+    HIP encoder does not implement is refused with ValueError."""
+    import json
+    import os
+    cfg = json.load(open(os.path.join(model_dir, "config.json")))
+    if cfg.get("model_type") != "mpnet":
+        raise ValueError(f"{model_dir}: model_type {cfg.get('model_type')!r} is not MPNet")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"{model_dir}: hidden_act {cfg.get('hidden_act')!r} (the HIP encoder implements erf GELU)")
+    H, heads = cfg["hidden_size"], cfg["num_attention_heads"]
+    if H % heads or H // heads not in (32, 64):
+        raise ValueError(f"{model_dir}: head size {H / heads:g} (the HIP encoder implements 32 and 64)")
+    if int(cfg.get("relative_attention_num_buckets", 32)) < MPNET_NUM_BUCKETS:
+        raise ValueError(f"{model_dir}: relative_attention_num_buckets {cfg.get('relative_attention_num_buckets')} < 32 "
+                         "(MPNet's position bias indexes 32 buckets)")
+    max_pos = int(cfg["max_position_embeddings"]) - MPNET_PADDING_IDX - 1
+    if max_pos < 32:
+        raise ValueError(f"{model_dir}: max_position_embeddings {cfg['max_position_embeddings']} leaves fewer than 32 positions")
+    st, pt = os.path.join(model_dir, "model.safetensors"), os.path.join(model_dir, "pytorch_model.bin")
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+        sd = load_file(st)
+    elif os.path.exists(pt):
+        import torch
+        sd = torch.load(pt, map_location="cpu", weights_only=True)
+    else:
+        raise FileNotFoundError(f"{model_dir}: neither model.safetensors nor pytorch_model.bin")
+    sd = {(k[6:] if k.startswith("mpnet.") else k): v.float() for k, v in sd.items()}
+    L = cfg["num_hidden_layers"]
+    pos_full = sd["embeddings.position_embeddings.weight"].numpy()
+    w = {"word_emb": sd["embeddings.word_embeddings.weight"], "pos_emb": pos_full,
+         "emb_ln_g": sd["embeddings.LayerNorm.weight"], "emb_ln_b": sd["embeddings.LayerNorm.bias"]}
+    for l in range(L):
+        p, q = f"encoder.layer.{l}.", f"l{l}."
+        for hf, m in MPNET_LAYER_NAMES:
+            w[q + m] = sd[p + hf]
+    w = mpnet_encoder_weights(w, pos_full)
+    shape = (cfg["vocab_size"], H, L, heads, cfg["intermediate_size"], min(max_pos, 512))
+    return shape, w, sd["encoder.relative_attention_bias.weight"], float(cfg.get("layer_norm_eps", 1e-12))

@@ -322,6 +322,19 @@ int ak_encoder_forward(ak_encoder_t h, const int32_t *ids_dev, const int32_t *ma
 int ak_encoder_forward_lens(ak_encoder_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
                             int pooling, int normalise, float *out_dev, void *stream);
 
+/* Relative-position bias (MPNet: sentence-transformers/all-mpnet-base-v2 and its family, the default model of
+ * HuggingFaceEmbeddings behind manager.py:373): an additive per-head term bias[h][key - query] in every attention layer, added after
+ * the 1 / sqrt(head size) scaling and before the softmax, as HF MPNet adds compute_position_bias's output.
+ *   bias_dev  [heads][2 n_rel - 1] float32 on device, natural-log domain: entry [h][d + n_rel - 1] is the bias of distance
+ *             d = key - query, |d| < n_rel (one value per distance: any bucketing scheme is resolved by the caller)
+ *   heads     must equal cfg->heads; 1 <= n_rel <= 1023
+ * The library copies the table at the call (bias_dev may be freed afterwards). Call it once, before the first forward pass; a
+ * forward pass with S > n_rel then fails. Served in every precision; the single-launch query forward (AK_QUERY_FUSED) is not
+ * taken by such an encoder. The rest of MPNet needs no entry point of its own: its RoBERTa-style positions are pos_emb offset by
+ * padding_idx + 1 rows with max_position = max_position_embeddings - padding_idx - 1, and its missing token types one zero
+ * type_emb row with type_vocab = 1. */
+int ak_encoder_set_rel_bias(ak_encoder_t h, const float *bias_dev, int heads, int n_rel);
+
 /* The 8192-entry bf16 table the fused hidden-384 layer kernel and the wide FFN-up tile read their GELU from (csrc/gelu_table.h):
  * entry i = bf16(gelu(v)), v = the MIDPOINT of the IEEE half bit patterns [8 i, 8 i + 8) (sign, 5 exponent bits, 7 mantissa bits;
  * the lookup truncates, so the midpoint halves its error), exact erf GELU
@@ -373,6 +386,12 @@ int ak_decoder_rope_table(float theta, int head_dim, int n_pos, float *cos_out, 
  * vocab_path: the checkpoint's vocab.txt (one token per line, id = line number; needs [CLS] [SEP] [UNK]). */
 typedef void *ak_wordpiece_t;
 int ak_wordpiece_create(const char *vocab_path, int lowercase, ak_wordpiece_t *out);
+/* The same tokenizer with the model's own special tokens (MPNet: cls "<s>", sep "</s>", unk "[UNK]"): cls / sep / unk are
+ * emitted by name (each must be in the vocabulary), and a text that holds any of the n_specials strings `specials` literally
+ * gets length -1 from ak_wordpiece_encode (the full tokenizer matches them in the raw text). ak_wordpiece_create is this with
+ * "[CLS]", "[SEP]", "[UNK]" and the specials [CLS] [SEP] [UNK] [PAD] [MASK]. */
+int ak_wordpiece_create_ex(const char *vocab_path, int lowercase, const char *cls, const char *sep, const char *unk,
+                           const char *const *specials, int n_specials, ak_wordpiece_t *out);
 int ak_wordpiece_destroy(ak_wordpiece_t h);
 /* n texts as one UTF-8 blob, text i = blob[offsets[i] : offsets[i+1]]. out_ids: [n][max_len] int32, zero padded;
  * out_len[i] = ids of text i including [CLS] and [SEP], truncated to max_len (the last kept id is [SEP]), or -1 when
