@@ -119,6 +119,7 @@ SYMBOLS = [
     ("ak_encoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_encoder_gelu_table", _I, [_P]),
     ("ak_encoder_set_rel_bias", _I, [_P, _P, _I, _I]),
+    ("ak_encoder_set_positions_from_ids", _I, [_P, _I, _I]),
     ("ak_decoder_create", _I, [ctypes.POINTER(AkDecoderConfig), _P, _I, ctypes.POINTER(_P)]),
     ("ak_decoder_destroy", _I, [_P]),
     ("ak_decoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),

@@ -22,6 +22,10 @@ EMBEDDING_DIMENSIONS = {
     "all-mpnet-base-v2": 768,
     "sentence-transformers/multi-qa-mpnet-base-dot-v1": 768,
     "sentence-transformers/paraphrase-mpnet-base-v2": 768,
+    "BAAI/bge-m3": 1024,
+    "intfloat/multilingual-e5-large": 1024,
+    "intfloat/multilingual-e5-base": 768,
+    "sentence-transformers/paraphrase-multilingual-mpnet-base-v2": 768,
     "Qwen/Qwen3-Embedding-0.6B": 1024,
     "Qwen/Qwen3-Embedding-4B": 2560,
     "Qwen/Qwen3-Embedding-8B": 4096,

@@ -1236,6 +1236,7 @@ int launch_attn(const AttnArgs &a0, hipStream_t st) {
     const int hd = a.H / a.heads;
     if (a.qk_ld == 0) { a.qk_ld = a.H; a.qk_hs = hd; }        // token-major q / k
     if (hd != 32 && hd != 64) AK_FAIL(-1, "attention: head size must be 32 or 64");
+    if (a.S > 512 && a.rowlen) return launch_attn_long(a0, st);            // rows longer than 512 tokens (attn_long.hip)
     if (a.S % 32 || a.S > 512) AK_FAIL(-1, "attention: S must be a multiple of 32 and <= 512");
     size_t lds = (size_t)a.S * (hd * 2 + 16) + (size_t)hd * (a.S * 2 + 16) + (size_t)a.S * 4;
     const bool hasb = a.rel != nullptr;

@@ -1,0 +1,156 @@
+// attn_long.hip -- bidirectional flash attention of the BERT encoder for rows longer than 512 tokens (512 < S <= 8192, head size 64,
+// bf16; XLM-RoBERTa / bge-m3 encoders given ak_encoder_set_positions_from_ids(max_seq > 512)):
+//   ctx = softmax(q k^T / sqrt(64) + mask) v      per (sequence, head)
+// Tiles with S <= 512 never come here (attention.hip). q arrives pre-scaled by log2(e) / 8 from the QKV GEMM, so the softmax runs in
+// the base-2 domain on v_exp_f32; v arrives transposed ([B][H][S], keys of every 16-group in vt_pos order) as attention.hip takes it.
+//
+// Workgroup = (128-query block, head, sequence), four waves of 32 queries. The 32-key blocks of K and V^T stream through two LDS
+// buffers: block kb + 1 is loaded into registers while block kb is computed, then written to the other buffer (one barrier per
+// block). Per wave and key block:
+//   S^T = K Q^T    4 x v_mfma_f32_32x32x16_bf16: A = K (rows = keys, from LDS), B = Q^T (16 VGPRs held for the whole loop). Keys on
+//                  M: a lane owns ONE query and 16 of the 32 keys (the other 16 in lane ^ 32): row max and sum take one cross-lane step.
+//   + mask         the block's additive mask (0 / -inf from the int mask) staged beside K: pad keys of the last block, and any hole
+//                  of an explicit mask, are excluded.
+//   online softmax in base 2 (running max / sum; a block with no real key leaves them unchanged)
+//   O^T += V^T P^T 4 MFMAs: A = V^T rows (d) from LDS, B = P^T straight from the S^T accumulators.
+// Key blocks wholly past the row's length (rowlen, k_positions) are not loaded; query blocks wholly past it write zero context rows.
+// K tile [32 keys][64 d]: 128-byte rows, chunk c of key r at c ^ (r & 7); V^T tile [64 d][32 keys]: 64-byte rows, chunk c of row d at
+// c ^ ((d >> 1) & 3) (the XOR swizzles of attn_causal.hip: the lanes of a ds_read_b128 phase hit distinct bank groups).
+#include "encoder_kernels.h"
+#include "mfma_tile.h"
+
+namespace ak {
+using namespace mt;
+
+namespace {
+constexpr int AL_HD = 64, AL_QB = 128;
+constexpr int AL_K_BYTES = 32 * AL_HD * 2, AL_V_BYTES = AL_HD * 64;
+
+__global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
+    __shared__ __attribute__((aligned(16))) char sK[2][AL_K_BYTES];
+    __shared__ __attribute__((aligned(16))) char sV[2][AL_V_BYTES];
+    __shared__ float sM[2][32];
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int S = a.S, H = a.H;
+    const int len = min(max(a.rowlen[b], 0), S);
+    const int q_begin = blockIdx.x * AL_QB, q0 = q_begin + 32 * wave;
+    const int r = lane & 31, kh = lane >> 5;
+    const int64_t row0 = (int64_t)b * S;
+    const bool has_q = q0 < S;                                 // this wave's 32 rows exist (S % 32 == 0)
+    if (q_begin >= len) {                                      // wholly past the length (uniform): zero context rows
+        if (has_q) {
+            uint16_t *crow = a.ctx + (row0 + q0 + r) * H + h * AL_HD;
+            for (int c = kh; c < AL_HD / 8; c += 2) *(uint4 *)(crow + c * 8) = uint4{0, 0, 0, 0};
+        }
+        return;
+    }
+    const int kb_stop = (len + 31) / 32;
+    // staging assignment: thread tid moves K chunk (key tid / 8, chunk tid % 8) and V^T chunk (row d = tid / 4, chunk tid % 4)
+    const int k_key = tid >> 3, k_c = tid & 7, v_d = tid >> 2, v_c = tid & 3;
+    const uint16_t *kg = a.k + row0 * H + (int64_t)h * a.qk_hs + (int64_t)k_key * a.qk_ld + k_c * 8;
+    const uint16_t *vg = a.vt + ((int64_t)b * H + h * AL_HD + v_d) * S + v_c * 8;
+    const int k_dst = k_key * 128 + ((k_c ^ (k_key & 7)) << 4), v_dst = v_d * 64 + ((v_c ^ ((v_d >> 1) & 3)) << 4);
+    uint4 kreg = *(const uint4 *)kg, vreg = *(const uint4 *)vg;
+    float mreg = tid < 32 ? (a.mask[row0 + tid] ? 0.f : -INFINITY) : 0.f;
+    *(uint4 *)(sK[0] + k_dst) = kreg;
+    *(uint4 *)(sV[0] + v_dst) = vreg;
+    if (tid < 32) sM[0][tid] = mreg;
+
+    uint4 qf[4];
+    {
+        const int qrow = has_q ? q0 + r : S - 1;
+        const uint16_t *qp = a.q + row0 * H + (int64_t)h * a.qk_hs + (int64_t)qrow * a.qk_ld + kh * 8;
+#pragma unroll
+        for (int c = 0; c < 4; c++) qf[c] = *(const uint4 *)(qp + c * 16);
+    }
+    f32x16 o[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) o[i] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+    __syncthreads();
+    for (int kb = 0; kb < kb_stop; kb++) {
+        const int cur = kb & 1;
+        const bool more = kb + 1 < kb_stop;
+        if (more) {                                            // next block into registers: in flight under this block's MFMAs
+            kreg = *(const uint4 *)(kg + (int64_t)(kb + 1) * 32 * a.qk_ld);
+            vreg = *(const uint4 *)(vg + (kb + 1) * 32);
+            if (tid < 32) mreg = a.mask[row0 + (kb + 1) * 32 + tid] ? 0.f : -INFINITY;
+        }
+        if (has_q) {
+            const char *k_t = sK[cur], *v_t = sV[cur];
+            f32x16 s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const uint4 ka = *(const uint4 *)(k_t + r * 128 + (((2 * c + kh) ^ (r & 7)) << 4));
+                s = mfma_bf16(ka, qf[c], s);
+            }
+            // accumulator i: key kb * 32 + 8 (i / 4) + 4 kh + i % 4 of this lane's query
+            float mb = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                s[i] += sM[cur][8 * (i >> 2) + 4 * kh + (i & 3)];
+                mb = fmaxf(mb, s[i]);
+            }
+            mb = fmaxf(mb, __shfl_xor(mb, 32));
+            const float mn = fmaxf(m, mb);
+            const float mref = mn == -INFINITY ? 0.f : mn;     // no real key seen yet: p = 0, nothing rescaled
+            const float alpha = exp2f(m - mref);
+            m = mn;
+            float ps = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; i++) { s[i] = exp2f(s[i] - mref); ps += s[i]; }
+            l = l * alpha + ps;
+#pragma unroll
+            for (int db = 0; db < 2; db++) o[db] = o[db] * alpha;
+            uint4 pb[2];
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+                pb[t] = uint4{pack_bf16x2(s[8 * t + 0], s[8 * t + 1]), pack_bf16x2(s[8 * t + 2], s[8 * t + 3]),
+                              pack_bf16x2(s[8 * t + 4], s[8 * t + 5]), pack_bf16x2(s[8 * t + 6], s[8 * t + 7])};
+#pragma unroll
+            for (int db = 0; db < 2; db++) {
+                const int d = db * 32 + r;
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    const uint4 va = *(const uint4 *)(v_t + d * 64 + (((2 * t + kh) ^ ((d >> 1) & 3)) << 4));
+                    o[db] = mfma_bf16(va, pb[t], o[db]);
+                }
+            }
+        }
+        if (more) {                                            // the other buffer: its last readers passed the previous barrier
+            *(uint4 *)(sK[cur ^ 1] + k_dst) = kreg;
+            *(uint4 *)(sV[cur ^ 1] + v_dst) = vreg;
+            if (tid < 32) sM[cur ^ 1][tid] = mreg;
+        }
+        __syncthreads();
+    }
+    if (!has_q) return;
+    const float lt = l + __shfl_xor(l, 32);
+    const float inv = lt > 0.f ? 1.0f / lt : 0.f;
+    uint16_t *crow = a.ctx + (row0 + q0 + r) * H + h * AL_HD;
+    // O^T accumulators: d = 32 db + 8 (i / 4) + 4 kh + i % 4 of this lane's query: four consecutive d per 8-byte store
+#pragma unroll
+    for (int db = 0; db < 2; db++)
+#pragma unroll
+        for (int gq = 0; gq < 4; gq++) {
+            const int d = db * 32 + 8 * gq + 4 * kh;
+            *(uint2 *)(crow + d) = uint2{pack_bf16x2(o[db][4 * gq + 0] * inv, o[db][4 * gq + 1] * inv),
+                                         pack_bf16x2(o[db][4 * gq + 2] * inv, o[db][4 * gq + 3] * inv)};
+        }
+}
+}  // namespace
+
+int launch_attn_long(const AttnArgs &a0, hipStream_t st) {
+    AttnArgs a = a0;
+    if (a.qk_ld == 0) { a.qk_ld = a.H; a.qk_hs = a.H / a.heads; }      // token-major q / k
+    if (a.H != a.heads * AL_HD) AK_FAIL(-1, "attention (rows > 512 tokens): head size must be 64");
+    if (a.S % 32 || a.S <= 512 || a.S > ATTN_LONG_MAX_S) AK_FAIL(-1, "attention (rows > 512 tokens): S must be a multiple of 32 in (512, 8192]");
+    if (!a.rowlen || !a.mask || a.rel) AK_FAIL(-1, "attention (rows > 512 tokens): needs the row lengths and the mask, no bias");
+    const dim3 grid((unsigned)((a.S + AL_QB - 1) / AL_QB), (unsigned)a.heads, (unsigned)a.B);
+    k_attn_long<<<grid, 256, 0, st>>>(a);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace ak

@@ -175,13 +175,14 @@ static bool launch_layernorm16(int np, const uint16_t *x16in, const float *g, co
 // one 4 * NP-byte run of each table row, so a wave instruction covers whole rows -- 12 bytes per lane at H = 384 instead of
 // three passes of 4; 44 -> ~20 us per 65 536 tokens); H % 128 == 0, H <= 1024. The kernel is a chain of dependent round trips
 // (id -> table row -> two reductions -> store) at whatever the occupancy keeps in flight: two independent tokens per wave
-// double that (29 -> ~20 us per 65 536 tokens at hidden 384).
+// double that (29 -> ~20 us per 65 536 tokens at hidden 384). posid != NULL: token t's position row is posid[t] (positions from
+// ids, k_positions) instead of t % S.
 template <int NP>
 __global__ __launch_bounds__(256) void k_embed(const int *__restrict__ ids, int T, int S, int vocab,
                                                const uint16_t *__restrict__ word, const uint16_t *__restrict__ pos,
                                                const uint16_t *__restrict__ type, const float *__restrict__ g,
                                                const float *__restrict__ bta, float eps, float *__restrict__ y32 /* nullable */,
-                                               uint16_t *__restrict__ y16) {
+                                               uint16_t *__restrict__ y16, const int *__restrict__ posid /* nullable */) {
     constexpr int H = NP * 128, RW = 2;
     struct __attribute__((packed, aligned(4))) Run { uint32_t w[NP]; };
     struct __attribute__((packed, aligned(8))) RunF { float2 w[NP]; };
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(256) void k_embed(const int *__restrict__ ids, int 
 #pragma unroll
     for (int q = 0; q < RW; q++) {
         a[q] = *(const Run *)(word + (int64_t)id[q] * H + lane * 2 * NP);
-        b[q] = *(const Run *)(pos + (int64_t)(rowq[q] % S) * H + lane * 2 * NP);
+        b[q] = *(const Run *)(pos + (int64_t)(posid ? posid[rowq[q]] : rowq[q] % S) * H + lane * 2 * NP);
     }
     const Run c = *(const Run *)(type + lane * 2 * NP);
     const RunF gg = *(const RunF *)(g + lane * 2 * NP), bb = *(const RunF *)(bta + lane * 2 * NP);
@@ -246,13 +247,13 @@ __global__ __launch_bounds__(256) void k_embed(const int *__restrict__ ids, int 
 }
 template <int NP = 1>
 static int launch_embed(int np, const int *ids, int T, int S, int vocab, const uint16_t *word, const uint16_t *pos, const uint16_t *type,
-                        const float *g, const float *bta, float eps, float *y32, uint16_t *y16, hipStream_t st) {
+                        const float *g, const float *bta, float eps, float *y32, uint16_t *y16, hipStream_t st, const int *posid) {
     if constexpr (NP <= 8) {
         if (np == NP) {
-            k_embed<NP><<<(unsigned)((T + 7) / 8), 256, 0, st>>>(ids, T, S, vocab, word, pos, type, g, bta, eps, y32, y16);
+            k_embed<NP><<<(unsigned)((T + 7) / 8), 256, 0, st>>>(ids, T, S, vocab, word, pos, type, g, bta, eps, y32, y16, posid);
             return 0;
         }
-        return launch_embed<NP + 1>(np, ids, T, S, vocab, word, pos, type, g, bta, eps, y32, y16, st);
+        return launch_embed<NP + 1>(np, ids, T, S, vocab, word, pos, type, g, bta, eps, y32, y16, st, posid);
     } else return -1;
 }
 
@@ -261,7 +262,8 @@ static int launch_embed(int np, const int *ids, int T, int S, int vocab, const u
 // 16-byte chunk t % (H / 8) for the tokens s = t / (H / 8), + G, + 2G, ... (G = 256 / (H / 8) token groups; four independent
 // loads in flight), the groups are then added through LDS in a fixed order (one thread per feature pair looped over all
 // S tokens with 4-byte loads before: 47 us per 256 x 256 tokens, 1 TB/s). H % 8 == 0, H / 8 <= 256, H <= 1024.
-template <bool IN16>
+// LONG (rows longer than 512 tokens): the per-token weights are read from the mask where they are used instead of from LDS
+template <bool IN16, bool LONG = false>
 __global__ __launch_bounds__(256) void k_pool(const float *__restrict__ x, const uint16_t *__restrict__ x16,
                                               const int *__restrict__ mask, int S, int H,
                                               int pooling, int normalise, float *__restrict__ out) {
@@ -270,7 +272,12 @@ __global__ __launch_bounds__(256) void k_pool(const float *__restrict__ x, const
     __shared__ float part[8][1024];
     const int b = blockIdx.x, tid = threadIdx.x;
     float c = 0.f;
-    for (int s = tid; s < S; s += 256) { float w = mask[b * S + s] ? 1.f : 0.f; wgt[s] = w; c += w; }
+    for (int s = tid; s < S; s += 256) {
+        float w = mask[(int64_t)b * S + s] ? 1.f : 0.f;
+        if constexpr (!LONG) wgt[s] = w;
+        c += w;
+    }
+    auto wt = [&](int s) { if constexpr (LONG) return mask[(int64_t)b * S + s] ? 1.f : 0.f; else return wgt[s]; };
     red[tid] = c;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
@@ -301,14 +308,14 @@ __global__ __launch_bounds__(256) void k_pool(const float *__restrict__ x, const
             for (; s + 3 * G < S; s += 4 * G) {
                 float v0[8], v1[8], v2[8], v3[8];
                 at8(s, v0); at8(s + G, v1); at8(s + 2 * G, v2); at8(s + 3 * G, v3);
-                const float w0 = wgt[s], w1 = wgt[s + G], w2 = wgt[s + 2 * G], w3 = wgt[s + 3 * G];
+                const float w0 = wt(s), w1 = wt(s + G), w2 = wt(s + 2 * G), w3 = wt(s + 3 * G);
 #pragma unroll
                 for (int i = 0; i < 8; i++) acc[i] = fmaf(w3, v3[i], fmaf(w2, v2[i], fmaf(w1, v1[i], fmaf(w0, v0[i], acc[i]))));
             }
             for (; s < S; s += G) {
                 float v0[8];
                 at8(s, v0);
-                const float w0 = wgt[s];
+                const float w0 = wt(s);
 #pragma unroll
                 for (int i = 0; i < 8; i++) acc[i] = fmaf(w0, v0[i], acc[i]);
             }
@@ -352,12 +359,13 @@ __global__ __launch_bounds__(256) void k_pool(const float *__restrict__ x, const
 __global__ __launch_bounds__(256) void k32_embed(const int *__restrict__ ids, int T, int S, int H, int vocab,
                                                  const float *__restrict__ word, const float *__restrict__ pos,
                                                  const float *__restrict__ type, const float *__restrict__ g,
-                                                 const float *__restrict__ bta, float eps, float *__restrict__ y) {
+                                                 const float *__restrict__ bta, float eps, float *__restrict__ y,
+                                                 const int *__restrict__ posid /* nullable: position rows, as k_embed */) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= T) return;
     int id = ids[row];
     if (id < 0 || id >= vocab) id = 0;
-    const float *w = word + (int64_t)id * H, *p = pos + (int64_t)(row % S) * H;
+    const float *w = word + (int64_t)id * H, *p = pos + (int64_t)(posid ? posid[row] : row % S) * H;
     float v[16];
     float s = 0.f;
 #pragma unroll
@@ -531,6 +539,10 @@ struct Encoder {
     // relative-position bias (ak_encoder_set_rel_bias): per-distance tables [heads][REL_ROW] (encoder_kernels.h), natural domain
     // (float32 attention) and scaled by log2(e) (the base-2 kernels); NULL: none. rel_n: distances |d| < rel_n are covered
     float *rel = nullptr, *rel2 = nullptr; int rel_n = 0;
+    // positions from ids (ak_encoder_set_positions_from_ids, RoBERTa / XLM-R): padding_idx (-1: a token's position is its index in
+    // the row), the longest row then accepted, and the per-token position rows k_positions writes before the embedding (grown on demand)
+    int pos_pad = -1, pos_max_seq = 0;
+    int *posid = nullptr; int64_t posid_cap = 0;      // posid [tokens], then the rows' lengths [B] (the long-row attention)
     std::mutex mu;
 };
 
@@ -547,6 +559,7 @@ static int reserve_ws(Encoder &e, int64_t tpad) {
     if (tpad <= e.cap_tokens) return 0;
     free_ws(e);
     const int H = e.cfg.hidden, I = e.cfg.intermediate;
+    const int64_t VT_PAD = e.pos_max_seq > 512 ? e.pos_max_seq : ak::VT_PAD;      // (rows longer than 512 tokens: up to max_seq)
     AK_HIP(hipMalloc((void **)&e.x32, tpad * H * 4)); AK_HIP(hipMalloc((void **)&e.y32, tpad * H * 4));
     AK_HIP(hipMalloc((void **)&e.x16, tpad * H * 2)); AK_HIP(hipMalloc((void **)&e.q, tpad * H * 2));
     AK_HIP(hipMalloc((void **)&e.k, tpad * H * 2)); AK_HIP(hipMalloc((void **)&e.vt, (tpad + VT_PAD) * H * 2));
@@ -575,7 +588,8 @@ constexpr int X3_PADN_DEFAULT = 1;      // MiniLM 256 x 256, ms per forward: non
 // x3: nullptr = exact float32 GEMMs (precision 1); else the layer matrices split into bf16 hi / lo (precision 2: every GEMM as
 // hi.hi + lo.hi + hi.lo on the bf16 matrix cores, encoder_f32.hip k3_gemm). Everything else is the same float32 code.
 static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16_t *const *x3, const int *ids, const int *mask, int B, int S, int pooling,
-                       int normalise, float *out, float **ws, size_t *ws_bytes, hipStream_t st, const float *rel = nullptr, const float *rel2 = nullptr) {
+                       int normalise, float *out, float **ws, size_t *ws_bytes, hipStream_t st, const float *rel = nullptr, const float *rel2 = nullptr,
+                       const int *posid = nullptr) {
     const int H = c.hidden, I = c.intermediate, L = c.layers;
     const int64_t T = (int64_t)B * S;
     // Split mode on gemm.hip's tiles (x3_tiles below): whole 256-token tiles, so the rows are padded to one (rows past T: zeros in,
@@ -607,7 +621,7 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
     const unsigned rows4 = (unsigned)((T + 3) / 4);
     if (!x3_tiles) {
         k32_embed<<<rows4, 256, 0, st>>>(ids, (int)T, S, H, c.vocab_size, (const float *)w[0], (const float *)w[1], (const float *)w[2],
-                                         (const float *)w[3], (const float *)w[4], c.ln_eps, x);
+                                         (const float *)w[3], (const float *)w[4], c.ln_eps, x, posid);
         AK_HIP(hipGetLastError());
     }
     // the matrix-core kernels (encoder_f32.hip); the scalar kernels above stay as their cross-check in libarchi_hip_dbg.so
@@ -621,7 +635,7 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
         uint16_t *cs = (uint16_t *)(qkv2 + Ta * Qn), *xs = cs + Ta * 2 * H, *fs = (uint16_t *)f;
         if ((const char *)(xs + Ta * 2 * H) > (const char *)f) AK_FAIL(-1, "forward (split bf16): workspace layout");
         if (launch_embed_split(ids, T, S, H, c.vocab_size, (const float *)w[0], (const float *)w[1], (const float *)w[2], (const float *)w[3],
-                               (const float *)w[4], c.ln_eps, x, xs, st)) return -10;
+                               (const float *)w[4], c.ln_eps, x, xs, st, posid)) return -10;
         for (int l = 0; l < L; l++) {
             const void *const *p = w + 5 + 16 * l;
             const uint16_t *const *s3 = x3 + X3_SLOTS * l;
@@ -877,6 +891,7 @@ extern "C" int ak_encoder_destroy(ak_encoder_t h) {
     if (e->qf_fail) hipHostFree(e->qf_fail);
     if (e->rel) hipFree(e->rel);
     if (e->rel2) hipFree(e->rel2);
+    if (e->posid) hipFree(e->posid);
     for (void *p : e->owned) hipFree(p);
     delete e;
     return 0;
@@ -903,6 +918,7 @@ extern "C" int ak_encoder_set_rel_bias(ak_encoder_t h, const float *bias_dev, in
     if (n_rel < 1 || n_rel > REL_MID - 1) AK_FAIL(-1, "ak_encoder_set_rel_bias: n_rel must be in [1, 1023]");
     std::lock_guard<std::mutex> lk(e.mu);
     if (e.rel) AK_FAIL(-1, "ak_encoder_set_rel_bias: the encoder already has a relative-position bias");
+    if (e.pos_pad >= 0) AK_FAIL(-1, "ak_encoder_set_rel_bias: the encoder takes its positions from the ids; the two are not combined");
     float *rel = nullptr, *rel2 = nullptr;
     const size_t bytes = (size_t)heads * REL_ROW * 4;
     if (hipMalloc((void **)&rel, bytes) != hipSuccess) AK_FAIL(-10, "ak_encoder_set_rel_bias: hipMalloc failed");
@@ -913,6 +929,61 @@ extern "C" int ak_encoder_set_rel_bias(ak_encoder_t h, const float *bias_dev, in
         AK_FAIL(-10, "ak_encoder_set_rel_bias: table launch failed");
     }
     e.rel = rel; e.rel2 = rel2; e.rel_n = n_rel;
+    return 0;
+}
+
+namespace ak {
+// RoBERTa positions (HF create_position_ids_from_input_ids) of ids / 0-1 mask [B][S]: a token counts when it is inside the row
+// (mask != 0) and is not the pad id. HF looks at the ids alone; the mask is consulted on purpose, so that whatever lies past a row's
+// length is ignored -- the two agree on right-padded rows (the provider's tiles), and differ only for an explicit mask with zeros on
+// non-pad ids in front of real tokens; a counted token's position is padding_idx + (counted tokens up to and including it), every other
+// token's padding_idx. One workgroup per row walks it in 256-token steps: per wave a ballot and a popcount of the lanes below, the
+// four wave totals through LDS, a running count carried between steps. Positions are clamped to the table (max_pos rows);
+// ak_encoder_set_positions_from_ids already keeps padding_idx + S inside it.
+__global__ __launch_bounds__(256) void k_positions(const int *__restrict__ ids, const int *__restrict__ mask, int S, int pad, int max_pos,
+                                                   int *__restrict__ pos, int *__restrict__ rowlen) {
+    __shared__ int wsum[4];
+    __shared__ int last;                                   // the row's last token with mask != 0: its length is last + 1
+    if (threadIdx.x == 0) last = -1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t row = (int64_t)blockIdx.x * S;
+    int carry = 0;
+    for (int s0 = 0; s0 < S; s0 += 256) {
+        const int s = s0 + tid;
+        const bool in_row = s < S && mask[row + s] != 0;
+        const bool live = in_row && ids[row + s] != pad;
+        if (in_row) atomicMax(&last, s);
+        const unsigned long long bal = __ballot(live);
+        const int incl = __popcll(bal & (lane == 63 ? ~0ull : (2ull << lane) - 1ull));       // counted lanes <= this one
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int before = carry;
+        for (int w = 0; w < wave; w++) before += wsum[w];
+        if (s < S) {
+            const int p = live ? pad + before + incl : pad;
+            pos[row + s] = p < max_pos ? p : max_pos - 1;
+        }
+        carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) rowlen[blockIdx.x] = last + 1;
+}
+}  // namespace ak
+
+extern "C" int ak_encoder_set_positions_from_ids(ak_encoder_t h, int padding_idx, int max_seq) {
+    AK_BIND();
+    if (!h) AK_FAIL(-1, "ak_encoder_set_positions_from_ids: NULL encoder");
+    Encoder &e = *(Encoder *)h;
+    if (padding_idx < 0) AK_FAIL(-1, "ak_encoder_set_positions_from_ids: padding_idx must be >= 0");
+    if (max_seq < 1 || max_seq > ATTN_LONG_MAX_S) AK_FAIL(-1, "ak_encoder_set_positions_from_ids: max_seq must be in [1, 8192]");
+    if (max_seq > 512 && (e.cfg.precision != 0 || e.cfg.hidden / e.cfg.heads != 64 || e.cfg.hidden == 384))
+        AK_FAIL(-1, "ak_encoder_set_positions_from_ids: rows longer than 512 tokens run in precision bf16 at head size 64 (hidden != 384) only");
+    if ((int64_t)padding_idx + 1 + max_seq > e.cfg.max_position)
+        AK_FAIL(-1, "ak_encoder_set_positions_from_ids: padding_idx + 1 + max_seq exceeds max_position (the position table's rows)");
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (e.rel) AK_FAIL(-1, "ak_encoder_set_positions_from_ids: the encoder has a relative-position bias; the two are not combined");
+    if (e.pos_pad >= 0) AK_FAIL(-1, "ak_encoder_set_positions_from_ids: already set on this encoder");
+    e.pos_pad = padding_idx; e.pos_max_seq = max_seq;
     return 0;
 }
 
@@ -929,9 +1000,11 @@ extern "C" int ak_encoder_forward(ak_encoder_t h, const int32_t *ids, const int3
     RoctxRange range("ak_encoder_forward");
     Encoder &e = *(Encoder *)h;
     if (B <= 0) return 0;
-    if (S % 32 || S > 512 || S > e.cfg.max_position) AK_FAIL(-1, "ak_encoder_forward: S must be a multiple of 32, <= 512 and <= max_position (pad with mask 0)");
+    if (S % 32 || S > (e.pos_max_seq > 512 ? e.pos_max_seq : 512) || S > e.cfg.max_position)
+        AK_FAIL(-1, "ak_encoder_forward: S must be a multiple of 32, <= 512 (or the max_seq of ak_encoder_set_positions_from_ids) and <= max_position (pad with mask 0)");
     std::lock_guard<std::mutex> lk(e.mu);
     if (e.rel && S > e.rel_n) AK_FAIL(-1, "ak_encoder_forward: S exceeds the n_rel of the relative-position bias table");
+    if (e.pos_pad >= 0 && S > e.pos_max_seq) AK_FAIL(-1, "ak_encoder_forward: S exceeds the max_seq of ak_encoder_set_positions_from_ids");
     return forward_locked(e, ids, mask, B, S, pooling, normalise, out, (hipStream_t)stream);
 }
 
@@ -958,9 +1031,11 @@ extern "C" int ak_encoder_forward_lens(ak_encoder_t h, const int32_t *ids, int l
     Encoder &e = *(Encoder *)h;
     if (B <= 0) return 0;
     if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, "ak_encoder_forward_lens: bad arguments");
-    if (S % 32 || S > 512 || S > e.cfg.max_position) AK_FAIL(-1, "ak_encoder_forward_lens: S must be a multiple of 32, <= 512 and <= max_position");
+    if (S % 32 || S > (e.pos_max_seq > 512 ? e.pos_max_seq : 512) || S > e.cfg.max_position)
+        AK_FAIL(-1, "ak_encoder_forward_lens: S must be a multiple of 32, <= 512 (or the max_seq of ak_encoder_set_positions_from_ids) and <= max_position");
     std::lock_guard<std::mutex> lk(e.mu);
     if (e.rel && S > e.rel_n) AK_FAIL(-1, "ak_encoder_forward_lens: S exceeds the n_rel of the relative-position bias table");
+    if (e.pos_pad >= 0 && S > e.pos_max_seq) AK_FAIL(-1, "ak_encoder_forward_lens: S exceeds the max_seq of ak_encoder_set_positions_from_ids");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)B * S;
     if (n > e.lens_cap) {
@@ -1029,10 +1104,27 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
         lens_in = nullptr;
         return 0;
     };
+    // positions from ids: the per-token position rows of the laid-out ids / mask, for the embedding kernel (NULL: token index)
+    const int *posid = nullptr, *rowlen = nullptr;
+    auto positions = [&]() -> int {
+        if (e.pos_pad < 0) return 0;
+        const int64_t n = (int64_t)B * S;
+        if (n + B > e.posid_cap) {
+            if (e.posid) hipFree(e.posid);
+            e.posid = nullptr; e.posid_cap = 0;
+            AK_HIP(hipMalloc((void **)&e.posid, (size_t)(n + B) * 4));
+            e.posid_cap = n + B;
+        }
+        k_positions<<<(unsigned)B, 256, 0, st>>>(ids, mask, S, e.pos_pad, e.cfg.max_position, e.posid, e.posid + n);
+        AK_HIP(hipGetLastError());
+        posid = e.posid;
+        rowlen = S > 512 ? e.posid + n : nullptr;
+        return 0;
+    };
     if (e.cfg.precision == 1 || e.cfg.precision == 2) {
-        if (lens_to_mask()) return -10;
+        if (lens_to_mask() || positions()) return -10;
         return forward_f32(e.cfg, e.raw.data(), e.cfg.precision == 2 ? e.x3.data() : nullptr, ids, mask, B, S, pooling, normalise, out,
-                           &e.ws32, &e.ws32_bytes, st, e.rel, e.rel2);
+                           &e.ws32, &e.ws32_bytes, st, e.rel, e.rel2, posid);
     }
     const int H = e.cfg.hidden, I = e.cfg.intermediate, heads = e.cfg.heads;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
@@ -1040,15 +1132,15 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
     // <= 64 token rows (embed_query): the whole forward pass as ONE launch on one XCD (query_forward.hip), bit-identical to the
     // launches below; 1 = not taken / gave up safely
     const int qf_mode = switches().query_fused.load(std::memory_order_relaxed);      // 0 off (default), 1 when it applies, 2 required (tests)
-    // (the single launch has no relative-position bias: an encoder with one always takes the launches below)
-    if (!e.qf_off && !e.rel2 && query_forward_supported(H, I, heads, T, S) && (lens_in == nullptr || e.lens_ids != nullptr)) {
+    // (the single launch has no relative-position bias and no positions from ids: an encoder with either always takes the launches below)
+    if (!e.qf_off && !e.rel2 && e.pos_pad < 0 && query_forward_supported(H, I, heads, T, S) && (lens_in == nullptr || e.lens_ids != nullptr)) {
         const int rc = run_query_forward(e, lens_in, ids, mask, B, S, pooling, normalise, out, tpad, st);
         if (rc <= 0) return rc;
         if (qf_mode == 2) AK_FAIL(-10, "ak_encoder_forward: the single-launch query forward gave up (a bounded wait ran out) and AK_QUERY_FUSED=2 requires it");
     } else if (qf_mode == 2 && T <= 64) {
         AK_FAIL(-1, "ak_encoder_forward: AK_QUERY_FUSED=2 requires the single-launch query forward, which does not take this shape / encoder");
     }
-    if (lens_to_mask()) return -10;
+    if (lens_to_mask() || positions()) return -10;
     const float eps = e.cfg.ln_eps;
     // H = 384: residual add + LayerNorm run in the epilogue of the GEMM that feeds them (gemm_ln.hip)
     static const bool nofuse = env_get("AK_ENC_NOFUSE") != nullptr;
@@ -1063,15 +1155,15 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
     // 768 1.30 / 1.43, 1024 1.32 / 1.68. One embed call per file (the reference's manager.py:373) lands exactly here.
     static const int skinny_env = env_get("AK_ENC_SKINNY_MAX") ? atoi(env_get("AK_ENC_SKINNY_MAX")) : -1;
     const int skinny_max = skinny_env >= 0 ? skinny_env : (H == 384 ? 2816 : 640);
-    const bool skinny = T <= skinny_max && gemm_skinny_supported(H, H) && gemm_skinny_supported(H, I) &&
+    const bool skinny = S <= 512 && T <= skinny_max && gemm_skinny_supported(H, H) && gemm_skinny_supported(H, I) &&
                         gemm_skinny_supported(I, H);
     const int t32 = (int)((T + 31) / 32 * 32);
     // unfused GEMM -> LayerNorm path (hidden != 384) in bf16-residual mode: the GEMM output travels as bf16 too
     static const bool y32_forced = env_get("AK_ENC_Y32") != nullptr;
     const bool y16 = r16 && !y32_forced;
-    if (launch_embed(H / 128, ids, (int)T, S, e.cfg.vocab_size, e.word, e.pos, e.type, e.eg, e.eb, eps, x32, e.x16, st)) AK_FAIL(-1, "ak_encoder_forward: hidden size");
+    if (launch_embed(H / 128, ids, (int)T, S, e.cfg.vocab_size, e.word, e.pos, e.type, e.eg, e.eb, eps, x32, e.x16, st, posid)) AK_FAIL(-1, "ak_encoder_forward: hidden size");
     AK_HIP(hipGetLastError());
-    if (launch_attn_prepare(mask, B, S, e.maskf, (uint32_t *)(e.maskf + tpad), st)) return -10;
+    if (S <= 512 && launch_attn_prepare(mask, B, S, e.maskf, (uint32_t *)(e.maskf + tpad), st)) return -10;   // (S > 512: attn_long reads the mask)
     static const bool head_major = !env_get("AK_QK_TOKEN_MAJOR");     // A/B: q / k of the hidden-384 path as [T][384]
     // LAZY LayerNorm (gemm.hip): no LayerNorm launch between the sub-layers. e.q holds the gamma-scaled rows behind the attention
     // block (gamma1 (.) r1, statistics of r1 in st1), e.x16 those behind the feed-forward block (gamma2 (.) r2, st2); in layer 0 e.x16
@@ -1088,7 +1180,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
             g.nslot = H / 128; g.inv_h = 1.0f / (float)H; g.eps = eps;
             if (l == 0) { g.W = ly.wqkv; g.bias = ly.bqkv; if (launch_gemm(0, g, st)) return -10; }
             else { g.W = ly.wqkv; g.bias = ly.bqkv_f; g.fold_c = ly.cqkv; g.a_stats = e.st2; if (launch_gemm_lazy(0, g, st)) return -10; }
-            AttnArgs a{e.q, e.k, e.vt, mask, e.ctx, B, S, H, heads, e.maskf, (const uint32_t *)(e.maskf + tpad), 0, 0, e.rel2};
+            AttnArgs a{e.q, e.k, e.vt, mask, e.ctx, B, S, H, heads, e.maskf, (const uint32_t *)(e.maskf + tpad), 0, 0, e.rel2, rowlen};
             if (launch_attn(a, st)) return -10;
             GemmArgs o{};                         // r1 = ctx Wo^T + bo + LN2_prev(r2) -> e.q, st1
             o.X = e.ctx; o.W = ly.wo; o.bias = ly.bo; o.T = (int)tpad; o.N = H; o.K = H; o.out_bf16 = e.q; o.ldo = H; o.res16 = e.x16;
@@ -1111,7 +1203,8 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
         const Layer &last = e.layers[L - 1];
         k_ln_apply16<<<(unsigned)((T * (H / 8) + 255) / 256), 256, 0, st>>>(e.x16, e.st2, last.ln2g, last.ln2b, T, H, e.q);
         AK_HIP(hipGetLastError());
-        k_pool<true><<<B, 256, 0, st>>>(nullptr, e.q, mask, S, H, pooling, normalise, out);
+        if (S > 512) k_pool<true, true><<<B, 256, 0, st>>>(nullptr, e.q, mask, S, H, pooling, normalise, out);
+        else k_pool<true><<<B, 256, 0, st>>>(nullptr, e.q, mask, S, H, pooling, normalise, out);
         AK_HIP(hipGetLastError());
         return 0;
     }
@@ -1129,7 +1222,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
             qk_head_major = head_major;
         } else if (launch_gemm(0, g, st)) return -10;
         AttnArgs a{e.q, e.k, e.vt, mask, e.ctx, B, S, H, heads, e.maskf, (const uint32_t *)(e.maskf + tpad),
-                   qk_head_major ? H / heads : 0, qk_head_major ? S * (H / heads) : 0, e.rel2};
+                   qk_head_major ? H / heads : 0, qk_head_major ? S * (H / heads) : 0, e.rel2, rowlen};
         if (launch_attn(a, st)) return -10;
         static const bool noffn = dbg_env_int("AK_ENC_NOFFN", 0) != 0;
         const bool ffn_fused = !skinny && fuse && r16 && ly.wf && !noffn && ffn_fused_supported(H, I, tpad);
@@ -1183,7 +1276,10 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
         }
         AK_HIP(hipGetLastError());
     }
-    if (x32) k_pool<false><<<B, 256, 0, st>>>(x32, e.x16, mask, S, H, pooling, normalise, out);
+    if (S > 512) {
+        if (x32) k_pool<false, true><<<B, 256, 0, st>>>(x32, e.x16, mask, S, H, pooling, normalise, out);
+        else k_pool<true, true><<<B, 256, 0, st>>>(x32, e.x16, mask, S, H, pooling, normalise, out);
+    } else if (x32) k_pool<false><<<B, 256, 0, st>>>(x32, e.x16, mask, S, H, pooling, normalise, out);
     else k_pool<true><<<B, 256, 0, st>>>(x32, e.x16, mask, S, H, pooling, normalise, out);
     AK_HIP(hipGetLastError());
     return 0;

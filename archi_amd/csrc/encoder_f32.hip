@@ -763,16 +763,18 @@ __global__ __launch_bounds__(256) void k3_add_ln(const float *y, int ldy, const 
     }
 }
 // embeddings of the split mode's tile path: LayerNorm(word[id] + pos[t % S] + type[0]) as float32 rows and as [hi | lo] rows, one wave
-// per token, 16 bytes per lane and access (k32_embed of encoder.hip reads and writes single floats and leaves the split to a second pass)
+// per token, 16 bytes per lane and access (k32_embed of encoder.hip reads and writes single floats and leaves the split to a second pass).
+// posid != NULL: the token's position row is posid[t] instead (positions from ids, encoder.hip k_positions)
 __global__ __launch_bounds__(256) void k3_embed(const int *__restrict__ ids, int64_t T, int S, int H, int vocab, const float *__restrict__ word,
                                                 const float *__restrict__ pos, const float *__restrict__ type, const float *__restrict__ g,
-                                                const float *__restrict__ bta, float eps, float *__restrict__ out, uint16_t *__restrict__ out2) {
+                                                const float *__restrict__ bta, float eps, float *__restrict__ out, uint16_t *__restrict__ out2,
+                                                const int *__restrict__ posid) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, H4 = H >> 2;
     if (row >= T) return;
     int id = ids[row];
     if (id < 0 || id >= vocab) id = 0;
-    const float *w = word + (int64_t)id * H, *p = pos + (int64_t)(row % S) * H;
+    const float *w = word + (int64_t)id * H, *p = pos + (int64_t)(posid ? posid[row] : row % S) * H;
     f32x4v v[4];
     float s = 0.f;
 #pragma unroll
@@ -812,9 +814,9 @@ __global__ __launch_bounds__(256) void k3_embed(const int *__restrict__ ids, int
     }
 }
 int launch_embed_split(const int *ids, int64_t T, int S, int H, int vocab, const float *word, const float *pos, const float *type, const float *g,
-                       const float *b, float eps, float *out, uint16_t *out2, hipStream_t st) {
+                       const float *b, float eps, float *out, uint16_t *out2, hipStream_t st, const int *posid) {
     if (H % 4 || H > 1024) AK_FAIL(-1, "launch_embed_split: H must be a multiple of 4, at most 1024");
-    k3_embed<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(ids, T, S, H, vocab, word, pos, type, g, b, eps, out, out2);
+    k3_embed<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(ids, T, S, H, vocab, word, pos, type, g, b, eps, out, out2, posid);
     AK_HIP(hipGetLastError());
     return 0;
 }

@@ -42,7 +42,13 @@ struct AttnArgs {
     // additive relative-position bias (MPNet): rel[h * REL_ROW + REL_MID + (key - query)], base-2 domain (scaled by log2(e) like q);
     // zero outside |key - query| < n_rel. NULL: no bias (the kernels run the code they ran before it existed)
     const float *rel = nullptr;
+    // per-sequence row lengths [B] (k_positions): the long-row kernel (launch_attn_long) skips key and query blocks past them
+    const int *rowlen = nullptr;
 };
+// rows longer than 512 tokens (encoders given ak_encoder_set_positions_from_ids(max_seq > 512); bf16, head size 64): attn_long.hip,
+// 512 < S <= ATTN_LONG_MAX_S. Tiles with S <= 512 always run the kernels of attention.hip.
+constexpr int ATTN_LONG_MAX_S = 8192;
+int launch_attn_long(const AttnArgs &a, hipStream_t st);
 // layout of the library's per-distance bias tables (ak_encoder_set_rel_bias): one row of REL_ROW floats per head, distance d at
 // REL_MID + d. Any (key, query) pair of a 32-query block of a wave / workgroup, S <= 512, lands inside the row.
 constexpr int REL_ROW = 2048, REL_MID = 1024;
@@ -123,8 +129,9 @@ int split_rows(const float *x, int64_t rows, int K, uint16_t *out, hipStream_t s
 // out = LayerNorm(y + r) * g + b (float32, in place over r allowed; y rows of ldy floats) and its [hi | lo] rows; r == NULL: no residual
 int launch_add_ln_split(const float *y, int ldy, const float *r, int64_t T, int H, const float *g, const float *b, float eps, float *out, uint16_t *out2,
                         hipStream_t st);
+// embeddings + LayerNorm: float32 rows and [hi | lo] rows; posid: per-token position rows (positions from ids), NULL: t % S
 int launch_embed_split(const int *ids, int64_t T, int S, int H, int vocab, const float *word, const float *pos, const float *type, const float *g,
-                       const float *b, float eps, float *out, uint16_t *out2, hipStream_t st);       // embeddings + LayerNorm: float32 rows and [hi | lo] rows
+                       const float *b, float eps, float *out, uint16_t *out2, hipStream_t st, const int *posid = nullptr);
 // k3_attn over qkv rows of ldq floats (q | k | v in the first 3 H), context as [hi | lo] rows
 int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, hipStream_t st,
                          const float *rel = nullptr);

@@ -29,8 +29,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .encoder import (MODEL_SHAPES, MPNET_SHAPES, HipEncoder, load_hf_weights, load_mpnet_weights, mpnet_rel_bias_table,
-                      random_init_weights, random_mpnet_weights, read_sentence_transformers_config)
+from .encoder import (LONG_MAX_SEQ, MODEL_SHAPES, MPNET_SHAPES, XLMR_PADDING_IDX, XLMR_SHAPES, HipEncoder, load_hf_weights,
+                      load_mpnet_weights, load_xlmr_weights, long_rows_supported, mpnet_rel_bias_table, random_init_weights,
+                      random_mpnet_weights, random_xlmr_weights, read_sentence_transformers_config)
 from .decoder import MAX_SEQ, QWEN3_SHAPES, BpeTokenizer, HipDecoder, load_qwen3_weights, random_qwen3_weights, read_decoder_st_config
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
@@ -184,6 +185,19 @@ def _is_mpnet(model_name: str) -> bool:
     return model_name in MPNET_SHAPES
 
 
+def _is_xlmr(model_name: str) -> bool:
+    """An XLM-RoBERTa / RoBERTa checkpoint directory (config.json model_type "xlm-roberta" | "roberta") or a named XLM-R shape."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") in ("xlm-roberta", "roberta")
+    return model_name in XLMR_SHAPES
+
+
+# longest row of the parity modes (and of bf16 at head size 32 / hidden 384); bf16 at head size 64 runs up to LONG_MAX_SEQ
+ENCODER_MAX_SEQ = 512
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -208,8 +222,10 @@ class ArchiHipEmbeddings:
         if _is_qwen3(model_name):
             self._init_decoder(model_name, device)
             return
-        rel_bias = None
-        if _is_mpnet(model_name):
+        rel_bias = pos_pad = None
+        if _is_xlmr(model_name):
+            vocab, H, L, heads, I, max_pos, weights, eps, pos_pad = self._init_xlmr(model_name)
+        elif _is_mpnet(model_name):
             vocab, H, L, heads, I, max_pos, weights, eps, rel_bias = self._init_mpnet(model_name)
         elif os.path.isdir(model_name):
             shape, weights, eps = load_hf_weights(model_name)
@@ -218,14 +234,19 @@ class ArchiHipEmbeddings:
             self.pooling = self.model_kwargs.get("pooling", st_pool)
             self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, 512)
             self.normalize = self.normalize or st_norm     # a Normalize module in the checkpoint always applies
-            vf = os.path.join(model_name, "vocab.txt")
-            if not os.path.exists(vf):
+            vf, tf = os.path.join(model_name, "vocab.txt"), os.path.join(model_name, "tokenizer.json")
+            if os.path.exists(vf):
+                self.tokenizer = NativeWordPiece(vf, lowercase=_do_lower_case(model_name))
+            elif os.path.exists(tf):
+                # BERT weights with an XLM-R tokenizer and no vocab.txt (paraphrase-multilingual-MiniLM-L12-v2,
+                # multilingual-e5-small): the checkpoint's own tokenizer.json, as AutoTokenizer would load it
+                self.tokenizer = BpeTokenizer(tf)
+            else:
                 # real weights + hashed token ids = garbage embeddings with no error. The reference's embedder
                 # (HuggingFaceEmbeddings -> SentenceTransformer -> AutoTokenizer [upstream]) raises when the checkpoint
                 # has no tokenizer; HashWordPiece is only for seeded random-init models (synthetic_seed).
-                raise FileNotFoundError(f"{model_name}: vocab.txt not found -- a checkpoint directory needs its WordPiece "
-                                        "vocabulary (the hashing stand-in tokenizer is only used with synthetic_seed)")
-            self.tokenizer = NativeWordPiece(vf, lowercase=_do_lower_case(model_name))
+                raise FileNotFoundError(f"{model_name}: neither vocab.txt nor tokenizer.json found -- a checkpoint directory needs "
+                                        "its tokenizer (the hashing stand-in tokenizer is only used with synthetic_seed)")
         elif model_name in MODEL_SHAPES and "synthetic_seed" in self.model_kwargs:
             vocab, H, L, heads, I, max_pos, self.pooling, self.max_seq_length = MODEL_SHAPES[model_name]
             weights = random_init_weights(vocab, H, L, I, max_pos, seed=int(self.model_kwargs["synthetic_seed"]))
@@ -239,7 +260,54 @@ class ArchiHipEmbeddings:
         self.dimensions = H
         self.encoder = HipEncoder(vocab, H, L, heads, I, max_pos, weights, ln_eps=eps, device=device,
                                   residual=str(self.model_kwargs.get("residual", "bf16")),
-                                  precision=str(self.model_kwargs.get("precision", "bf16")), rel_bias=rel_bias)
+                                  precision=str(self.model_kwargs.get("precision", "bf16")), rel_bias=rel_bias,
+                                  positions_from_ids=pos_pad)
+
+    def _init_xlmr(self, model_name: str):
+        """XLM-RoBERTa (bge-m3, multilingual-e5, paraphrase-multilingual-mpnet-base-v2): a local checkpoint directory (config.json
+        model_type xlm-roberta | roberta, safetensors, tokenizer.json, the sentence-transformers files) or a named shape with
+        synthetic_seed. The BERT encoder with positions from the ids (ak_encoder_set_positions_from_ids), the model's token-type row
+        and its tokenizer.json; every precision. Rows up to 8192 tokens in bf16 at head size 64 (csrc/attn_long.hip), 512 otherwise:
+        a max_seq_length above that is refused before any GPU work (the provider never truncates silently)."""
+        precision = str(self.model_kwargs.get("precision", "bf16"))
+        if os.path.isdir(model_name):
+            import json
+            cfg = json.load(open(os.path.join(model_name, "config.json")))
+            hidden, heads = int(cfg.get("hidden_size", 0)), int(cfg.get("num_attention_heads", 1))
+            pad = int(cfg.get("pad_token_id", XLMR_PADDING_IDX))
+            usable = int(cfg.get("max_position_embeddings", 514)) - pad - 1
+            st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
+            self.pooling = self.model_kwargs.get("pooling", st_pool)
+            self.normalize = self.normalize or st_norm
+        elif "synthetic_seed" in self.model_kwargs:
+            shape = XLMR_SHAPES[model_name]
+            hidden, heads = shape[1], shape[3]
+            pad, usable = XLMR_PADDING_IDX, shape[5] - XLMR_PADDING_IDX - 1
+            st_len = shape[7]
+            self.pooling = self.model_kwargs.get("pooling", shape[6])
+            self.normalize = True                      # the released sentence-transformers models carry a Normalize module
+        else:
+            raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass an XLM-RoBERTa checkpoint "
+                                    "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
+        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or usable)), usable, LONG_MAX_SEQ)
+        if self.max_seq_length > ENCODER_MAX_SEQ and not long_rows_supported(hidden, heads, precision):
+            raise ValueError(f"{model_name}: max_seq_length {self.max_seq_length} -- rows longer than {ENCODER_MAX_SEQ} tokens run in "
+                             f"precision 'bf16' at head size 64 only (here precision {precision!r}, head size {hidden / heads:g}); pass "
+                             f"model_kwargs={{'max_seq_length': {ENCODER_MAX_SEQ}}} to truncate chunks at {ENCODER_MAX_SEQ} tokens")
+        if os.path.isdir(model_name):
+            shape, weights, eps, pad = load_xlmr_weights(model_name)
+            vocab, H, L, heads, I, max_pos = shape
+            tf = os.path.join(model_name, "tokenizer.json")
+            if not os.path.exists(tf):
+                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- an XLM-RoBERTa checkpoint needs its tokenizer")
+            self.tokenizer = BpeTokenizer(tf)
+        else:
+            vocab, H, L, heads, I, max_pos = shape[:6]
+            weights = random_xlmr_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]))
+            eps = 1e-5
+            tf = self.model_kwargs.get("tokenizer_file")
+            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(vocab)
+        return vocab, H, L, heads, I, max_pos, weights, eps, pad
 
     def _init_mpnet(self, model_name: str):
         """MPNet (all-mpnet-base-v2 and its family): a local checkpoint directory (config.json model_type mpnet, safetensors,

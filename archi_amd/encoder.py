@@ -38,6 +38,23 @@ MPNET_PADDING_IDX = 1           # MPNetEmbeddings.padding_idx: token p of a row 
 MPNET_NUM_BUCKETS = 32          # MPNetEncoder.compute_position_bias buckets with its default, whatever the config holds
 MPNET_MAX_DISTANCE = 128
 
+# XLM-RoBERTa (bge-m3, multilingual-e5, paraphrase-multilingual-mpnet-base-v2): name -> (vocab, hidden, layers, heads, intermediate,
+# max_position_embeddings, pooling, max_seq_length) from their published config.json / sentence-transformers files (not checked
+# offline; they only shape synthetic benchmarks). Not in MODEL_SHAPES: other code indexes that table as BERT.
+XLMR_SHAPES = {
+    "BAAI/bge-m3": (250002, 1024, 24, 16, 4096, 8194, "cls", 8192),
+    "intfloat/multilingual-e5-large": (250002, 1024, 24, 16, 4096, 514, "mean", 512),
+    "intfloat/multilingual-e5-base": (250002, 768, 12, 12, 3072, 514, "mean", 512),
+    "sentence-transformers/paraphrase-multilingual-mpnet-base-v2": (250002, 768, 12, 12, 3072, 514, "mean", 128),
+    # small shapes of the test fixtures (tests/golden/make_xlmr_fixtures.py): head size 64 and 32, a two-layer cut of the hidden-1024
+    # shape, and a head-size-64 shape with bge-m3's 8194-row position table
+    "xlmr-tiny-hd64": (1000, 256, 2, 4, 512, 514, "mean", 512),
+    "xlmr-tiny-hd32": (1000, 256, 2, 8, 512, 514, "mean", 512),
+    "xlmr-1024-cut2": (1000, 1024, 2, 16, 4096, 514, "cls", 512),
+    "xlmr-long-hd64": (1000, 256, 2, 4, 512, 8194, "cls", 8192),
+}
+XLMR_PADDING_IDX = 1            # XLM-R's pad id = the position embedding's padding_idx
+
 LAYER_KEYS = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b", "w1", "b1", "w2", "b2", "ln2_g", "ln2_b")
 MATRIX_KEYS = {"wq", "wk", "wv", "wo", "w1", "w2"}
 
@@ -50,12 +67,18 @@ def weight_order(layers: int):
 
 
 PRECISIONS = {"bf16": 0, "f32": 1, "bf16x3": 2}        # AkBertConfig.precision
+LONG_MAX_SEQ = 8192                                     # longest row of an encoder with positions from ids (csrc/attn_long.hip)
+
+
+def long_rows_supported(hidden: int, heads: int, precision: str) -> bool:
+    """Rows longer than 512 tokens (positions from ids): bf16, head size 64, hidden != 384 (ak_encoder_set_positions_from_ids)."""
+    return precision == "bf16" and hidden == 64 * heads and hidden != 384
 
 
 class HipEncoder:
     def __init__(self, vocab: int, hidden: int, layers: int, heads: int, intermediate: int, max_position: int,
                  weights: Dict[str, np.ndarray], ln_eps: float = 1e-12, device: Optional[int] = None,
-                 residual: str = "bf16", precision: str = "bf16", rel_bias=None):
+                 residual: str = "bf16", precision: str = "bf16", rel_bias=None, positions_from_ids: Optional[int] = None):
         """residual: "bf16" keeps the residual stream between layers in bf16 only (hidden size 384: 60% less epilogue
         traffic; adds ~1e-6 of cosine deviation from the fp32 reference to the ~2e-6 the bf16 GEMM inputs already
         cost); "f32" keeps it in fp32 like the reference's CPU path. ARCHI_ENCODER_RESIDUAL overrides.
@@ -66,7 +89,10 @@ class HipEncoder:
         (~1e-6 per component from float64, scores within 1e-5 of the CPU path, ~3x the "f32" mode's rate).
         rel_bias: an additive relative-position bias [heads][2 n_rel - 1] (distance key - query at column d + n_rel - 1, natural-log
         domain; MPNet: mpnet_rel_bias_table) added to every attention score (ak_encoder_set_rel_bias); sequences are then limited
-        to n_rel tokens. None: no bias."""
+        to n_rel tokens. None: no bias.
+        positions_from_ids: RoBERTa / XLM-R positions (ak_encoder_set_positions_from_ids) with this padding_idx: weights["pos_emb"]
+        is then the full position table and sequences are limited to max_position - padding_idx - 1 tokens, at most 8192
+        (long_rows_supported) and 512 otherwise. None: a token's position is its index in the row."""
         import os
         import torch
         residual = os.environ.get("ARCHI_ENCODER_RESIDUAL", residual)
@@ -111,6 +137,13 @@ class HipEncoder:
             check(self._lib.ak_encoder_set_rel_bias(self._h, ctypes.c_void_p(rb.data_ptr()), heads, (rb.shape[1] + 1) // 2),
                   "ak_encoder_set_rel_bias")
         self.rel_bias = rel_bias is not None
+        self.positions_from_ids = positions_from_ids
+        self.max_seq = 512
+        if positions_from_ids is not None:
+            cap = LONG_MAX_SEQ if long_rows_supported(hidden, heads, precision) else 512
+            max_seq = self.max_seq = min(max_position - int(positions_from_ids) - 1, cap)
+            check(self._lib.ak_encoder_set_positions_from_ids(self._h, int(positions_from_ids), max_seq),
+                  "ak_encoder_set_positions_from_ids")
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -129,7 +162,7 @@ class HipEncoder:
         ids_t = torch.as_tensor(ids, dtype=torch.int32, device=self._dev)
         mask_t = torch.as_tensor(mask, dtype=torch.int32, device=self._dev)
         B, S = ids_t.shape
-        if S > self.max_position or S > 512:
+        if S > self.max_position or S > self.max_seq:
             raise ValueError(f"sequence length {S} exceeds the encoder limit")
         Sp = (S + 31) // 32 * 32
         if Sp != S:   # pad with masked tokens (attention ignores them, pooling skips them)
@@ -154,7 +187,7 @@ class HipEncoder:
             raise ValueError("forward_lens: stage must be a contiguous int32 CUDA tensor [n_rows, S + 1]")
         if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n_rows, self.hidden):
             raise ValueError("forward_lens: out must be a contiguous float32 CUDA tensor [n_rows, hidden]")
-        if S % 32 or S > self.max_position or S > 512:
+        if S % 32 or S > self.max_position or S > self.max_seq:
             raise ValueError(f"sequence length {S} must be a multiple of 32 within the encoder limit")
         base = stage.data_ptr()
         check(self._lib.ak_encoder_forward_lens(self._h, ctypes.c_void_p(base), S + 1, ctypes.c_void_p(base + 4 * S), S + 1, n_rows, S,
@@ -392,3 +425,96 @@ def load_mpnet_weights(model_dir: str):
     w = mpnet_encoder_weights(w, pos_full)
     shape = (cfg["vocab_size"], H, L, heads, cfg["intermediate_size"], min(max_pos, 512))
     return shape, w, sd["encoder.relative_attention_bias.weight"], float(cfg.get("layer_norm_eps", 1e-12))
+
+
+# HF XLMRobertaLayer / BertLayer names (under encoder.layer.{l}.) -> ours
+XLMR_LAYER_NAMES = (("attention.self.query.weight", "wq"), ("attention.self.query.bias", "bq"),
+                    ("attention.self.key.weight", "wk"), ("attention.self.key.bias", "bk"),
+                    ("attention.self.value.weight", "wv"), ("attention.self.value.bias", "bv"),
+                    ("attention.output.dense.weight", "wo"), ("attention.output.dense.bias", "bo"),
+                    ("attention.output.LayerNorm.weight", "ln1_g"), ("attention.output.LayerNorm.bias", "ln1_b"),
+                    ("intermediate.dense.weight", "w1"), ("intermediate.dense.bias", "b1"),
+                    ("output.dense.weight", "w2"), ("output.dense.bias", "b2"),
+                    ("output.LayerNorm.weight", "ln2_g"), ("output.LayerNorm.bias", "ln2_b"))
+
+
+def load_xlmr_weights(model_dir: str):
+    """Load a local HF XLM-RoBERTa / RoBERTa checkpoint directory (config.json model_type "xlm-roberta" | "roberta" +
+    model.safetensors | pytorch_model.bin; a "roberta." or "model." prefix on the names is stripped). No network. Returns
+    (shape, weights, eps, padding_idx): shape as load_hf_weights' with max_position = max_position_embeddings (the FULL position table,
+    padding_idx row included: the encoder takes its positions from the ids, ak_encoder_set_positions_from_ids), weights in the
+    encoder's order with the model's own token-type row. What the HIP encoder does not implement is refused with ValueError."""
+    import json
+    import os
+    cfg = json.load(open(os.path.join(model_dir, "config.json")))
+    if cfg.get("model_type") not in ("xlm-roberta", "roberta"):
+        raise ValueError(f"{model_dir}: model_type {cfg.get('model_type')!r} is not XLM-RoBERTa / RoBERTa")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"{model_dir}: hidden_act {cfg.get('hidden_act')!r} (the HIP encoder implements erf GELU)")
+    if cfg.get("position_embedding_type", "absolute") != "absolute":
+        raise ValueError(f"{model_dir}: position_embedding_type {cfg.get('position_embedding_type')!r} is not supported")
+    H, heads = cfg["hidden_size"], cfg["num_attention_heads"]
+    if H > 1024:
+        raise ValueError(f"{model_dir}: hidden_size {H} (the HIP encoder implements hidden <= 1024)")
+    if H % heads or H // heads not in (32, 64):
+        raise ValueError(f"{model_dir}: head size {H / heads:g} (the HIP encoder implements 32 and 64)")
+    pad = int(cfg.get("pad_token_id", XLMR_PADDING_IDX))
+    max_pos = int(cfg["max_position_embeddings"])
+    if max_pos - pad - 1 < 32:
+        raise ValueError(f"{model_dir}: max_position_embeddings {max_pos} leaves fewer than 32 positions")
+    st, pt = os.path.join(model_dir, "model.safetensors"), os.path.join(model_dir, "pytorch_model.bin")
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+        sd = load_file(st)
+    elif os.path.exists(pt):
+        import torch
+        sd = torch.load(pt, map_location="cpu", weights_only=True)
+    else:
+        raise FileNotFoundError(f"{model_dir}: neither model.safetensors nor pytorch_model.bin")
+    strip = lambda k: k[8:] if k.startswith("roberta.") else (k[6:] if k.startswith("model.") else k)
+    sd = {strip(k): v.float() for k, v in sd.items()}
+    L = cfg["num_hidden_layers"]
+    w = {"word_emb": sd["embeddings.word_embeddings.weight"], "pos_emb": sd["embeddings.position_embeddings.weight"],
+         "type_emb": sd["embeddings.token_type_embeddings.weight"][:1], "emb_ln_g": sd["embeddings.LayerNorm.weight"],
+         "emb_ln_b": sd["embeddings.LayerNorm.bias"]}
+    for l in range(L):
+        p, q = f"encoder.layer.{l}.", f"l{l}."
+        for hf, m in XLMR_LAYER_NAMES:
+            w[q + m] = sd[p + hf]
+    shape = (cfg["vocab_size"], H, L, heads, cfg["intermediate_size"], max_pos)
+    return shape, w, float(cfg.get("layer_norm_eps", 1e-5)), pad
+
+
+def random_xlmr_weights(shape, seed: int = 0):
+    """Seeded random weights of an XLM-R shape (an XLMR_SHAPES name or tuple) in the encoder's order: the full position table
+    [max_position_embeddings][H] and ONE non-zero token-type row (XLM-R's type_vocab_size is 1 and its row is trained). Matrices are
+    ROUNDED TO bf16 (kept as float32), so a float32 reference on the same values measures the kernels' activation rounding alone.
+    The position table is drawn with std 0.1 and the attention projections with std 0.06 (five and three times the rest): which
+    position a token gets must visibly move the output, or a kernel that ignored the positions pass would pass."""
+    import torch
+    if isinstance(shape, str):
+        shape = XLMR_SHAPES[shape]
+    vocab, H, L, heads, I, max_pos = shape[:6]
+    w = random_init_weights(vocab, H, L, I, max_pos, seed=seed)
+    w["type_emb"] = w["type_emb"][:1]
+    w["pos_emb"] = w["pos_emb"] * 5.0
+    for k, v in list(w.items()):
+        if k.split(".")[-1] in ("wq", "wk", "wv", "wo"):
+            w[k] = v = v * 3.0
+        if k in ("word_emb", "pos_emb", "type_emb") or k.split(".")[-1] in MATRIX_KEYS:
+            w[k] = torch.from_numpy(v).to(torch.bfloat16).float().numpy()
+    return w
+
+
+def xlmr_hf_state_dict(w, layers: int):
+    """Our weight names (random_xlmr_weights form) -> HF XLMRobertaModel's state dict (no "roberta." prefix)."""
+    import torch
+    t = lambda x: torch.as_tensor(np.asarray(x, np.float32))
+    sd = {"embeddings.word_embeddings.weight": t(w["word_emb"]), "embeddings.position_embeddings.weight": t(w["pos_emb"]),
+          "embeddings.token_type_embeddings.weight": t(w["type_emb"]), "embeddings.LayerNorm.weight": t(w["emb_ln_g"]),
+          "embeddings.LayerNorm.bias": t(w["emb_ln_b"])}
+    for l in range(layers):
+        p, q = f"encoder.layer.{l}.", f"l{l}."
+        for hf, m in XLMR_LAYER_NAMES:
+            sd[p + hf] = t(w[q + m])
+    return sd

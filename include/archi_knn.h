@@ -335,6 +335,23 @@ int ak_encoder_forward_lens(ak_encoder_t h, const int32_t *ids_dev, int ld_ids, 
  * type_emb row with type_vocab = 1. */
 int ak_encoder_set_rel_bias(ak_encoder_t h, const float *bias_dev, int heads, int n_rel);
 
+/* Positions from the ids (RoBERTa / XLM-R: BAAI/bge-m3, intfloat/multilingual-e5-*, paraphrase-multilingual-mpnet-base-v2, the
+ * multilingual embedders an archi deployment names behind manager.py:373), as HF's create_position_ids_from_input_ids computes them:
+ * a token inside the row (mask != 0, or before the row's length) whose id is not padding_idx sits at position padding_idx + the number
+ * of such tokens up to and including it; every other token at padding_idx. A text holding a literal <pad> thus shifts the positions of
+ * the tokens behind it, as in HF. (HF looks at the ids alone; here a token outside the mask never counts, so that ids past a row's
+ * length are ignored. The two agree on right-padded rows; they differ only for a mask with zeros on non-pad ids before real tokens.) pos_emb is then the FULL position table (max_position = max_position_embeddings rows, the
+ * padding_idx row included) and type_emb the model's one token-type row (type_vocab = 1).
+ *   padding_idx  >= 0; the model's pad id
+ *   max_seq      the longest row (S) the encoder then accepts: 1 <= max_seq <= 8192 and padding_idx + 1 + max_seq <= max_position;
+ *                above 512 only in precision bf16 at head size 64 (hidden != 384): tiles with S > 512 run the long-row flash attention
+ *                (csrc/attn_long.hip), tiles with S <= 512 the kernels they ran before
+ * Call it once, after ak_encoder_create and before the first forward pass; it applies to ak_encoder_forward and
+ * ak_encoder_forward_lens in every precision. Not combined with ak_encoder_set_rel_bias (either call fails once the other was made);
+ * the single-launch query forward (AK_QUERY_FUSED) is not taken by such an encoder. An encoder on which it is not called keeps
+ * position = token index. */
+int ak_encoder_set_positions_from_ids(ak_encoder_t h, int padding_idx, int max_seq);
+
 /* The 8192-entry bf16 table the fused hidden-384 layer kernel and the wide FFN-up tile read their GELU from (csrc/gelu_table.h):
  * entry i = bf16(gelu(v)), v = the MIDPOINT of the IEEE half bit patterns [8 i, 8 i + 8) (sign, 5 exponent bits, 7 mantissa bits;
  * the lookup truncates, so the midpoint halves its error), exact erf GELU
