@@ -70,6 +70,25 @@ class AkDecoderConfig(ctypes.Structure):
     ]
 
 
+MBERT_MAX_LAYERS = 64     # AK_MBERT_MAX_LAYERS
+
+
+class AkModernBertConfig(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("heads", ctypes.c_int),
+        ("intermediate", ctypes.c_int),
+        ("max_position", ctypes.c_int),
+        ("norm_eps", ctypes.c_float),
+        ("global_rope_theta", ctypes.c_float),
+        ("local_rope_theta", ctypes.c_float),
+        ("half_window", ctypes.c_int),
+        ("layer_global", ctypes.c_int * MBERT_MAX_LAYERS),
+    ]
+
+
 _lock = threading.Lock()
 _lib = None
 _inited_device = None
@@ -124,6 +143,9 @@ SYMBOLS = [
     ("ak_decoder_destroy", _I, [_P]),
     ("ak_decoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     ("ak_decoder_rope_table", _I, [ctypes.c_float, _I, _I, _P, _P]),
+    ("ak_mbert_create", _I, [ctypes.POINTER(AkModernBertConfig), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_mbert_destroy", _I, [_P]),
+    ("ak_mbert_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_create_ex", _I, [ctypes.c_char_p, _I, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.POINTER(ctypes.c_char_p), _I, ctypes.POINTER(_P)]),

@@ -29,6 +29,11 @@ EMBEDDING_DIMENSIONS = {
     "Qwen/Qwen3-Embedding-0.6B": 1024,
     "Qwen/Qwen3-Embedding-4B": 2560,
     "Qwen/Qwen3-Embedding-8B": 4096,
+    "nomic-ai/modernbert-embed-base": 768,
+    "Alibaba-NLP/gte-modernbert-base": 768,
+    "lightonai/modernbert-embed-large": 1024,
+    "answerdotai/ModernBERT-base": 768,
+    "answerdotai/ModernBERT-large": 1024,
 }
 
 

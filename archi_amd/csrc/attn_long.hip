@@ -1,7 +1,9 @@
 // attn_long.hip -- bidirectional flash attention of the BERT encoder for rows longer than 512 tokens (512 < S <= 8192, head size 64,
 // bf16; XLM-RoBERTa / bge-m3 encoders given ak_encoder_set_positions_from_ids(max_seq > 512)):
 //   ctx = softmax(q k^T / sqrt(64) + mask) v      per (sequence, head)
-// Tiles with S <= 512 never come here (attention.hip). q arrives pre-scaled by log2(e) / 8 from the QKV GEMM, so the softmax runs in
+// The encoder's tiles with S <= 512 never come here (attention.hip). ModernBERT (mbert.hip) runs every tile, 32 <= S <= 8192, on this
+// kernel through launch_attn_window: its global layers on the same instantiation, its sliding-window layers on k_attn_long<true> (below).
+// q arrives pre-scaled by log2(e) / 8 from the QKV GEMM, so the softmax runs in
 // the base-2 domain on v_exp_f32; v arrives transposed ([B][H][S], keys of every 16-group in vt_pos order) as attention.hip takes it.
 //
 // Workgroup = (128-query block, head, sequence), four waves of 32 queries. The 32-key blocks of K and V^T stream through two LDS
@@ -16,6 +18,7 @@
 // Key blocks wholly past the row's length (rowlen, k_positions) are not loaded; query blocks wholly past it write zero context rows.
 // K tile [32 keys][64 d]: 128-byte rows, chunk c of key r at c ^ (r & 7); V^T tile [64 d][32 keys]: 64-byte rows, chunk c of row d at
 // c ^ ((d >> 1) & 3) (the XOR swizzles of attn_causal.hip: the lanes of a ds_read_b128 phase hit distinct bank groups).
+// LDS per workgroup: 16 640 bytes (2 x 4 KB K, 2 x 4 KB V^T, 2 x 32 mask floats), both instantiations.
 #include "encoder_kernels.h"
 #include "mfma_tile.h"
 
@@ -26,6 +29,11 @@ namespace {
 constexpr int AL_HD = 64, AL_QB = 128;
 constexpr int AL_K_BYTES = 32 * AL_HD * 2, AL_V_BYTES = AL_HD * 64;
 
+// WIN (ModernBERT's sliding layers, a.window = half-window w >= 1): key k is visible to query q iff |q - k| <= w. The workgroup walks
+// only the key blocks that intersect [q_begin - w, q_begin + 127 + w] (9 at most for w = 64); a wave skips the blocks that lie wholly
+// outside the band of its own 32 queries and applies the band (-inf) only in the blocks that straddle its edge -- blocks wholly inside
+// take the same instructions as WIN = false. WIN = false is the kernel as it was (every key block up to the row's length).
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) char sK[2][AL_K_BYTES];
     __shared__ __attribute__((aligned(16))) char sV[2][AL_V_BYTES];
@@ -45,17 +53,22 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
         }
         return;
     }
-    const int kb_stop = (len + 31) / 32;
+    int kb_stop = (len + 31) / 32, kb_start = 0;
+    if constexpr (WIN) {
+        kb_start = max(q_begin - a.window, 0) / 32;            // q_begin < len: block q_begin / 32 is inside [kb_start, kb_stop)
+        kb_stop = min(kb_stop, (q_begin + AL_QB - 1 + a.window) / 32 + 1);
+    }
     // staging assignment: thread tid moves K chunk (key tid / 8, chunk tid % 8) and V^T chunk (row d = tid / 4, chunk tid % 4)
     const int k_key = tid >> 3, k_c = tid & 7, v_d = tid >> 2, v_c = tid & 3;
     const uint16_t *kg = a.k + row0 * H + (int64_t)h * a.qk_hs + (int64_t)k_key * a.qk_ld + k_c * 8;
+    const int c0 = kb_start & 1;                               // LDS buffer of the first block (buffers go by block parity)
     const uint16_t *vg = a.vt + ((int64_t)b * H + h * AL_HD + v_d) * S + v_c * 8;
     const int k_dst = k_key * 128 + ((k_c ^ (k_key & 7)) << 4), v_dst = v_d * 64 + ((v_c ^ ((v_d >> 1) & 3)) << 4);
-    uint4 kreg = *(const uint4 *)kg, vreg = *(const uint4 *)vg;
-    float mreg = tid < 32 ? (a.mask[row0 + tid] ? 0.f : -INFINITY) : 0.f;
-    *(uint4 *)(sK[0] + k_dst) = kreg;
-    *(uint4 *)(sV[0] + v_dst) = vreg;
-    if (tid < 32) sM[0][tid] = mreg;
+    uint4 kreg = *(const uint4 *)(kg + (int64_t)kb_start * 32 * a.qk_ld), vreg = *(const uint4 *)(vg + kb_start * 32);
+    float mreg = tid < 32 ? (a.mask[row0 + kb_start * 32 + tid] ? 0.f : -INFINITY) : 0.f;
+    *(uint4 *)(sK[c0] + k_dst) = kreg;
+    *(uint4 *)(sV[c0] + v_dst) = vreg;
+    if (tid < 32) sM[c0][tid] = mreg;
 
     uint4 qf[4];
     {
@@ -69,7 +82,7 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
     for (int i = 0; i < 2; i++) o[i] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
     __syncthreads();
-    for (int kb = 0; kb < kb_stop; kb++) {
+    for (int kb = kb_start; kb < kb_stop; kb++) {
         const int cur = kb & 1;
         const bool more = kb + 1 < kb_stop;
         if (more) {                                            // next block into registers: in flight under this block's MFMAs
@@ -77,7 +90,10 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
             vreg = *(const uint4 *)(vg + (kb + 1) * 32);
             if (tid < 32) mreg = a.mask[row0 + (kb + 1) * 32 + tid] ? 0.f : -INFINITY;
         }
-        if (has_q) {
+        // the block against this wave's queries q0 .. q0 + 31 (wave-uniform): dk_hi / dk_lo = largest key - query / query - key
+        const int dk_hi = kb * 32 + 31 - q0, dk_lo = q0 + 31 - kb * 32;
+        const bool in_band = !WIN || (dk_hi - 62 <= a.window && dk_lo - 62 <= a.window);      // some (query, key) pair is visible
+        if (has_q && in_band) {
             const char *k_t = sK[cur], *v_t = sV[cur];
             f32x16 s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -90,7 +106,19 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 s[i] += sM[cur][8 * (i >> 2) + 4 * kh + (i & 3)];
-                mb = fmaxf(mb, s[i]);
+                if constexpr (!WIN) mb = fmaxf(mb, s[i]);
+            }
+            if constexpr (WIN) {
+                if (dk_hi > a.window || dk_lo > a.window) {    // an edge block: the band, per (query r, key) pair
+                    const int dq = kb * 32 + 4 * kh - (q0 + r);    // key - query of accumulator 0
+#pragma unroll
+                    for (int i = 0; i < 16; i++) {
+                        const int dk = dq + 8 * (i >> 2) + (i & 3);
+                        if (dk > a.window || -dk > a.window) s[i] = -INFINITY;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 16; i++) mb = fmaxf(mb, s[i]);
             }
             mb = fmaxf(mb, __shfl_xor(mb, 32));
             const float mn = fmaxf(m, mb);
@@ -141,6 +169,21 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
 }
 }  // namespace
 
+// the same kernel for any S % 32 == 0 in [32, 8192] with an optional band (ModernBERT, mbert.hip): window < 0 or >= S: every key
+int launch_attn_window(const AttnArgs &a0, int window, hipStream_t st) {
+    AttnArgs a = a0;
+    if (a.qk_ld == 0) { a.qk_ld = a.H; a.qk_hs = a.H / a.heads; }
+    if (a.H != a.heads * AL_HD) AK_FAIL(-1, "attention (windowed): head size must be 64");
+    if (a.S <= 0 || a.S % 32 || a.S > ATTN_LONG_MAX_S) AK_FAIL(-1, "attention (windowed): S must be a positive multiple of 32, <= 8192");
+    if (!a.rowlen || !a.mask || a.rel) AK_FAIL(-1, "attention (windowed): needs the row lengths and the mask, no bias");
+    const dim3 grid((unsigned)((a.S + AL_QB - 1) / AL_QB), (unsigned)a.heads, (unsigned)a.B);
+    a.window = window;
+    if (window >= 0 && window < a.S) k_attn_long<true><<<grid, 256, 0, st>>>(a);
+    else k_attn_long<false><<<grid, 256, 0, st>>>(a);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_attn_long(const AttnArgs &a0, hipStream_t st) {
     AttnArgs a = a0;
     if (a.qk_ld == 0) { a.qk_ld = a.H; a.qk_hs = a.H / a.heads; }      // token-major q / k
@@ -148,7 +191,7 @@ int launch_attn_long(const AttnArgs &a0, hipStream_t st) {
     if (a.S % 32 || a.S <= 512 || a.S > ATTN_LONG_MAX_S) AK_FAIL(-1, "attention (rows > 512 tokens): S must be a multiple of 32 in (512, 8192]");
     if (!a.rowlen || !a.mask || a.rel) AK_FAIL(-1, "attention (rows > 512 tokens): needs the row lengths and the mask, no bias");
     const dim3 grid((unsigned)((a.S + AL_QB - 1) / AL_QB), (unsigned)a.heads, (unsigned)a.B);
-    k_attn_long<<<grid, 256, 0, st>>>(a);
+    k_attn_long<false><<<grid, 256, 0, st>>>(a);
     AK_HIP(hipGetLastError());
     return 0;
 }

@@ -44,11 +44,15 @@ struct AttnArgs {
     const float *rel = nullptr;
     // per-sequence row lengths [B] (k_positions): the long-row kernel (launch_attn_long) skips key and query blocks past them
     const int *rowlen = nullptr;
+    // half-window of the banded instantiation (launch_attn_window sets it): key k visible to query q iff |q - k| <= window
+    int window = -1;
 };
 // rows longer than 512 tokens (encoders given ak_encoder_set_positions_from_ids(max_seq > 512); bf16, head size 64): attn_long.hip,
 // 512 < S <= ATTN_LONG_MAX_S. Tiles with S <= 512 always run the kernels of attention.hip.
 constexpr int ATTN_LONG_MAX_S = 8192;
 int launch_attn_long(const AttnArgs &a, hipStream_t st);
+// the long-row kernel at any S % 32 == 0 in [32, 8192] with a band of half-width `window` (< 0 or >= S: none): ModernBERT (mbert.hip)
+int launch_attn_window(const AttnArgs &a, int window, hipStream_t st);
 // layout of the library's per-distance bias tables (ak_encoder_set_rel_bias): one row of REL_ROW floats per head, distance d at
 // REL_MID + d. Any (key, query) pair of a 32-query block of a wave / workgroup, S <= 512, lands inside the row.
 constexpr int REL_ROW = 2048, REL_MID = 1024;

@@ -1,0 +1,451 @@
+// mbert.hip -- the ModernBERT encoder forward pass (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base,
+// lightonai/modernbert-embed-large) behind ak_mbert_*: orchestration and the small kernels. As HF ModernBertModel:
+//   x = LayerNorm(tok_embeddings[id]; w)               k_mb_embed (float32 x, bf16 h = x: attn_norm of layer 0 is the identity)
+// per layer (pre-norm, no bias anywhere, LayerNorms with a weight only):
+//   q | k | v = h Wqkv^T                               k_gemm MODE 0 (gemm.hip): q pre-scaled by log2(e) / 8, k as [T][H], V transposed
+//   q, k = RoPE(q), RoPE(k)                            k_mb_rope, in place: rotate_half at head size 64, the table of the layer's type
+//                                                      (global theta / local theta)
+//   a = softmax(q k^T + band + pad mask) v             k_attn_long<WIN> (attn_long.hip): WIN = true with the half-window in a sliding layer
+//   x += a Wo^T; h = LayerNorm(x; mlp_norm)            k_gemm MODE 2 (float32 out) + k_mb_add_ln
+//   f = gelu(h Wi_a^T) (h Wi_g^T)                      k_gemm MODE 8 (GeGLU epilogue; the halves of Wi interleaved at create, and padded
+//                                                      with zero rows to 2 I % 256 == 0 -- large: 5248 -> 5376 -- for the wide tile)
+//   x += f Wo^T; h = LayerNorm(x; next attn_norm)      k_gemm MODE 2 + k_mb_add_ln
+// then final_norm per token, mean / cls pooling over the valid tokens and L2 normalisation in float32 (k_mb_pool_part, k_mb_pool_fin).
+// The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in decoder.hip.
+// LDS per workgroup: k_mb_embed / k_mb_add_ln / k_mb_rope none; k_mb_pool_part 4 * H * 4 bytes (dynamic: 12 KB at H = 768, 16 KB at
+// 1024); k_mb_pool_fin 16 bytes; the GEMMs and the attention kernel as their files state.
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#include "encoder_kernels.h"
+#include "mfma_tile.h"
+
+namespace ak {
+
+namespace {
+constexpr int MB_HD = 64, MB_MAX_S = ATTN_LONG_MAX_S, MB_MAX_H = 1024, MB_POOL_CHUNK = 64;
+
+__device__ inline float mb_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// LayerNorm statistics of one float32 row held in memory (H % 4 == 0), by one wave: mean, then the variance about it (two passes,
+// as torch's float32 kernel -- not E[x^2] - mean^2)
+__device__ inline void mb_row_stats(const float *__restrict__ xr, int H, int lane, float eps, float &mean, float &rstd) {
+    float s = 0.f;
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 f = *(const float4 *)(xr + c);
+        s += (f.x + f.y) + (f.z + f.w);
+    }
+    mean = mb_wave_sum(s) / (float)H;
+    float q = 0.f;
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 f = *(const float4 *)(xr + c);
+        const float a = f.x - mean, b = f.y - mean, cc = f.z - mean, d = f.w - mean;
+        q += (a * a + b * b) + (cc * cc + d * d);
+    }
+    rstd = rsqrtf(mb_wave_sum(q) / (float)H + eps);
+}
+
+// one wave per token slot t < B * S: ids past the row's length read as 0; x32 = LayerNorm(tok_embeddings[id]; w), h16 = bf16(x32).
+// Also the int key mask (slot < length) the attention kernel stages, and per row the clamped length.
+__global__ __launch_bounds__(256) void k_mb_embed(const int *__restrict__ ids, int ld_ids, const int *__restrict__ lens, int lens_stride, int B, int S,
+                                                  int H, int vocab, const uint16_t *__restrict__ emb, const float *__restrict__ w, float eps,
+                                                  float *__restrict__ x32, uint16_t *__restrict__ h16, int *__restrict__ mask, int *__restrict__ lens_out) {
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (t >= (int64_t)B * S) return;
+    const int b = (int)(t / S), sq = (int)(t - (int64_t)b * S);
+    int len = lens[(int64_t)b * lens_stride];
+    len = len < 0 ? 0 : (len > S ? S : len);
+    if (lane == 0) {
+        mask[t] = sq < len;
+        if (sq == 0) lens_out[b] = len;
+    }
+    int id = sq < len ? ids[(int64_t)b * ld_ids + sq] : 0;
+    if (id < 0 || id >= vocab) id = 0;                         // a stray id must not read out of bounds
+    const uint16_t *e = emb + (int64_t)id * H;
+    float *xr = x32 + t * H;
+    for (int c = lane * 4; c < H; c += 256) {
+        const uint2 v = *(const uint2 *)(e + c);
+        *(float4 *)(xr + c) = float4{bf16_to_f32((uint16_t)v.x), bf16_to_f32((uint16_t)(v.x >> 16)), bf16_to_f32((uint16_t)v.y), bf16_to_f32((uint16_t)(v.y >> 16))};
+    }
+    float mean, rstd;
+    mb_row_stats(xr, H, lane, eps, mean, rstd);                // (a lane re-reads only what it wrote itself)
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 f = *(const float4 *)(xr + c), g = *(const float4 *)(w + c);
+        const float4 y = {(f.x - mean) * rstd * g.x, (f.y - mean) * rstd * g.y, (f.z - mean) * rstd * g.z, (f.w - mean) * rstd * g.w};
+        *(float4 *)(xr + c) = y;
+        *(uint2 *)(h16 + t * H + c) = uint2{mt::pack_bf16x2(y.x, y.y), mt::pack_bf16x2(y.z, y.w)};
+    }
+}
+
+// one wave per token t < T: x32 += y32 (the sub-layer's float32 GEMM output), then h16 = LayerNorm(x32; w) (w == NULL: the add only).
+// The LayerNorm twin of k_dec_add_rmsnorm. The row stays in registers between the add, the two reductions and the store (NJ float4 per
+// lane, NJ = ceil(H / 256)): one pass over memory. Mean, then the variance about it, as mb_row_stats.
+template <int NJ>
+__global__ __launch_bounds__(256) void k_mb_add_ln(float *__restrict__ x32, const float *__restrict__ y32, int64_t T, int H, const float *__restrict__ w,
+                                                   float eps, uint16_t *__restrict__ h16) {
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (t >= T) return;
+    float *xr = x32 + t * H;
+    const float *yr = y32 + t * H;
+    float4 f[NJ];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int c = lane * 4 + j * 256;
+        f[j] = float4{0.f, 0.f, 0.f, 0.f};
+        if (c < H) {
+            f[j] = *(const float4 *)(xr + c);
+            const float4 y = *(const float4 *)(yr + c);
+            f[j].x += y.x; f[j].y += y.y; f[j].z += y.z; f[j].w += y.w;
+            *(float4 *)(xr + c) = f[j];
+            s += (f[j].x + f[j].y) + (f[j].z + f[j].w);
+        }
+    }
+    if (!w) return;
+    const float mean = mb_wave_sum(s) / (float)H;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+        if (lane * 4 + j * 256 < H) {
+            const float a = f[j].x - mean, b = f[j].y - mean, cc = f[j].z - mean, d = f[j].w - mean;
+            q += (a * a + b * b) + (cc * cc + d * d);
+        }
+    const float rstd = rsqrtf(mb_wave_sum(q) / (float)H + eps);
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int c = lane * 4 + j * 256;
+        if (c < H) {
+            const float4 g = *(const float4 *)(w + c);
+            *(uint2 *)(h16 + t * H + c) = uint2{mt::pack_bf16x2((f[j].x - mean) * rstd * g.x, (f[j].y - mean) * rstd * g.y),
+                                                mt::pack_bf16x2((f[j].z - mean) * rstd * g.z, (f[j].w - mean) * rstd * g.w)};
+        }
+    }
+}
+
+int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st) {
+    const unsigned rows4 = (unsigned)((T + 3) / 4);
+    switch ((H + 255) / 256) {
+        case 1: k_mb_add_ln<1><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;
+        case 2: k_mb_add_ln<2><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;
+        case 3: k_mb_add_ln<3><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;
+        default: k_mb_add_ln<4><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;      // H <= MB_MAX_H = 1024
+    }
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+// RoPE in place on the q and k rows the QKV GEMM wrote ([T][H] bf16 each, q already scaled: the rotation is linear). One thread per
+// (token, q | k, head, 8-element chunk c < 4): it takes elements 8 c .. 8 c + 7 and their rotate_half partners 32 + 8 c .. of one head,
+// 16 bytes each: x' = x cos + rot(x) sin, rot(x)[d] = -x[d + 32], rot(x)[d + 32] = x[d], at position t % S. rc / rs: the layer's
+// table [n_pos][32].
+__global__ __launch_bounds__(256) void k_mb_rope(uint16_t *__restrict__ q, uint16_t *__restrict__ k, int64_t T, int S, int H, const float *__restrict__ rc,
+                                                 const float *__restrict__ rs) {
+    const int per_tok = H / 8;                                 // 2 (q | k) x heads x 4 chunks
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t t = idx / per_tok;
+    if (t >= T) return;
+    const int rem = (int)(idx - t * per_tok), c = rem & 3, hs = rem >> 2, heads = H / MB_HD;
+    const int sq = (int)(t % S);
+    uint16_t *row = (hs < heads ? q + t * H + hs * MB_HD : k + t * H + (hs - heads) * MB_HD) + c * 8;
+    const uint4 a = *(const uint4 *)row, b = *(const uint4 *)(row + 32);
+    const float4 c0 = *(const float4 *)(rc + (int64_t)sq * 32 + c * 8), c1 = *(const float4 *)(rc + (int64_t)sq * 32 + c * 8 + 4);
+    const float4 s0 = *(const float4 *)(rs + (int64_t)sq * 32 + c * 8), s1 = *(const float4 *)(rs + (int64_t)sq * 32 + c * 8 + 4);
+    const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+    uint32_t ao[4], bo[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const float x0l = bf16_to_f32((uint16_t)aw[i]), x0h = bf16_to_f32((uint16_t)(aw[i] >> 16));
+        const float x1l = bf16_to_f32((uint16_t)bw[i]), x1h = bf16_to_f32((uint16_t)(bw[i] >> 16));
+        ao[i] = (uint32_t)f32_to_bf16(x0l * cs[2 * i] - x1l * sn[2 * i]) | ((uint32_t)f32_to_bf16(x0h * cs[2 * i + 1] - x1h * sn[2 * i + 1]) << 16);
+        bo[i] = (uint32_t)f32_to_bf16(x1l * cs[2 * i] + x0l * sn[2 * i]) | ((uint32_t)f32_to_bf16(x1h * cs[2 * i + 1] + x0h * sn[2 * i + 1]) << 16);
+    }
+    *(uint4 *)row = uint4{ao[0], ao[1], ao[2], ao[3]};
+    *(uint4 *)(row + 32) = uint4{bo[0], bo[1], bo[2], bo[3]};
+}
+
+// Pooling, stage 1. Workgroup (chunk ck, row b), 4 waves: y_t = (x_t - mean_t) rstd_t (the final LayerNorm without its weight) summed over
+// the pooled tokens of chunk ck -- tokens 64 ck .. 64 ck + 63 below n (mean: n = the row's length; cls: n = 1) --, wave v taking tokens
+// v, v + 4, ...; the four wave partials added in wave order -> part[b][ck][H]. Chunks at or past n write nothing (stage 2 does not read
+// them). Which tokens meet in which sum depends on the row's length alone, not on S or the batch around it.
+__global__ __launch_bounds__(256) void k_mb_pool_part(const float *__restrict__ x32, const int *__restrict__ lens, int S, int H, float eps, int pooling,
+                                                      float *__restrict__ part) {
+    extern __shared__ float mb_part[];                         // [4][H]
+    const int ck = blockIdx.x, b = blockIdx.y, nch = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len = lens[b];
+    const int n = len <= 0 ? 0 : (pooling == AK_POOL_CLS ? 1 : len);
+    if (ck * MB_POOL_CHUNK >= n) return;
+    const int stop = min(n, (ck + 1) * MB_POOL_CHUNK);
+    float4 acc[MB_MAX_H / 256];
+#pragma unroll
+    for (int j = 0; j < MB_MAX_H / 256; j++) acc[j] = float4{0.f, 0.f, 0.f, 0.f};
+    for (int tk = ck * MB_POOL_CHUNK + wave; tk < stop; tk += 4) {
+        const float *xr = x32 + ((int64_t)b * S + tk) * H;
+        float mean, rstd;
+        mb_row_stats(xr, H, lane, eps, mean, rstd);
+#pragma unroll
+        for (int j = 0; j < MB_MAX_H / 256; j++) {
+            const int c = lane * 4 + j * 256;
+            if (c < H) {
+                const float4 f = *(const float4 *)(xr + c);
+                acc[j].x += (f.x - mean) * rstd; acc[j].y += (f.y - mean) * rstd; acc[j].z += (f.z - mean) * rstd; acc[j].w += (f.w - mean) * rstd;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MB_MAX_H / 256; j++) {
+        const int c = lane * 4 + j * 256;
+        if (c < H) *(float4 *)(mb_part + wave * H + c) = acc[j];
+    }
+    __syncthreads();
+    float *o = part + ((int64_t)b * nch + ck) * H;
+    for (int c = tid; c < H; c += 256) o[c] = ((mb_part[c] + mb_part[H + c]) + mb_part[2 * H + c]) + mb_part[3 * H + c];
+}
+
+// Pooling, stage 2. One workgroup per row b: the chunk sums added in chunk order, * w / n, then the L2 normalisation. A row of length 0
+// embeds to zeros.
+__global__ __launch_bounds__(256) void k_mb_pool_fin(const float *__restrict__ part, int nch, const int *__restrict__ lens, int H, const float *__restrict__ w,
+                                                     int pooling, int normalise, float *__restrict__ out) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len = lens[b];
+    float *o = out + (int64_t)b * H;
+    if (len <= 0) {
+        for (int c = tid; c < H; c += 256) o[c] = 0.f;
+        return;
+    }
+    const int n = pooling == AK_POOL_CLS ? 1 : len, used = (n + MB_POOL_CHUNK - 1) / MB_POOL_CHUNK;
+    const float inv_n = 1.0f / (float)n;
+    float y[MB_MAX_H / 256];
+    float s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < MB_MAX_H / 256; j++) {
+        const int c = tid + j * 256;
+        y[j] = 0.f;
+        if (c < H) {
+            for (int ck = 0; ck < used; ck++) y[j] += part[((int64_t)b * nch + ck) * H + c];
+            y[j] = y[j] * w[c] * inv_n;
+            s2 += y[j] * y[j];
+        }
+    }
+    s2 = mb_wave_sum(s2);
+    if (lane == 0) red[wave] = s2;
+    __syncthreads();
+    const float tot = ((red[0] + red[1]) + red[2]) + red[3];
+    const float sc = normalise ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 1.0f;      // torch.nn.functional.normalize's eps
+#pragma unroll
+    for (int j = 0; j < MB_MAX_H / 256; j++) {
+        const int c = tid + j * 256;
+        if (c < H) o[c] = y[j] * sc;
+    }
+}
+
+// Wi [2 I][H] -> rows interleaved: row 2 j = Wi row j (GELU input), row 2 j + 1 = Wi row I + j (gate): gemm.hip MODE 8
+struct MbLayer {
+    const uint16_t *wqkv, *wo, *wi, *wo2;      // wi (interleaved) is owned, wo2 too when the intermediate size is padded
+    const float *attn_norm, *mlp_norm;         // attn_norm of layer 0: not read
+    bool global;
+};
+struct MBert {
+    AkModernBertConfig cfg;
+    const uint16_t *emb = nullptr; const float *emb_norm = nullptr, *final_norm = nullptr;
+    std::vector<MbLayer> layers;
+    std::vector<void *> owned;
+    float *zero_bias = nullptr, *rope_c[2] = {nullptr, nullptr}, *rope_s[2] = {nullptr, nullptr};      // [0] local theta, [1] global theta
+    int n_pos = 0;
+    int Ip = 0;                                // intermediate size as the GEMMs see it (>= cfg.intermediate: ak_mbert_create)
+    int64_t cap = 0, cap_v = 0; int cap_B = 0;
+    float *x32 = nullptr, *y32 = nullptr;
+    uint16_t *h16 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *f = nullptr;
+    float *part = nullptr;                     // pooling: chunk sums [B][ceil(S / 64)][H]
+    int *mask = nullptr, *lens = nullptr;
+    std::mutex mu;
+};
+
+void mb_free_ws(MBert &d) {
+    void *p[] = {d.x32, d.y32, d.h16, d.q, d.k, d.vt, d.ctx, d.f, d.mask, d.lens, d.part};
+    for (void *x : p) if (x) hipFree(x);
+    d.x32 = d.y32 = d.part = nullptr; d.h16 = d.q = d.k = d.vt = d.ctx = d.f = nullptr; d.mask = d.lens = nullptr;
+    d.cap = 0; d.cap_B = 0;
+}
+
+// workspace for tpad token rows (a multiple of 256) and B rows; zeroed when (re)allocated, so rows that no kernel writes (GEMM
+// padding rows past B * S) stay finite
+int mb_reserve(MBert &d, int64_t tpad, int B) {
+    if (tpad <= d.cap && B <= d.cap_B) return 0;
+    if (tpad < d.cap) tpad = d.cap;
+    if (B < d.cap_B) B = d.cap_B;
+    mb_free_ws(d);
+    const int64_t H = d.cfg.hidden, I = d.Ip;
+    struct { void **p; size_t bytes; } bufs[] = {
+        {(void **)&d.x32, (size_t)(tpad * H * 4)}, {(void **)&d.y32, (size_t)(tpad * H * 4)}, {(void **)&d.h16, (size_t)(tpad * H * 2)},
+        {(void **)&d.q, (size_t)(tpad * H * 2)}, {(void **)&d.k, (size_t)(tpad * H * 2)}, {(void **)&d.vt, (size_t)(tpad * H * 2)},
+        {(void **)&d.ctx, (size_t)(tpad * H * 2)}, {(void **)&d.f, (size_t)(tpad * I * 2)}, {(void **)&d.mask, (size_t)tpad * 4},
+        {(void **)&d.lens, (size_t)B * 4}, {(void **)&d.part, (size_t)((tpad / MB_POOL_CHUNK + B) * H * 4)},      // B ceil(S / 64) <= T / 64 + B
+    };
+    for (auto &bf : bufs) {
+        AK_HIP(hipMalloc(bf.p, bf.bytes));
+        AK_HIP(hipMemset(*bf.p, 0, bf.bytes));
+    }
+    d.cap = tpad; d.cap_B = B;
+    return 0;
+}
+
+int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling, int normalise,
+                      float *out, hipStream_t st) {
+    const AkModernBertConfig &c = d.cfg;
+    const int H = c.hidden, I = d.Ip, heads = c.heads;
+    const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
+    if (mb_reserve(d, tpad, B)) return -10;
+    const unsigned rows4 = (unsigned)((T + 3) / 4);
+    k_mb_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.emb_norm, c.norm_eps, d.x32, d.h16, d.mask, d.lens);
+    AK_HIP(hipGetLastError());
+    for (size_t l = 0; l < d.layers.size(); l++) {
+        const MbLayer &ly = d.layers[l];
+        GemmArgs g{};
+        g.bias = d.zero_bias; g.T = (int)tpad;
+        // q (scaled) | k | V^T
+        g.X = d.h16; g.W = ly.wqkv; g.N = 3 * H; g.K = H;
+        g.q = d.q; g.k = d.k; g.vt = d.vt; g.H = H; g.S = S; g.qscale = 1.4426950408889634f / sqrtf((float)MB_HD);
+        g.ldo = (int)T;                                        // MODE 0: number of real tokens (rows beyond it have no V^T slot)
+        if (launch_gemm(0, g, st)) return -10;
+        const int tb = ly.global ? 1 : 0;
+        k_mb_rope<<<(unsigned)((T * (H / 8) + 255) / 256), 256, 0, st>>>(d.q, d.k, T, S, H, d.rope_c[tb], d.rope_s[tb]);
+        AK_HIP(hipGetLastError());
+        AttnArgs a{d.q, d.k, d.vt, d.mask, d.ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, d.lens};
+        if (launch_attn_window(a, ly.global ? -1 : c.half_window, st)) return -10;
+        // x += ctx Wo^T; h = LayerNorm(x; mlp_norm)
+        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
+        g.X = d.ctx; g.W = ly.wo; g.N = H; g.K = H; g.out_f32 = d.y32;
+        if (launch_gemm(2, g, st)) return -10;
+        if (launch_mb_add_ln(d.x32, d.y32, T, H, ly.mlp_norm, c.norm_eps, d.h16, st)) return -10;
+        // f = gelu(h Wi_a^T) (h Wi_g^T)
+        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
+        g.X = d.h16; g.W = ly.wi; g.N = 2 * I; g.K = H; g.out_bf16 = d.f; g.ldo = I;
+        if (launch_gemm(8, g, st)) return -10;
+        // x += f Wo^T; h = LayerNorm(x; next layer's attn_norm) (after the last layer: the add only, the pool applies final_norm)
+        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
+        g.X = d.f; g.W = ly.wo2; g.N = H; g.K = I; g.out_f32 = d.y32;
+        if (launch_gemm(2, g, st)) return -10;
+        const float *wn = l + 1 < d.layers.size() ? d.layers[l + 1].attn_norm : nullptr;
+        if (launch_mb_add_ln(d.x32, d.y32, T, H, wn, c.norm_eps, d.h16, st)) return -10;
+    }
+    const int nch = (S + MB_POOL_CHUNK - 1) / MB_POOL_CHUNK;
+    k_mb_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(d.x32, d.lens, S, H, c.norm_eps, pooling, d.part);
+    AK_HIP(hipGetLastError());
+    k_mb_pool_fin<<<B, 256, 0, st>>>(d.part, nch, d.lens, H, d.final_norm, pooling, normalise, out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+}  // namespace ak
+
+using namespace ak;
+
+extern "C" int ak_mbert_destroy(ak_mbert_t h) {
+    AK_BIND();
+    if (!h) return 0;
+    MBert *d = (MBert *)h;
+    hipDeviceSynchronize();
+    mb_free_ws(*d);
+    for (void *p : d->owned) hipFree(p);
+    delete d;
+    return 0;
+}
+
+extern "C" int ak_mbert_create(const AkModernBertConfig *cfg, const void *const *w, int n_weights, ak_mbert_t *out) {
+    AK_BIND();
+    if (!cfg || !w || !out) AK_FAIL(-1, "ak_mbert_create: NULL argument");
+    *out = nullptr;
+    const AkModernBertConfig c = *cfg;
+    const int H = c.hidden, I = c.intermediate, L = c.layers;
+    if (L <= 0 || c.vocab_size <= 0 || c.heads <= 0 || H <= 0 || I <= 0 || c.max_position <= 0) AK_FAIL(-1, "ak_mbert_create: sizes must be positive");
+    if (L > AK_MBERT_MAX_LAYERS) AK_FAIL(-1, "ak_mbert_create: more than AK_MBERT_MAX_LAYERS layers");
+    if (H != c.heads * MB_HD) AK_FAIL(-1, "ak_mbert_create: head size (hidden / heads) must be 64");
+    if (H % 128 || H > MB_MAX_H || I % 64) AK_FAIL(-1, "ak_mbert_create: hidden must be a multiple of 128 (<= 1024), intermediate a multiple of 64");
+    if (c.half_window < 1) AK_FAIL(-1, "ak_mbert_create: half_window must be >= 1");
+    if (!(c.norm_eps > 0.f) || !(c.global_rope_theta > 0.f) || !(c.local_rope_theta > 0.f)) AK_FAIL(-1, "ak_mbert_create: norm_eps and the rope thetas must be positive");
+    if (n_weights != 3 + 6 * L) AK_FAIL(-1, "ak_mbert_create: expected 3 + 6 * layers weight pointers");
+    for (int i = 0; i < n_weights; i++)
+        if (!w[i]) AK_FAIL(-1, "ak_mbert_create: NULL weight pointer");
+    MBert *d = new MBert();
+    d->cfg = c;
+    d->emb = (const uint16_t *)w[0];
+    d->emb_norm = (const float *)w[1];
+    d->final_norm = (const float *)w[2];
+    auto fail = [&](const char *what) { set_error(what); ak_mbert_destroy(d); return -10; };
+    auto dev = [&](size_t bytes) -> void * {
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        d->owned.push_back(p);
+        return p;
+    };
+    // 2 I off the wide GEMM tile (large: 5248 = 41 x 128): the interleaved Wi gets zero rows up to a multiple of 256 and mlp.Wo zero
+    // columns to match (gelu(0) 0 = 0 meets a zero weight: bit-identical results). Measured, large shape 128 x 512: 62.9 ms against 67.2
+    const int Ip = (2 * I) % 256 ? (I + 127) / 128 * 128 : I;
+    d->Ip = Ip;
+    const size_t zb = std::max<size_t>((size_t)3 * H, (size_t)2 * Ip);
+    d->zero_bias = (float *)dev(zb * 4);
+    if (!d->zero_bias || hipMemset(d->zero_bias, 0, zb * 4) != hipSuccess) return fail("ak_mbert_create: hipMalloc failed");
+    // the two rotary tables, positions 0 .. min(max_position, 8192) - 1 (the decoder's host routine at head size 64)
+    d->n_pos = c.max_position < MB_MAX_S ? c.max_position : MB_MAX_S;
+    for (int tb = 0; tb < 2; tb++) {
+        std::vector<float> hc((size_t)d->n_pos * 32), hs((size_t)d->n_pos * 32);
+        if (ak_decoder_rope_table(tb ? c.global_rope_theta : c.local_rope_theta, MB_HD, d->n_pos, hc.data(), hs.data())) return fail("ak_mbert_create: rotary table failed");
+        d->rope_c[tb] = (float *)dev(hc.size() * 4);
+        d->rope_s[tb] = (float *)dev(hs.size() * 4);
+        if (!d->rope_c[tb] || !d->rope_s[tb] || hipMemcpy(d->rope_c[tb], hc.data(), hc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d->rope_s[tb], hs.data(), hs.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return fail("ak_mbert_create: rotary table upload failed");
+    }
+    for (int l = 0; l < L; l++) {
+        const void *const *p = w + 3 + 6 * l;      // attn_norm wqkv wo mlp_norm wi mlp_wo
+        MbLayer ly{};
+        uint16_t *wi = (uint16_t *)dev((size_t)2 * Ip * H * 2);
+        if (!wi || (Ip != I && hipMemset(wi, 0, (size_t)2 * Ip * H * 2) != hipSuccess)) return fail("ak_mbert_create: hipMalloc failed");
+        // row 2 j = Wi row j, row 2 j + 1 = Wi row I + j (gemm.hip MODE 8)
+        const uint16_t *src = (const uint16_t *)p[4];
+        if (hipMemcpy2D(wi, (size_t)4 * H, src, (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy2D(wi + H, (size_t)4 * H, src + (size_t)I * H, (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess)
+            return fail("ak_mbert_create: Wi interleave failed");
+        ly.attn_norm = (const float *)p[0]; ly.wqkv = (const uint16_t *)p[1]; ly.wo = (const uint16_t *)p[2];
+        ly.mlp_norm = (const float *)p[3]; ly.wi = wi; ly.wo2 = (const uint16_t *)p[5];
+        if (Ip != I) {                             // mlp.Wo [H][I] -> [H][Ip] with zero columns behind I
+            uint16_t *wo2 = (uint16_t *)dev((size_t)H * Ip * 2);
+            if (!wo2 || hipMemset(wo2, 0, (size_t)H * Ip * 2) != hipSuccess ||
+                hipMemcpy2D(wo2, (size_t)2 * Ip, p[5], (size_t)2 * I, (size_t)2 * I, H, hipMemcpyDeviceToDevice) != hipSuccess)
+                return fail("ak_mbert_create: mlp.Wo padding failed");
+            ly.wo2 = wo2;
+        }
+        ly.global = c.layer_global[l] != 0;
+        d->layers.push_back(ly);
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail("ak_mbert_create: weight preparation failed");
+    *out = d;
+    return 0;
+}
+
+extern "C" int ak_mbert_forward_lens(ak_mbert_t h, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling,
+                                     int normalise, float *out, void *stream) {
+    AK_BIND();
+    if (!h) AK_FAIL(-1, "ak_mbert_forward_lens: NULL handle");
+    RoctxRange range("ak_mbert_forward_lens");
+    MBert &d = *(MBert *)h;
+    if (B <= 0) return 0;
+    if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, "ak_mbert_forward_lens: bad arguments");
+    if (pooling != AK_POOL_MEAN && pooling != AK_POOL_CLS) AK_FAIL(-1, "ak_mbert_forward_lens: pooling must be AK_POOL_MEAN or AK_POOL_CLS");
+    if (S <= 0 || S % 32 || S > MB_MAX_S) AK_FAIL(-1, "ak_mbert_forward_lens: S must be a positive multiple of 32, <= 8192");
+    if (S > d.n_pos) AK_FAIL(-1, "ak_mbert_forward_lens: S exceeds max_position");
+    if (B > 65535) AK_FAIL(-1, "ak_mbert_forward_lens: at most 65535 rows per call");      // a grid dimension of the attention and pooling launches
+    std::lock_guard<std::mutex> lk(d.mu);
+    return mb_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, (hipStream_t)stream);
+}

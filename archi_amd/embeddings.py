@@ -14,7 +14,8 @@ Errors are RAISED (never partial results): the manager records a failed file per
 Host side (this file): text normalisation, WordPiece tokenisation, length-sorted batching.
 Device side: archi_amd.encoder.HipEncoder (hand-written HIP). No CPU fallback.
 Qwen3-Embedding checkpoints (config.json model_type "qwen3") run on archi_amd.decoder.HipDecoder instead, tokenised by the
-checkpoint's own tokenizer.json, pooled on the last token; the same batching harness drives both.
+checkpoint's own tokenizer.json, pooled on the last token; ModernBERT checkpoints (model_type "modernbert") run on
+archi_amd.modernbert.HipModernBert; the same batching harness drives all of them.
 """
 from __future__ import annotations
 
@@ -33,6 +34,8 @@ from .encoder import (LONG_MAX_SEQ, MODEL_SHAPES, MPNET_SHAPES, XLMR_PADDING_IDX
                       load_mpnet_weights, load_xlmr_weights, long_rows_supported, mpnet_rel_bias_table, random_init_weights,
                       random_mpnet_weights, random_xlmr_weights, read_sentence_transformers_config)
 from .decoder import MAX_SEQ, QWEN3_SHAPES, BpeTokenizer, HipDecoder, load_qwen3_weights, random_qwen3_weights, read_decoder_st_config
+from .modernbert import MODERNBERT_SHAPES, HipModernBert, load_modernbert_weights, random_modernbert_weights
+from .modernbert import MAX_SEQ as MODERNBERT_MAX_SEQ
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
 # special tokens by name: (cls, sep, unk, the strings the full tokenizer matches in raw text)
@@ -176,6 +179,15 @@ def _is_qwen3(model_name: str) -> bool:
     return model_name in QWEN3_SHAPES
 
 
+def _is_modernbert(model_name: str) -> bool:
+    """A ModernBERT checkpoint directory (config.json model_type "modernbert") or one of the named ModernBERT shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "modernbert"
+    return model_name in MODERNBERT_SHAPES
+
+
 def _is_mpnet(model_name: str) -> bool:
     """An MPNet checkpoint directory (config.json model_type "mpnet") or one of the named MPNet shapes."""
     import json
@@ -221,6 +233,9 @@ class ArchiHipEmbeddings:
         self._stage_lock = threading.Lock()
         if _is_qwen3(model_name):
             self._init_decoder(model_name, device)
+            return
+        if _is_modernbert(model_name):
+            self._init_modernbert(model_name, device)
             return
         rel_bias = pos_pad = None
         if _is_xlmr(model_name):
@@ -369,6 +384,40 @@ class ArchiHipEmbeddings:
         self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, MAX_SEQ)
         self.dimensions = int(shape[1])
         self.encoder = HipDecoder(shape, weights, device=device)
+
+    def _init_modernbert(self, model_name: str, device: Optional[int]) -> None:
+        """ModernBERT (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base, lightonai/modernbert-embed-large): a local
+        checkpoint directory (config.json model_type modernbert, safetensors, tokenizer.json, the sentence-transformers files) or
+        a named shape with synthetic_seed. bf16 only; rows up to 8192 tokens. Query / document prompts ("search_query: ") stay
+        with the caller, as the reference's retrievers handle instructions themselves."""
+        precision = str(self.model_kwargs.get("precision", "bf16"))
+        if precision != "bf16":
+            raise ValueError(f"precision {precision!r}: ModernBERT models run in bf16 only")
+        if os.path.isdir(model_name):
+            tf = os.path.join(model_name, "tokenizer.json")
+            if not os.path.exists(tf):
+                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- a ModernBERT checkpoint needs its BPE tokenizer")
+            shape, weights = load_modernbert_weights(model_name)
+            st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
+            self.pooling = self.model_kwargs.get("pooling", st_pool)
+            self.normalize = self.normalize or st_norm
+            self.tokenizer = BpeTokenizer(tf)
+        else:
+            if "synthetic_seed" not in self.model_kwargs:
+                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass a ModernBERT checkpoint "
+                                        "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
+            shape = MODERNBERT_SHAPES[model_name]
+            weights = random_modernbert_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]),
+                                                std=float(self.model_kwargs.get("synthetic_std", 0.02)))
+            st_len = None
+            self.pooling = self.model_kwargs.get("pooling", shape[11])
+            self.normalize = True                      # the released sentence-transformers models carry a Normalize module
+            tf = self.model_kwargs.get("tokenizer_file")
+            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
+        max_pos = int(shape[5])
+        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, MODERNBERT_MAX_SEQ)
+        self.dimensions = int(shape[1])
+        self.encoder = HipModernBert(shape, weights, device=device)
 
     # -- LangChain Embeddings duck type -------------------------------------
     def embed_documents(self, texts: List[str]) -> List[List[float]]:

@@ -397,6 +397,44 @@ int ak_decoder_forward_lens(ak_decoder_t h, const int32_t *ids_dev, int ld_ids, 
  * work; exported so that the CPU suite can hold the table to HF's. */
 int ak_decoder_rope_table(float theta, int head_dim, int n_pos, float *cos_out, float *sin_out);
 
+/* ---- ModernBERT encoders (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base, lightonai/modernbert-embed-large) ---- */
+/* The forward pass of HF ModernBertModel: token embedding + LayerNorm, pre-norm layers (fused Wqkv, rotate_half RoPE at head size 64
+ * with one theta for the global and one for the sliding-window layers, bidirectional attention -- in a sliding layer key k is visible
+ * to query q iff |q - k| <= half_window --, GeGLU MLP), the final LayerNorm, then mean / cls pooling over the valid tokens and L2
+ * normalisation. No bias anywhere, LayerNorms carry a weight only. bf16 MFMA GEMMs, float32 residual stream / norms / softmax. */
+typedef void *ak_mbert_t;
+#define AK_MBERT_MAX_LAYERS 64
+typedef struct AkModernBertConfig {
+    int vocab_size;     /* 50368 */
+    int hidden;         /* 768 / 1024; a multiple of 128, <= 1024 */
+    int layers;         /* 22 / 28; <= AK_MBERT_MAX_LAYERS */
+    int heads;          /* 12 / 16; hidden / heads must be 64 */
+    int intermediate;   /* 1152 / 2624; a multiple of 64 */
+    int max_position;   /* 8192 (rows are limited to min(max_position, 8192) tokens) */
+    float norm_eps;     /* 1e-5 */
+    float global_rope_theta;   /* 160000: layers with layer_global[l] != 0 */
+    float local_rope_theta;    /* 10000: the sliding-window layers */
+    int half_window;    /* local_attention / 2 = 64; >= 1 */
+    int layer_global[AK_MBERT_MAX_LAYERS];   /* per layer: != 0 full attention, 0 sliding window */
+} AkModernBertConfig;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] as torch.nn.Linear.weight, vectors float32):
+ *   0 tok_embeddings [vocab][H] bf16, 1 embeddings.norm [H], 2 final_norm [H],
+ *   per layer l (base 3 + 6 * l):
+ *     +0 attn_norm [H] (layer 0: the identity in the model -- the pointer is not read, pass any valid one) +1 Wqkv [3 H][H]
+ *     +2 attn.Wo [H][H] +3 mlp_norm [H] +4 mlp.Wi [2 I][H] +5 mlp.Wo [H][I]
+ * The library interleaves the two halves of Wi at create (row 2 j = Wi row j, row 2 j + 1 = Wi row I + j; when 2 I is not a multiple
+ * of 256 it also pads Wi with zero rows and copies mlp.Wo with zero columns to match); the other pointers must stay valid until the
+ * handle is destroyed. Refused (non-zero, message in the last-error string): head size != 64, hidden % 128 or > 1024,
+ * intermediate % 64, half_window < 1, layers > AK_MBERT_MAX_LAYERS, a weight count other than 3 + 6 * layers. */
+int ak_mbert_create(const AkModernBertConfig *cfg, const void *const *weights_dev, int n_weights, ak_mbert_t *out);
+int ak_mbert_destroy(ak_mbert_t h);
+/* The tile layout of the other forward_lens calls: B right-padded rows of S token ids `ld_ids` int32 apart, lengths `lens_stride`
+ * apart (clamped to [0, S]; ids past a row's length are ignored; a row of length 0 embeds to zeros). pooling: AK_POOL_MEAN /
+ * AK_POOL_CLS over the final norm of the valid tokens; out_dev [B][H] float32, L2-normalised when `normalise` != 0. S a multiple of
+ * 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
+int ak_mbert_forward_lens(ak_mbert_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                          int pooling, int normalise, float *out_dev, void *stream);
+
 /* ---- host tokenizer: the tokenisation step inside Embeddings.embed_documents -------- */
 /* manager.py:373 -> HuggingFaceEmbeddings -> sentence-transformers' BERT WordPiece tokenizer [upstream]. Pure host
  * code (no GPU work): multi-threaded, so that text -> token ids keeps up with ak_encoder_forward at ingestion.
