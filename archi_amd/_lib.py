@@ -154,6 +154,32 @@ SYMBOLS = [
 ]
 
 
+class AkKtGemm(ctypes.Structure):
+    """Argument block of ak_kt_gemm (csrc/kernel_test.hip): the GemmArgs fields that modes 0, 1, 2, 4, 7 and 8 read."""
+    _fields_ = [
+        ("X", _P), ("W", _P), ("bias", _P),
+        ("T", _I), ("N", _I), ("K", _I),
+        ("out_bf16", _P), ("ldo", _I),
+        ("out_f32", _P),
+        ("res16", _P),
+        ("q", _P), ("k", _P), ("vt", _P), ("H", _I), ("S", _I), ("qscale", ctypes.c_float),
+    ]
+
+
+# single-launch entry points for the kernel-level tests (csrc/kernel_test.hip): libarchi_hip_dbg.so only, bound only when
+# load() picked that library. They are not part of include/archi_knn.h.
+KT_SYMBOLS = [
+    ("ak_kt_attn", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    ("ak_kt_attn_long", _I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    ("ak_kt_attn_window", _I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    ("ak_kt_attn_causal", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    ("ak_kt_gemm", _I, [_I, ctypes.POINTER(AkKtGemm), _P]),
+    ("ak_kt_gemm_skinny", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    ("ak_kt_gemm_skinny_qkv", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, ctypes.c_float, _P]),
+    ("ak_kt_vt_pos", _I, [_I]),
+]
+
+
 def load() -> ctypes.CDLL:
     """dlopen the library and bind every declared symbol (no GPU needed)."""
     global _lib
@@ -180,6 +206,11 @@ def load() -> ctypes.CDLL:
                 fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
                 fn.restype = res
                 fn.argtypes = args
+            if path != LIB_PATH:
+                for name, res, args in KT_SYMBOLS:
+                    fn = getattr(lib, name)
+                    fn.restype = res
+                    fn.argtypes = args
             got = lib.ak_abi_version()
             if got != ABI_VERSION:
                 raise HipBackendError(f"{path}: ABI version {got}, this binding expects {ABI_VERSION} "

@@ -91,8 +91,10 @@ __device__ inline uint2 cvt_bf16x4(f32x4 v) { return __builtin_bit_cast(uint2, _
 
 // exact-GELU 0.5 x (1 + erf(x / sqrt 2)) on four values (two independent v_pk_* chains, so the dependent
 // Horner steps of one hide under the other). erf(u) = u Q(u^2) on |u| <= 3.2 with a degree-9 minimax Q fitted
-// offline against scipy's erf (max abs error 7.8e-6; 1 - erf(3.2) = 6e-6), u clamped to +-3.2 and the result to
-// +-1; odd in u, so no abs/sign handling. No rcp, no exp: the output is rounded to bf16 (2^-9 relative) anyway.
+// offline against scipy's erf, u clamped to +-3.2 and the result to +-1; odd in u, so no abs/sign handling. With the
+// coefficients as printed here the distance from erf is <= 8e-6 on |u| <= 1.9 and grows to 2.7e-5 towards the clamp (the
+// polynomial holds 0.99997 from 3.2 on; 4e-5 with float32 Horner rounding: tests/test_kernel_refs_cpu.py) -- 0.5 |x| times
+// that in the GELU, against 2^-9 |x| for the bf16 rounding of the output. No rcp, no exp.
 __device__ inline float clamp3(float v, float lo, float hi) { return __builtin_amdgcn_fmed3f(v, lo, hi); }
 __device__ inline f32x4 gelu_erf4(f32x4 x) {
     f32x4 u = x * 0.70710678118654752f;

@@ -61,6 +61,26 @@ def test_product_library_reads_no_environment_on_call_paths_and_knows_no_wrong_r
     assert built.load().ak_debug_set(b"AK_TAIL_ABLATE", b"1") != 0      # the product library refuses the name
 
 
+def test_kernel_test_entry_points_exist_in_the_dbg_library_only(built):
+    """csrc/kernel_test.hip: the single-launch wrappers the kernel-level tests call are test infrastructure. The product library
+    exports none of them; the dbg library exports every one that KT_SYMBOLS binds."""
+    import subprocess
+
+    def exported(name):
+        out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "archi_amd", "lib", name)], stdout=subprocess.PIPE,
+                             check=True).stdout.decode()
+        return set(re.findall(r"\b(ak_kt_[a-z0-9_]+)\b", out))
+
+    assert exported("libarchi_hip.so") == set()
+    assert exported("libarchi_hip_dbg.so") == {name for name, _, _ in built.KT_SYMBOLS} and len(built.KT_SYMBOLS) == 8
+    # the one host-only wrapper: the V^T key order the tests' packers assume is the kernels' vt_pos
+    import ctypes
+    import numpy as np
+    from tests import kernel_refs as kr
+    dbg = ctypes.CDLL(os.path.join(ROOT, "archi_amd", "lib", "libarchi_hip_dbg.so"))
+    assert [dbg.ak_kt_vt_pos(s) for s in range(8192)] == kr.vt_pos(np.arange(8192)).tolist()
+
+
 @pytest.mark.parametrize("target,binary", [("tsan", "index_host_tsan"), ("asan-index", "index_host_asan")])
 def test_index_host_side_under_sanitizers(target, binary):
     """the host-side C++ under sanitizers in a CPU-only target (GPU sanitizers are not available on the
