@@ -94,7 +94,7 @@ _lib = None
 _inited_device = None
 
 # every symbol include/archi_knn.h declares: (name, restype, argtypes)
-_P, _I, _I64, _U64, _U32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32
+_P, _I, _I64, _U64, _U32, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
 SYMBOLS = [
     ("ak_last_error", ctypes.c_char_p, []),
     ("ak_version", ctypes.c_char_p, []),
@@ -113,6 +113,12 @@ SYMBOLS = [
     ("ak_index_lookup", _I, [_P, _P, _I64, _P]),
     ("ak_index_distances", _I, [_P, _P, _P, _I64, _P, _P]),
     ("ak_index_search", _I, [_P, _P, _I, _I, _I, _P, _I64, _U64, _P, _P, _P, _P]),
+    ("ak_index_lex_attach", _I, [_P, _P, _I64, _P, _P, _P, _P, _U64]),
+    ("ak_index_lex_clear", _I, [_P, _U64]),
+    ("ak_index_lex_info", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    ("ak_index_lex_scores", _I, [_P, _P, _I, _D, _D, _D, _P, _P, _P]),
+    ("ak_index_hybrid_search", _I, [_P, _P, _P, _I, _D, _D, _D, _D, _D, _P, _I64, _P, _I64, _U64, _I, _P, _P, ctypes.POINTER(_I),
+                                    _P, _P, ctypes.POINTER(_I), _P]),
     ("ak_index_search_dev", _I, [_P, _P, _I, _I, _I, _P, _I64, _U64, _P, _P, _P, _P]),
     ("ak_index_slots", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_U64)]),
     ("ak_index_compact", _I, [_P, ctypes.POINTER(_I64)]),

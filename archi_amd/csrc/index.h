@@ -10,6 +10,8 @@
 //                     dead or zero-norm(cosine) rows: ea = 0, eb = -inf (never a candidate)
 //   ids   [cap] i64   document_chunks.id of each row slot
 //   alive [cap] u8    0 after ak_index_remove (tombstone)
+//   lex_off [cap] i64, lex_cnt [cap] i32, lex_len [cap] i32   the row's sorted (term id, tf) list in the entry arena and its length in
+//                     tokens (lexical.hip: the BM25 leg of the hybrid query); a row without a list has cnt = len = 0
 #pragma once
 #include <condition_variable>
 #include <mutex>
@@ -39,6 +41,21 @@ struct Index : IndexBook {
     float *gb = nullptr;      // [ceil(cap/32)][4]: per 32-row block {max ea | rows 8q+0..3, max ea | rows 8q+4..7, max eb .., max eb ..}
     int64_t *ids = nullptr;
     uint8_t *alive = nullptr;
+    // ---- lexical store (lexical.hip), doc-major: per slot an offset into the append-only arena of (term id, tf) entries -- 8 bytes
+    // each, ascending in term id within a row, every row starting on an even entry (16-byte loads) --, the entry count and the
+    // document length. rebuild() carries the three per-slot arrays along and, on a gathering rebuild, copies the arena compacted.
+    int64_t *lex_off = nullptr;
+    int32_t *lex_cnt = nullptr, *lex_len = nullptr;
+    uint2 *lex_arena = nullptr;
+    int64_t lex_arena_cap = 0, lex_used = 0;     // entries allocated / entries up to the append position (alignment gaps included)
+    int64_t lex_entries = 0, lex_rows = 0;       // entries of attached rows / live rows with a list
+    uint64_t lex_gen = 0;                        // whose lists these are (ak_index_lex_clear / ak_index_lex_attach)
+    std::vector<int32_t> h_lex_cnt;              // host mirror of lex_cnt (shorter than n: the missing slots hold 0)
+    std::vector<uint8_t> h_lex_att;              // 1 = a list was attached to the slot (an empty text attaches an empty list)
+    Workspace ws_lex;                            // workspace of the lexical / hybrid query (one at a time: lex_mu)
+    std::mutex lex_mu;
+    char *lex_pin = nullptr; size_t lex_pin_cap = 0;       // pinned landing pad of the query's small copies
+    hipEvent_t lex_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // ak_index_profile: stage boundaries of the hybrid query
     float max_na = 0.f;  // max over rows of na (for the ip / l2 error bound)
     float max_rho = 0.f; // f32 corpora: max over rows of |a - shadow(a)| / |a| (measured at ingest; certificate term rho_c)
     Coalescer co;
@@ -99,6 +116,23 @@ int query_norms(const float *queries_dev, int nq, int dim, float *nb_dev, hipStr
 // keys/ids [nq][k] -> distances + counts
 int emit_results(const uint64_t *keys, const int64_t *ids, int nq, int k, int64_t *out_ids,
                  double *out_dist, int *out_cnt, hipStream_t st);
+
+// ---- pieces of index.hip the lexical store (lexical.hip) builds on ---------------------------------------------------------
+int thread_stream(hipStream_t *out);                  // the calling host thread's stream
+char *thread_scratch(size_t bytes);                   // the calling host thread's grow-only device scratch (NULL: hipMalloc failed)
+void thread_scratch_trim();
+int writer_fence(Index &ix);                          // wait for the last asynchronous device search (caller holds the unique lock)
+int filter_is_current(const Index &ix, const void *row_filter, int64_t filter_len, uint64_t filter_epoch, const char *who);
+// ak_index_search_dev behind its argument checks; the caller holds ix.mu (shared) and has checked the filter's epoch
+int search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, int mode, const uint8_t *row_filter_dev, int64_t *out_ids_dev,
+                      double *out_dist_dev, int *out_cert_dev, hipStream_t st);
+// lexical.hip: what rebuild() / ak_index_remove / ak_index_destroy do to the lexical store
+struct LexMove { int64_t *off = nullptr; int32_t *cnt = nullptr, *len = nullptr; };   // the new per-slot arrays (zeroed, new capacity)
+int lex_rebuild(Index &ix, const LexMove &to, const std::vector<int64_t> *src, hipStream_t st, uint2 **new_arena, int64_t *new_cap,
+                int64_t *new_used);
+void lex_rebuilt(Index &ix, const std::vector<int64_t> *src, uint2 *new_arena, int64_t new_cap, int64_t new_used);
+void lex_removed(Index &ix, const std::vector<int64_t> &slots);
+void lex_release(Index &ix);
 
 // ---- fast path (scan.hip) ----------------------------------------------------
 // per-query certificate terms: s~_units = a * s~' + b where s~' is the scan's score; eps in score units

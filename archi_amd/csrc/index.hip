@@ -203,11 +203,14 @@ struct ThreadCtxHandle {
 };
 static thread_local ThreadCtxHandle t_ctx_handle;
 #define t_ctx (t_ctx_handle.get())
-static int thread_stream(hipStream_t *out) {
+int thread_stream(hipStream_t *out) {
     if (!t_ctx.stream) AK_HIP(hipStreamCreateWithFlags(&t_ctx.stream, hipStreamNonBlocking));
     *out = t_ctx.stream;
     return 0;
 }
+static int scratch_reserve(char **p, size_t *cap, size_t need, bool pinned);
+char *thread_scratch(size_t bytes) { return scratch_reserve(&t_ctx.dev, &t_ctx.dev_cap, bytes, false) ? nullptr : t_ctx.dev; }
+void thread_scratch_trim() { t_ctx.trim(); }
 static int scratch_reserve(char **p, size_t *cap, size_t need, bool pinned) {
     if (need <= *cap) return 0;
     if (*p) { if (pinned) hipHostFree(*p); else hipFree(*p); *p = nullptr; *cap = 0; }
@@ -509,7 +512,7 @@ __global__ void k_fill_int(int *p, int n, int v) {
 }
 
 // Writers wait (on the host) for the last asynchronous device search: its kernels read rows / ea / eb / gb / ids.
-static int writer_fence(Index &ix) {
+int writer_fence(Index &ix) {
     std::lock_guard<std::mutex> wl(ix.ws_mu);
     if (ix.ws_pending) {
         AK_HIP(hipEventSynchronize(ix.ws_event));
@@ -523,6 +526,8 @@ struct IndexBuffers {
     float *na = nullptr, *ea = nullptr, *eb = nullptr, *gb = nullptr;
     int64_t *ids = nullptr;
     uint8_t *alive = nullptr;
+    int64_t *lex_off = nullptr;
+    int32_t *lex_cnt = nullptr, *lex_len = nullptr;
     void release() {
         if (rows) hipFree(rows);
         if (shadow) hipFree(shadow);
@@ -532,6 +537,9 @@ struct IndexBuffers {
         if (gb) hipFree(gb);
         if (ids) hipFree(ids);
         if (alive) hipFree(alive);
+        if (lex_off) hipFree(lex_off);
+        if (lex_cnt) hipFree(lex_cnt);
+        if (lex_len) hipFree(lex_len);
         *this = IndexBuffers();
     }
 };
@@ -548,12 +556,21 @@ static hipError_t alloc_buffers(IndexBuffers &b, int64_t capacity, int dim, int 
     if (e == hipSuccess) e = hipMalloc((void **)&b.gb, ((capacity + 31) / 32) * 16 + 256);
     if (e == hipSuccess) e = hipMalloc((void **)&b.ids, capacity * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&b.alive, capacity);
+    // the lexical store's per-slot arrays start out as "no list": a row nobody attached one to has length 0 and no terms
+    if (e == hipSuccess) e = hipMalloc((void **)&b.lex_off, capacity * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.lex_cnt, capacity * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.lex_len, capacity * 4);
+    if (e == hipSuccess) e = hipMemset(b.lex_off, 0, capacity * 8);
+    if (e == hipSuccess) e = hipMemset(b.lex_cnt, 0, capacity * 4);
+    if (e == hipSuccess) e = hipMemset(b.lex_len, 0, capacity * 4);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the fills ran on the null stream; the copies that follow run on the caller's
     if (e != hipSuccess) b.release();
     return e;
 }
 static void take_buffers(Index &ix, IndexBuffers &b) {   // ix <- b, b <- what ix held
     std::swap(ix.rows, b.rows); std::swap(ix.shadow, b.shadow); std::swap(ix.na, b.na); std::swap(ix.ea, b.ea);
     std::swap(ix.eb, b.eb); std::swap(ix.gb, b.gb); std::swap(ix.ids, b.ids); std::swap(ix.alive, b.alive);
+    std::swap(ix.lex_off, b.lex_off); std::swap(ix.lex_cnt, b.lex_cnt); std::swap(ix.lex_len, b.lex_len);
 }
 
 
@@ -569,6 +586,11 @@ static int rebuild(Index &ix, int64_t new_cap, bool compact, hipStream_t st) {
     int rc = 0;
     std::vector<int64_t> src;
     const bool gather = compact && ix.n_alive != ix.n;
+    // the lexical store follows the same row permutation; on a gathering rebuild its arena is copied compacted (lexical.hip)
+    uint2 *lex_arena2 = nullptr;
+    int64_t lex_cap2 = 0, lex_used2 = 0;
+    LexMove lex_to;
+    lex_to.off = nb.lex_off; lex_to.cnt = nb.lex_cnt; lex_to.len = nb.lex_len;
     if (!gather) {
         do {
             if (ix.n == 0) break;
@@ -580,6 +602,7 @@ static int rebuild(Index &ix, int64_t new_cap, bool compact, hipStream_t st) {
             hipMemcpyAsync(nb.gb, ix.gb, ((ix.n + 31) / 32) * 16, hipMemcpyDeviceToDevice, st);
             hipMemcpyAsync(nb.ids, ix.ids, ix.n * 8, hipMemcpyDeviceToDevice, st);
             hipMemcpyAsync(nb.alive, ix.alive, ix.n, hipMemcpyDeviceToDevice, st);
+            if (lex_rebuild(ix, lex_to, nullptr, st, &lex_arena2, &lex_cap2, &lex_used2)) { rc = -10; break; }
         } while (0);
     } else {
         ix.live_slots(src);
@@ -596,13 +619,19 @@ static int rebuild(Index &ix, int64_t new_cap, bool compact, hipStream_t st) {
             k_group_bounds<<<(unsigned)((nblk * 2 + 255) / 256), 256, 0, st>>>(nb.ea, nb.eb, m, 0, nblk, nb.gb);
             if (hipGetLastError() != hipSuccess) { rc = -10; break; }
         } while (0);
+        if (rc == 0 && lex_rebuild(ix, lex_to, &src, st, &lex_arena2, &lex_cap2, &lex_used2)) rc = -10;
         if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = -10;
         if (dsrc) hipFree(dsrc);
     }
     if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = -10;
-    if (rc) { nb.release(); AK_FAIL(-10, "index growth / compaction: device copy failed"); }
+    if (rc) {
+        nb.release();
+        if (lex_arena2) hipFree(lex_arena2);
+        AK_FAIL(-10, "index growth / compaction: device copy failed");
+    }
     take_buffers(ix, nb);
     nb.release();        // the old buffers
+    lex_rebuilt(ix, gather ? &src : nullptr, lex_arena2, lex_cap2, lex_used2);      // before the book renumbers: it reads the old n
     ix.rebuilt(new_cap, gather ? &src : nullptr);      // the host mirror follows (new slot numbers, layout epoch)
     return 0;
 }
@@ -703,6 +732,7 @@ int ak_index_destroy(ak_index_t h) {
     b.release();
     ix->ws_dev.release();
     ix->ws_fb.release();
+    lex_release(*ix);
     if (ix->ws_event) hipEventDestroy(ix->ws_event);
     if (ix->dbg_dev) hipFree(ix->dbg_dev);
     if (switches().coalesce_stats.load(std::memory_order_relaxed) && ix->co.n_launch)
@@ -828,6 +858,7 @@ int ak_index_remove(ak_index_t h, const int64_t *ids, int64_t n, int64_t *n_remo
     k_kill<<<(unsigned)((slots.size() + 255) / 256), 256, 0, st>>>(d, (int64_t)slots.size(), ix.alive, ix.ea, ix.eb);
     AK_HIP(hipStreamSynchronize(st));
     ix.removed(slots, live_ids);
+    lex_removed(ix, slots);
     if (n_removed) *n_removed = (int64_t)slots.size();
     t_ctx.trim();
     return 0;
@@ -1034,13 +1065,9 @@ static int rerun_uncertified(Index &ix, const float *dq, const float *dnb, int n
     return 0;
 }
 
-}  // namespace ak
-
-extern "C" {
-
 // a row_filter is a statement about ONE layout of the index: the caller says which (ak_index_slots), and a mask of another
 // layout is refused before a byte of it is read. Caller holds the shared lock.
-static int filter_is_current(const Index &ix, const void *row_filter, int64_t filter_len, uint64_t filter_epoch, const char *who) {
+int filter_is_current(const Index &ix, const void *row_filter, int64_t filter_len, uint64_t filter_epoch, const char *who) {
     if (!row_filter) return 0;
     if (!ix.filter_matches(filter_len, filter_epoch))
         AK_FAIL(AK_ERR_STALE_FILTER, std::string(who) + ": stale row_filter (built for " + std::to_string(filter_len) + " slots at layout epoch " +
@@ -1048,6 +1075,10 @@ static int filter_is_current(const Index &ix, const void *row_filter, int64_t fi
                                          std::to_string(ix.epoch) + "): rebuild the mask from ak_index_slots / ak_index_lookup and retry");
     return 0;
 }
+
+}  // namespace ak
+
+extern "C" {
 
 static int search_host(Index &ix, const float *queries, int nq, int k, int mode, const uint8_t *row_filter, int64_t filter_len,
                        uint64_t filter_epoch, int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats) {
@@ -1196,8 +1227,14 @@ int ak_index_search_dev(ak_index_t h, const float *queries_dev, int nq, int k, i
     RoctxRange range("ak_index_search_dev");
     std::shared_lock<std::shared_mutex> lk(ix.mu);
     if (int frc = filter_is_current(ix, row_filter_dev, filter_len, filter_epoch, "ak_index_search_dev")) return frc;
+    return search_dev_locked(ix, queries_dev, nq, k, mode, row_filter_dev, out_ids_dev, out_dist_dev, out_cert_dev, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+int ak::search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, int mode, const uint8_t *row_filter_dev,
+                          int64_t *out_ids_dev, double *out_dist_dev, int *out_cert_dev, hipStream_t st) {
     std::lock_guard<std::mutex> wl(ix.ws_mu);
-    hipStream_t st = (hipStream_t)stream;
     // the previous call's kernels may still be running out of ws_dev on another stream
     if (ix.ws_pending && ix.ws_stream != st) AK_HIP(hipStreamWaitEvent(st, ix.ws_event, 0));
     const bool fast = mode != AK_SEARCH_EXACT && fast_supported(ix, nq, k);
@@ -1249,6 +1286,8 @@ int ak_index_search_dev(ak_index_t h, const float *queries_dev, int nq, int k, i
     ix.ws_pending = false;
     return 0;
 }
+
+extern "C" {
 
 int ak_index_debug_read(ak_index_t h, int64_t *out, int n) {
     AK_BIND();

@@ -154,6 +154,67 @@ class HipIndex:
                   "ak_index_distances")
         return out, found.astype(bool)
 
+    # -- lexical store + hybrid query (csrc/lexical.hip) ------------------
+    def lex_attach(self, ids, row_offsets, terms, tfs, doc_len, generation: int) -> None:
+        """Attach sorted (term id, tf) lists to live rows by id, CSR layout; all or nothing (ak_index_lex_attach)."""
+        ids_a = np.ascontiguousarray(ids, dtype=np.int64)
+        ro = np.ascontiguousarray(row_offsets, dtype=np.int64)
+        te = np.ascontiguousarray(terms, dtype=np.int32)
+        tf = np.ascontiguousarray(tfs, dtype=np.int32)
+        dl = np.ascontiguousarray(doc_len, dtype=np.int32)
+        n = ids_a.size
+        if ro.shape != (n + 1,) or dl.shape != (n,) or te.shape != tf.shape or (n and te.size != int(ro[-1])):
+            raise ValueError("lex_attach: ids [n], row_offsets [n + 1], doc_len [n], terms / tfs [row_offsets[n]]")
+        check(self._lib.ak_index_lex_attach(self._h, _ptr(ids_a), n, _ptr(ro), _ptr(te), _ptr(tf), _ptr(dl), int(generation)),
+              "ak_index_lex_attach")
+
+    def lex_clear(self, new_generation: int) -> None:
+        check(self._lib.ak_index_lex_clear(self._h, int(new_generation)), "ak_index_lex_clear")
+
+    def lex_info(self) -> dict:
+        g, r, e, b = ctypes.c_uint64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._lib.ak_index_lex_info(self._h, ctypes.byref(g), ctypes.byref(r), ctypes.byref(e), ctypes.byref(b)), "ak_index_lex_info")
+        return {"generation": g.value, "rows_attached": r.value, "entries": e.value, "arena_bytes": b.value}
+
+    def lex_generation(self) -> int:
+        g = ctypes.c_uint64(0)
+        check(self._lib.ak_index_lex_info(self._h, ctypes.byref(g), None, None, None), "ak_index_lex_info")
+        return g.value
+
+    def lex_scores(self, terms, k1: float, b: float, sign: float):
+        """BM25 of every row slot for one query -> (bm [slots] float64, hit [slots] uint8, info dict)."""
+        te = np.ascontiguousarray(terms, dtype=np.int32)
+        slots = self.slots
+        bm = np.zeros(slots, dtype=np.float64)
+        hit = np.zeros(slots, dtype=np.uint8)
+        info = np.zeros(4, dtype=np.int64)
+        check(self._lib.ak_index_lex_scores(self._h, _ptr(te), te.size, float(k1), float(b), float(sign), _ptr(bm), _ptr(hit), _ptr(info)),
+              "ak_index_lex_scores")
+        return bm, hit, {"n": int(info[0]), "sum_len": int(info[1]), "hits": int(info[2]), "terms": int(info[3])}
+
+    def hybrid_search(self, query, terms, k1: float, b: float, sign: float, w_s: float, w_b: float, also_ids, k: int,
+                      row_filter: Optional[np.ndarray] = None, filter_epoch: Optional[int] = None):
+        """The hybrid query's two legs in one call (ak_index_hybrid_search) -> (hit ids, hit combined scores, scan ids, scan
+        distances, info [12] int64). StaleFilterError as search()."""
+        q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
+        if q.size != self.dim:
+            raise ValueError(f"query has {q.size} values, index dimension is {self.dim}")
+        te = np.ascontiguousarray(terms, dtype=np.int32)
+        al = np.ascontiguousarray(also_ids, dtype=np.int64)
+        flt, flen, fep = None, 0, 0
+        if row_filter is not None:
+            flt = np.ascontiguousarray(row_filter, dtype=np.uint8)
+            flen = flt.shape[0]
+            fep = self.layout()[1] if filter_epoch is None else int(filter_epoch)
+        hi, hc = np.full(k, -1, np.int64), np.full(k, np.nan, np.float64)
+        si, sd = np.full(k, -1, np.int64), np.full(k, np.nan, np.float64)
+        nh, ns = ctypes.c_int(0), ctypes.c_int(0)
+        info = np.zeros(12, dtype=np.int64)
+        check(self._lib.ak_index_hybrid_search(self._h, _ptr(q), _ptr(te), te.size, float(k1), float(b), float(sign), float(w_s), float(w_b),
+                                               _ptr(al), al.size, _ptr(flt), flen, fep, k, _ptr(hi), _ptr(hc), ctypes.byref(nh),
+                                               _ptr(si), _ptr(sd), ctypes.byref(ns), _ptr(info)), "ak_index_hybrid_search")
+        return hi[: nh.value], hc[: nh.value], si[: ns.value], sd[: ns.value], info
+
     def fetch(self, slots: Sequence[int]) -> np.ndarray:
         """Stored rows (exact stored values widened to float32) by row slot."""
         s = np.ascontiguousarray(slots, dtype=np.int64)

@@ -1078,6 +1078,21 @@ class ArchiHipHybridVectorStore(ArchiHipVectorStore):
         if col is not None and k > 0:
             t = col.table
             q = np.asarray([float(x) for x in query_embedding], dtype=np.float32)    # a4 round trip (:389)
+            # a scorer whose index lives in HBM (lexical.DeviceBm25): both legs are one library call in slot space. A degenerate
+            # query vector (every distance NaN: every row joins the hit leg) keeps the host path below, fed by its scores_arrays
+            on_device = callable(getattr(self._bm25, "device_query", None))
+            if on_device:
+                self._bm25.use_index(col.index)          # raises on an index without the lexical entry points: no fallback
+            if on_device and not bool(_suspect_rows(q[None, :])[0]):
+                # a writer may delete rows of the answer between the library call and the reading of their text: the statement's
+                # snapshot would still have held them, so the query runs again on the later state (as
+                # similarity_search_by_vector_with_score does); after the retries the shortened list stands
+                for attempt in range(self.STALE_RETRIES + 1):
+                    c_score, c_id = self._hybrid_device_legs(col, q, query, k, semantic_weight, bm25_weight, metadata_filter, include_deleted)
+                    results, vanished = self._hybrid_results(col, c_score, c_id, k)
+                    if not vanished:
+                        break
+                return results or self.similarity_search_with_score(query, k=k, **kwargs)
             def allowed_mask(rids: np.ndarray) -> np.ndarray:
                 if allowed is None:
                     return np.ones(len(rids), bool)
@@ -1154,3 +1169,53 @@ class ArchiHipHybridVectorStore(ArchiHipVectorStore):
         if not results:                                                              # :467-469
             return self.similarity_search_with_score(query, k=k, **kwargs)
         return results
+
+    def _hybrid_device_legs(self, col: _Collection, q: np.ndarray, query: str, k: int, semantic_weight: float, bm25_weight: float,
+                            metadata_filter: Dict[str, Any], include_deleted: bool) -> Tuple[np.ndarray, np.ndarray]:
+        """Both legs of the hybrid query through HipIndex.hybrid_search -> (combined scores, row ids) of the <= 2 k candidates.
+        Under the table lock: the scorer attaches the lists of new rows and resolves the query's words, the WHERE mask and its
+        layout epoch are read, the suspects are listed. The library call runs without the lock and refuses a mask of another
+        layout (StaleFilterError: everything is rebuilt; after STALE_RETRIES collisions the call runs under the lock) -- the
+        discipline of _search_snapshot. Rows that arrive between the two count, for this one query, as rows without words."""
+        t, bm = col.table, self._bm25
+
+        def prepare():
+            terms = bm.device_query(query, t, col.index)
+            rf, _, epoch = self._where(col, metadata_filter, include_deleted)
+            return terms, rf, epoch, np.fromiter(t.suspects, np.int64, len(t.suspects))
+
+        def call(terms, rf, epoch, also):
+            return col.index.hybrid_search(q, terms, bm.k1, bm.b, bm.sign, semantic_weight, bm25_weight, also, k,
+                                           row_filter=rf, filter_epoch=epoch)
+        out = None
+        for _ in range(self.STALE_RETRIES):
+            with t.lock:
+                args = prepare()
+            try:
+                out = call(*args)
+                break
+            except StaleFilterError:
+                continue
+        if out is None:
+            with t.lock:
+                out = call(*prepare())
+        hit_ids, hit_comb, scan_ids, scan_dist, _ = out
+        c_score = np.concatenate([hit_comb, (1.0 - scan_dist.astype(np.float64)) * semantic_weight + 0 * bm25_weight])
+        return c_score, np.concatenate([hit_ids, scan_ids]).astype(np.int64)
+
+    def _hybrid_results(self, col: _Collection, c_score: np.ndarray, c_id: np.ndarray, k: int) -> Tuple[List[Tuple[Any, float]], int]:
+        """ORDER BY combined_score DESC LIMIT k over the two legs' candidates, as hybrid_search orders them -> (results, number of
+        selected rows that were deleted before their text could be read)."""
+        t = col.table
+        isnan = c_score != c_score
+        order = np.lexsort((c_id, -np.where(isnan, 0.0, c_score), ~isnan))[:k]
+        results: List[Tuple[Any, float]] = []
+        vanished = 0
+        with t.lock:
+            for j in order.tolist():
+                pz = t.pos(int(c_id[j]))
+                if pz >= 0:
+                    results.append((self._document(t, pz), float(c_score[j])))
+                else:
+                    vanished += 1
+        return results, vanished

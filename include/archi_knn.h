@@ -133,6 +133,56 @@ int ak_index_lookup(ak_index_t h, const int64_t *ids, int64_t n, int64_t *out_sl
 int ak_index_distances(ak_index_t h, const float *query, const int64_t *ids, int64_t n, double *out_dist,
                        uint8_t *out_found);
 
+/* ---- lexical store + the hybrid query: replaces the pg_textsearch BM25 index and hybrid_search's SQL ------------------
+ * init.sql:294-300 (CREATE INDEX ... USING bm25 on document_chunks.chunk_text) and postgres_vectorstore.py:366-491. The index
+ * keeps, per row, a list of (term id, tf) entries ascending in term id and the row's length in tokens, in HBM next to the
+ * embedding; the caller owns the tokeniser and the term dictionary (archi_amd/lexical.py). 8 bytes per entry (uint32 term id,
+ * uint32 tf): any term id below 2^31 and any tf are held exactly. A delete is ak_index_remove's tombstone; growth, reclaim and
+ * ak_index_compact move the lists with their rows (a compaction drops the dead rows' entries).
+ *
+ * ak_index_lex_attach: the INSERT's effect on the bm25 index (postgres_vectorstore.py:168-180 with init.sql:294-300). Lists for
+ *   n LIVE rows by document_chunks.id, CSR: row i holds terms / tfs [row_offsets[i], row_offsets[i+1]), doc_len[i] tokens. An id
+ *   that is unknown or dead, listed twice, a list that does not ascend, a tf < 1 or a `generation` other than the store's is an
+ *   error and NOTHING is attached. Takes the index's writer lock; the layout epoch does not move. A row attached again gets the
+ *   new list.
+ * ak_index_lex_clear: DROP + CREATE of that index (a changed text_config / REINDEX): every list and the arena go, and the store
+ *   belongs to `new_generation` -- the owner's mark, so that a scorer notices lists it did not write.
+ * ak_index_lex_info: any pointer may be NULL. rows_attached: live rows with a list; entries: their entries (a dead row's stay
+ *   counted until a compaction drops them); arena_bytes: bytes of the arena up to its append position. */
+int ak_index_lex_attach(ak_index_t h, const int64_t *ids, int64_t n, const int64_t *row_offsets, const int32_t *terms,
+                        const int32_t *tfs, const int32_t *doc_len, uint64_t generation);
+int ak_index_lex_clear(ak_index_t h, uint64_t new_generation);
+int ak_index_lex_info(ak_index_t h, uint64_t *generation, int64_t *rows_attached, int64_t *entries, int64_t *arena_bytes);
+/* `chunk_text <@> to_bm25query(...)` for every row (postgres_vectorstore.py:421-433, the bm25_scores CTE): Okapi BM25 of one
+ * query over the LIVE rows, in float64 with one rounding per operation, in the order of the scalar formulation:
+ *   n = live rows, avg = sum of their lengths / n, df_t = live rows holding term t, idf_t = log(1.0 + (n - df_t + 0.5) / (df_t + 0.5))
+ *   (the host C library's log); terms with df_t = 0 drop out; per row, terms in the query's first-occurrence order from acc = 0.0:
+ *   acc = acc + ((idf * tf) * (k1 + 1.0)) / (tf + k1 * ((1.0 - b) + (b * len) / avg))   [avg == 0: tf + k1 * (1.0 - b)];  bm = sign * acc
+ * terms [T]: the query's term ids (repeats are dropped; any T). out_bm / out_hit: [slots] float64 / bytes on the HOST indexed by
+ * row slot (ak_index_slots, ak_index_lookup): out_hit = 1 and out_bm = the score for live rows holding a query term, 0 elsewhere.
+ * out_info: NULL or int64[4] = {n, sum of lengths, matching rows, terms with df > 0}. */
+int ak_index_lex_scores(ak_index_t h, const int32_t *terms, int T, double k1, double b, double sign, double *out_bm,
+                        uint8_t *out_hit, int64_t *out_info);
+/* The hybrid query (postgres_vectorstore.py:420-457) as ONE call under the index's reader lock:
+ *   combined = (1.0 - distance) * w_s + COALESCE(bm25, 0) * w_b ... ORDER BY combined DESC LIMIT k
+ * evaluated as two legs whose union holds the answer (w_s >= 0): the HIT leg -- rows holding a query term and the rows listed in
+ * also_ids [n_also] (ids whose distance can be NaN; unknown ids are ignored), restricted to live rows that pass row_filter: their
+ * exact distances in the search's arithmetic, BM25 as ak_index_lex_scores (+0.0 for an also-row without a match), the best k by
+ * (NaN first, combined descending, id ascending) -- and the SCAN leg: ak_index_search (AUTO) of the other rows that pass row_filter.
+ *   query      : [dim] float32, host
+ *   row_filter : NULL or [filter_len] bytes on the host with (filter_len, filter_epoch) as for ak_index_search: AK_ERR_STALE_FILTER
+ *                when the index has moved on, nothing read
+ *   out_hit_ids / out_hit_combined [k], *n_hit; out_scan_ids / out_scan_dist [k] (float8 distance), *n_scan: the two lists; the
+ *                caller merges the <= 2 k entries (the scan rows' combined = (1.0 - d) * w_s + 0 * w_b)
+ *   out_info   : NULL or int64[12] = {n, sum of lengths, matching rows that pass the filter, rows of the hit leg, terms with
+ *                df > 0, arena entries streamed per pass, then -- when ak_index_profile is on -- nanoseconds of the statistics
+ *                pass, the score pass (with the host's idf step), the hit leg and the scan leg, 0, 0}
+ * Workspace comes from the index (grown on first use); calls on one index are serialised. */
+int ak_index_hybrid_search(ak_index_t h, const float *query, const int32_t *terms, int T, double k1, double b, double sign,
+                           double w_s, double w_b, const int64_t *also_ids, int64_t n_also, const uint8_t *row_filter,
+                           int64_t filter_len, uint64_t filter_epoch, int k, int64_t *out_hit_ids, double *out_hit_combined,
+                           int *n_hit, int64_t *out_scan_ids, double *out_scan_dist, int *n_scan, int64_t *out_info);
+
 /* SELECT ... embedding <op> %s::vector AS distance ... WHERE ... ORDER BY distance
  * ASC LIMIT k   (postgres_vectorstore.py:317-332).
  *   queries   : [nq][dim] float32, host memory
