@@ -172,6 +172,20 @@ class AkKtGemm(ctypes.Structure):
     ]
 
 
+class AkKtGemmLazy(ctypes.Structure):
+    """Argument block of ak_kt_gemm_lazy (csrc/kernel_test.hip): the GemmArgs fields the lazy-LayerNorm modes 0, 1 and 4 read."""
+    _fields_ = [
+        ("X", _P), ("W", _P), ("bias", _P),
+        ("T", _I), ("N", _I), ("K", _I),
+        ("out_bf16", _P), ("ldo", _I),
+        ("res16", _P),
+        ("q", _P), ("k", _P), ("vt", _P), ("H", _I), ("S", _I), ("qscale", ctypes.c_float),
+        ("fold_c", _P), ("a_stats", _P), ("res_stats", _P), ("res_g", _P), ("res_b", _P), ("out_g", _P),
+        ("out_stats", _P),
+        ("nslot", _I), ("inv_h", ctypes.c_float), ("eps", ctypes.c_float),
+    ]
+
+
 # single-launch entry points for the kernel-level tests (csrc/kernel_test.hip): libarchi_hip_dbg.so only, bound only when
 # load() picked that library. They are not part of include/archi_knn.h.
 KT_SYMBOLS = [
@@ -183,6 +197,17 @@ KT_SYMBOLS = [
     ("ak_kt_gemm_skinny", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
     ("ak_kt_gemm_skinny_qkv", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, ctypes.c_float, _P]),
     ("ak_kt_vt_pos", _I, [_I]),
+    ("ak_kt_gemm_ln", _I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P]),
+    ("ak_kt_ffn384_weight_bytes", _I64, [_I]),
+    ("ak_kt_ffn384", _I, [_P] * 13 + [_I, _I, ctypes.c_float, _P]),
+    ("ak_kt_qkv384_weight_bytes", _I64, []),
+    ("ak_kt_qkv384", _I, [_P] * 7 + [_I, _I, _I, ctypes.c_float, _I, _P]),
+    ("ak_kt_gemm_lazy", _I, [_I, ctypes.POINTER(AkKtGemmLazy), _P]),
+    ("ak_kt_ln_finalize", _I, [_P, _I, _I64, ctypes.c_float, ctypes.c_float, _P, _P]),
+    ("ak_kt_fold_ln", _I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    ("ak_kt_layernorm", _I, [_P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P, _P]),
+    ("ak_kt_layernorm16", _I, [_P, _P, _P, _I, _I, ctypes.c_float, _P, _P]),
+    ("ak_kt_ln_apply16", _I, [_P, _P, _P, _P, _I64, _I, _P, _P]),
 ]
 
 

@@ -161,14 +161,25 @@ __global__ __launch_bounds__(256) void k_ln_apply16(const uint16_t *__restrict__
 }
 
 template <int NP = 1>
-static bool launch_layernorm16(int np, const uint16_t *x16in, const float *g, const float *bta, int T, float eps, uint16_t *y16, hipStream_t st) {
+static bool launch_layernorm16_np(int np, const uint16_t *x16in, const float *g, const float *bta, int T, float eps, uint16_t *y16, hipStream_t st) {
     if constexpr (NP <= 8) {
         if (np == NP) {
             k_layernorm16<NP><<<(unsigned)((T + 7) / 8), 256, 0, st>>>(x16in, g, bta, T, eps, y16);
             return true;
         }
-        return launch_layernorm16<NP + 1>(np, x16in, g, bta, T, eps, y16, st);
+        return launch_layernorm16_np<NP + 1>(np, x16in, g, bta, T, eps, y16, st);
     } else return false;
+}
+// the three stand-alone LayerNorm launches of the forward pass (declared in encoder_kernels.h: the kernel-level tests run them too)
+void launch_layernorm(const float *x, const float *res, const uint16_t *res16, const float *g, const float *bta, int T, int H, float eps,
+                      float *y32, uint16_t *y16, const uint16_t *x16in, hipStream_t st) {
+    k_layernorm<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(x, res, res16, g, bta, T, H, eps, y32, y16, x16in);
+}
+bool launch_layernorm16(int H, const uint16_t *x16in, const float *g, const float *bta, int T, float eps, uint16_t *y16, hipStream_t st) {
+    return H % 128 == 0 && launch_layernorm16_np(H / 128, x16in, g, bta, T, eps, y16, st);
+}
+void launch_ln_apply16(const uint16_t *rt, const float *stats, const float *g, const float *bta, int64_t T, int H, uint16_t *y16, hipStream_t st) {
+    k_ln_apply16<<<(unsigned)((T * (H / 8) + 255) / 256), 256, 0, st>>>(rt, stats, g, bta, T, H, y16);
 }
 
 // One wave per TWO tokens: LN(word[id] + pos[s] + type[0]). A lane owns NP = H / 128 adjacent feature PAIRS (H / 64 features:
@@ -1201,7 +1212,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
         }
         // the last LayerNorm is a launch: the pooling kernel reads normalised rows (e.q is free again)
         const Layer &last = e.layers[L - 1];
-        k_ln_apply16<<<(unsigned)((T * (H / 8) + 255) / 256), 256, 0, st>>>(e.x16, e.st2, last.ln2g, last.ln2b, T, H, e.q);
+        launch_ln_apply16(e.x16, e.st2, last.ln2g, last.ln2b, T, H, e.q, st);
         AK_HIP(hipGetLastError());
         if (S > 512) k_pool<true, true><<<B, 256, 0, st>>>(nullptr, e.q, mask, S, H, pooling, normalise, out);
         else k_pool<true><<<B, 256, 0, st>>>(nullptr, e.q, mask, S, H, pooling, normalise, out);
@@ -1234,7 +1245,7 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
         }
         if (skinny) {
             if (launch_gemm_skinny(e.ctx, ly.wo, ly.bo, t32, H, H, e.y32, nullptr, 0, st)) return -10;
-            k_layernorm<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(e.y32, x32, r16 ? e.x16 : nullptr, ly.ln1g, ly.ln1b, (int)T, H, eps, x32, e.x16);
+            launch_layernorm(e.y32, x32, r16 ? e.x16 : nullptr, ly.ln1g, ly.ln1b, (int)T, H, eps, x32, e.x16, nullptr, st);
         } else if (fuse) {
             GemmLnArgs o{e.ctx, ly.wo, ly.bo, ly.ln1g, ly.ln1b, x32, e.x16, (int)tpad, H, eps, nullptr};
             if (launch_gemm_ln(o, st)) return -10;
@@ -1244,15 +1255,15 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
             o.out_bf16 = e.q; o.ldo = H;       // y16: the Q buffer is free once attention has run
             o.res16 = e.x16;                   // ... and the residual is added in the GEMM's store pass (MODE 4): the LayerNorm reads one array
             if (launch_gemm(y16 ? 4 : 2, o, st)) return -10;
-            if (!(y16 && !x32 && H % 128 == 0 && launch_layernorm16(H / 128, e.q, ly.ln1g, ly.ln1b, (int)T, eps, e.x16, st)))
-                k_layernorm<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(e.y32, x32, (r16 && !y16) ? e.x16 : nullptr, ly.ln1g, ly.ln1b, (int)T, H, eps, x32, e.x16, y16 ? e.q : nullptr);
+            if (!(y16 && !x32 && launch_layernorm16(H, e.q, ly.ln1g, ly.ln1b, (int)T, eps, e.x16, st)))
+                launch_layernorm(e.y32, x32, (r16 && !y16) ? e.x16 : nullptr, ly.ln1g, ly.ln1b, (int)T, H, eps, x32, e.x16, y16 ? e.q : nullptr, st);
         }
         GemmArgs f1{};
         f1.X = e.x16; f1.W = ly.w1; f1.bias = ly.b1; f1.T = (int)tpad; f1.N = I; f1.K = H; f1.out_bf16 = e.f; f1.ldo = I;
         if (skinny) {
             if (launch_gemm_skinny(e.x16, ly.w1, ly.b1, t32, I, H, nullptr, e.f, I, st)) return -10;
             if (launch_gemm_skinny(e.f, ly.w2, ly.b2, t32, H, I, e.y32, nullptr, 0, st)) return -10;
-            k_layernorm<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(e.y32, x32, r16 ? e.x16 : nullptr, ly.ln2g, ly.ln2b, (int)T, H, eps, x32, e.x16);
+            launch_layernorm(e.y32, x32, r16 ? e.x16 : nullptr, ly.ln2g, ly.ln2b, (int)T, H, eps, x32, e.x16, nullptr, st);
             AK_HIP(hipGetLastError());
             continue;
         }
@@ -1271,8 +1282,8 @@ static int forward_locked(Encoder &e, const int32_t *ids, const int32_t *mask, i
             f2.X = e.f; f2.W = ly.w2; f2.bias = ly.b2; f2.T = (int)tpad; f2.N = H; f2.K = I; f2.out_f32 = e.y32; f2.res_f32 = e.x32;
             f2.out_bf16 = e.q; f2.ldo = H; f2.res16 = e.x16;
             if (launch_gemm(y16 ? 4 : 2, f2, st)) return -10;
-            if (!(y16 && !x32 && H % 128 == 0 && launch_layernorm16(H / 128, e.q, ly.ln2g, ly.ln2b, (int)T, eps, e.x16, st)))
-                k_layernorm<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(e.y32, x32, (r16 && !y16) ? e.x16 : nullptr, ly.ln2g, ly.ln2b, (int)T, H, eps, x32, e.x16, y16 ? e.q : nullptr);
+            if (!(y16 && !x32 && launch_layernorm16(H, e.q, ly.ln2g, ly.ln2b, (int)T, eps, e.x16, st)))
+                launch_layernorm(e.y32, x32, (r16 && !y16) ? e.x16 : nullptr, ly.ln2g, ly.ln2b, (int)T, H, eps, x32, e.x16, y16 ? e.q : nullptr, st);
         }
         AK_HIP(hipGetLastError());
     }

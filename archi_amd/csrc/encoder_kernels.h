@@ -110,6 +110,13 @@ int launch_attn(const AttnArgs &a, hipStream_t st);
 int launch_attn_prepare(const int *mask, int B, int S, float *maskf, uint32_t *blkmask, hipStream_t st);
 // position of key s inside its V^T row: the keys of a group of 16 are stored [0-3, 8-11, 4-7, 12-15] (attention.hip)
 __host__ __device__ inline int vt_pos(int s) { return (s & ~12) | ((s & 4) << 1) | ((s & 8) >> 1); }
+// the stand-alone LayerNorm launches of encoder.hip: y = LN(x + residual) g + b, one wave per row (H % 4 == 0, H <= 1024; x float32 rows or,
+// x16in != NULL, bf16 rows; residual res (float32) or res16 (bf16) or neither; y32 may be NULL); bf16 rows in and out without a
+// residual (returns false without launching unless H % 128 == 0 and H <= 1024); the lazy path's last LayerNorm over rows gamma (.) r
+void launch_layernorm(const float *x, const float *res, const uint16_t *res16, const float *g, const float *bta, int T, int H, float eps,
+                      float *y32, uint16_t *y16, const uint16_t *x16in, hipStream_t st);
+bool launch_layernorm16(int H, const uint16_t *x16in, const float *g, const float *bta, int T, float eps, uint16_t *y16, hipStream_t st);
+void launch_ln_apply16(const uint16_t *rt, const float *stats, const float *g, const float *bta, int64_t T, int H, uint16_t *y16, hipStream_t st);
 bool gemm_ln_supported(int H, int64_t T, int K);
 int launch_gemm_ln(const GemmLnArgs &a, hipStream_t st);
 int launch_gemm_ln_x3(const GemmLnArgs &a, hipStream_t st);   // split-bf16 operands ([hi | lo] rows, K = 3 K'), float32 residual, LayerNorm output as float32 + [hi | lo] rows

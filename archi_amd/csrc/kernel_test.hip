@@ -95,6 +95,108 @@ extern "C" int ak_kt_gemm_skinny_qkv(const uint16_t *X, const uint16_t *W, const
     return launch_gemm_skinny_qkv(X, W, bias, rows, H, K, q, k, vt, S, T, qscale, (hipStream_t)stream);
 }
 
+// launch_gemm_ln: x32 != NULL the float32 residual stream (in place) with its bf16 copy x16; x32 == NULL: x16 alone, in place
+extern "C" int ak_kt_gemm_ln(const uint16_t *X, const uint16_t *W, const float *bias, const float *gamma, const float *beta, float *x32,
+                             uint16_t *x16, int T, int K, float eps, void *stream) {
+    AK_BIND();
+    if (!gemm_ln_supported(384, T, K)) AK_FAIL(-1, "ak_kt_gemm_ln: gemm_ln_supported refuses this shape");
+    GemmLnArgs a{X, W, bias, gamma, beta, x32, x16, T, K, eps, nullptr};
+    return launch_gemm_ln(a, (hipStream_t)stream);
+}
+
+// ffn_relayout into wbuf (ak_kt_ffn384_weight_bytes(I) bytes), as ak_encoder_create does, then launch_ffn384. ctx == NULL: the
+// feed-forward block alone (wo, bo, gamma1, beta1 unused by the kernel; wo is still laid out: one relayout call)
+extern "C" long long ak_kt_ffn384_weight_bytes(int I) { return (long long)ffn_weight_bytes(I); }
+extern "C" int ak_kt_ffn384(uint16_t *x16, const uint16_t *wo, const uint16_t *w1, const uint16_t *w2, const float *b1, const float *b2,
+                            const float *gamma2, const float *beta2, const uint16_t *ctx, const float *bo, const float *gamma1,
+                            const float *beta1, uint16_t *wbuf, int T, int I, float eps, void *stream) {
+    AK_BIND();
+    hipStream_t st = (hipStream_t)stream;
+    if (!ffn_fused_supported(384, I, T)) AK_FAIL(-1, "ak_kt_ffn384: ffn_fused_supported refuses this shape");
+    const uint16_t *wf = nullptr;
+    if (int rc = ffn_relayout(wo, w1, w2, I, wbuf, &wf, st)) return rc;
+    FfnArgs a{x16, wf, b1, b2, gamma2, beta2, ctx, ctx ? wbuf : nullptr, ctx ? bo : nullptr, ctx ? gamma1 : nullptr, ctx ? beta1 : nullptr, T, I, eps, nullptr};
+    return launch_ffn384(a, st);
+}
+
+// qkv384_relayout into wbuf (ak_kt_qkv384_weight_bytes() bytes), then launch_qkv384
+extern "C" long long ak_kt_qkv384_weight_bytes() { return (long long)qkv384_weight_bytes(); }
+extern "C" int ak_kt_qkv384(const uint16_t *x16, const uint16_t *wqkv, const float *bqkv, uint16_t *wbuf, uint16_t *q, uint16_t *k,
+                            uint16_t *vt, int Tpad, int T, int S, float qscale, int head_major, void *stream) {
+    AK_BIND();
+    hipStream_t st = (hipStream_t)stream;
+    if (!qkv384_supported(384, Tpad, S) || T < 0 || T > Tpad) AK_FAIL(-1, "ak_kt_qkv384: qkv384_supported refuses this shape");
+    if (int rc = qkv384_relayout(wqkv, bqkv, wbuf, st)) return rc;
+    QkvArgs a{x16, wbuf, nullptr, q, k, vt, Tpad, T, S, qscale, 0, head_major};
+    return launch_qkv384(a, st);
+}
+
+// the GemmArgs fields the lazy-LayerNorm modes 0, 1 and 4 read (tests/kernel_worker.py mirrors this struct with ctypes)
+struct AkKtGemmLazy {
+    const uint16_t *X, *W; const float *bias;
+    int T, N, K;
+    uint16_t *out_bf16; int ldo;
+    const uint16_t *res16;
+    uint16_t *q, *k, *vt; int H, S; float qscale;
+    const float *fold_c, *a_stats, *res_stats, *res_g, *res_b, *out_g;
+    float *out_stats;
+    int nslot; float inv_h, eps;
+};
+
+extern "C" int ak_kt_gemm_lazy(int mode, const AkKtGemmLazy *g, void *stream) {
+    AK_BIND();
+    if (!g) AK_FAIL(-1, "ak_kt_gemm_lazy: NULL argument block");
+    GemmArgs a{};
+    a.X = g->X; a.W = g->W; a.bias = g->bias;
+    a.T = g->T; a.N = g->N; a.K = g->K;
+    a.out_bf16 = g->out_bf16; a.ldo = g->ldo;
+    a.res16 = g->res16;
+    a.q = g->q; a.k = g->k; a.vt = g->vt; a.H = g->H; a.S = g->S; a.qscale = g->qscale;
+    a.fold_c = g->fold_c; a.a_stats = g->a_stats; a.res_stats = g->res_stats; a.res_g = g->res_g; a.res_b = g->res_b; a.out_g = g->out_g;
+    a.out_stats = g->out_stats;
+    a.nslot = g->nslot; a.inv_h = g->inv_h; a.eps = g->eps;
+    return launch_gemm_lazy(mode, a, (hipStream_t)stream);
+}
+
+extern "C" int ak_kt_ln_finalize(const float *part, int nslot, long long T, float inv_h, float eps, float *out, void *stream) {
+    AK_BIND();
+    if (nslot <= 0 || T <= 0) AK_FAIL(-1, "ak_kt_ln_finalize: nslot, T > 0");
+    return launch_ln_finalize(part, nslot, T, inv_h, eps, out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kt_fold_ln(const uint16_t *W, const float *gamma, const float *beta, const float *bias, int N, int K, float *c, float *bf,
+                             void *stream) {
+    AK_BIND();
+    if (N <= 0 || K <= 0) AK_FAIL(-1, "ak_kt_fold_ln: N, K > 0");
+    return launch_fold_ln(W, gamma, beta, bias, N, K, c, bf, (hipStream_t)stream);
+}
+
+// the stand-alone LayerNorm launches of the forward pass (encoder.hip)
+extern "C" int ak_kt_layernorm(const float *x, const float *res, const uint16_t *res16, const float *g, const float *bta, int T, int H,
+                               float eps, float *y32, uint16_t *y16, const uint16_t *x16in, void *stream) {
+    AK_BIND();
+    if (T <= 0 || H <= 0 || H % 4 || H > 1024) AK_FAIL(-1, "ak_kt_layernorm: H % 4 == 0, H <= 1024");
+    launch_layernorm(x, res, res16, g, bta, T, H, eps, y32, y16, x16in, (hipStream_t)stream);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ak_kt_layernorm16(const uint16_t *x16in, const float *g, const float *bta, int T, int H, float eps, uint16_t *y16, void *stream) {
+    AK_BIND();
+    if (T <= 0 || !launch_layernorm16(H, x16in, g, bta, T, eps, y16, (hipStream_t)stream)) AK_FAIL(-1, "ak_kt_layernorm16: H % 128 == 0, H <= 1024");
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ak_kt_ln_apply16(const uint16_t *rt, const float *stats, const float *g, const float *bta, long long T, int H, uint16_t *y16,
+                                void *stream) {
+    AK_BIND();
+    if (T <= 0 || H <= 0 || H % 8) AK_FAIL(-1, "ak_kt_ln_apply16: H % 8 == 0");
+    launch_ln_apply16(rt, stats, g, bta, T, H, y16, (hipStream_t)stream);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
 // host only: where key s sits inside its V^T row
 extern "C" int ak_kt_vt_pos(int s) { return vt_pos(s); }
 

@@ -72,7 +72,11 @@ def test_kernel_test_entry_points_exist_in_the_dbg_library_only(built):
         return set(re.findall(r"\b(ak_kt_[a-z0-9_]+)\b", out))
 
     assert exported("libarchi_hip.so") == set()
-    assert exported("libarchi_hip_dbg.so") == {name for name, _, _ in built.KT_SYMBOLS} and len(built.KT_SYMBOLS) == 8
+    assert exported("libarchi_hip_dbg.so") == {name for name, _, _ in built.KT_SYMBOLS} and len(built.KT_SYMBOLS) == 19
+    # ... the wrappers of the kernels that carry a LayerNorm among them
+    assert {name for name, _, _ in built.KT_SYMBOLS} >= {"ak_kt_gemm_ln", "ak_kt_ffn384", "ak_kt_ffn384_weight_bytes", "ak_kt_qkv384", "ak_kt_qkv384_weight_bytes",
+                                                          "ak_kt_gemm_lazy", "ak_kt_ln_finalize", "ak_kt_fold_ln", "ak_kt_layernorm", "ak_kt_layernorm16",
+                                                          "ak_kt_ln_apply16"}
     # the one host-only wrapper: the V^T key order the tests' packers assume is the kernels' vt_pos
     import ctypes
     import numpy as np
