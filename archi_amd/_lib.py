@@ -89,6 +89,35 @@ class AkModernBertConfig(ctypes.Structure):
     ]
 
 
+GEMMA_MAX_LAYERS = 64     # AK_GEMMA_MAX_LAYERS
+
+
+class AkGemmaConfig(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("q_heads", ctypes.c_int),
+        ("kv_heads", ctypes.c_int),
+        ("head_dim", ctypes.c_int),
+        ("intermediate", ctypes.c_int),
+        ("max_position", ctypes.c_int),
+        ("rms_eps", ctypes.c_float),
+        ("global_rope_theta", ctypes.c_float),
+        ("local_rope_theta", ctypes.c_float),
+        ("query_pre_attn_scalar", ctypes.c_float),
+        ("half_window", ctypes.c_int),
+        ("attn_softcap", ctypes.c_float),
+        ("final_softcap", ctypes.c_float),
+        ("rope_type", ctypes.c_int),
+        ("activation", ctypes.c_int),
+        ("attention_bias", ctypes.c_int),
+        ("n_dense", ctypes.c_int),
+        ("dense_out", ctypes.c_int * 2),
+        ("layer_global", ctypes.c_int * GEMMA_MAX_LAYERS),
+    ]
+
+
 _lock = threading.Lock()
 _lib = None
 _inited_device = None
@@ -149,9 +178,14 @@ SYMBOLS = [
     ("ak_decoder_destroy", _I, [_P]),
     ("ak_decoder_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     ("ak_decoder_rope_table", _I, [ctypes.c_float, _I, _I, _P, _P]),
+    ("ak_decoder_rope_table_inv", _I, [_P, _I, _I, _P, _P]),
     ("ak_mbert_create", _I, [ctypes.POINTER(AkModernBertConfig), _P, _I, ctypes.POINTER(_P)]),
     ("ak_mbert_destroy", _I, [_P]),
     ("ak_mbert_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("ak_gemma_create", _I, [ctypes.POINTER(AkGemmaConfig), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_gemma_destroy", _I, [_P]),
+    ("ak_gemma_set_rope_inv_freq", _I, [_P, _P, _P]),
+    ("ak_gemma_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_create_ex", _I, [ctypes.c_char_p, _I, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.POINTER(ctypes.c_char_p), _I, ctypes.POINTER(_P)]),
@@ -210,6 +244,14 @@ KT_SYMBOLS = [
     ("ak_kt_ln_apply16", _I, [_P, _P, _P, _P, _I64, _I, _P, _P]),
 ]
 
+# the EmbeddingGemma kernels' single-launch entry points (tests/test_gemma_kernels_gpu.py): libarchi_hip_dbg.so only, like
+# KT_SYMBOLS, and a set of their own (ak_ktg_*)
+KTG_SYMBOLS = [
+    ("ak_ktg_attn_gqa", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    ("ak_ktg_qk_norm_rope", _I, [_P, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, ctypes.c_float, _P, _P, _P, _P]),
+    ("ak_ktg_gemm_geglu_tanh", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+]
+
 
 def load() -> ctypes.CDLL:
     """dlopen the library and bind every declared symbol (no GPU needed)."""
@@ -238,7 +280,7 @@ def load() -> ctypes.CDLL:
                 fn.restype = res
                 fn.argtypes = args
             if path != LIB_PATH:
-                for name, res, args in KT_SYMBOLS:
+                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS:
                     fn = getattr(lib, name)
                     fn.restype = res
                     fn.argtypes = args

@@ -23,6 +23,7 @@ EMBEDDING_DIMENSIONS = {
     "sentence-transformers/multi-qa-mpnet-base-dot-v1": 768,
     "sentence-transformers/paraphrase-mpnet-base-v2": 768,
     "BAAI/bge-m3": 1024,
+    "google/embeddinggemma-300m": 768,
     "intfloat/multilingual-e5-large": 1024,
     "intfloat/multilingual-e5-base": 768,
     "sentence-transformers/paraphrase-multilingual-mpnet-base-v2": 768,

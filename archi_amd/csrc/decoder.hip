@@ -24,6 +24,15 @@ constexpr int DEC_HD = 128, DEC_MAX_S = 8192;
 // inv_freq[i] = 1 / theta^(2 i / hd) (the exponent 2 i / hd is exact in float32; the power is rounded once from double),
 // angle = float(pos) * inv_freq[i] (one float32 product, as HF's float32 matmul of a 1-deep product), cos / sin rounded once from
 // double. Table rows [n_pos][hd / 2]: HF's cos / sin are these rows twice (cat(freqs, freqs)).
+// the second half of the routine on given inverse frequencies (ak_decoder_rope_table_inv: a caller that holds HF's own buffer)
+static void rope_table_from_inv(const float *inv, int half, int n_pos, float *c, float *s) {
+    for (int p = 0; p < n_pos; p++)
+        for (int i = 0; i < half; i++) {
+            const float ang = (float)p * inv[i];
+            c[(size_t)p * half + i] = (float)std::cos((double)ang);
+            s[(size_t)p * half + i] = (float)std::sin((double)ang);
+        }
+}
 static void rope_table_host(float theta, int hd, int n_pos, float *c, float *s) {
     const int half = hd / 2;
     std::vector<float> inv(half);
@@ -31,12 +40,7 @@ static void rope_table_host(float theta, int hd, int n_pos, float *c, float *s) 
         const float e = (float)(2 * i) / (float)hd;
         inv[i] = 1.0f / (float)std::pow((double)theta, (double)e);
     }
-    for (int p = 0; p < n_pos; p++)
-        for (int i = 0; i < half; i++) {
-            const float ang = (float)p * inv[i];
-            c[(size_t)p * half + i] = (float)std::cos((double)ang);
-            s[(size_t)p * half + i] = (float)std::sin((double)ang);
-        }
+    rope_table_from_inv(inv.data(), half, n_pos, c, s);
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------
@@ -290,6 +294,12 @@ extern "C" int ak_decoder_rope_table(float theta, int head_dim, int n_pos, float
     if (!cos_out || !sin_out || head_dim <= 0 || head_dim % 2 || n_pos < 0 || !(theta > 0.f))
         AK_FAIL(-1, "ak_decoder_rope_table: bad arguments");
     rope_table_host(theta, head_dim, n_pos, cos_out, sin_out);
+    return 0;
+}
+
+extern "C" int ak_decoder_rope_table_inv(const float *inv_freq, int half, int n_pos, float *cos_out, float *sin_out) {
+    if (!inv_freq || !cos_out || !sin_out || half <= 0 || n_pos < 0) AK_FAIL(-1, "ak_decoder_rope_table_inv: bad arguments");
+    rope_table_from_inv(inv_freq, half, n_pos, cos_out, sin_out);
     return 0;
 }
 

@@ -177,6 +177,24 @@ struct CausalAttnArgs {
 };
 bool attn_causal_supported(int nq, int nkv, int head_dim, int S);
 int launch_attn_causal(const CausalAttnArgs &a, hipStream_t st);
+// bidirectional grouped-query attention at head dim 256 with an optional band (attn_gqa.hip; EmbeddingGemma, gemma.hip): q
+// [B][nq][S][256] pre-scaled by log2(e) * scalar^-0.5, k [B][nkv][S][256], vt [B][nkv][256][S] (keys of a 16-group in vt_pos order),
+// ctx [B * S][nq * 256]; lens [B]. nq / nkv in 1 .. 4, S % 32 == 0, S <= ATTN_GQA_MAX_S.
+struct GqaAttnArgs {
+    const uint16_t *q, *k, *vt;
+    const int *lens;
+    uint16_t *ctx;
+    int B, S, nq, nkv;
+    int window = 0;              // set by launch_attn_gqa: key k visible to query q iff |q - k| <= window
+};
+constexpr int ATTN_GQA_MAX_S = 2048;
+bool attn_gqa_supported(int nq, int nkv, int head_dim, int S);
+// half_window 0 (or >= S): every key below the row's length
+int launch_attn_gqa(const GqaAttnArgs &a, int half_window, hipStream_t st);
+// gemma.hip: per-head RMSNorm (weights with the 1 folded in) + rotate_half RoPE of the q and k heads of QKV rows [T][(nq + 2 nkv) 256],
+// q scaled; q / k head-major, v transposed -- the layouts of GqaAttnArgs. rc / rs: [n_pos][128]
+int launch_gm_qk_norm_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
+                           const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *vt, hipStream_t st);
 bool gemm_skinny_supported(int N, int K);
 int launch_gemm_skinny(const uint16_t *X, const uint16_t *W, const float *bias, int rows, int N, int K, float *out_f32,
                        uint16_t *out_bf16, int ldo, hipStream_t st);

@@ -20,6 +20,8 @@
 //           N / 2 columns wide (a.ldo = N / 2) -- the 2I-wide product never reaches memory
 //   MODE 8  GeGLU (ModernBERT's Wi, mbert.hip): the same interleaved layout (row 2 j = row j of Wi's first half, the GELU input a_j;
 //           row 2 j + 1 = row j of its second half, the gate g_j); it stores gelu_erf(a) g as bf16, N / 2 columns wide
+//   MODE 9  GeGLU with the TANH GELU (EmbeddingGemma's gate / up projection, gemma.hip: gelu_pytorch_tanh): MODE 8's layout with
+//           row 2 j = gate_proj row j (the GELU input), row 2 j + 1 = up_proj row j; it stores gelu_tanh(a) g
 // Replaces the torch CPU GEMMs behind SentenceTransformer.encode as called at
 // /root/reference/src/data_manager/vectorstore/manager.py:373.
 //
@@ -293,6 +295,11 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
             // (a_j, g_j, a_j+1, g_j+1): gelu(a) g with the erf polynomial of MODE 1 (the gate lanes of gelu_erf4 are not used)
             const f32x4 ge = gelu_erf4(o);
             *(uint32_t *)(a.out_bf16 + (int64_t)t * a.ldo + (n >> 1)) = pack_bf16x2(ge.x * o.y, ge.z * o.w);
+        } else if constexpr (MODE == 9) {
+            // gelu_tanh(a) = 0.5 a (1 + tanh(u)) = a / (1 + exp(-2 u)), u = sqrt(2 / pi) (a + 0.044715 a^3)
+            const float u0 = 0.7978845608028654f * (o.x + 0.044715f * o.x * o.x * o.x), u1 = 0.7978845608028654f * (o.z + 0.044715f * o.z * o.z * o.z);
+            const float s0 = o.x * o.y / (1.0f + __expf(-2.0f * u0)), s1 = o.z * o.w / (1.0f + __expf(-2.0f * u1));
+            *(uint32_t *)(a.out_bf16 + (int64_t)t * a.ldo + (n >> 1)) = pack_bf16x2(s0, s1);
         } else {
             *(uint2 *)(a.out_bf16 + (int64_t)t * a.ldo + n) = cvt_bf16x4(o);
         }
@@ -579,7 +586,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
     auto tile_out = [&](char *scr, int tn) {
         if constexpr (MODE == 1 || MODE == 3 || MODE == 4) rows_out(scr, a.out_bf16, a.ldo, tn * G_BN, 1.0f);
         else if constexpr (MODE == 6) rows_out_split(scr, tn * G_BN);
-        else if constexpr (MODE == 7 || MODE == 8) all_pieces();
+        else if constexpr (MODE == 7 || MODE == 8 || MODE == 9) all_pieces();
         else if constexpr (MODE == 0 && G_BN == 256) {     // H % 256 == 0: a tile is all Q, all K or all V
             if (tn * G_BN >= 2 * a.H) v_out(scr);
             else {
@@ -860,8 +867,10 @@ static int launch_gemm_bn(int mode, const GemmArgs &a, hipStream_t st) {
         AK_HIP(hipFuncSetAttribute((const void *)k_gemm<3, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
         AK_HIP(hipFuncSetAttribute((const void *)k_gemm<4, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
         AK_HIP(hipFuncSetAttribute((const void *)k_gemm<7, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
-        if constexpr (BN == 128 || PH)
+        if constexpr (BN == 128 || PH) {
             AK_HIP(hipFuncSetAttribute((const void *)k_gemm<8, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
+            AK_HIP(hipFuncSetAttribute((const void *)k_gemm<9, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
+        }
         attr = true;
     }
     const int ntiles = (a.T / G_BT) * (a.N / BN);
@@ -875,6 +884,10 @@ static int launch_gemm_bn(int mode, const GemmArgs &a, hipStream_t st) {
         case 8:       // (not instantiated on the wide tile's in-step loop, where the epilogue's registers would spill: launch_gemm)
             if constexpr (BN == 128 || PH) k_gemm<8, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a);
             else AK_FAIL(-1, "gemm: MODE 8 runs on the narrow tile or the wide phased tile");
+            break;
+        case 9:       // the tanh twin of MODE 8, on the same two tiles
+            if constexpr (BN == 128 || PH) k_gemm<9, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a);
+            else AK_FAIL(-1, "gemm: MODE 9 runs on the narrow tile or the wide phased tile");
             break;
         default: k_gemm<3, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a); break;
     }
@@ -1044,7 +1057,7 @@ int launch_gemm(int mode, const GemmArgs &a_in, hipStream_t st) {
     if (force_bn == 128) wide = false;
     if (force_bn == 256 && a.N % 256 == 0 && (mode != 0 || a.H % 256 == 0)) wide = true;
     static const int phased = env_get("AK_GEMM_PHASED") ? atoi(env_get("AK_GEMM_PHASED")) : 1;      // A/B: 0 = the in-step loop on the wide tile
-    if (mode == 8 && !(phased && a.K >= 192)) wide = false;      // MODE 8 has no wide in-step instantiation (it would spill)
+    if ((mode == 8 || mode == 9) && !(phased && a.K >= 192)) wide = false;      // MODE 8 / 9 have no wide in-step instantiation (it would spill)
     if (wide) a.fb = gemm_fb(a.N / 256);
     if (wide && phased && a.K >= 192) return launch_gemm_bn<256, true>(mode, a, st);
     return wide ? launch_gemm_bn<256>(mode, a, st) : launch_gemm_bn<128>(mode, a, st);

@@ -200,4 +200,30 @@ extern "C" int ak_kt_ln_apply16(const uint16_t *rt, const float *stats, const fl
 // host only: where key s sits inside its V^T row
 extern "C" int ak_kt_vt_pos(int s) { return vt_pos(s); }
 
+// ---- EmbeddingGemma (tests/test_gemma_kernels_gpu.py). Named ak_ktg_*: they are not part of the ak_kt_* set ----
+// one launch_attn_gqa: q [B][nq][S][256], k [B][nkv][S][256], vt [B][nkv][256][S] (vt_pos order), ctx [B * S][nq * 256]; half_window 0 = every key
+extern "C" int ak_ktg_attn_gqa(const uint16_t *q, const uint16_t *k, const uint16_t *vt, const int *lens, uint16_t *ctx, int B, int S, int nq,
+                               int nkv, int half_window, void *stream) {
+    AK_BIND();
+    GqaAttnArgs a{};
+    a.q = q; a.k = k; a.vt = vt; a.lens = lens; a.ctx = ctx;
+    a.B = B; a.S = S; a.nq = nq; a.nkv = nkv;
+    return launch_attn_gqa(a, half_window, (hipStream_t)stream);
+}
+
+// one k_gm_qk_norm_rope launch: qkv [B * S][(nq + 2 nkv) 256]; qn / kn the folded (1 + w) head-norm weights; rc / rs [n_pos][128]
+extern "C" int ak_ktg_qk_norm_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps,
+                                   const float *rc, const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *vt, void *stream) {
+    AK_BIND();
+    return launch_gm_qk_norm_rope(qkv, B, S, nq, nkv, qn, kn, eps, rc, rs, qscale, q, k, vt, (hipStream_t)stream);
+}
+
+// one launch_gemm(9): the tanh-GeGLU epilogue; X [T][K], W [N][K] (gate / up rows interleaved), out [T][N / 2] bf16
+extern "C" int ak_ktg_gemm_geglu_tanh(const uint16_t *X, const uint16_t *W, const float *bias, int T, int N, int K, uint16_t *out, void *stream) {
+    AK_BIND();
+    GemmArgs a{};
+    a.X = X; a.W = W; a.bias = bias; a.T = T; a.N = N; a.K = K; a.out_bf16 = out; a.ldo = N / 2;
+    return launch_gemm(9, a, (hipStream_t)stream);
+}
+
 #endif  // AK_DBG_KERNELS

@@ -275,6 +275,16 @@ class HipDecoder:
         return out
 
 
+def rope_table_inv(inv_freq, n_pos: int):
+    """ak_decoder_rope_table_inv (host only): cos, sin [n_pos][len(inv_freq)] float32 from given float32 inverse frequencies."""
+    lib = _lib.load()
+    inv = np.ascontiguousarray(inv_freq, np.float32)
+    c = np.empty((n_pos, inv.size), np.float32)
+    s = np.empty((n_pos, inv.size), np.float32)
+    check(lib.ak_decoder_rope_table_inv(inv.ctypes.data, inv.size, n_pos, c.ctypes.data, s.ctypes.data), "ak_decoder_rope_table_inv")
+    return c, s
+
+
 def rope_table(theta: float, n_pos: int, head_dim: int = HEAD_DIM):
     """ak_decoder_rope_table (host only): cos, sin [n_pos][head_dim / 2] float32."""
     lib = _lib.load()

@@ -36,6 +36,8 @@ from .encoder import (LONG_MAX_SEQ, MODEL_SHAPES, MPNET_SHAPES, XLMR_PADDING_IDX
 from .decoder import MAX_SEQ, QWEN3_SHAPES, BpeTokenizer, HipDecoder, load_qwen3_weights, random_qwen3_weights, read_decoder_st_config
 from .modernbert import MODERNBERT_SHAPES, HipModernBert, load_modernbert_weights, random_modernbert_weights
 from .modernbert import MAX_SEQ as MODERNBERT_MAX_SEQ
+from .gemma import GEMMA_SHAPES, HipGemma, load_gemma_weights, random_gemma_weights
+from .gemma import MAX_SEQ as GEMMA_MAX_SEQ
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
 # special tokens by name: (cls, sep, unk, the strings the full tokenizer matches in raw text)
@@ -188,6 +190,15 @@ def _is_modernbert(model_name: str) -> bool:
     return model_name in MODERNBERT_SHAPES
 
 
+def _is_gemma(model_name: str) -> bool:
+    """An EmbeddingGemma checkpoint directory (config.json model_type "gemma3_text") or one of the named Gemma shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "gemma3_text"
+    return model_name in GEMMA_SHAPES
+
+
 def _is_mpnet(model_name: str) -> bool:
     """An MPNet checkpoint directory (config.json model_type "mpnet") or one of the named MPNet shapes."""
     import json
@@ -236,6 +247,9 @@ class ArchiHipEmbeddings:
             return
         if _is_modernbert(model_name):
             self._init_modernbert(model_name, device)
+            return
+        if _is_gemma(model_name):
+            self._init_gemma(model_name, device)
             return
         rel_bias = pos_pad = None
         if _is_xlmr(model_name):
@@ -418,6 +432,41 @@ class ArchiHipEmbeddings:
         self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, MODERNBERT_MAX_SEQ)
         self.dimensions = int(shape[1])
         self.encoder = HipModernBert(shape, weights, device=device)
+
+    def _init_gemma(self, model_name: str, device: Optional[int]) -> None:
+        """EmbeddingGemma (google/embeddinggemma-300m): a local checkpoint directory (config.json model_type gemma3_text with
+        use_bidirectional_attention, safetensors, tokenizer.json -- its post-processor adds <bos> / <eos> --, the sentence-transformers
+        files with the 2_Dense / 3_Dense modules) or a named shape with synthetic_seed. bf16 only, mean pooling, rows up to 2048
+        tokens. Prompts ("task: search result | query: ") stay with the caller."""
+        precision = str(self.model_kwargs.get("precision", "bf16"))
+        if precision != "bf16":
+            raise ValueError(f"precision {precision!r}: Gemma embedders run in bf16 only")
+        if os.path.isdir(model_name):
+            tf = os.path.join(model_name, "tokenizer.json")
+            if not os.path.exists(tf):
+                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- an EmbeddingGemma checkpoint needs its tokenizer")
+            shape, weights = load_gemma_weights(model_name)
+            st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
+            if self.model_kwargs.get("pooling", st_pool) != "mean":
+                raise ValueError(f"{model_name}: pooling {self.model_kwargs.get('pooling', st_pool)!r} (Gemma embedders pool 'mean')")
+            self.normalize = self.normalize or st_norm
+            self.tokenizer = BpeTokenizer(tf)
+        else:
+            if "synthetic_seed" not in self.model_kwargs:
+                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass an EmbeddingGemma checkpoint "
+                                        "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
+            shape = GEMMA_SHAPES[model_name]
+            weights = random_gemma_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]),
+                                           std=float(self.model_kwargs.get("synthetic_std", 0.02)))
+            st_len = None
+            self.normalize = True                      # the released sentence-transformers model carries a Normalize module
+            tf = self.model_kwargs.get("tokenizer_file")
+            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
+        self.pooling = "mean"
+        max_pos = int(shape[7])
+        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, GEMMA_MAX_SEQ)
+        self.encoder = HipGemma(shape, weights, device=device)
+        self.dimensions = int(self.encoder.out_dim)
 
     # -- LangChain Embeddings duck type -------------------------------------
     def embed_documents(self, texts: List[str]) -> List[List[float]]:

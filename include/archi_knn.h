@@ -446,6 +446,10 @@ int ak_decoder_forward_lens(ak_decoder_t h, const int32_t *ids_dev, int ld_ids, 
  * inv_freq[i] = 1 / theta^(2 i / head_dim) (HF's default rotary embedding; its cos / sin are these rows twice). Host only -- no GPU
  * work; exported so that the CPU suite can hold the table to HF's. */
 int ak_decoder_rope_table(float theta, int head_dim, int n_pos, float *cos_out, float *sin_out);
+/* The same table from GIVEN inverse frequencies inv_freq[half] (the second half of the routine above): angle = float(pos) * inv_freq[i].
+ * For a caller that holds the model's own inv_freq buffer: torch's vectorised float32 pow, from which HF's buffer comes, is 1 ulp off
+ * the correctly rounded 1 / theta^(2 i / head_dim) at one frequency in 128 (head_dim 256), and a binding can hand over HF's bits. */
+int ak_decoder_rope_table_inv(const float *inv_freq, int half, int n_pos, float *cos_out, float *sin_out);
 
 /* ---- ModernBERT encoders (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base, lightonai/modernbert-embed-large) ---- */
 /* The forward pass of HF ModernBertModel: token embedding + LayerNorm, pre-norm layers (fused Wqkv, rotate_half RoPE at head size 64
@@ -483,6 +487,65 @@ int ak_mbert_destroy(ak_mbert_t h);
  * AK_POOL_CLS over the final norm of the valid tokens; out_dev [B][H] float32, L2-normalised when `normalise` != 0. S a multiple of
  * 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
 int ak_mbert_forward_lens(ak_mbert_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                          int pooling, int normalise, float *out_dev, void *stream);
+
+/* ---- EmbeddingGemma encoders (google/embeddinggemma-300m) ---- */
+/* The forward pass of HF Gemma3TextModel run bidirectionally (use_bidirectional_attention): token embedding times sqrt(hidden), layers
+ * with four RMSNorms each (x rsqrt(mean(x^2) + eps) (1 + w): before and after both sub-layers), per-head q / k RMSNorm, rotate_half RoPE
+ * at head size 256 with one theta for the full and one for the sliding-window layers, grouped-query attention (query head h reads kv
+ * head h / (q_heads / kv_heads)) scaled by query_pre_attn_scalar^-0.5 -- in a sliding layer key k is visible to query q iff
+ * |q - k| <= half_window --, a GeGLU MLP with the tanh GELU, the final norm; then the sentence-transformers tail: mean pooling over the
+ * valid tokens, 0 - 2 Dense matrices (no bias, identity activation) in float32, L2 normalisation. No bias anywhere. bf16 MFMA GEMMs,
+ * float32 residual stream / norms / softmax. */
+typedef void *ak_gemma_t;
+#define AK_GEMMA_MAX_LAYERS 64
+typedef struct AkGemmaConfig {
+    int vocab_size;     /* 262144 */
+    int hidden;         /* 768; a multiple of 128, <= 1024 */
+    int layers;         /* 24; <= AK_GEMMA_MAX_LAYERS */
+    int q_heads;        /* 3 */
+    int kv_heads;       /* 1; q_heads a multiple of it, q_heads / kv_heads <= 4 */
+    int head_dim;       /* 256 (the only head size the attention kernel takes) */
+    int intermediate;   /* 1152; a multiple of 64 */
+    int max_position;   /* 2048 (rows are limited to min(max_position, 2048) tokens) */
+    float rms_eps;      /* 1e-6 */
+    float global_rope_theta;      /* 1e6: layers with layer_global[l] != 0 */
+    float local_rope_theta;       /* 1e4: the sliding-window layers */
+    float query_pre_attn_scalar;  /* 256: scores are scaled by its inverse square root, not by head_dim's */
+    int half_window;    /* sliding_window / 2 = 256 (what the bidirectional config leaves a query to each side); >= 1 */
+    float attn_softcap; /* attn_logit_softcapping: must be 0 (none) */
+    float final_softcap;/* final_logit_softcapping: must be 0 (none) */
+    int rope_type;      /* 0 = default; anything else is refused */
+    int activation;     /* 0 = gelu_pytorch_tanh; anything else is refused */
+    int attention_bias; /* must be 0 */
+    int n_dense;        /* Dense modules behind the pooling: 0, 1 or 2 */
+    int dense_out[2];   /* their output widths (3072, 768); the input width of the first is hidden, of the second dense_out[0] */
+    int layer_global[AK_GEMMA_MAX_LAYERS];   /* per layer: != 0 full attention, 0 sliding window */
+} AkGemmaConfig;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] as torch.nn.Linear.weight, norm vectors float32 AS STORED -- the
+ * library adds the 1 --, Dense matrices float32):
+ *   0 embed_tokens [vocab][H] bf16, 1 norm [H],
+ *   per layer l (base 2 + 13 * l):
+ *     +0 input_layernorm [H] +1 q_proj [q_heads 256][H] +2 k_proj [kv_heads 256][H] +3 v_proj [kv_heads 256][H] +4 q_norm [256]
+ *     +5 k_norm [256] +6 o_proj [H][q_heads 256] +7 post_attention_layernorm [H] +8 pre_feedforward_layernorm [H] +9 gate_proj [I][H]
+ *     +10 up_proj [I][H] +11 down_proj [H][I] +12 post_feedforward_layernorm [H]
+ *   then n_dense Dense matrices [dense_out[i]][in] float32.
+ * The library concatenates q / k / v_proj, interleaves gate / up_proj (row 2 j = gate row j, row 2 j + 1 = up row j; padded with zero
+ * rows when 2 I is not a multiple of 256, down_proj with zero columns to match) and folds 1 + w into copies of the norm vectors at
+ * create; embed_tokens, o_proj, down_proj and the Dense matrices must stay valid until the handle is destroyed. Refused (non-zero,
+ * message naming the field in the last-error string): head_dim != 256, q_heads % kv_heads, a group > 4, hidden % 128 or > 1024,
+ * intermediate % 64, a soft-cap, rope_type / activation / attention_bias != 0, half_window < 1, layers > AK_GEMMA_MAX_LAYERS, a
+ * weight count other than 2 + 13 * layers + n_dense. */
+int ak_gemma_create(const AkGemmaConfig *cfg, const void *const *weights_dev, int n_weights, ak_gemma_t *out);
+int ak_gemma_destroy(ak_gemma_t h);
+/* Replace the two rotary tables ak_gemma_create built from the thetas (ak_decoder_rope_table at head size 256) by the tables of GIVEN
+ * inverse frequencies (ak_decoder_rope_table_inv): global_inv / local_inv, 128 host floats each -- the full-attention and the
+ * sliding-attention layers' inv_freq buffers of the HF model. Optional; archi_amd.gemma.HipGemma calls it with the frequencies of HF's
+ * own torch expression, so that the tables are HF's to the bit of every frequency. Waits for the handle's work in flight. */
+int ak_gemma_set_rope_inv_freq(ak_gemma_t h, const float *global_inv, const float *local_inv);
+/* The tile layout of ak_mbert_forward_lens. pooling: AK_POOL_MEAN only; out_dev [B][D] float32, D = the last Dense module's width (hidden
+ * without one), L2-normalised when `normalise` != 0. S a multiple of 32, <= 2048 and <= max_position. Asynchronous on `stream`. */
+int ak_gemma_forward_lens(ak_gemma_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
                           int pooling, int normalise, float *out_dev, void *stream);
 
 /* ---- host tokenizer: the tokenisation step inside Embeddings.embed_documents -------- */

@@ -1,0 +1,381 @@
+"""CPU tests of the EmbeddingGemma path: config.json -> shape (and what is refused), weight naming against transformers.Gemma3TextModel,
+the Dense head read from a sentence-transformers directory, the interleaved gate / up layout of the tanh-GeGLU epilogue, the host
+rotary tables at head size 256 for both thetas, the provider's routing and refusals, the new symbols in header / binding / library
+(and none of the single-launch test wrappers in the product library), the register use of the new kernels and of the instantiations
+that must not have moved, and the committed fixtures: reproduced from Gemma3TextModel (float32, eager attention) and sensitive enough
+to the direction of attention, the window, the second theta and the score scale that a forward pass without them could not pass."""
+import concurrent.futures
+import ctypes
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import archi_amd.gemma as gm
+from archi_amd.gemma import GEMMA_SHAPES
+from tests.gemma_ref import PROJECT_BAR_ABS, PROJECT_BAR_COS, hf_model, write_checkpoint
+from tests.golden import make_gemma_fixtures as fx
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BASE = "google/embeddinggemma-300m"
+TINY = "gm-tiny"
+
+
+def _cfg(**change):
+    """config.json of the released model, as the file holds it (sliding_window 512, before the constructor's rewrite)."""
+    d = gm.shape_config_dict(BASE)
+    d.update(change)
+    for k in [k for k, v in change.items() if v is None]:
+        d.pop(k)
+    return d
+
+
+def test_released_config_is_the_base_shape():
+    shape = gm.gemma_config_shape(_cfg(), dense=(3072, 768))
+    assert shape == GEMMA_SHAPES[BASE]
+    assert shape[:7] == (262144, 768, 24, 3, 1, 256, 1152) and shape[11] // 2 == 256 and shape[12] == 256
+    assert shape[13] == (0, 0, 0, 0, 0, 1) * 4 and (shape[9], shape[10]) == (1e6, 1e4)
+    assert gm.gemma_config_shape(_cfg())[14] == ()                                            # a plain Gemma3 text checkpoint: no Dense
+
+
+def test_window_is_what_transformers_makes_of_it():
+    """The constructor rewrites sliding_window W to W // 2 + 1 for a bidirectional model and the mask keeps |q - k| < that: a
+    half-window of W // 2, which is what the handle passes down."""
+    for name in (BASE, TINY):
+        W = GEMMA_SHAPES[name][11]
+        assert gm.shape_hf_config(name).sliding_window == W // 2 + 1
+
+
+def test_config_of_transformers_4_checkpoints():
+    """sliding_window_pattern / rope_theta / rope_local_base_freq instead of layer_types / rope_parameters."""
+    old = _cfg(layer_types=None, rope_parameters=None, sliding_window_pattern=6, rope_theta=1e6, rope_local_base_freq=1e4)
+    assert gm.gemma_config_shape(old, dense=(3072, 768)) == GEMMA_SHAPES[BASE]
+    assert gm.gemma_config_shape(_cfg(layer_types=None, rope_parameters=None), dense=(3072, 768)) == GEMMA_SHAPES[BASE]      # HF's defaults
+
+
+@pytest.mark.parametrize("change,msg", [
+    ({"use_bidirectional_attention": False}, "use_bidirectional_attention"), ({"use_bidirectional_attention": None}, "use_bidirectional_attention"),
+    ({"attention_bias": True}, "attention_bias"), ({"attn_logit_softcapping": 50.0}, "attn_logit_softcapping"),
+    ({"final_logit_softcapping": 30.0}, "final_logit_softcapping"), ({"hidden_activation": "gelu"}, "hidden_activation"),
+    ({"head_dim": 128}, "head_dim"), ({"num_attention_heads": 3, "num_key_value_heads": 2}, "num_key_value_heads"),
+    ({"num_attention_heads": 8, "num_key_value_heads": 1}, "num_attention_heads / num_key_value_heads"),
+    ({"rope_parameters": {"full_attention": {"rope_type": "yarn", "rope_theta": 1e6},
+                          "sliding_attention": {"rope_type": "default", "rope_theta": 1e4}}}, "rope_type"),
+    ({"rope_scaling": {"rope_type": "linear", "factor": 8.0}}, "rope_scaling"),
+    ({"layer_types": ["full_attention"] * 23}, "layer_types"), ({"num_hidden_layers": 65, "layer_types": None}, "num_hidden_layers"),
+    ({"model_type": "gemma3"}, "model_type"), ({"hidden_size": 704}, "hidden_size"), ({"hidden_size": 1152}, "hidden_size"),
+    ({"intermediate_size": 1100}, "intermediate_size"), ({"sliding_window": 1}, "sliding_window"),
+])
+def test_config_refusals_name_the_field(change, msg):
+    with pytest.raises(ValueError, match=msg):
+        gm.gemma_config_shape(_cfg(**change))
+
+
+def test_weight_names_load_strictly_and_round_trip(tmp_path):
+    import torch
+    from transformers import Gemma3TextModel
+    shape = GEMMA_SHAPES[TINY]
+    w = gm.random_gemma_weights(shape, seed=3)
+    assert sorted(w) == sorted(gm.weight_names(shape[2], 2)) and len(w) == 2 + 13 * shape[2] + 2
+    assert all(np.array_equal(v, torch.from_numpy(v).to(torch.bfloat16).float().numpy()) for k, v in w.items() if v.ndim == 2)
+    model = Gemma3TextModel(gm.shape_hf_config(shape))
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in gm.hf_state_dict(w).items()}, strict=True)
+    d = str(tmp_path / "ckpt")
+    write_checkpoint(d, TINY, seed=3, std=0.02)
+    got_shape, got = gm.load_gemma_weights(d)
+    assert got_shape == shape
+    assert sorted(got) == sorted(w) and all(np.array_equal(np.asarray(got[k]), w[k]) for k in w)
+    # a "model." prefix is stripped
+    from safetensors.torch import load_file, save_file
+    sd = load_file(os.path.join(d, "model.safetensors"))
+    save_file({"model." + k: v for k, v in sd.items()}, os.path.join(d, "model.safetensors"))
+    _, again = gm.load_gemma_weights(d)
+    assert all(np.array_equal(np.asarray(again[k]), w[k]) for k in w)
+
+
+@pytest.mark.parametrize("n_dense", [0, 1, 2])
+def test_dense_head_is_read_from_a_sentence_transformers_directory(tmp_path, n_dense):
+    """Zero, one or two Dense modules load, in modules.json order; a bias or an activation is refused by name."""
+    d = str(tmp_path / "ckpt")
+    _, dense = write_checkpoint(d, TINY, seed=5, n_dense=n_dense, tokenizer_json=False)
+    got = gm.read_dense_modules(d)
+    assert len(got) == n_dense and all(np.array_equal(a.numpy(), b.numpy()) for a, b in zip(got, dense))
+    shape, w = gm.load_gemma_weights(d)
+    assert shape[14] == ((1536, 384)[:n_dense]) and sum(k.startswith("dense") for k in w) == n_dense
+    if n_dense:
+        cj = os.path.join(d, "2_Dense", "config.json")
+        c = json.load(open(cj))
+        json.dump(dict(c, bias=True), open(cj, "w"))
+        with pytest.raises(ValueError, match="bias"):
+            gm.read_dense_modules(d)
+        json.dump(dict(c, activation_function="torch.nn.modules.activation.Tanh"), open(cj, "w"))
+        with pytest.raises(ValueError, match="activation_function"):
+            gm.read_dense_modules(d)
+
+
+def test_interleaved_tanh_geglu_equals_hf_mlp():
+    """gemm.hip MODE 9 restated in numpy on the interleaved rows (row 2 j = gate_proj row j, row 2 j + 1 = up_proj row j) against HF's
+    Gemma3MLP (gelu_pytorch_tanh) on the original rows; and it is NOT the erf GELU of MODE 8."""
+    import torch
+    from archi_amd.modernbert import geglu_interleaved
+    shape = GEMMA_SHAPES[TINY]
+    w = gm.random_gemma_weights(shape, seed=8, std=0.1)
+    mlp = hf_model(shape, w).layers[1].mlp
+    x = torch.randn(37, shape[1], generator=torch.Generator().manual_seed(8)) * 2
+    with torch.no_grad():
+        want = mlp(x).numpy()
+    wgu = gm.interleave_gate_up(w["l1.w_gate"], w["l1.w_up"])
+    assert np.array_equal(wgu[0::2], w["l1.w_gate"]) and np.array_equal(wgu[1::2], w["l1.w_up"])
+    y = x.numpy() @ wgu.T
+    got = gm.geglu_tanh_interleaved(y) @ w["l1.w_down"].T
+    scale = max(1.0, np.abs(want).max())
+    assert np.abs(got - want).max() <= 1e-5 * scale
+    assert np.abs(geglu_interleaved(y) - gm.geglu_tanh_interleaved(y)).max() > 1e-3           # (the two GELUs differ by up to 5e-4 |gate|)
+
+
+def _ulp_diff(a, b):
+    ai, bi = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
+    ai = np.where(ai < 0, -(ai & 0x7fffffff), ai)
+    bi = np.where(bi < 0, -(bi & 0x7fffffff), bi)
+    return np.abs(ai - bi)
+
+
+@pytest.mark.parametrize("kind,theta", [("full_attention", 1e6), ("sliding_attention", 1e4)])
+def test_rope_tables_at_head_size_256_match_hf(kind, theta):
+    """The tables the handle uploads (HipGemma: gemma.rope_inv_freq -> ak_gemma_set_rope_inv_freq -> the decoder's host routine on
+    given frequencies, ak_decoder_rope_table_inv: two [n_pos][128] tables) against HF's Gemma3RotaryEmbedding, positions 0 .. 2047: the
+    same 128 float32 inverse frequencies bit for bit, cos / sin within 1 ulp in every column.
+
+    Why the frequencies come from torch: the host routine on a THETA (ak_decoder_rope_table, what ak_gemma_create builds before the
+    handle replaces it, and what a caller without torch keeps) rounds theta^(2 i / 256) once from double; HF's buffer comes from
+    torch's vectorised float32 pow, which is 1 ulp off that correctly rounded value at one frequency in 128 (i = 74 at theta 1e6,
+    i = 111 at 1e4; glibc's powf and torch's pow on one scalar agree with the routine). Measured for that table: 127 of 128 frequencies
+    equal, cos / sin 1 ulp where they agree, 2 ulp and 6.0e-8 over all columns -- asserted below as what it is, beside the check proper."""
+    import torch
+    from archi_amd.decoder import rope_table, rope_table_inv
+    from transformers.models.gemma3.modeling_gemma3 import Gemma3RotaryEmbedding
+    n = 2048
+    rot = Gemma3RotaryEmbedding(config=gm.shape_hf_config(TINY))
+    hc, hs = rot(torch.zeros(1, dtype=torch.float32), torch.arange(n)[None], layer_type=kind)
+    hc, hs = hc[0].numpy(), hs[0].numpy()
+    inv = getattr(rot, f"{kind}_inv_freq").numpy()
+    assert hc.shape == (n, 256) and np.array_equal(hc[:, :128], hc[:, 128:])
+    mine = gm.rope_inv_freq(theta)
+    assert mine.dtype == np.float32 and mine.shape == (128,)
+    c, s = rope_table_inv(mine, n)
+    assert c.shape == (n, 128)
+    same = mine.view(np.int32) == inv.view(np.int32)
+    ulp_all = max(_ulp_diff(c, hc[:, :128]).max(), _ulp_diff(s, hs[:, :128]).max())
+    worst_abs = max(np.abs(c - hc[:, :128]).max(), np.abs(s - hs[:, :128]).max())
+    print(f"{kind} theta {theta:g}: {same.sum()} of 128 frequencies equal HF's bits; cos / sin worst ulp distance {ulp_all}, worst |d| {worst_abs:.3g}")
+    assert same.all(), f"{same.sum()} of 128 inverse frequencies equal HF's bit for bit"
+    assert ulp_all <= 1
+    # the table from the theta alone (no torch): one frequency 1 ulp apart, the rest as above
+    c0, s0 = rope_table(theta, n, head_dim=256)
+    e = np.arange(0, 256, 2, dtype=np.float32) / np.float32(256)
+    host = (np.float32(1) / np.power(np.float64(theta), e.astype(np.float64)).astype(np.float32)).astype(np.float32)
+    agree = host == inv
+    assert agree.sum() >= 127 and _ulp_diff(host, inv).max() <= 1
+    assert np.array_equal(c0[:, agree], c[:, agree]) and np.array_equal(s0[:, agree], s[:, agree])
+    assert max(np.abs(c0 - hc[:, :128]).max(), np.abs(s0 - hs[:, :128]).max()) <= 2.0 ** -23
+
+
+def test_provider_routes_gemma_checkpoints(tmp_path):
+    """A model_type gemma3_text directory reaches the GPU initialisation (HipBackendError on a machine without a GPU) instead of "no
+    local checkpoint directory / unknown model"; without tokenizer.json: FileNotFoundError; the parity precisions: ValueError, before
+    any GPU work."""
+    from archi_amd._lib import HipBackendError
+    from archi_amd.embeddings import ArchiHipEmbeddings, _is_gemma
+    d = str(tmp_path / "ckpt")
+    write_checkpoint(d, TINY, seed=1, max_seq_length=96)
+    assert _is_gemma(d) and _is_gemma(BASE) and not _is_gemma("BAAI/bge-base-en-v1.5") and not _is_gemma("nomic-ai/modernbert-embed-base")
+    try:
+        emb = ArchiHipEmbeddings(d)
+    except HipBackendError:
+        pass
+    else:       # a GPU is present: the checkpoint's sentence-transformers files were read
+        assert (emb.pooling, emb.max_seq_length, emb.normalize, emb.dimensions) == ("mean", 96, True, 384)
+        emb.encoder.close()
+    for p in ("f32", "bf16x3"):
+        with pytest.raises(ValueError, match="bf16 only"):
+            ArchiHipEmbeddings(d, model_kwargs={"precision": p})
+        with pytest.raises(ValueError, match="bf16 only"):
+            ArchiHipEmbeddings(BASE, model_kwargs={"precision": p, "synthetic_seed": 0})
+    os.remove(os.path.join(d, "tokenizer.json"))
+    with pytest.raises(FileNotFoundError, match="tokenizer.json"):
+        ArchiHipEmbeddings(d)
+    with pytest.raises(FileNotFoundError, match="synthetic_seed"):
+        ArchiHipEmbeddings(BASE)
+    cfg = json.load(open(os.path.join(d, "config.json")))
+    json.dump(dict(cfg, attn_logit_softcapping=50.0), open(os.path.join(d, "config.json"), "w"))
+    open(os.path.join(d, "tokenizer.json"), "w").write("{}")
+    with pytest.raises(ValueError, match="attn_logit_softcapping"):
+        ArchiHipEmbeddings(d)
+
+
+def test_tokenizer_adds_bos_and_eos_like_transformers_fast(tmp_path):
+    from archi_amd.decoder import BpeTokenizer
+    from tests.gemma_ref import TEXTS, hf_tokenizer, make_tokenizer_json
+    tf = make_tokenizer_json(str(tmp_path / "tokenizer.json"))
+    ours, theirs = BpeTokenizer(tf), hf_tokenizer(tf)
+    for max_len in (16, 128):
+        want = theirs(list(TEXTS), truncation=True, max_length=max_len)["input_ids"]
+        assert ours.encode_batch(list(TEXTS), max_len) == want
+    assert all(r[0] == 2 and r[-1] == 1 for r in want)                                        # <bos> ... <eos>
+
+
+def test_symbols_in_header_binding_and_library():
+    from archi_amd import _lib
+    src = open(os.path.join(ROOT, "include", "archi_knn.h")).read()
+    assert int(re.search(r"#define AK_ABI_VERSION (\d+)", src).group(1)) == _lib.ABI_VERSION == 5
+    lib = _lib.load()
+    assert lib.ak_abi_version() == 5
+    bound = {n for n, _, _ in _lib.SYMBOLS}
+    for name in ("ak_gemma_create", "ak_gemma_forward_lens", "ak_gemma_destroy", "ak_gemma_set_rope_inv_freq", "ak_decoder_rope_table_inv"):
+        assert re.search(rf"\bint {name}\(", src) and name in bound and hasattr(lib, name)
+    assert int(re.search(r"#define AK_GEMMA_MAX_LAYERS (\d+)", src).group(1)) == _lib.GEMMA_MAX_LAYERS
+    args = {n: a for n, _, a in _lib.SYMBOLS}
+    assert args["ak_gemma_forward_lens"] == args["ak_mbert_forward_lens"]                     # the argument list of ak_mbert_forward_lens
+
+
+def test_config_struct_matches_header():
+    from archi_amd._lib import GEMMA_MAX_LAYERS, AkGemmaConfig
+    src = open(os.path.join(ROOT, "include", "archi_knn.h")).read()
+    body = re.search(r"typedef struct AkGemmaConfig \{(.*?)\} AkGemmaConfig;", src, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"\b(int|float)\s+(\w+)\s*(\[\w+\])?;", body)
+    assert [n for _, n, _ in fields] == [n for n, _ in AkGemmaConfig._fields_]
+    assert fields[-1][2] == "[AK_GEMMA_MAX_LAYERS]" and fields[-2][1:] == ("dense_out", "[2]") and all(not a for _, _, a in fields[:-2])
+    assert ctypes.sizeof(AkGemmaConfig) == 4 * (len(fields) - 2) + 4 * 2 + 4 * GEMMA_MAX_LAYERS
+    kinds = {"int": ctypes.c_int, "float": ctypes.c_float}
+    assert all(kinds[k] is t for (k, _, _), (_, t) in zip(fields[:-2], AkGemmaConfig._fields_))
+
+
+def test_single_launch_wrappers_stay_out_of_the_product_library():
+    """ak_ktg_* (csrc/kernel_test.hip) exist in libarchi_hip_dbg.so only, are exactly _lib.KTG_SYMBOLS, and none of them is an ak_kt_*."""
+    from archi_amd import _lib
+
+    def exported(name):
+        out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "archi_amd", "lib", name)], stdout=subprocess.PIPE,
+                             check=True).stdout.decode()
+        return set(re.findall(r"\b(ak_ktg_[a-z0-9_]+)\b", out))
+
+    _lib.load()                                                                               # (the libraries are built)
+    assert exported("libarchi_hip.so") == set()
+    names = {n for n, _, _ in _lib.KTG_SYMBOLS}
+    assert exported("libarchi_hip_dbg.so") == names and "ak_ktg_attn_gqa" in names
+    assert not names & {n for n, _, _ in _lib.KT_SYMBOLS} and not any(n.startswith("ak_kt_") for n in names)
+
+
+def test_handle_refuses_without_touching_the_gpu_what_python_can_see():
+    base = GEMMA_SHAPES["gm-global"]
+    with pytest.raises(ValueError, match="layer types"):
+        gm.HipGemma(base[:13] + ((1,),) + base[14:], {})
+    with pytest.raises(ValueError, match="Dense"):
+        gm.HipGemma(base[:14] + ((384, 384, 384),), {})
+
+
+def test_embedding_dimension_for_embeddinggemma():
+    from archi_amd.config_plugin import EMBEDDING_DIMENSIONS
+    assert EMBEDDING_DIMENSIONS[BASE] == 768 == GEMMA_SHAPES[BASE][14][-1]
+
+
+def test_fixture_set_covers_what_the_gpu_test_needs():
+    names = sorted(fx.CASES)
+    assert names == ["g2", "global", "local", "tiny"] and all(os.path.exists(fx.path(n)) for n in names)
+    assert sorted(fx.load("tiny")["lens"].tolist()) == [1, 32, 33, 34, 65, 66, 97, 130, 300, 513, 1024, 2048]
+    assert all(os.path.getsize(fx.path(n)) < 128 * 1024 for n in names)
+    assert all(GEMMA_SHAPES[fx.CASES[n][0]][5] == 256 for n in names)                          # the kernel takes no other head size
+    assert GEMMA_SHAPES["gm-tiny"][11] // 2 == 32 and GEMMA_SHAPES["gm-tiny"][12] == 128
+
+
+@pytest.mark.parametrize("name", sorted(fx.CASES))
+def test_fixture_is_reproduced_and_can_see_the_features(name):
+    """The committed fixture against the generating script run now: expected to 1e-6; and, from Gemma3TextModel alone, the float32
+    reference run causally, without the window, with both thetas equal and with head_dim ** -0.5 as the scale each differs from the
+    true reference by at least 10x the fixture's 1 - cos bar on every row of 66 to 1024 tokens (whichever the shape's layer types can
+    show). The bar is per figure the larger of the project's bf16 bar and the all-bf16 Gemma3TextModel's own error stored in the
+    fixture. The 2048-token row's values are stored too (gm-tiny: all four above 10x as well) but not asserted: they were not part
+    of what was measured when the check was set. The ablations are re-run here on the rows up to 300 tokens and must agree with the
+    stored values; the longer rows' stored values are asserted as stored."""
+    stored = fx.load(name)
+    shape, seed, std, lens = fx.CASES[name]
+    assert (stored["shape_name"], stored["seed"], stored["std"]) == (shape, seed, std) and list(stored["lens"]) == list(lens)
+    assert stored["bar_cos"] == max(PROJECT_BAR_COS, stored["bf16_cos"]) and stored["bar_abs"] == max(PROJECT_BAR_ABS, stored["bf16_abs"])
+    from tests.gemma_ref import ABLATIONS, cos_gap, dense_matrices, make_ids, reference_embed
+    sh = GEMMA_SHAPES[shape]
+    w = gm.random_gemma_weights(sh, seed=seed, std=std)
+    assert np.array_equal(make_ids(sh, seed, lens), stored["ids"])
+    dense = dense_matrices(sh, w)
+    now = reference_embed(hf_model(sh, w), stored["ids"], stored["lens"], dense)
+    assert np.abs(now - stored["expected"]).max() <= 1e-6
+    types = sh[13]
+    shows = {"causal": True, "no_window": 0 in types, "same_theta": 0 in types and 1 in types, "wrong_scale": sh[12] != sh[5]}
+    need = 10.0 * stored["bar_cos"]
+    rows = (stored["lens"] >= fx.SENS_MIN_ROW) & (stored["lens"] <= fx.SENS_MAX_ROW)
+    short = np.flatnonzero(stored["lens"] <= 300)
+    text = []
+    for ab in ABLATIONS:
+        s = stored["sens_" + ab]
+        assert (s.size > 0) == shows[ab], ab
+        if not s.size:
+            continue
+        again = cos_gap(reference_embed(hf_model(sh, w, ablate=ab), stored["ids"][short], stored["lens"][short], dense), now[short])
+        assert np.allclose(again, s[short], rtol=1e-2, atol=1e-6), ab
+        text.append(f"{ab} min {s[rows].min():.3g}")
+        assert s[rows].min() >= need, (ab, s[rows].min(), need)
+    print(f"{name}: bar {stored['bar_cos']:.3g} / {stored['bar_abs']:.3g}; need {need:.3g}: " + ", ".join(text))
+
+
+# VGPRs of the instantiations this family must not have moved, from the parent commit's files compiled with the Makefile's flags
+PARENT_VGPRS = {"k_gemmILi8ELi256ELb1ELb0E": 244, "k_gemmILi8ELi128ELb0ELb0E": 194, "k_attn_longILb1E": 124, "k_attn_longILb0E": 117,
+                "k_attn_causalE": 154}
+
+
+def _resource_usage(src):
+    csrc = os.path.join(ROOT, "archi_amd", "csrc")
+    flags = re.search(r"^FLAGS\s*:=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
+                                          os.path.join(csrc, src)], capture_output=True, text=True, cwd=csrc)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+        m = re.search(r"(VGPRs|AGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
+        if m and name:
+            out.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    return out
+
+
+def test_new_kernels_do_not_spill_and_the_old_ones_did_not_move():
+    """-Rpass-analysis=kernel-resource-usage with the Makefile's flags: every kernel of gemma.hip, every instantiation of k_attn_gqa and
+    both k_gemm MODE 9 instantiations report no spilled register and no scratch; k_attn_gqa holds 65 536 bytes of LDS; the k_gemm MODE 8,
+    k_attn_long and k_attn_causal instantiations report the VGPR counts of the parent commit."""
+    srcs = ("gemma.hip", "attn_gqa.hip", "gemm.hip", "attn_long.hip", "attn_causal.hip")
+    with concurrent.futures.ThreadPoolExecutor(max_workers=len(srcs)) as pool:
+        use = dict(zip(srcs, pool.map(_resource_usage, srcs)))
+    new = {n: u for n, u in use["gemma.hip"].items() if "k_gm_" in n}
+    new.update({n: u for n, u in use["attn_gqa.hip"].items() if "k_attn_gqa" in n})
+    new.update({n: u for n, u in use["gemm.hip"].items() if "k_gemmILi9E" in n})
+    for k in ("k_gm_embed", "k_gm_norm_add_norm", "k_gm_qk_norm_rope", "k_gm_pool_part", "k_gm_pool_fin", "k_gm_dense", "k_gm_l2", "k_gm_fold1p",
+              "k_gemmILi9ELi256ELb1E", "k_gemmILi9ELi128ELb0E") + tuple(f"k_attn_gqaILi{G}ELb{b}E" for G in (1, 2, 3, 4) for b in (0, 1)):
+        assert any(k in n for n in new), (k, sorted(new))
+    assert not any("k_gemmILi9ELi256ELb0E" in n for n in new)      # no wide in-step MODE 9 (MODE 8's would spill)
+    for n, u in new.items():
+        assert u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0 and u["ScratchSize [bytes/lane]"] == 0, (n, u)
+    gqa = {n: u for n, u in new.items() if "k_attn_gqa" in n}
+    assert all(u["LDS Size [bytes/block]"] == 65536 and u["VGPRs"] + u["AGPRs"] <= 512 for u in gqa.values())
+    for n, u in sorted(gqa.items()):
+        print(f"{n}: {u['VGPRs']} VGPRs + {u['AGPRs']} AGPRs, {u['LDS Size [bytes/block]']} bytes of LDS")
+    old = {}
+    for src in ("gemm.hip", "attn_long.hip", "attn_causal.hip"):
+        old.update(use[src])
+    for key, want in PARENT_VGPRS.items():
+        hit = [u for n, u in old.items() if key in n]
+        assert len(hit) == 1 and hit[0]["VGPRs"] == want and hit[0]["ScratchSize [bytes/lane]"] == 0, (key, hit, want)
