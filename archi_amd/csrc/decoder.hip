@@ -8,48 +8,20 @@
 //   x = x + (silu(h Wg^T) (h Wu^T)) Wd^T          k_gemm MODE 7 (SwiGLU epilogue, gate / up rows interleaved at create), MODE 2, add
 // then the final norm on each row's last valid token and L2 normalisation (k_dec_pool): sentence-transformers' lasttoken Pooling
 // + Normalize. The residual stream x is float32 throughout, like the reference's CPU path; GEMM operands are bf16.
+// Here: the config checks, the layer struct, the layer loop and the family's own kernels. The plumbing shared with mbert.hip and gemma.hip
+// is stack.h / stack.hip: the token-slot prologue and the row helpers of k_dec_embed / k_dec_add_rmsnorm, the L2 tail of k_dec_pool, the
+// workspace, the weight preparation at create, the rotary tables (ak_decoder_rope_table* are thin wrappers), the GemmArgs of the launches.
 #include <cmath>
-#include <mutex>
-#include <vector>
+#include <string>
 
-#include "encoder_kernels.h"
-#include "mfma_tile.h"
+#include "stack.h"
 #include "switches.h"
 
 namespace ak {
 
 constexpr int DEC_HD = 128, DEC_MAX_S = 8192;
 
-// ---- RoPE table (host): HF's default rotary embedding in float32 --------------------------------------------------------
-// inv_freq[i] = 1 / theta^(2 i / hd) (the exponent 2 i / hd is exact in float32; the power is rounded once from double),
-// angle = float(pos) * inv_freq[i] (one float32 product, as HF's float32 matmul of a 1-deep product), cos / sin rounded once from
-// double. Table rows [n_pos][hd / 2]: HF's cos / sin are these rows twice (cat(freqs, freqs)).
-// the second half of the routine on given inverse frequencies (ak_decoder_rope_table_inv: a caller that holds HF's own buffer)
-static void rope_table_from_inv(const float *inv, int half, int n_pos, float *c, float *s) {
-    for (int p = 0; p < n_pos; p++)
-        for (int i = 0; i < half; i++) {
-            const float ang = (float)p * inv[i];
-            c[(size_t)p * half + i] = (float)std::cos((double)ang);
-            s[(size_t)p * half + i] = (float)std::sin((double)ang);
-        }
-}
-static void rope_table_host(float theta, int hd, int n_pos, float *c, float *s) {
-    const int half = hd / 2;
-    std::vector<float> inv(half);
-    for (int i = 0; i < half; i++) {
-        const float e = (float)(2 * i) / (float)hd;
-        inv[i] = 1.0f / (float)std::pow((double)theta, (double)e);
-    }
-    rope_table_from_inv(inv.data(), half, n_pos, c, s);
-}
-
 // ---- kernels ------------------------------------------------------------------------------------------------------------
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // one wave per token slot t < B * S: ids past the row's length read as 0; x32 = embed_tokens[id] (float32 of the bf16 row),
 // h16 = RMSNorm(x) * ln_in of layer 0. The wave of a row's slot 0 stores the clamped length (attention and pooling read it).
 __global__ __launch_bounds__(256) void k_dec_embed(const int *__restrict__ ids, int ld_ids, const int *__restrict__ lens, int lens_stride, int B, int S,
@@ -58,25 +30,19 @@ __global__ __launch_bounds__(256) void k_dec_embed(const int *__restrict__ ids, 
     const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (t >= (int64_t)B * S) return;
-    const int b = (int)(t / S), sq = (int)(t - (int64_t)b * S);
-    int len = lens[(int64_t)b * lens_stride];
-    len = len < 0 ? 0 : (len > S ? S : len);
-    if (sq == 0 && lane == 0) lens_out[b] = len;
-    int id = sq < len ? ids[(int64_t)b * ld_ids + sq] : 0;
-    if (id < 0 || id >= vocab) id = 0;                         // (the tokenizer's ids are in range; a stray id must not read out of bounds)
+    const int id = token_slot<false>(ids, ld_ids, lens, lens_stride, S, vocab, t, lane, nullptr, lens_out);
     const uint16_t *e = emb + (int64_t)id * H;
     float *xr = x32 + t * H;
     float ss = 0.f;
     for (int c = lane * 4; c < H; c += 256) {
-        const uint2 v = *(const uint2 *)(e + c);
-        const float4 f = {bf16_to_f32((uint16_t)v.x), bf16_to_f32((uint16_t)(v.x >> 16)), bf16_to_f32((uint16_t)v.y), bf16_to_f32((uint16_t)(v.y >> 16))};
+        const float4 f = load_bf16x4(e + c);
         *(float4 *)(xr + c) = f;
         ss += f.x * f.x + f.y * f.y + f.z * f.z + f.w * f.w;
     }
     const float rs = rsqrtf(wave_sum(ss) / (float)H + eps);
     for (int c = lane * 4; c < H; c += 256) {
         const float4 f = *(const float4 *)(xr + c), g = *(const float4 *)(w + c);
-        *(uint2 *)(h16 + t * H + c) = uint2{mt::pack_bf16x2(f.x * rs * g.x, f.y * rs * g.y), mt::pack_bf16x2(f.z * rs * g.z, f.w * rs * g.w)};
+        store_bf16x4(h16 + t * H + c, f.x * rs * g.x, f.y * rs * g.y, f.z * rs * g.z, f.w * rs * g.w);
     }
 }
 
@@ -100,7 +66,7 @@ __global__ __launch_bounds__(256) void k_dec_add_rmsnorm(float *__restrict__ x32
     const float rs = rsqrtf(wave_sum(ss) / (float)H + eps);
     for (int c = lane * 4; c < H; c += 256) {
         const float4 f = *(const float4 *)(xr + c), g = *(const float4 *)(w + c);
-        *(uint2 *)(h16 + t * H + c) = uint2{mt::pack_bf16x2(f.x * rs * g.x, f.y * rs * g.y), mt::pack_bf16x2(f.z * rs * g.z, f.w * rs * g.w)};
+        store_bf16x4(h16 + t * H + c, f.x * rs * g.x, f.y * rs * g.y, f.z * rs * g.z, f.w * rs * g.w);
     }
 }
 
@@ -141,7 +107,7 @@ __global__ __launch_bounds__(256) void k_dec_qk_rope(const uint16_t *__restrict_
 // a row of length 0 embeds to zeros
 __global__ __launch_bounds__(256) void k_dec_pool(const float *__restrict__ x32, const int *__restrict__ lens, int S, int H, const float *__restrict__ w,
                                                   float eps, int normalise, float *__restrict__ out) {
-    __shared__ float red[2][4];
+    __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int len = lens[b];
     float *o = out + (int64_t)b * H;
@@ -153,16 +119,12 @@ __global__ __launch_bounds__(256) void k_dec_pool(const float *__restrict__ x32,
     float ss = 0.f;
     for (int c = tid; c < H; c += 256) ss += xr[c] * xr[c];
     ss = wave_sum(ss);
-    if (lane == 0) red[0][wave] = ss;
+    if (lane == 0) red[wave] = ss;
     __syncthreads();
-    const float rs = rsqrtf((red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (float)H + eps);
+    const float rs = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)H + eps);
     float s2 = 0.f;
     for (int c = tid; c < H; c += 256) { const float y = xr[c] * rs * w[c]; s2 += y * y; }
-    s2 = wave_sum(s2);
-    if (lane == 0) red[1][wave] = s2;
-    __syncthreads();
-    const float nrm = sqrtf(red[1][0] + red[1][1] + red[1][2] + red[1][3]);
-    const float sc = normalise ? 1.0f / fmaxf(nrm, 1e-12f) : 1.0f;      // torch.nn.functional.normalize's eps
+    const float sc = block_l2_scale(s2, lane, wave, normalise);
     for (int c = tid; c < H; c += 256) o[c] = xr[c] * rs * w[c] * sc;
 }
 
@@ -181,54 +143,19 @@ struct DecLayer {
     const uint16_t *wqkv, *wo, *wgu, *wd;      // wqkv [(nq + 2 nkv) 128][H] and wgu [2 I][H] (interleaved) are owned
     const float *qn, *kn, *ln_in, *ln_post;
 };
-struct Decoder {
+struct Decoder : Stack {
     AkDecoderConfig cfg;
     const uint16_t *emb = nullptr; const float *norm = nullptr;
     std::vector<DecLayer> layers;
-    std::vector<void *> owned;
-    float *zero_bias = nullptr, *rope_c = nullptr, *rope_s = nullptr;
-    int n_pos = 0;
-    int64_t cap = 0; int cap_B = 0;
+    float *rope_c = nullptr, *rope_s = nullptr;
     float *x32 = nullptr, *y32 = nullptr;
     uint16_t *h16 = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *ctx = nullptr, *f = nullptr;
     int *lens = nullptr;
-    std::mutex mu;
 };
-
-static void dec_free_ws(Decoder &d) {
-    void *p[] = {d.x32, d.y32, d.h16, d.qkv, d.q, d.k, d.v, d.ctx, d.f, d.lens};
-    for (void *x : p) if (x) hipFree(x);
-    d.x32 = d.y32 = nullptr; d.h16 = d.qkv = d.q = d.k = d.v = d.ctx = d.f = nullptr; d.lens = nullptr;
-    d.cap = 0; d.cap_B = 0;
-}
 
 static bool swiglu_unfused() {
     static const bool u = env_get("AK_DEC_SWIGLU") && std::string(env_get("AK_DEC_SWIGLU")) == "unfused";
     return u;
-}
-
-// workspace for tpad token rows (a multiple of 256) and B rows; zeroed when (re)allocated, so rows that no kernel writes (GEMM
-// padding rows past B * S) stay finite
-static int dec_reserve(Decoder &d, int64_t tpad, int B) {
-    if (tpad <= d.cap && B <= d.cap_B) return 0;
-    if (tpad < d.cap) tpad = d.cap;
-    if (B < d.cap_B) B = d.cap_B;
-    dec_free_ws(d);
-    const int64_t H = d.cfg.hidden, I = d.cfg.intermediate, nq = d.cfg.q_heads, nkv = d.cfg.kv_heads;
-    const int64_t nqkv = (nq + 2 * nkv) * DEC_HD;
-    const int64_t fcols = swiglu_unfused() ? 3 * I : I;          // un-fused A/B: the 2I-wide product behind f
-    struct { void **p; size_t bytes; } bufs[] = {
-        {(void **)&d.x32, (size_t)(tpad * H * 4)}, {(void **)&d.y32, (size_t)(tpad * H * 4)}, {(void **)&d.h16, (size_t)(tpad * H * 2)},
-        {(void **)&d.qkv, (size_t)(tpad * nqkv * 2)}, {(void **)&d.q, (size_t)(tpad * nq * DEC_HD * 2)},
-        {(void **)&d.k, (size_t)(tpad * nkv * DEC_HD * 2)}, {(void **)&d.v, (size_t)(tpad * nkv * DEC_HD * 2)},
-        {(void **)&d.ctx, (size_t)(tpad * nq * DEC_HD * 2)}, {(void **)&d.f, (size_t)(tpad * fcols * 2)}, {(void **)&d.lens, (size_t)B * 4},
-    };
-    for (auto &bf : bufs) {
-        AK_HIP(hipMalloc(bf.p, bf.bytes));
-        AK_HIP(hipMemset(*bf.p, 0, bf.bytes));
-    }
-    d.cap = tpad; d.cap_B = B;
-    return 0;
 }
 
 static int dec_forward_locked(Decoder &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int normalise,
@@ -236,47 +163,35 @@ static int dec_forward_locked(Decoder &d, const int32_t *ids, int ld_ids, const 
     const AkDecoderConfig &c = d.cfg;
     const int H = c.hidden, I = c.intermediate, nq = c.q_heads, nkv = c.kv_heads, nqkv = (nq + 2 * nkv) * DEC_HD;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
-    if (dec_reserve(d, tpad, B)) return -10;
+    if (d.reserve(tpad, B)) return -10;
     const unsigned rows4 = (unsigned)((T + 3) / 4);
     const float qscale = 1.4426950408889634f / sqrtf((float)DEC_HD);
-    const bool unfused = swiglu_unfused();
     k_dec_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.layers[0].ln_in, c.rms_eps, d.x32, d.h16, d.lens);
     AK_HIP(hipGetLastError());
     for (size_t l = 0; l < d.layers.size(); l++) {
         const DecLayer &ly = d.layers[l];
-        GemmArgs g{};
-        g.bias = d.zero_bias; g.T = (int)tpad;
         // q | k | v
-        g.X = d.h16; g.W = ly.wqkv; g.N = nqkv; g.K = H; g.out_bf16 = d.qkv; g.ldo = nqkv;
-        if (launch_gemm(3, g, st)) return -10;
+        if (launch_gemm(3, d.gemm_bf16(tpad, d.h16, ly.wqkv, nqkv, H, d.qkv), st)) return -10;
         k_dec_qk_rope<<<(unsigned)T, 256, 0, st>>>(d.qkv, S, nq, nkv, ly.qn, ly.kn, c.rms_eps, d.rope_c, d.rope_s, qscale, d.q, d.k, d.v);
         AK_HIP(hipGetLastError());
         CausalAttnArgs aa{d.q, d.k, d.v, d.lens, d.ctx, B, S, nq, nkv};
         if (launch_attn_causal(aa, st)) return -10;
         // x += ctx Wo^T; h = RMSNorm(x; ln_post)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.ctx; g.W = ly.wo; g.N = H; g.K = nq * DEC_HD; g.out_f32 = d.y32;
-        if (launch_gemm(2, g, st)) return -10;
+        if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, nq * DEC_HD, d.y32), st)) return -10;
         k_dec_add_rmsnorm<<<rows4, 256, 0, st>>>(d.x32, d.y32, T, H, ly.ln_post, c.rms_eps, d.h16);
         AK_HIP(hipGetLastError());
         // f = silu(h Wg^T) (h Wu^T)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.h16; g.W = ly.wgu; g.N = 2 * I; g.K = H;
-        if (unfused) {
+        if (swiglu_unfused()) {
             uint16_t *gu = d.f + tpad * I;
-            g.out_bf16 = gu; g.ldo = 2 * I;
-            if (launch_gemm(3, g, st)) return -10;
+            if (launch_gemm(3, d.gemm_bf16(tpad, d.h16, ly.wgu, 2 * I, H, gu), st)) return -10;
             const int64_t n = tpad * I;
             k_dec_swiglu<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(gu, n, d.f);
             AK_HIP(hipGetLastError());
-        } else {
-            g.out_bf16 = d.f; g.ldo = I;
-            if (launch_gemm(7, g, st)) return -10;
+        } else if (launch_gemm(7, d.gemm_gated(tpad, d.h16, ly.wgu, I, H, d.f), st)) {
+            return -10;
         }
         // x += f Wd^T; h = RMSNorm(x; next layer's ln_in) (after the last layer: the add only, the pool applies the final norm)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.f; g.W = ly.wd; g.N = H; g.K = I; g.out_f32 = d.y32;
-        if (launch_gemm(2, g, st)) return -10;
+        if (launch_gemm(2, d.gemm_f32(tpad, d.f, ly.wd, H, I, d.y32), st)) return -10;
         const float *wn = l + 1 < d.layers.size() ? d.layers[l + 1].ln_in : nullptr;
         k_dec_add_rmsnorm<<<rows4, 256, 0, st>>>(d.x32, d.y32, T, H, wn, c.rms_eps, d.h16);
         AK_HIP(hipGetLastError());
@@ -290,6 +205,7 @@ static int dec_forward_locked(Decoder &d, const int32_t *ids, int ld_ids, const 
 
 using namespace ak;
 
+// the rotary table routines of stack.hip, for callers that hold HF's own buffers (host only)
 extern "C" int ak_decoder_rope_table(float theta, int head_dim, int n_pos, float *cos_out, float *sin_out) {
     if (!cos_out || !sin_out || head_dim <= 0 || head_dim % 2 || n_pos < 0 || !(theta > 0.f))
         AK_FAIL(-1, "ak_decoder_rope_table: bad arguments");
@@ -303,16 +219,7 @@ extern "C" int ak_decoder_rope_table_inv(const float *inv_freq, int half, int n_
     return 0;
 }
 
-extern "C" int ak_decoder_destroy(ak_decoder_t h) {
-    AK_BIND();
-    if (!h) return 0;
-    Decoder *d = (Decoder *)h;
-    hipDeviceSynchronize();
-    dec_free_ws(*d);
-    for (void *p : d->owned) hipFree(p);
-    delete d;
-    return 0;
-}
+extern "C" int ak_decoder_destroy(ak_decoder_t h) { return stack_destroy<Decoder>(h); }
 
 extern "C" int ak_decoder_create(const AkDecoderConfig *cfg, const void *const *w, int n_weights, ak_decoder_t *out) {
     AK_BIND();
@@ -334,41 +241,19 @@ extern "C" int ak_decoder_create(const AkDecoderConfig *cfg, const void *const *
     d->emb = (const uint16_t *)w[0];
     d->norm = (const float *)w[1];
     auto fail = [&](const char *what) { set_error(what); ak_decoder_destroy(d); return -10; };
-    auto dev = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        d->owned.push_back(p);
-        return p;
-    };
-    const size_t qrows = (size_t)nq * DEC_HD, kvrows = (size_t)nkv * DEC_HD;
-    const size_t zb = std::max<size_t>({qrows + 2 * kvrows, (size_t)2 * I, (size_t)H});
-    d->zero_bias = (float *)dev(zb * 4);
-    if (!d->zero_bias || hipMemset(d->zero_bias, 0, zb * 4) != hipSuccess) return fail("ak_decoder_create: hipMalloc failed");
+    const size_t qrows = (size_t)nq * DEC_HD, kvrows = (size_t)nkv * DEC_HD, nqkv = qrows + 2 * kvrows;
+    d->zero_bias = d->dev_as<float>(std::max<size_t>({nqkv, (size_t)2 * I, (size_t)H}), true);
+    if (!d->zero_bias) return fail("ak_decoder_create: hipMalloc failed");
     // RoPE table, positions 0 .. min(max_position, 8192) - 1
     d->n_pos = c.max_position < DEC_MAX_S ? c.max_position : DEC_MAX_S;
-    {
-        std::vector<float> hc((size_t)d->n_pos * 64), hs((size_t)d->n_pos * 64);
-        rope_table_host(c.rope_theta, DEC_HD, d->n_pos, hc.data(), hs.data());
-        d->rope_c = (float *)dev(hc.size() * 4);
-        d->rope_s = (float *)dev(hs.size() * 4);
-        if (!d->rope_c || !d->rope_s || hipMemcpy(d->rope_c, hc.data(), hc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d->rope_s, hs.data(), hs.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return fail("ak_decoder_create: RoPE table upload failed");
-    }
+    if (!d->rope_tables(c.rope_theta, DEC_HD, &d->rope_c, &d->rope_s)) return fail("ak_decoder_create: RoPE table upload failed");
     for (int l = 0; l < L; l++) {
         const void *const *p = w + 2 + 11 * l;      // wq wk wv q_norm k_norm wo ln_in ln_post w_gate w_up w_down
         DecLayer ly{};
-        uint16_t *wqkv = (uint16_t *)dev((qrows + 2 * kvrows) * H * 2);
-        uint16_t *wgu = (uint16_t *)dev((size_t)2 * I * H * 2);
+        uint16_t *wqkv = d->dev_as<uint16_t>(nqkv * H), *wgu = d->dev_as<uint16_t>((size_t)2 * I * H);
         if (!wqkv || !wgu) return fail("ak_decoder_create: hipMalloc failed");
-        if (hipMemcpy(wqkv, p[0], qrows * H * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy(wqkv + qrows * H, p[1], kvrows * H * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy(wqkv + (qrows + kvrows) * H, p[2], kvrows * H * 2, hipMemcpyDeviceToDevice) != hipSuccess)
-            return fail("ak_decoder_create: QKV concatenation failed");
-        // gate / up rows interleaved: row 2 j = gate j, row 2 j + 1 = up j (gemm.hip MODE 7)
-        if (hipMemcpy2D(wgu, (size_t)4 * H, p[8], (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy2D(wgu + H, (size_t)4 * H, p[9], (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess)
-            return fail("ak_decoder_create: gate / up interleave failed");
+        if (!d->concat_rows(wqkv, H, {{p[0], qrows}, {p[1], kvrows}, {p[2], kvrows}})) return fail("ak_decoder_create: QKV concatenation failed");
+        if (!d->interleave_rows(wgu, p[8], p[9], I, H)) return fail("ak_decoder_create: gate / up interleave failed");      // gemm.hip MODE 7
         ly.wqkv = wqkv; ly.wgu = wgu;
         ly.qn = (const float *)p[3]; ly.kn = (const float *)p[4];
         ly.wo = (const uint16_t *)p[5];
@@ -376,6 +261,10 @@ extern "C" int ak_decoder_create(const AkDecoderConfig *cfg, const void *const *
         ly.wd = (const uint16_t *)p[10];
         d->layers.push_back(ly);
     }
+    const size_t fcols = swiglu_unfused() ? 3 * I : I;          // un-fused A/B: the 2I-wide product behind f
+    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, (size_t)H * 2);
+    d->buffer(&d->qkv, nqkv * 2); d->buffer(&d->q, qrows * 2); d->buffer(&d->k, kvrows * 2); d->buffer(&d->v, kvrows * 2);
+    d->buffer(&d->ctx, qrows * 2); d->buffer(&d->f, fcols * 2); d->buffer(&d->lens, 0, 4);
     if (hipDeviceSynchronize() != hipSuccess) return fail("ak_decoder_create: weight preparation failed");
     *out = d;
     return 0;
@@ -388,9 +277,8 @@ extern "C" int ak_decoder_forward_lens(ak_decoder_t h, const int32_t *ids, int l
     RoctxRange range("ak_decoder_forward_lens");
     Decoder &d = *(Decoder *)h;
     if (B <= 0) return 0;
-    if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, "ak_decoder_forward_lens: bad arguments");
-    if (S <= 0 || S % 32 || S > DEC_MAX_S) AK_FAIL(-1, "ak_decoder_forward_lens: S must be a positive multiple of 32, <= 8192");
-    if (S > d.n_pos) AK_FAIL(-1, "ak_decoder_forward_lens: S exceeds max_position");
+    // (no limit on B here, unlike the other two families)
+    if (check_forward_lens("ak_decoder_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, DEC_MAX_S, d.n_pos, nullptr, 0)) return -1;
     std::lock_guard<std::mutex> lk(d.mu);
     return dec_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, normalise, out, (hipStream_t)stream);
 }

@@ -10,32 +10,27 @@
 //                                                      the half-window in a sliding layer, every key in a full one
 //   x += RMSNorm(a Wo^T; post_attn_ln); h = RMSNorm(x; pre_ffn_ln)           k_gemm MODE 2 (float32 out) + k_gm_norm_add_norm
 //   f = gelu_tanh(h Wgate^T) (h Wup^T)                 k_gemm MODE 9 (tanh-GeGLU epilogue; gate / up rows interleaved at create, and padded
-//                                                      with zero rows to 2 I % 256 == 0 for the wide tile, as mbert.hip)
+//                                                      with zero rows to 2 I % 256 == 0 for the wide tile: padded_intermediate, stack.h)
 //   x += RMSNorm(f Wdown^T; post_ffn_ln); h = RMSNorm(x; next input_ln)      k_gemm MODE 2 + k_gm_norm_add_norm
 // after the last layer the second norm of the join is the model's final norm, written as float32 rows; then mean pooling over the valid
 // tokens in chunks of 64 (k_gm_pool_part, k_gm_pool_fin: which tokens meet in which sum depends on the row's length alone), the Dense
 // head of the sentence-transformers checkpoint in float32 (0 - 2 matrices without bias, k_gm_dense) and the L2 normalisation (k_gm_l2).
 // The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in mbert.hip.
+// Here: the config checks, the layer struct, the layer loop and the family's own kernels and formulas. The plumbing shared with decoder.hip
+// and mbert.hip is stack.h / stack.hip: the token-slot prologue and the row load of k_gm_embed, the body of k_gm_pool_part, the L2 tail of
+// k_gm_l2, the NJ dispatch, the workspace, the weight preparation at create (concatenation, interleave, the pad-to-256 rule), the rotary
+// tables (also behind ak_gemma_set_rope_inv_freq), the GemmArgs of the launches.
 // LDS per workgroup: k_gm_embed / k_gm_norm_add_norm / k_gm_dense none; k_gm_qk_norm_rope 16 KB (the V transposition); k_gm_pool_part
 // 4 * H * 4 bytes (dynamic); k_gm_l2 16 bytes; the GEMMs and the attention kernel as their files state.
 #include <algorithm>
 #include <cmath>
-#include <mutex>
-#include <vector>
 
-#include "encoder_kernels.h"
-#include "mfma_tile.h"
+#include "stack.h"
 
 namespace ak {
 
 namespace {
-constexpr int GM_HD = 256, GM_MAX_S = ATTN_GQA_MAX_S, GM_MAX_H = 1024, GM_POOL_CHUNK = 64, GM_MAX_DENSE = 4096;
-
-__device__ inline float gm_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+constexpr int GM_HD = 256, GM_MAX_S = ATTN_GQA_MAX_S, GM_MAX_H = POOL_MAX_H, GM_MAX_DENSE = 4096;
 
 // w1[i] = 1 + w[i]: the RMSNorm weights as the kernels multiply by them
 __global__ __launch_bounds__(256) void k_gm_fold1p(const float *__restrict__ w, int n, float *__restrict__ w1) {
@@ -52,12 +47,7 @@ __global__ __launch_bounds__(256) void k_gm_embed(const int *__restrict__ ids, i
     const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (t >= (int64_t)B * S) return;
-    const int b = (int)(t / S), sq = (int)(t - (int64_t)b * S);
-    int len = lens[(int64_t)b * lens_stride];
-    len = len < 0 ? 0 : (len > S ? S : len);
-    if (sq == 0 && lane == 0) lens_out[b] = len;
-    int id = sq < len ? ids[(int64_t)b * ld_ids + sq] : 0;
-    if (id < 0 || id >= vocab) id = 0;                         // a stray id must not read out of bounds
+    const int id = token_slot<false>(ids, ld_ids, lens, lens_stride, S, vocab, t, lane, nullptr, lens_out);
     const uint16_t *e = emb + (int64_t)id * H;
     float4 f[NJ];
     float ss = 0.f;
@@ -66,14 +56,13 @@ __global__ __launch_bounds__(256) void k_gm_embed(const int *__restrict__ ids, i
         const int c = lane * 4 + j * 256;
         f[j] = float4{0.f, 0.f, 0.f, 0.f};
         if (c < H) {
-            const uint2 v = *(const uint2 *)(e + c);
-            f[j] = float4{bf16_to_f32((uint16_t)v.x) * scale, bf16_to_f32((uint16_t)(v.x >> 16)) * scale, bf16_to_f32((uint16_t)v.y) * scale,
-                          bf16_to_f32((uint16_t)(v.y >> 16)) * scale};
+            const float4 v = load_bf16x4(e + c);
+            f[j] = float4{v.x * scale, v.y * scale, v.z * scale, v.w * scale};
             *(float4 *)(x32 + t * H + c) = f[j];
             ss += (f[j].x * f[j].x + f[j].y * f[j].y) + (f[j].z * f[j].z + f[j].w * f[j].w);
         }
     }
-    const float rs = rsqrtf(gm_wave_sum(ss) / (float)H + eps);
+    const float rs = rsqrtf(wave_sum(ss) / (float)H + eps);
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
         const int c = lane * 4 + j * 256;
@@ -107,7 +96,7 @@ __global__ __launch_bounds__(256) void k_gm_norm_add_norm(float *__restrict__ x3
             ss += (y[j].x * y[j].x + y[j].y * y[j].y) + (y[j].z * y[j].z + y[j].w * y[j].w);
         }
     }
-    const float rp = rsqrtf(gm_wave_sum(ss) / (float)H + eps);
+    const float rp = rsqrtf(wave_sum(ss) / (float)H + eps);
     float s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(256) void k_gm_norm_add_norm(float *__restrict__ x3
             s2 += (f[j].x * f[j].x + f[j].y * f[j].y) + (f[j].z * f[j].z + f[j].w * f[j].w);
         }
     }
-    const float rs = rsqrtf(gm_wave_sum(s2) / (float)H + eps);
+    const float rs = rsqrtf(wave_sum(s2) / (float)H + eps);
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
         const int c = lane * 4 + j * 256;
@@ -135,12 +124,7 @@ __global__ __launch_bounds__(256) void k_gm_norm_add_norm(float *__restrict__ x3
 int launch_gm_norm_add_norm(float *x32, const float *y32, int64_t T, int H, const float *w_post, const float *w_pre, float eps, uint16_t *h16,
                             float *out32, hipStream_t st) {
     const unsigned rows4 = (unsigned)((T + 3) / 4);
-    switch ((H + 255) / 256) {
-        case 1: k_gm_norm_add_norm<1><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); break;
-        case 2: k_gm_norm_add_norm<2><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); break;
-        case 3: k_gm_norm_add_norm<3><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); break;
-        default: k_gm_norm_add_norm<4><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); break;      // H <= GM_MAX_H = 1024
-    }
+    dispatch_nj(H, [&](auto nj) { k_gm_norm_add_norm<decltype(nj)::value><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); });
     AK_HIP(hipGetLastError());
     return 0;
 }
@@ -219,43 +203,22 @@ __global__ __launch_bounds__(256) void k_gm_qk_norm_rope(const uint16_t *__restr
     *(uint4 *)(dst + 136) = uint4{bo[4], bo[5], bo[6], bo[7]};
 }
 
-// Pooling, stage 1. Workgroup (chunk ck, row b), 4 waves: the float32 final-norm rows of tokens 64 ck .. 64 ck + 63 below the row's length
-// summed, wave v taking tokens v, v + 4, ...; the four wave partials added in wave order -> part[b][ck][H]. Chunks at or past the
-// length write nothing (stage 2 does not read them).
+// Pooling, stage 1 (pool_part of stack.h) over the float32 final-norm rows below the row's length, as they are.
+struct GmIdentity {
+    struct Token {
+        __device__ float apply(float x) const { return x; }
+    };
+    __device__ int count(int len) const { return len; }
+    __device__ Token begin(const float *, int, int) const { return Token{}; }
+};
 __global__ __launch_bounds__(256) void k_gm_pool_part(const float *__restrict__ y32, const int *__restrict__ lens, int S, int H, float *__restrict__ part) {
-    extern __shared__ float gm_part[];                         // [4][H]
-    const int ck = blockIdx.x, b = blockIdx.y, nch = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lens[b];
-    if (ck * GM_POOL_CHUNK >= n) return;
-    const int stop = min(n, (ck + 1) * GM_POOL_CHUNK);
-    float4 acc[GM_MAX_H / 256];
-#pragma unroll
-    for (int j = 0; j < GM_MAX_H / 256; j++) acc[j] = float4{0.f, 0.f, 0.f, 0.f};
-    for (int tk = ck * GM_POOL_CHUNK + wave; tk < stop; tk += 4) {
-        const float *xr = y32 + ((int64_t)b * S + tk) * H;
-#pragma unroll
-        for (int j = 0; j < GM_MAX_H / 256; j++) {
-            const int c = lane * 4 + j * 256;
-            if (c < H) {
-                const float4 f = *(const float4 *)(xr + c);
-                acc[j].x += f.x; acc[j].y += f.y; acc[j].z += f.z; acc[j].w += f.w;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < GM_MAX_H / 256; j++) {
-        const int c = lane * 4 + j * 256;
-        if (c < H) *(float4 *)(gm_part + wave * H + c) = acc[j];
-    }
-    __syncthreads();
-    float *o = part + ((int64_t)b * nch + ck) * H;
-    for (int c = tid; c < H; c += 256) o[c] = ((gm_part[c] + gm_part[H + c]) + gm_part[2 * H + c]) + gm_part[3 * H + c];
+    pool_part(y32, lens, S, H, GmIdentity{}, part);
 }
 
 // Pooling, stage 2. One workgroup per row b: the chunk sums added in chunk order, / n -> pooled[b][H] (a row of length 0: zeros)
 __global__ __launch_bounds__(256) void k_gm_pool_fin(const float *__restrict__ part, int nch, const int *__restrict__ lens, int H, float *__restrict__ pooled) {
     const int b = blockIdx.x, n = lens[b];
-    const int used = n <= 0 ? 0 : (n + GM_POOL_CHUNK - 1) / GM_POOL_CHUNK;
+    const int used = n <= 0 ? 0 : (n + POOL_CHUNK - 1) / POOL_CHUNK;
     const float inv_n = n > 0 ? 1.0f / (float)n : 0.f;
     for (int c = threadIdx.x; c < H; c += 256) {
         float y = 0.f;
@@ -275,22 +238,17 @@ __global__ __launch_bounds__(256) void k_gm_dense(const float *__restrict__ in, 
         const float4 w = *(const float4 *)(wr + c), x = *(const float4 *)(xr + c);
         s += (w.x * x.x + w.y * x.y) + (w.z * x.z + w.w * x.w);
     }
-    s = gm_wave_sum(s);
+    s = wave_sum(s);
     if (lane == 0) out[(int64_t)b * N + n] = s;
 }
 
 // out[b] = in[b] / max(|in[b]|, 1e-12) (normalise != 0; torch.nn.functional.normalize's eps) or a copy; one workgroup per row
 __global__ __launch_bounds__(256) void k_gm_l2(const float *__restrict__ in, int D, int normalise, float *__restrict__ out) {
-    __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float *x = in + (int64_t)b * D;
     float s2 = 0.f;
     for (int c = tid; c < D; c += 256) s2 += x[c] * x[c];
-    s2 = gm_wave_sum(s2);
-    if ((tid & 63) == 0) red[tid >> 6] = s2;
-    __syncthreads();
-    const float tot = ((red[0] + red[1]) + red[2]) + red[3];
-    const float sc = normalise ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 1.0f;
+    const float sc = block_l2_scale(s2, tid & 63, tid >> 6, normalise);
     for (int c = tid; c < D; c += 256) out[(int64_t)b * D + c] = x[c] * sc;
 }
 
@@ -299,100 +257,54 @@ struct GmLayer {
     const float *input_ln, *q_norm, *k_norm, *post_attn_ln, *pre_ffn_ln, *post_ffn_ln;      // owned: 1 + w
     bool global;
 };
-struct Gemma {
+struct Gemma : Stack {
     AkGemmaConfig cfg;
     const uint16_t *emb = nullptr; const float *final_norm = nullptr;
     std::vector<GmLayer> layers;
     const float *dense[2] = {nullptr, nullptr};
     int dense_in[2] = {0, 0}, dense_out[2] = {0, 0}, out_dim = 0;
-    std::vector<void *> owned;
-    float *zero_bias = nullptr, *rope_c[2] = {nullptr, nullptr}, *rope_s[2] = {nullptr, nullptr};      // [0] local theta, [1] global theta
-    int n_pos = 0, Ip = 0, NQKV = 0;
+    float *rope_c[2] = {nullptr, nullptr}, *rope_s[2] = {nullptr, nullptr};      // [0] local theta, [1] global theta
+    int Ip = 0, NQKV = 0;                          // Ip: intermediate size as the GEMMs see it (padded_intermediate)
     float qscale = 0.f;
-    int64_t cap = 0; int cap_B = 0;
     float *x32 = nullptr, *y32 = nullptr, *part = nullptr, *pool_a = nullptr, *pool_b = nullptr;
     uint16_t *h16 = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *f = nullptr;
     int *lens = nullptr;
-    std::mutex mu;
 };
-
-void gm_free_ws(Gemma &d) {
-    void *p[] = {d.x32, d.y32, d.part, d.pool_a, d.pool_b, d.h16, d.qkv, d.q, d.k, d.vt, d.ctx, d.f, d.lens};
-    for (void *x : p) if (x) hipFree(x);
-    d.x32 = d.y32 = d.part = d.pool_a = d.pool_b = nullptr; d.h16 = d.qkv = d.q = d.k = d.vt = d.ctx = d.f = nullptr; d.lens = nullptr;
-    d.cap = 0; d.cap_B = 0;
-}
-
-// workspace for tpad token rows (a multiple of 256) and B rows; zeroed when (re)allocated, so rows that no kernel writes (GEMM
-// padding rows past B * S) stay finite
-int gm_reserve(Gemma &d, int64_t tpad, int B) {
-    if (tpad <= d.cap && B <= d.cap_B) return 0;
-    if (tpad < d.cap) tpad = d.cap;
-    if (B < d.cap_B) B = d.cap_B;
-    gm_free_ws(d);
-    const int64_t H = d.cfg.hidden, I = d.Ip, NQ = (int64_t)d.cfg.q_heads * GM_HD, NK = (int64_t)d.cfg.kv_heads * GM_HD;
-    const int64_t pw = std::max<int64_t>(H, std::max(d.dense_out[0], d.dense_out[1]));
-    struct { void **p; size_t bytes; } bufs[] = {
-        {(void **)&d.x32, (size_t)(tpad * H * 4)}, {(void **)&d.y32, (size_t)(tpad * H * 4)}, {(void **)&d.h16, (size_t)(tpad * H * 2)},
-        {(void **)&d.qkv, (size_t)(tpad * d.NQKV * 2)}, {(void **)&d.q, (size_t)(tpad * NQ * 2)}, {(void **)&d.k, (size_t)(tpad * NK * 2)},
-        {(void **)&d.vt, (size_t)(tpad * NK * 2)}, {(void **)&d.ctx, (size_t)(tpad * NQ * 2)}, {(void **)&d.f, (size_t)(tpad * I * 2)},
-        {(void **)&d.lens, (size_t)B * 4}, {(void **)&d.part, (size_t)((tpad / GM_POOL_CHUNK + B) * H * 4)},      // B ceil(S / 64) <= T / 64 + B
-        {(void **)&d.pool_a, (size_t)(B * pw * 4)}, {(void **)&d.pool_b, (size_t)(B * pw * 4)},
-    };
-    for (auto &bf : bufs) {
-        AK_HIP(hipMalloc(bf.p, bf.bytes));
-        AK_HIP(hipMemset(*bf.p, 0, bf.bytes));
-    }
-    d.cap = tpad; d.cap_B = B;
-    return 0;
-}
 
 int gm_forward_locked(Gemma &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int normalise, float *out,
                       hipStream_t st) {
     const AkGemmaConfig &c = d.cfg;
     const int H = c.hidden, I = d.Ip, nq = c.q_heads, nkv = c.kv_heads;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
-    if (gm_reserve(d, tpad, B)) return -10;
+    if (d.reserve(tpad, B)) return -10;
     const unsigned rows4 = (unsigned)((T + 3) / 4);
     const float scale = sqrtf((float)H);
-    const float *ln0 = d.layers[0].input_ln;
-    switch ((H + 255) / 256) {
-        case 1: k_gm_embed<1><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, scale, ln0, c.rms_eps, d.x32, d.h16, d.lens); break;
-        case 2: k_gm_embed<2><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, scale, ln0, c.rms_eps, d.x32, d.h16, d.lens); break;
-        case 3: k_gm_embed<3><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, scale, ln0, c.rms_eps, d.x32, d.h16, d.lens); break;
-        default: k_gm_embed<4><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, scale, ln0, c.rms_eps, d.x32, d.h16, d.lens); break;
-    }
+    dispatch_nj(H, [&](auto nj) {
+        k_gm_embed<decltype(nj)::value><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, scale, d.layers[0].input_ln,
+                                                               c.rms_eps, d.x32, d.h16, d.lens);
+    });
     AK_HIP(hipGetLastError());
     for (size_t l = 0; l < d.layers.size(); l++) {
         const GmLayer &ly = d.layers[l];
         const bool last = l + 1 == d.layers.size();
-        GemmArgs g{};
-        g.bias = d.zero_bias; g.T = (int)tpad;
         // q | k | v rows
-        g.X = d.h16; g.W = ly.wqkv; g.N = d.NQKV; g.K = H; g.out_bf16 = d.qkv; g.ldo = d.NQKV;
-        if (launch_gemm(3, g, st)) return -10;
+        if (launch_gemm(3, d.gemm_bf16(tpad, d.h16, ly.wqkv, d.NQKV, H, d.qkv), st)) return -10;
         const int tb = ly.global ? 1 : 0;
         if (launch_gm_qk_norm_rope(d.qkv, B, S, nq, nkv, ly.q_norm, ly.k_norm, c.rms_eps, d.rope_c[tb], d.rope_s[tb], d.qscale, d.q, d.k, d.vt, st)) return -10;
         GqaAttnArgs a{d.q, d.k, d.vt, d.lens, d.ctx, B, S, nq, nkv};
         if (launch_attn_gqa(a, ly.global ? 0 : c.half_window, st)) return -10;
         // x += RMSNorm(ctx Wo^T; post_attn_ln); h = RMSNorm(x; pre_ffn_ln)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.ctx; g.W = ly.wo; g.N = H; g.K = nq * GM_HD; g.out_f32 = d.y32;
-        if (launch_gemm(2, g, st)) return -10;
+        if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, nq * GM_HD, d.y32), st)) return -10;
         if (launch_gm_norm_add_norm(d.x32, d.y32, T, H, ly.post_attn_ln, ly.pre_ffn_ln, c.rms_eps, d.h16, nullptr, st)) return -10;
         // f = gelu_tanh(h Wgate^T) (h Wup^T)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.h16; g.W = ly.wgu; g.N = 2 * I; g.K = H; g.out_bf16 = d.f; g.ldo = I;
-        if (launch_gemm(9, g, st)) return -10;
+        if (launch_gemm(9, d.gemm_gated(tpad, d.h16, ly.wgu, I, H, d.f), st)) return -10;
         // x += RMSNorm(f Wdown^T; post_ffn_ln); h = RMSNorm(x; next layer's input_ln) (after the last layer: the final norm, float32 rows)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.f; g.W = ly.wdown; g.N = H; g.K = I; g.out_f32 = d.y32;
-        if (launch_gemm(2, g, st)) return -10;
+        if (launch_gemm(2, d.gemm_f32(tpad, d.f, ly.wdown, H, I, d.y32), st)) return -10;
         if (launch_gm_norm_add_norm(d.x32, d.y32, T, H, ly.post_ffn_ln, last ? d.final_norm : d.layers[l + 1].input_ln, c.rms_eps, d.h16,
                                     last ? d.y32 : nullptr, st))
             return -10;
     }
-    const int nch = (S + GM_POOL_CHUNK - 1) / GM_POOL_CHUNK;
+    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
     k_gm_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(d.y32, d.lens, S, H, d.part);
     AK_HIP(hipGetLastError());
     k_gm_pool_fin<<<B, 256, 0, st>>>(d.part, nch, d.lens, H, d.pool_a);
@@ -423,16 +335,7 @@ int launch_gm_qk_norm_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, c
 
 using namespace ak;
 
-extern "C" int ak_gemma_destroy(ak_gemma_t h) {
-    AK_BIND();
-    if (!h) return 0;
-    Gemma *d = (Gemma *)h;
-    hipDeviceSynchronize();
-    gm_free_ws(*d);
-    for (void *p : d->owned) hipFree(p);
-    delete d;
-    return 0;
-}
+extern "C" int ak_gemma_destroy(ak_gemma_t h) { return stack_destroy<Gemma>(h); }
 
 extern "C" int ak_gemma_create(const AkGemmaConfig *cfg, const void *const *w, int n_weights, ak_gemma_t *out) {
     AK_BIND();
@@ -470,60 +373,34 @@ extern "C" int ak_gemma_create(const AkGemmaConfig *cfg, const void *const *w, i
     d->NQKV = (nq + 2 * nkv) * GM_HD;
     d->qscale = 1.4426950408889634f / sqrtf(c.query_pre_attn_scalar);
     auto fail = [&](const char *what) { set_error(what); ak_gemma_destroy(d); return -10; };
-    auto dev = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        d->owned.push_back(p);
-        return p;
-    };
     auto fold = [&](const void *src, int n) -> const float * {      // 1 + w
-        float *p = (float *)dev((size_t)n * 4);
+        float *p = d->dev_as<float>(n);
         if (!p) return nullptr;
         k_gm_fold1p<<<(n + 255) / 256, 256>>>((const float *)src, n, p);
         return hipGetLastError() == hipSuccess ? p : nullptr;
     };
     if (!(d->final_norm = fold(w[1], H))) return fail("ak_gemma_create: hipMalloc failed");
-    // 2 I off the wide GEMM tile: zero rows up to a multiple of 256 and zero columns of down_proj to match (mbert.hip's rule)
-    const int Ip = (2 * I) % 256 ? (I + 127) / 128 * 128 : I;
-    d->Ip = Ip;
-    const size_t zb = std::max<size_t>(std::max<size_t>((size_t)d->NQKV, (size_t)2 * Ip), (size_t)H);
-    d->zero_bias = (float *)dev(zb * 4);
-    if (!d->zero_bias || hipMemset(d->zero_bias, 0, zb * 4) != hipSuccess) return fail("ak_gemma_create: hipMalloc failed");
-    // the two rotary tables, positions 0 .. min(max_position, 2048) - 1 (the decoder's host routine at head size 256)
+    const int Ip = d->Ip = padded_intermediate(I);
+    d->zero_bias = d->dev_as<float>(std::max<size_t>(std::max<size_t>((size_t)d->NQKV, (size_t)2 * Ip), (size_t)H), true);
+    if (!d->zero_bias) return fail("ak_gemma_create: hipMalloc failed");
+    // the two rotary tables, positions 0 .. min(max_position, 2048) - 1, at head size 256
     d->n_pos = c.max_position < GM_MAX_S ? c.max_position : GM_MAX_S;
-    for (int tb = 0; tb < 2; tb++) {
-        std::vector<float> hc((size_t)d->n_pos * (GM_HD / 2)), hs((size_t)d->n_pos * (GM_HD / 2));
-        if (ak_decoder_rope_table(tb ? c.global_rope_theta : c.local_rope_theta, GM_HD, d->n_pos, hc.data(), hs.data())) return fail("ak_gemma_create: rotary table failed");
-        d->rope_c[tb] = (float *)dev(hc.size() * 4);
-        d->rope_s[tb] = (float *)dev(hs.size() * 4);
-        if (!d->rope_c[tb] || !d->rope_s[tb] || hipMemcpy(d->rope_c[tb], hc.data(), hc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d->rope_s[tb], hs.data(), hs.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    for (int tb = 0; tb < 2; tb++)
+        if (!d->rope_tables(tb ? c.global_rope_theta : c.local_rope_theta, GM_HD, &d->rope_c[tb], &d->rope_s[tb]))
             return fail("ak_gemma_create: rotary table upload failed");
-    }
     const size_t NQ = (size_t)nq * GM_HD, NK = (size_t)nkv * GM_HD;
     for (int l = 0; l < L; l++) {
         // input_ln wq wk wv q_norm k_norm wo post_attn_ln pre_ffn_ln w_gate w_up w_down post_ffn_ln
         const void *const *p = w + 2 + 13 * l;
         GmLayer ly{};
-        uint16_t *wqkv = (uint16_t *)dev((size_t)d->NQKV * H * 2);
-        if (!wqkv || hipMemcpy(wqkv, p[1], NQ * H * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy(wqkv + NQ * H, p[2], NK * H * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy(wqkv + (NQ + NK) * H, p[3], NK * H * 2, hipMemcpyDeviceToDevice) != hipSuccess)
-            return fail("ak_gemma_create: QKV concatenation failed");
-        uint16_t *wgu = (uint16_t *)dev((size_t)2 * Ip * H * 2);
-        if (!wgu || (Ip != I && hipMemset(wgu, 0, (size_t)2 * Ip * H * 2) != hipSuccess)) return fail("ak_gemma_create: hipMalloc failed");
+        uint16_t *wqkv = d->dev_as<uint16_t>((size_t)d->NQKV * H);
+        if (!wqkv || !d->concat_rows(wqkv, H, {{p[1], NQ}, {p[2], NK}, {p[3], NK}})) return fail("ak_gemma_create: QKV concatenation failed");
+        uint16_t *wgu = d->dev_as<uint16_t>((size_t)2 * Ip * H, Ip != I);
+        if (!wgu) return fail("ak_gemma_create: hipMalloc failed");
         // row 2 j = gate_proj row j, row 2 j + 1 = up_proj row j (gemm.hip MODE 9)
-        if (hipMemcpy2D(wgu, (size_t)4 * H, p[9], (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy2D(wgu + H, (size_t)4 * H, p[10], (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess)
-            return fail("ak_gemma_create: gate / up interleave failed");
+        if (!d->interleave_rows(wgu, p[9], p[10], I, H)) return fail("ak_gemma_create: gate / up interleave failed");
         ly.wqkv = wqkv; ly.wo = (const uint16_t *)p[6]; ly.wgu = wgu; ly.wdown = (const uint16_t *)p[11];
-        if (Ip != I) {                             // down_proj [H][I] -> [H][Ip] with zero columns behind I
-            uint16_t *wd = (uint16_t *)dev((size_t)H * Ip * 2);
-            if (!wd || hipMemset(wd, 0, (size_t)H * Ip * 2) != hipSuccess ||
-                hipMemcpy2D(wd, (size_t)2 * Ip, p[11], (size_t)2 * I, (size_t)2 * I, H, hipMemcpyDeviceToDevice) != hipSuccess)
-                return fail("ak_gemma_create: down_proj padding failed");
-            ly.wdown = wd;
-        }
+        if (Ip != I && !(ly.wdown = d->pad_cols(p[11], H, I, Ip))) return fail("ak_gemma_create: down_proj padding failed");
         ly.input_ln = fold(p[0], H); ly.q_norm = fold(p[4], GM_HD); ly.k_norm = fold(p[5], GM_HD);
         ly.post_attn_ln = fold(p[7], H); ly.pre_ffn_ln = fold(p[8], H); ly.post_ffn_ln = fold(p[12], H);
         if (!ly.input_ln || !ly.q_norm || !ly.k_norm || !ly.post_attn_ln || !ly.pre_ffn_ln || !ly.post_ffn_ln) return fail("ak_gemma_create: norm weight fold failed");
@@ -536,6 +413,12 @@ extern "C" int ak_gemma_create(const AkGemmaConfig *cfg, const void *const *w, i
         d->dense_in[i] = din; d->dense_out[i] = c.dense_out[i];
         din = c.dense_out[i];
     }
+    const size_t pw = (size_t)std::max(H, std::max(d->dense_out[0], d->dense_out[1])) * 4;      // widest pooled row
+    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, (size_t)H * 2);
+    d->buffer(&d->qkv, (size_t)d->NQKV * 2); d->buffer(&d->q, NQ * 2); d->buffer(&d->k, NK * 2); d->buffer(&d->vt, NK * 2);
+    d->buffer(&d->ctx, NQ * 2); d->buffer(&d->f, (size_t)Ip * 2); d->buffer(&d->lens, 0, 4);
+    d->buffer(&d->part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
+    d->buffer(&d->pool_a, 0, pw); d->buffer(&d->pool_b, 0, pw);
     if (hipDeviceSynchronize() != hipSuccess) return fail("ak_gemma_create: weight preparation failed");
     *out = d;
     return 0;
@@ -547,12 +430,8 @@ extern "C" int ak_gemma_set_rope_inv_freq(ak_gemma_t h, const float *global_inv,
     Gemma &d = *(Gemma *)h;
     std::lock_guard<std::mutex> lk(d.mu);
     AK_HIP(hipDeviceSynchronize());                            // no forward of this handle reads the tables while they change
-    std::vector<float> hc((size_t)d.n_pos * (GM_HD / 2)), hs((size_t)d.n_pos * (GM_HD / 2));
-    for (int tb = 0; tb < 2; tb++) {                           // [0] local theta, [1] global theta
-        if (ak_decoder_rope_table_inv(tb ? global_inv : local_inv, GM_HD / 2, d.n_pos, hc.data(), hs.data())) return -1;
-        AK_HIP(hipMemcpy(d.rope_c[tb], hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
-        AK_HIP(hipMemcpy(d.rope_s[tb], hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-    }
+    for (int tb = 0; tb < 2; tb++)                             // [0] local theta, [1] global theta
+        if (d.rope_tables_set_inv(tb ? global_inv : local_inv, GM_HD / 2, d.rope_c[tb], d.rope_s[tb])) return -10;
     return 0;
 }
 
@@ -563,11 +442,9 @@ extern "C" int ak_gemma_forward_lens(ak_gemma_t h, const int32_t *ids, int ld_id
     RoctxRange range("ak_gemma_forward_lens");
     Gemma &d = *(Gemma *)h;
     if (B <= 0) return 0;
-    if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, "ak_gemma_forward_lens: bad arguments");
-    if (pooling != AK_POOL_MEAN) AK_FAIL(-1, "ak_gemma_forward_lens: pooling must be AK_POOL_MEAN");
-    if (S <= 0 || S % 32 || S > GM_MAX_S) AK_FAIL(-1, "ak_gemma_forward_lens: S must be a positive multiple of 32, <= 2048");
-    if (S > d.n_pos) AK_FAIL(-1, "ak_gemma_forward_lens: S exceeds max_position");
-    if (B > 65535) AK_FAIL(-1, "ak_gemma_forward_lens: at most 65535 rows per call");      // a grid dimension of the attention and pooling launches
+    if (check_forward_lens("ak_gemma_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, GM_MAX_S, d.n_pos,
+                           pooling == AK_POOL_MEAN ? nullptr : "pooling must be AK_POOL_MEAN", 65535))
+        return -1;
     std::lock_guard<std::mutex> lk(d.mu);
     return gm_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, normalise, out, (hipStream_t)stream);
 }

@@ -8,30 +8,26 @@
 //   a = softmax(q k^T + band + pad mask) v             k_attn_long<WIN> (attn_long.hip): WIN = true with the half-window in a sliding layer
 //   x += a Wo^T; h = LayerNorm(x; mlp_norm)            k_gemm MODE 2 (float32 out) + k_mb_add_ln
 //   f = gelu(h Wi_a^T) (h Wi_g^T)                      k_gemm MODE 8 (GeGLU epilogue; the halves of Wi interleaved at create, and padded
-//                                                      with zero rows to 2 I % 256 == 0 -- large: 5248 -> 5376 -- for the wide tile)
+//                                                      with zero rows to 2 I % 256 == 0 -- large: 5248 -> 5376 -- for the wide tile:
+//                                                      padded_intermediate, stack.h)
 //   x += f Wo^T; h = LayerNorm(x; next attn_norm)      k_gemm MODE 2 + k_mb_add_ln
 // then final_norm per token, mean / cls pooling over the valid tokens and L2 normalisation in float32 (k_mb_pool_part, k_mb_pool_fin).
 // The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in decoder.hip.
+// Here: the config checks, the layer struct, the layer loop and the family's own kernels and formulas. The plumbing shared with decoder.hip
+// and gemma.hip is stack.h / stack.hip: the token-slot prologue and the row helpers of k_mb_embed, the body of k_mb_pool_part (here: its
+// per-token transform), the L2 tail of k_mb_pool_fin, the NJ dispatch, the workspace, the weight preparation at create (interleave, the
+// pad-to-256 rule), the rotary tables, the GemmArgs of the launches.
 // LDS per workgroup: k_mb_embed / k_mb_add_ln / k_mb_rope none; k_mb_pool_part 4 * H * 4 bytes (dynamic: 12 KB at H = 768, 16 KB at
 // 1024); k_mb_pool_fin 16 bytes; the GEMMs and the attention kernel as their files state.
 #include <algorithm>
 #include <cmath>
-#include <mutex>
-#include <vector>
 
-#include "encoder_kernels.h"
-#include "mfma_tile.h"
+#include "stack.h"
 
 namespace ak {
 
 namespace {
-constexpr int MB_HD = 64, MB_MAX_S = ATTN_LONG_MAX_S, MB_MAX_H = 1024, MB_POOL_CHUNK = 64;
-
-__device__ inline float mb_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+constexpr int MB_HD = 64, MB_MAX_S = ATTN_LONG_MAX_S, MB_MAX_H = POOL_MAX_H;
 
 // LayerNorm statistics of one float32 row held in memory (H % 4 == 0), by one wave: mean, then the variance about it (two passes,
 // as torch's float32 kernel -- not E[x^2] - mean^2)
@@ -41,14 +37,14 @@ __device__ inline void mb_row_stats(const float *__restrict__ xr, int H, int lan
         const float4 f = *(const float4 *)(xr + c);
         s += (f.x + f.y) + (f.z + f.w);
     }
-    mean = mb_wave_sum(s) / (float)H;
+    mean = wave_sum(s) / (float)H;
     float q = 0.f;
     for (int c = lane * 4; c < H; c += 256) {
         const float4 f = *(const float4 *)(xr + c);
         const float a = f.x - mean, b = f.y - mean, cc = f.z - mean, d = f.w - mean;
         q += (a * a + b * b) + (cc * cc + d * d);
     }
-    rstd = rsqrtf(mb_wave_sum(q) / (float)H + eps);
+    rstd = rsqrtf(wave_sum(q) / (float)H + eps);
 }
 
 // one wave per token slot t < B * S: ids past the row's length read as 0; x32 = LayerNorm(tok_embeddings[id]; w), h16 = bf16(x32).
@@ -59,28 +55,17 @@ __global__ __launch_bounds__(256) void k_mb_embed(const int *__restrict__ ids, i
     const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (t >= (int64_t)B * S) return;
-    const int b = (int)(t / S), sq = (int)(t - (int64_t)b * S);
-    int len = lens[(int64_t)b * lens_stride];
-    len = len < 0 ? 0 : (len > S ? S : len);
-    if (lane == 0) {
-        mask[t] = sq < len;
-        if (sq == 0) lens_out[b] = len;
-    }
-    int id = sq < len ? ids[(int64_t)b * ld_ids + sq] : 0;
-    if (id < 0 || id >= vocab) id = 0;                         // a stray id must not read out of bounds
+    const int id = token_slot<true>(ids, ld_ids, lens, lens_stride, S, vocab, t, lane, mask, lens_out);
     const uint16_t *e = emb + (int64_t)id * H;
     float *xr = x32 + t * H;
-    for (int c = lane * 4; c < H; c += 256) {
-        const uint2 v = *(const uint2 *)(e + c);
-        *(float4 *)(xr + c) = float4{bf16_to_f32((uint16_t)v.x), bf16_to_f32((uint16_t)(v.x >> 16)), bf16_to_f32((uint16_t)v.y), bf16_to_f32((uint16_t)(v.y >> 16))};
-    }
+    for (int c = lane * 4; c < H; c += 256) *(float4 *)(xr + c) = load_bf16x4(e + c);
     float mean, rstd;
     mb_row_stats(xr, H, lane, eps, mean, rstd);                // (a lane re-reads only what it wrote itself)
     for (int c = lane * 4; c < H; c += 256) {
         const float4 f = *(const float4 *)(xr + c), g = *(const float4 *)(w + c);
         const float4 y = {(f.x - mean) * rstd * g.x, (f.y - mean) * rstd * g.y, (f.z - mean) * rstd * g.z, (f.w - mean) * rstd * g.w};
         *(float4 *)(xr + c) = y;
-        *(uint2 *)(h16 + t * H + c) = uint2{mt::pack_bf16x2(y.x, y.y), mt::pack_bf16x2(y.z, y.w)};
+        store_bf16x4(h16 + t * H + c, y.x, y.y, y.z, y.w);
     }
 }
 
@@ -110,7 +95,7 @@ __global__ __launch_bounds__(256) void k_mb_add_ln(float *__restrict__ x32, cons
         }
     }
     if (!w) return;
-    const float mean = mb_wave_sum(s) / (float)H;
+    const float mean = wave_sum(s) / (float)H;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; j++)
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(256) void k_mb_add_ln(float *__restrict__ x32, cons
             const float a = f[j].x - mean, b = f[j].y - mean, cc = f[j].z - mean, d = f[j].w - mean;
             q += (a * a + b * b) + (cc * cc + d * d);
         }
-    const float rstd = rsqrtf(mb_wave_sum(q) / (float)H + eps);
+    const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
         const int c = lane * 4 + j * 256;
@@ -132,12 +117,7 @@ __global__ __launch_bounds__(256) void k_mb_add_ln(float *__restrict__ x32, cons
 
 int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st) {
     const unsigned rows4 = (unsigned)((T + 3) / 4);
-    switch ((H + 255) / 256) {
-        case 1: k_mb_add_ln<1><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;
-        case 2: k_mb_add_ln<2><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;
-        case 3: k_mb_add_ln<3><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;
-        default: k_mb_add_ln<4><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); break;      // H <= MB_MAX_H = 1024
-    }
+    dispatch_nj(H, [&](auto nj) { k_mb_add_ln<decltype(nj)::value><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); });
     AK_HIP(hipGetLastError());
     return 0;
 }
@@ -172,49 +152,30 @@ __global__ __launch_bounds__(256) void k_mb_rope(uint16_t *__restrict__ q, uint1
     *(uint4 *)(row + 32) = uint4{bo[0], bo[1], bo[2], bo[3]};
 }
 
-// Pooling, stage 1. Workgroup (chunk ck, row b), 4 waves: y_t = (x_t - mean_t) rstd_t (the final LayerNorm without its weight) summed over
-// the pooled tokens of chunk ck -- tokens 64 ck .. 64 ck + 63 below n (mean: n = the row's length; cls: n = 1) --, wave v taking tokens
-// v, v + 4, ...; the four wave partials added in wave order -> part[b][ck][H]. Chunks at or past n write nothing (stage 2 does not read
-// them). Which tokens meet in which sum depends on the row's length alone, not on S or the batch around it.
+// Pooling, stage 1 (pool_part of stack.h) over the pooled tokens of a row -- mean: its length; cls: token 0 --, the per-token transform
+// y_t = (x_t - mean_t) rstd_t: the final LayerNorm without its weight.
+struct MbFinalNorm {
+    float eps; int pooling;
+    struct Token {
+        float mean, rstd;
+        __device__ float apply(float x) const { return (x - mean) * rstd; }
+    };
+    __device__ int count(int len) const { return len <= 0 ? 0 : (pooling == AK_POOL_CLS ? 1 : len); }
+    __device__ Token begin(const float *xr, int H, int lane) const {
+        Token t;
+        mb_row_stats(xr, H, lane, eps, t.mean, t.rstd);
+        return t;
+    }
+};
 __global__ __launch_bounds__(256) void k_mb_pool_part(const float *__restrict__ x32, const int *__restrict__ lens, int S, int H, float eps, int pooling,
                                                       float *__restrict__ part) {
-    extern __shared__ float mb_part[];                         // [4][H]
-    const int ck = blockIdx.x, b = blockIdx.y, nch = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int len = lens[b];
-    const int n = len <= 0 ? 0 : (pooling == AK_POOL_CLS ? 1 : len);
-    if (ck * MB_POOL_CHUNK >= n) return;
-    const int stop = min(n, (ck + 1) * MB_POOL_CHUNK);
-    float4 acc[MB_MAX_H / 256];
-#pragma unroll
-    for (int j = 0; j < MB_MAX_H / 256; j++) acc[j] = float4{0.f, 0.f, 0.f, 0.f};
-    for (int tk = ck * MB_POOL_CHUNK + wave; tk < stop; tk += 4) {
-        const float *xr = x32 + ((int64_t)b * S + tk) * H;
-        float mean, rstd;
-        mb_row_stats(xr, H, lane, eps, mean, rstd);
-#pragma unroll
-        for (int j = 0; j < MB_MAX_H / 256; j++) {
-            const int c = lane * 4 + j * 256;
-            if (c < H) {
-                const float4 f = *(const float4 *)(xr + c);
-                acc[j].x += (f.x - mean) * rstd; acc[j].y += (f.y - mean) * rstd; acc[j].z += (f.z - mean) * rstd; acc[j].w += (f.w - mean) * rstd;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < MB_MAX_H / 256; j++) {
-        const int c = lane * 4 + j * 256;
-        if (c < H) *(float4 *)(mb_part + wave * H + c) = acc[j];
-    }
-    __syncthreads();
-    float *o = part + ((int64_t)b * nch + ck) * H;
-    for (int c = tid; c < H; c += 256) o[c] = ((mb_part[c] + mb_part[H + c]) + mb_part[2 * H + c]) + mb_part[3 * H + c];
+    pool_part(x32, lens, S, H, MbFinalNorm{eps, pooling}, part);
 }
 
 // Pooling, stage 2. One workgroup per row b: the chunk sums added in chunk order, * w / n, then the L2 normalisation. A row of length 0
 // embeds to zeros.
 __global__ __launch_bounds__(256) void k_mb_pool_fin(const float *__restrict__ part, int nch, const int *__restrict__ lens, int H, const float *__restrict__ w,
                                                      int pooling, int normalise, float *__restrict__ out) {
-    __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int len = lens[b];
     float *o = out + (int64_t)b * H;
@@ -222,7 +183,7 @@ __global__ __launch_bounds__(256) void k_mb_pool_fin(const float *__restrict__ p
         for (int c = tid; c < H; c += 256) o[c] = 0.f;
         return;
     }
-    const int n = pooling == AK_POOL_CLS ? 1 : len, used = (n + MB_POOL_CHUNK - 1) / MB_POOL_CHUNK;
+    const int n = pooling == AK_POOL_CLS ? 1 : len, used = (n + POOL_CHUNK - 1) / POOL_CHUNK;
     const float inv_n = 1.0f / (float)n;
     float y[MB_MAX_H / 256];
     float s2 = 0.f;
@@ -236,11 +197,7 @@ __global__ __launch_bounds__(256) void k_mb_pool_fin(const float *__restrict__ p
             s2 += y[j] * y[j];
         }
     }
-    s2 = mb_wave_sum(s2);
-    if (lane == 0) red[wave] = s2;
-    __syncthreads();
-    const float tot = ((red[0] + red[1]) + red[2]) + red[3];
-    const float sc = normalise ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 1.0f;      // torch.nn.functional.normalize's eps
+    const float sc = block_l2_scale(s2, lane, wave, normalise);
 #pragma unroll
     for (int j = 0; j < MB_MAX_H / 256; j++) {
         const int c = tid + j * 256;
@@ -254,66 +211,31 @@ struct MbLayer {
     const float *attn_norm, *mlp_norm;         // attn_norm of layer 0: not read
     bool global;
 };
-struct MBert {
+struct MBert : Stack {
     AkModernBertConfig cfg;
     const uint16_t *emb = nullptr; const float *emb_norm = nullptr, *final_norm = nullptr;
     std::vector<MbLayer> layers;
-    std::vector<void *> owned;
-    float *zero_bias = nullptr, *rope_c[2] = {nullptr, nullptr}, *rope_s[2] = {nullptr, nullptr};      // [0] local theta, [1] global theta
-    int n_pos = 0;
-    int Ip = 0;                                // intermediate size as the GEMMs see it (>= cfg.intermediate: ak_mbert_create)
-    int64_t cap = 0, cap_v = 0; int cap_B = 0;
+    float *rope_c[2] = {nullptr, nullptr}, *rope_s[2] = {nullptr, nullptr};      // [0] local theta, [1] global theta
+    int Ip = 0;                                // intermediate size as the GEMMs see it (padded_intermediate)
     float *x32 = nullptr, *y32 = nullptr;
     uint16_t *h16 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *f = nullptr;
     float *part = nullptr;                     // pooling: chunk sums [B][ceil(S / 64)][H]
     int *mask = nullptr, *lens = nullptr;
-    std::mutex mu;
 };
-
-void mb_free_ws(MBert &d) {
-    void *p[] = {d.x32, d.y32, d.h16, d.q, d.k, d.vt, d.ctx, d.f, d.mask, d.lens, d.part};
-    for (void *x : p) if (x) hipFree(x);
-    d.x32 = d.y32 = d.part = nullptr; d.h16 = d.q = d.k = d.vt = d.ctx = d.f = nullptr; d.mask = d.lens = nullptr;
-    d.cap = 0; d.cap_B = 0;
-}
-
-// workspace for tpad token rows (a multiple of 256) and B rows; zeroed when (re)allocated, so rows that no kernel writes (GEMM
-// padding rows past B * S) stay finite
-int mb_reserve(MBert &d, int64_t tpad, int B) {
-    if (tpad <= d.cap && B <= d.cap_B) return 0;
-    if (tpad < d.cap) tpad = d.cap;
-    if (B < d.cap_B) B = d.cap_B;
-    mb_free_ws(d);
-    const int64_t H = d.cfg.hidden, I = d.Ip;
-    struct { void **p; size_t bytes; } bufs[] = {
-        {(void **)&d.x32, (size_t)(tpad * H * 4)}, {(void **)&d.y32, (size_t)(tpad * H * 4)}, {(void **)&d.h16, (size_t)(tpad * H * 2)},
-        {(void **)&d.q, (size_t)(tpad * H * 2)}, {(void **)&d.k, (size_t)(tpad * H * 2)}, {(void **)&d.vt, (size_t)(tpad * H * 2)},
-        {(void **)&d.ctx, (size_t)(tpad * H * 2)}, {(void **)&d.f, (size_t)(tpad * I * 2)}, {(void **)&d.mask, (size_t)tpad * 4},
-        {(void **)&d.lens, (size_t)B * 4}, {(void **)&d.part, (size_t)((tpad / MB_POOL_CHUNK + B) * H * 4)},      // B ceil(S / 64) <= T / 64 + B
-    };
-    for (auto &bf : bufs) {
-        AK_HIP(hipMalloc(bf.p, bf.bytes));
-        AK_HIP(hipMemset(*bf.p, 0, bf.bytes));
-    }
-    d.cap = tpad; d.cap_B = B;
-    return 0;
-}
 
 int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling, int normalise,
                       float *out, hipStream_t st) {
     const AkModernBertConfig &c = d.cfg;
     const int H = c.hidden, I = d.Ip, heads = c.heads;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
-    if (mb_reserve(d, tpad, B)) return -10;
+    if (d.reserve(tpad, B)) return -10;
     const unsigned rows4 = (unsigned)((T + 3) / 4);
     k_mb_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.emb_norm, c.norm_eps, d.x32, d.h16, d.mask, d.lens);
     AK_HIP(hipGetLastError());
     for (size_t l = 0; l < d.layers.size(); l++) {
         const MbLayer &ly = d.layers[l];
-        GemmArgs g{};
-        g.bias = d.zero_bias; g.T = (int)tpad;
         // q (scaled) | k | V^T
-        g.X = d.h16; g.W = ly.wqkv; g.N = 3 * H; g.K = H;
+        GemmArgs g = d.gemm(tpad, d.h16, ly.wqkv, 3 * H, H);
         g.q = d.q; g.k = d.k; g.vt = d.vt; g.H = H; g.S = S; g.qscale = 1.4426950408889634f / sqrtf((float)MB_HD);
         g.ldo = (int)T;                                        // MODE 0: number of real tokens (rows beyond it have no V^T slot)
         if (launch_gemm(0, g, st)) return -10;
@@ -323,22 +245,16 @@ int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *l
         AttnArgs a{d.q, d.k, d.vt, d.mask, d.ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, d.lens};
         if (launch_attn_window(a, ly.global ? -1 : c.half_window, st)) return -10;
         // x += ctx Wo^T; h = LayerNorm(x; mlp_norm)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.ctx; g.W = ly.wo; g.N = H; g.K = H; g.out_f32 = d.y32;
-        if (launch_gemm(2, g, st)) return -10;
+        if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, H, d.y32), st)) return -10;
         if (launch_mb_add_ln(d.x32, d.y32, T, H, ly.mlp_norm, c.norm_eps, d.h16, st)) return -10;
         // f = gelu(h Wi_a^T) (h Wi_g^T)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.h16; g.W = ly.wi; g.N = 2 * I; g.K = H; g.out_bf16 = d.f; g.ldo = I;
-        if (launch_gemm(8, g, st)) return -10;
+        if (launch_gemm(8, d.gemm_gated(tpad, d.h16, ly.wi, I, H, d.f), st)) return -10;
         // x += f Wo^T; h = LayerNorm(x; next layer's attn_norm) (after the last layer: the add only, the pool applies final_norm)
-        g = GemmArgs{}; g.bias = d.zero_bias; g.T = (int)tpad;
-        g.X = d.f; g.W = ly.wo2; g.N = H; g.K = I; g.out_f32 = d.y32;
-        if (launch_gemm(2, g, st)) return -10;
+        if (launch_gemm(2, d.gemm_f32(tpad, d.f, ly.wo2, H, I, d.y32), st)) return -10;
         const float *wn = l + 1 < d.layers.size() ? d.layers[l + 1].attn_norm : nullptr;
         if (launch_mb_add_ln(d.x32, d.y32, T, H, wn, c.norm_eps, d.h16, st)) return -10;
     }
-    const int nch = (S + MB_POOL_CHUNK - 1) / MB_POOL_CHUNK;
+    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
     k_mb_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(d.x32, d.lens, S, H, c.norm_eps, pooling, d.part);
     AK_HIP(hipGetLastError());
     k_mb_pool_fin<<<B, 256, 0, st>>>(d.part, nch, d.lens, H, d.final_norm, pooling, normalise, out);
@@ -351,16 +267,7 @@ int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *l
 
 using namespace ak;
 
-extern "C" int ak_mbert_destroy(ak_mbert_t h) {
-    AK_BIND();
-    if (!h) return 0;
-    MBert *d = (MBert *)h;
-    hipDeviceSynchronize();
-    mb_free_ws(*d);
-    for (void *p : d->owned) hipFree(p);
-    delete d;
-    return 0;
-}
+extern "C" int ak_mbert_destroy(ak_mbert_t h) { return stack_destroy<MBert>(h); }
 
 extern "C" int ak_mbert_create(const AkModernBertConfig *cfg, const void *const *w, int n_weights, ak_mbert_t *out) {
     AK_BIND();
@@ -383,52 +290,32 @@ extern "C" int ak_mbert_create(const AkModernBertConfig *cfg, const void *const 
     d->emb_norm = (const float *)w[1];
     d->final_norm = (const float *)w[2];
     auto fail = [&](const char *what) { set_error(what); ak_mbert_destroy(d); return -10; };
-    auto dev = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        d->owned.push_back(p);
-        return p;
-    };
-    // 2 I off the wide GEMM tile (large: 5248 = 41 x 128): the interleaved Wi gets zero rows up to a multiple of 256 and mlp.Wo zero
-    // columns to match (gelu(0) 0 = 0 meets a zero weight: bit-identical results). Measured, large shape 128 x 512: 62.9 ms against 67.2
-    const int Ip = (2 * I) % 256 ? (I + 127) / 128 * 128 : I;
-    d->Ip = Ip;
-    const size_t zb = std::max<size_t>((size_t)3 * H, (size_t)2 * Ip);
-    d->zero_bias = (float *)dev(zb * 4);
-    if (!d->zero_bias || hipMemset(d->zero_bias, 0, zb * 4) != hipSuccess) return fail("ak_mbert_create: hipMalloc failed");
-    // the two rotary tables, positions 0 .. min(max_position, 8192) - 1 (the decoder's host routine at head size 64)
+    const int Ip = d->Ip = padded_intermediate(I);             // large: 2624 -> 2688
+    d->zero_bias = d->dev_as<float>(std::max<size_t>((size_t)3 * H, (size_t)2 * Ip), true);
+    if (!d->zero_bias) return fail("ak_mbert_create: hipMalloc failed");
+    // the two rotary tables, positions 0 .. min(max_position, 8192) - 1, at head size 64
     d->n_pos = c.max_position < MB_MAX_S ? c.max_position : MB_MAX_S;
-    for (int tb = 0; tb < 2; tb++) {
-        std::vector<float> hc((size_t)d->n_pos * 32), hs((size_t)d->n_pos * 32);
-        if (ak_decoder_rope_table(tb ? c.global_rope_theta : c.local_rope_theta, MB_HD, d->n_pos, hc.data(), hs.data())) return fail("ak_mbert_create: rotary table failed");
-        d->rope_c[tb] = (float *)dev(hc.size() * 4);
-        d->rope_s[tb] = (float *)dev(hs.size() * 4);
-        if (!d->rope_c[tb] || !d->rope_s[tb] || hipMemcpy(d->rope_c[tb], hc.data(), hc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d->rope_s[tb], hs.data(), hs.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    for (int tb = 0; tb < 2; tb++)
+        if (!d->rope_tables(tb ? c.global_rope_theta : c.local_rope_theta, MB_HD, &d->rope_c[tb], &d->rope_s[tb]))
             return fail("ak_mbert_create: rotary table upload failed");
-    }
     for (int l = 0; l < L; l++) {
         const void *const *p = w + 3 + 6 * l;      // attn_norm wqkv wo mlp_norm wi mlp_wo
         MbLayer ly{};
-        uint16_t *wi = (uint16_t *)dev((size_t)2 * Ip * H * 2);
-        if (!wi || (Ip != I && hipMemset(wi, 0, (size_t)2 * Ip * H * 2) != hipSuccess)) return fail("ak_mbert_create: hipMalloc failed");
+        uint16_t *wi = d->dev_as<uint16_t>((size_t)2 * Ip * H, Ip != I);
+        if (!wi) return fail("ak_mbert_create: hipMalloc failed");
         // row 2 j = Wi row j, row 2 j + 1 = Wi row I + j (gemm.hip MODE 8)
-        const uint16_t *src = (const uint16_t *)p[4];
-        if (hipMemcpy2D(wi, (size_t)4 * H, src, (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy2D(wi + H, (size_t)4 * H, src + (size_t)I * H, (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) != hipSuccess)
-            return fail("ak_mbert_create: Wi interleave failed");
+        if (!d->interleave_rows(wi, p[4], (const uint16_t *)p[4] + (size_t)I * H, I, H)) return fail("ak_mbert_create: Wi interleave failed");
         ly.attn_norm = (const float *)p[0]; ly.wqkv = (const uint16_t *)p[1]; ly.wo = (const uint16_t *)p[2];
         ly.mlp_norm = (const float *)p[3]; ly.wi = wi; ly.wo2 = (const uint16_t *)p[5];
-        if (Ip != I) {                             // mlp.Wo [H][I] -> [H][Ip] with zero columns behind I
-            uint16_t *wo2 = (uint16_t *)dev((size_t)H * Ip * 2);
-            if (!wo2 || hipMemset(wo2, 0, (size_t)H * Ip * 2) != hipSuccess ||
-                hipMemcpy2D(wo2, (size_t)2 * Ip, p[5], (size_t)2 * I, (size_t)2 * I, H, hipMemcpyDeviceToDevice) != hipSuccess)
-                return fail("ak_mbert_create: mlp.Wo padding failed");
-            ly.wo2 = wo2;
-        }
+        if (Ip != I && !(ly.wo2 = d->pad_cols(p[5], H, I, Ip))) return fail("ak_mbert_create: mlp.Wo padding failed");
         ly.global = c.layer_global[l] != 0;
         d->layers.push_back(ly);
     }
+    const size_t row16 = (size_t)H * 2;
+    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, row16);
+    d->buffer(&d->q, row16); d->buffer(&d->k, row16); d->buffer(&d->vt, row16); d->buffer(&d->ctx, row16);
+    d->buffer(&d->f, (size_t)Ip * 2); d->buffer(&d->mask, 4); d->buffer(&d->lens, 0, 4);
+    d->buffer(&d->part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
     if (hipDeviceSynchronize() != hipSuccess) return fail("ak_mbert_create: weight preparation failed");
     *out = d;
     return 0;
@@ -441,11 +328,10 @@ extern "C" int ak_mbert_forward_lens(ak_mbert_t h, const int32_t *ids, int ld_id
     RoctxRange range("ak_mbert_forward_lens");
     MBert &d = *(MBert *)h;
     if (B <= 0) return 0;
-    if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, "ak_mbert_forward_lens: bad arguments");
-    if (pooling != AK_POOL_MEAN && pooling != AK_POOL_CLS) AK_FAIL(-1, "ak_mbert_forward_lens: pooling must be AK_POOL_MEAN or AK_POOL_CLS");
-    if (S <= 0 || S % 32 || S > MB_MAX_S) AK_FAIL(-1, "ak_mbert_forward_lens: S must be a positive multiple of 32, <= 8192");
-    if (S > d.n_pos) AK_FAIL(-1, "ak_mbert_forward_lens: S exceeds max_position");
-    if (B > 65535) AK_FAIL(-1, "ak_mbert_forward_lens: at most 65535 rows per call");      // a grid dimension of the attention and pooling launches
+    const bool pool_ok = pooling == AK_POOL_MEAN || pooling == AK_POOL_CLS;
+    if (check_forward_lens("ak_mbert_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, MB_MAX_S, d.n_pos,
+                           pool_ok ? nullptr : "pooling must be AK_POOL_MEAN or AK_POOL_CLS", 65535))
+        return -1;
     std::lock_guard<std::mutex> lk(d.mu);
     return mb_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, (hipStream_t)stream);
 }

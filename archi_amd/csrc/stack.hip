@@ -1,0 +1,120 @@
+// stack.hip -- the host side of stack.h: rotary tables, owned device memory and weight preparation, the workspace, the argument
+// checks of the ak_*_forward_lens entry points. No kernels.
+#include <cmath>
+#include <string>
+
+#include "stack.h"
+
+namespace ak {
+
+// ---- RoPE table (host): HF's default rotary embedding in float32 --------------------------------------------------------
+// inv_freq[i] = 1 / theta^(2 i / hd) (the exponent 2 i / hd is exact in float32; the power is rounded once from double),
+// angle = float(pos) * inv_freq[i] (one float32 product, as HF's float32 matmul of a 1-deep product), cos / sin rounded once from
+// double. Table rows [n_pos][hd / 2]: HF's cos / sin are these rows twice (cat(freqs, freqs)).
+// the second half of the routine on given inverse frequencies (ak_decoder_rope_table_inv: a caller that holds HF's own buffer)
+void rope_table_from_inv(const float *inv, int half, int n_pos, float *c, float *s) {
+    for (int p = 0; p < n_pos; p++)
+        for (int i = 0; i < half; i++) {
+            const float ang = (float)p * inv[i];
+            c[(size_t)p * half + i] = (float)std::cos((double)ang);
+            s[(size_t)p * half + i] = (float)std::sin((double)ang);
+        }
+}
+void rope_table_host(float theta, int hd, int n_pos, float *c, float *s) {
+    const int half = hd / 2;
+    std::vector<float> inv(half);
+    for (int i = 0; i < half; i++) {
+        const float e = (float)(2 * i) / (float)hd;
+        inv[i] = 1.0f / (float)std::pow((double)theta, (double)e);
+    }
+    rope_table_from_inv(inv.data(), half, n_pos, c, s);
+}
+
+static bool upload(float *dst, const std::vector<float> &src) {
+    return hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+bool Stack::rope_tables(float theta, int hd, float **c, float **s) {
+    std::vector<float> hc((size_t)n_pos * (hd / 2)), hs(hc.size());
+    rope_table_host(theta, hd, n_pos, hc.data(), hs.data());
+    *c = dev_as<float>(hc.size());
+    *s = dev_as<float>(hs.size());
+    return *c && *s && upload(*c, hc) && upload(*s, hs);
+}
+
+int Stack::rope_tables_set_inv(const float *inv, int half, float *c, float *s) {
+    std::vector<float> hc((size_t)n_pos * half), hs(hc.size());
+    rope_table_from_inv(inv, half, n_pos, hc.data(), hs.data());
+    AK_HIP(hipMemcpy(c, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
+    AK_HIP(hipMemcpy(s, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ---- owned memory and weight preparation ----------------------------------------------------------------------------------
+Stack::~Stack() {
+    for (void *p : owned) hipFree(p);
+}
+
+void *Stack::dev(size_t bytes, bool zero) {
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    owned.push_back(p);
+    if (zero && hipMemset(p, 0, bytes) != hipSuccess) return nullptr;
+    return p;
+}
+
+bool Stack::concat_rows(uint16_t *dst, int H, std::initializer_list<Rows> blocks) {
+    for (const Rows &b : blocks) {
+        if (hipMemcpy(dst, b.p, b.rows * H * 2, hipMemcpyDeviceToDevice) != hipSuccess) return false;
+        dst += b.rows * H;
+    }
+    return true;
+}
+
+bool Stack::interleave_rows(uint16_t *dst, const void *a, const void *b, int I, int H) {
+    return hipMemcpy2D(dst, (size_t)4 * H, a, (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) == hipSuccess &&
+           hipMemcpy2D(dst + H, (size_t)4 * H, b, (size_t)2 * H, (size_t)2 * H, I, hipMemcpyDeviceToDevice) == hipSuccess;
+}
+
+const uint16_t *Stack::pad_cols(const void *w, int H, int I, int Ip) {
+    uint16_t *p = dev_as<uint16_t>((size_t)H * Ip, true);
+    if (!p || hipMemcpy2D(p, (size_t)2 * Ip, w, (size_t)2 * I, (size_t)2 * I, H, hipMemcpyDeviceToDevice) != hipSuccess) return nullptr;
+    return p;
+}
+
+// ---- workspace -------------------------------------------------------------------------------------------------------------
+void Stack::release() {
+    for (Buf &b : bufs) {
+        if (*b.p) hipFree(*b.p);
+        *b.p = nullptr;
+    }
+    cap = 0; cap_B = 0;
+}
+
+int Stack::reserve(int64_t tpad, int B) {
+    if (tpad <= cap && B <= cap_B) return 0;
+    if (tpad < cap) tpad = cap;
+    if (B < cap_B) B = cap_B;
+    release();
+    for (Buf &b : bufs) {
+        const size_t bytes = (size_t)tpad * b.per_token + (size_t)B * b.per_row;
+        AK_HIP(hipMalloc(b.p, bytes));
+        AK_HIP(hipMemset(*b.p, 0, bytes));
+    }
+    cap = tpad; cap_B = B;
+    return 0;
+}
+
+// ---- entry-point checks ------------------------------------------------------------------------------------------------------
+int check_forward_lens(const char *fn, const void *ids, const void *lens, const void *out, int ld_ids, int lens_stride, int B, int S, int max_S,
+                       int n_pos, const char *pooling_error, int max_B) {
+    const std::string f = std::string(fn) + ": ";
+    if (!ids || !lens || !out || ld_ids < S || lens_stride < 1) AK_FAIL(-1, f + "bad arguments");
+    if (pooling_error) AK_FAIL(-1, f + pooling_error);
+    if (S <= 0 || S % 32 || S > max_S) AK_FAIL(-1, f + "S must be a positive multiple of 32, <= " + std::to_string(max_S));
+    if (S > n_pos) AK_FAIL(-1, f + "S exceeds max_position");
+    if (max_B && B > max_B) AK_FAIL(-1, f + "at most " + std::to_string(max_B) + " rows per call");
+    return 0;
+}
+
+}  // namespace ak

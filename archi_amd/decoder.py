@@ -17,7 +17,8 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import AkDecoderConfig, HipBackendError, check
+from ._lib import AkDecoderConfig, check
+from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
 
 MAX_SEQ = 8192          # longest sequence the decoder kernels take (attn_causal.hip)
 HEAD_DIM = 128
@@ -63,18 +64,10 @@ def random_qwen3_weights(shape, seed: int = 0) -> Dict[str, "np.ndarray"]:
     """Seeded random weights of a Qwen3 shape (a QWEN3_SHAPES tuple or name). Matrices are drawn with std 0.02 and ROUNDED TO
     bf16 (kept as float32 values): the released checkpoints are bf16, and a float32 reference on the same values measures the
     kernels' activation rounding alone. Norm weights are drawn around 1, not set to it."""
-    import torch
     if isinstance(shape, str):
         shape = QWEN3_SHAPES[shape]
     vocab, H, L, nq, nkv, I = shape[:6]
-    g = torch.Generator().manual_seed(seed)
-
-    def mat(r, c):
-        return (torch.randn(r, c, generator=g) * 0.02).to(torch.bfloat16).float().numpy()
-
-    def vec(n):
-        return (1.0 + 0.1 * torch.randn(n, generator=g)).numpy().astype(np.float32)
-
+    mat, vec = seeded_mat_vec(seed)
     w = {"embed_tokens": mat(vocab, H), "norm": vec(H)}
     for l in range(L):
         p = f"l{l}."
@@ -126,14 +119,7 @@ def load_qwen3_weights(model_dir: str):
     the header's names). A "model." prefix on the tensor names is stripped. No network."""
     cfg = json.load(open(os.path.join(model_dir, "config.json")))
     shape = qwen3_config_shape(cfg, os.path.join(model_dir, "config.json"))
-    from safetensors.torch import load_file     # torch loader: bf16 checkpoints load too
-    files = sorted(f for f in os.listdir(model_dir) if f.endswith(".safetensors"))
-    if not files:
-        raise FileNotFoundError(f"{model_dir}: no *.safetensors file")
-    sd = {}
-    for f in files:
-        sd.update(load_file(os.path.join(model_dir, f)))
-    sd = {(k[6:] if k.startswith("model.") else k): v for k, v in sd.items()}
+    sd = read_safetensors_dir(model_dir)
     L = shape[2]
     w = {"embed_tokens": sd["embed_tokens.weight"], "norm": sd["norm.weight"]}
     for l in range(L):
@@ -201,78 +187,31 @@ class BpeTokenizer:
         return ids, lens
 
 
-class HipDecoder:
+class HipDecoder(HipStack):
+    family, prefix, embed_key, matrix_keys, abi_pooling = "decoder", "decoder", "embed_tokens", MATRIX_KEYS, False
+
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
         """shape: a QWEN3_SHAPES tuple (vocab, hidden, layers, q_heads, kv_heads, intermediate, max_position, rope_theta, rms_eps);
         weights: the header's names (weight_order), numpy arrays or torch tensors."""
-        import torch
         vocab, H, L, nq, nkv, I, max_pos, theta, eps = shape
-        self._lib = _lib.init(device)
         self.shape = tuple(shape)
-        self.hidden, self.layers, self.vocab = H, L, vocab
+        self.hidden, self.layers, self.vocab, self.out_dim = H, L, vocab, H
         self.max_seq = min(int(max_pos), MAX_SEQ)
-        dev = torch.device("cuda", _lib.bound_device())
-        self._tensors = []
-        ptrs = []
-        for name in weight_order(L):
-            if name not in weights:
-                raise HipBackendError(f"decoder weight {name!r} missing")
-            arr = weights[name]
-            t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
-            is_matrix = name == "embed_tokens" or name.split(".")[-1] in MATRIX_KEYS
-            t = t.to(device=dev, dtype=torch.bfloat16 if is_matrix else torch.float32).contiguous()
-            self._tensors.append(t)
-            ptrs.append(t.data_ptr())
-        cfg = AkDecoderConfig(vocab, H, L, nq, nkv, HEAD_DIM, I, max_pos, eps, theta)
-        arr_t = ctypes.c_void_p * len(ptrs)
-        h = ctypes.c_void_p()
-        torch.cuda.synchronize(dev)
-        check(self._lib.ak_decoder_create(ctypes.byref(cfg), arr_t(*ptrs), len(ptrs), ctypes.byref(h)), "ak_decoder_create")
-        self._h = h
-        self._dev = dev
+        self._upload(weights, weight_order(L), device)
+        self._create(AkDecoderConfig(vocab, H, L, nq, nkv, HEAD_DIM, I, max_pos, eps, theta), weight_order(L))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.ak_decoder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def forward_lens(self, stage, n_rows: int, S: int, out, pooling: str = "last", normalise: bool = True) -> None:
-        """The provider's tile layout, as HipEncoder.forward_lens: `stage` an int32 CUDA tensor [n_rows, S + 1] (S ids per row,
-        the length in column S), `out` a float32 CUDA tensor view [n_rows, hidden]. Decoder models pool the last token only."""
-        import torch
+    def _pooling(self, pooling):
         if pooling != "last":
             raise ValueError(f"pooling {pooling!r}: the decoder implements last-token pooling only")
-        if stage.dtype != torch.int32 or not stage.is_cuda or not stage.is_contiguous() or tuple(stage.shape) != (n_rows, S + 1):
-            raise ValueError("forward_lens: stage must be a contiguous int32 CUDA tensor [n_rows, S + 1]")
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n_rows, self.hidden):
-            raise ValueError("forward_lens: out must be a contiguous float32 CUDA tensor [n_rows, hidden]")
-        if S % 32 or S > self.max_seq:
-            raise ValueError(f"sequence length {S} must be a multiple of 32, <= {self.max_seq}")
-        base = stage.data_ptr()
-        check(self._lib.ak_decoder_forward_lens(self._h, ctypes.c_void_p(base), S + 1, ctypes.c_void_p(base + 4 * S), S + 1, n_rows, S,
-                                                int(normalise), ctypes.c_void_p(out.data_ptr()),
-                                                ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)),
-              "ak_decoder_forward_lens")
+        return pooling
+
+    def forward_lens(self, stage, n_rows: int, S: int, out, pooling: str = "last", normalise: bool = True) -> None:
+        """HipStack.forward_lens with `out` [n_rows, hidden]. Decoder models pool the last token only."""
+        super().forward_lens(stage, n_rows, S, out, pooling=pooling, normalise=normalise)
 
     def forward(self, ids, lens, normalise: bool = True):
         """ids [B, W] (row i holds lens[i] ids), lens [B] -> [B, hidden] float32 CUDA tensor (one tile, S = W rounded up to 32)."""
-        import torch
-        ids = np.asarray(ids, np.int32)
-        B, W = ids.shape
-        S = max(32, (W + 31) // 32 * 32)
-        stage = np.zeros((B, S + 1), np.int32)
-        stage[:, :W] = ids
-        stage[:, S] = np.asarray(lens, np.int32)
-        st = torch.from_numpy(stage).to(self._dev)
-        out = torch.empty((B, self.hidden), dtype=torch.float32, device=self._dev)
-        self.forward_lens(st, B, S, out, pooling="last", normalise=normalise)
-        return out
+        return super().forward(ids, lens, pooling="last", normalise=normalise)
 
 
 def rope_table_inv(inv_freq, n_pos: int):

@@ -24,7 +24,7 @@ import os
 import re
 import threading
 import zlib
-from typing import Any, Dict, List, Optional
+from typing import Any, Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -221,6 +221,47 @@ def _is_xlmr(model_name: str) -> bool:
 ENCODER_MAX_SEQ = 512
 
 
+class _StackFamily(NamedTuple):
+    """What ArchiHipEmbeddings._init_stack needs to know of a pre-norm stack family."""
+    models: str                 # "<models> run in bf16 only"
+    checkpoint: str             # with its article: "Pass <checkpoint> checkpoint directory"
+    tokenizer: str              # "... checkpoint needs its <tokenizer>"
+    shapes: Dict[str, tuple]    # named shapes (synthetic_seed)
+    max_position: int           # index of max_position in a shape tuple (hidden is index 1 in all three)
+    max_seq: int                # longest row the kernels take
+    load: Callable              # checkpoint directory -> (shape, weights)
+    st_config: Callable         # checkpoint directory -> (pooling, max_seq_length | None, always_normalise)
+    random: Callable            # (shape, model_kwargs) -> seeded random weights
+    pooling: Callable           # (model_name, shape, model_kwargs, the checkpoint's pooling | None) -> pooling
+    handle: Callable            # the HipStack subclass
+
+
+def _seed_std(kw):
+    return dict(seed=int(kw["synthetic_seed"]), std=float(kw.get("synthetic_std", 0.02)))
+
+
+def _gemma_pooling(model_name, shape, kw, st_pool):
+    if st_pool is not None and kw.get("pooling", st_pool) != "mean":
+        raise ValueError(f"{model_name}: pooling {kw.get('pooling', st_pool)!r} (Gemma embedders pool 'mean')")
+    return "mean"
+
+
+# Qwen3-Embedding: lasttoken pooling, rows up to 8192 tokens
+_QWEN3 = _StackFamily("decoder models (Qwen3)", "a Qwen3", "byte-level BPE tokenizer", QWEN3_SHAPES, 6, MAX_SEQ, load_qwen3_weights,
+                      lambda d: ("last",) + tuple(read_decoder_st_config(d)),
+                      lambda shape, kw: random_qwen3_weights(shape, seed=int(kw["synthetic_seed"])),
+                      lambda name, shape, kw, st_pool: "last", HipDecoder)
+# ModernBERT (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base, lightonai/modernbert-embed-large): mean or cls pooling
+# as the checkpoint or the named shape says, rows up to 8192 tokens
+_MODERNBERT = _StackFamily("ModernBERT models", "a ModernBERT", "BPE tokenizer", MODERNBERT_SHAPES, 5, MODERNBERT_MAX_SEQ, load_modernbert_weights,
+                           read_sentence_transformers_config, lambda shape, kw: random_modernbert_weights(shape, **_seed_std(kw)),
+                           lambda name, shape, kw, st_pool: kw.get("pooling", st_pool or shape[11]), HipModernBert)
+# EmbeddingGemma (google/embeddinggemma-300m; its tokenizer.json's post-processor adds <bos> / <eos>; the 2_Dense / 3_Dense modules
+# come with the weights): mean pooling, rows up to 2048 tokens
+_GEMMA = _StackFamily("Gemma embedders", "an EmbeddingGemma", "tokenizer", GEMMA_SHAPES, 7, GEMMA_MAX_SEQ, load_gemma_weights,
+                      read_sentence_transformers_config, lambda shape, kw: random_gemma_weights(shape, **_seed_std(kw)), _gemma_pooling, HipGemma)
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -242,15 +283,10 @@ class ArchiHipEmbeddings:
         device = int(dev.split(":")[1]) if ":" in dev else None
         self._stage = self._stage_out = None
         self._stage_lock = threading.Lock()
-        if _is_qwen3(model_name):
-            self._init_decoder(model_name, device)
-            return
-        if _is_modernbert(model_name):
-            self._init_modernbert(model_name, device)
-            return
-        if _is_gemma(model_name):
-            self._init_gemma(model_name, device)
-            return
+        for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA)):
+            if is_family(model_name):
+                self._init_stack(family, model_name, device)
+                return
         rel_bias = pos_pad = None
         if _is_xlmr(model_name):
             vocab, H, L, heads, I, max_pos, weights, eps, pos_pad = self._init_xlmr(model_name)
@@ -369,103 +405,36 @@ class ArchiHipEmbeddings:
                                     "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
         return vocab, H, L, heads, I, max_pos, weights, eps, mpnet_rel_bias_table(rel_w, max_pos)
 
-    def _init_decoder(self, model_name: str, device: Optional[int]) -> None:
-        """Qwen3-Embedding: a local checkpoint directory (config.json model_type qwen3, safetensors, tokenizer.json, the
-        sentence-transformers files with lasttoken pooling) or a named shape with synthetic_seed. bf16 only."""
+    def _init_stack(self, fam: "_StackFamily", model_name: str, device: Optional[int]) -> None:
+        """A pre-norm stack (Qwen3-Embedding, ModernBERT, EmbeddingGemma; the _StackFamily records below): a local checkpoint
+        directory (config.json of the family's model_type, safetensors, tokenizer.json, the sentence-transformers files) or a named
+        shape with synthetic_seed. bf16 only. Query / document prompts stay with the caller, as the reference's retrievers handle
+        instructions themselves."""
         precision = str(self.model_kwargs.get("precision", "bf16"))
         if precision != "bf16":
-            raise ValueError(f"precision {precision!r}: decoder models (Qwen3) run in bf16 only")
-        self.pooling = "last"
-        if os.path.isdir(model_name):
-            shape, weights = load_qwen3_weights(model_name)
-            st_len, st_norm = read_decoder_st_config(model_name)
-            tf = os.path.join(model_name, "tokenizer.json")
-            if not os.path.exists(tf):
-                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- a Qwen3 checkpoint needs its byte-level BPE tokenizer")
-            self.tokenizer = BpeTokenizer(tf)
-            self.normalize = self.normalize or st_norm
-        else:
-            if "synthetic_seed" not in self.model_kwargs:
-                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass a Qwen3 checkpoint "
-                                        "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
-            shape = QWEN3_SHAPES[model_name]
-            weights = random_qwen3_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]))
-            st_len = None
-            self.normalize = True                      # the released models carry a Normalize module
-            tf = self.model_kwargs.get("tokenizer_file")
-            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
-        max_pos = int(shape[6])
-        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, MAX_SEQ)
-        self.dimensions = int(shape[1])
-        self.encoder = HipDecoder(shape, weights, device=device)
-
-    def _init_modernbert(self, model_name: str, device: Optional[int]) -> None:
-        """ModernBERT (nomic-ai/modernbert-embed-base, Alibaba-NLP/gte-modernbert-base, lightonai/modernbert-embed-large): a local
-        checkpoint directory (config.json model_type modernbert, safetensors, tokenizer.json, the sentence-transformers files) or
-        a named shape with synthetic_seed. bf16 only; rows up to 8192 tokens. Query / document prompts ("search_query: ") stay
-        with the caller, as the reference's retrievers handle instructions themselves."""
-        precision = str(self.model_kwargs.get("precision", "bf16"))
-        if precision != "bf16":
-            raise ValueError(f"precision {precision!r}: ModernBERT models run in bf16 only")
+            raise ValueError(f"precision {precision!r}: {fam.models} run in bf16 only")
         if os.path.isdir(model_name):
             tf = os.path.join(model_name, "tokenizer.json")
             if not os.path.exists(tf):
-                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- a ModernBERT checkpoint needs its BPE tokenizer")
-            shape, weights = load_modernbert_weights(model_name)
-            st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
-            self.pooling = self.model_kwargs.get("pooling", st_pool)
+                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- {fam.checkpoint} checkpoint needs its {fam.tokenizer}")
+            shape, weights = fam.load(model_name)
+            st_pool, st_len, st_norm = fam.st_config(model_name)
             self.normalize = self.normalize or st_norm
             self.tokenizer = BpeTokenizer(tf)
         else:
             if "synthetic_seed" not in self.model_kwargs:
-                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass a ModernBERT checkpoint "
+                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass {fam.checkpoint} checkpoint "
                                         "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
-            shape = MODERNBERT_SHAPES[model_name]
-            weights = random_modernbert_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]),
-                                                std=float(self.model_kwargs.get("synthetic_std", 0.02)))
-            st_len = None
-            self.pooling = self.model_kwargs.get("pooling", shape[11])
+            shape = fam.shapes[model_name]
+            weights = fam.random(shape, self.model_kwargs)
+            st_pool, st_len = None, None
             self.normalize = True                      # the released sentence-transformers models carry a Normalize module
             tf = self.model_kwargs.get("tokenizer_file")
             self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
-        max_pos = int(shape[5])
-        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, MODERNBERT_MAX_SEQ)
-        self.dimensions = int(shape[1])
-        self.encoder = HipModernBert(shape, weights, device=device)
-
-    def _init_gemma(self, model_name: str, device: Optional[int]) -> None:
-        """EmbeddingGemma (google/embeddinggemma-300m): a local checkpoint directory (config.json model_type gemma3_text with
-        use_bidirectional_attention, safetensors, tokenizer.json -- its post-processor adds <bos> / <eos> --, the sentence-transformers
-        files with the 2_Dense / 3_Dense modules) or a named shape with synthetic_seed. bf16 only, mean pooling, rows up to 2048
-        tokens. Prompts ("task: search result | query: ") stay with the caller."""
-        precision = str(self.model_kwargs.get("precision", "bf16"))
-        if precision != "bf16":
-            raise ValueError(f"precision {precision!r}: Gemma embedders run in bf16 only")
-        if os.path.isdir(model_name):
-            tf = os.path.join(model_name, "tokenizer.json")
-            if not os.path.exists(tf):
-                raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- an EmbeddingGemma checkpoint needs its tokenizer")
-            shape, weights = load_gemma_weights(model_name)
-            st_pool, st_len, st_norm = read_sentence_transformers_config(model_name)
-            if self.model_kwargs.get("pooling", st_pool) != "mean":
-                raise ValueError(f"{model_name}: pooling {self.model_kwargs.get('pooling', st_pool)!r} (Gemma embedders pool 'mean')")
-            self.normalize = self.normalize or st_norm
-            self.tokenizer = BpeTokenizer(tf)
-        else:
-            if "synthetic_seed" not in self.model_kwargs:
-                raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass an EmbeddingGemma checkpoint "
-                                        "directory, or model_kwargs={'synthetic_seed': N} for seeded random weights")
-            shape = GEMMA_SHAPES[model_name]
-            weights = random_gemma_weights(shape, seed=int(self.model_kwargs["synthetic_seed"]),
-                                           std=float(self.model_kwargs.get("synthetic_std", 0.02)))
-            st_len = None
-            self.normalize = True                      # the released sentence-transformers model carries a Normalize module
-            tf = self.model_kwargs.get("tokenizer_file")
-            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
-        self.pooling = "mean"
-        max_pos = int(shape[7])
-        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, GEMMA_MAX_SEQ)
-        self.encoder = HipGemma(shape, weights, device=device)
+        self.pooling = fam.pooling(model_name, shape, self.model_kwargs, st_pool)
+        max_pos = int(shape[fam.max_position])
+        self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, fam.max_seq)
+        self.encoder = fam.handle(shape, weights, device=device)
         self.dimensions = int(self.encoder.out_dim)
 
     # -- LangChain Embeddings duck type -------------------------------------

@@ -15,8 +15,8 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import _lib
-from ._lib import GEMMA_MAX_LAYERS, POOLING, AkGemmaConfig, HipBackendError, check
+from ._lib import GEMMA_MAX_LAYERS, AkGemmaConfig, check
+from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
 
 MAX_SEQ = 2048          # longest row the kernels take (attn_gqa.hip)
 HEAD_DIM = 256
@@ -78,18 +78,10 @@ def random_gemma_weights(shape, seed: int = 0, std: float = 0.02) -> Dict[str, "
     """Seeded random weights of a Gemma shape (a GEMMA_SHAPES tuple or name). Matrices are drawn with `std` and ROUNDED TO bf16 (kept
     as float32 values), as random_modernbert_weights does: a float32 reference on the same values measures the kernels' activation
     rounding alone. Norm weights are drawn around 0 (the model multiplies by 1 + w). Dense matrices are drawn with std in ** -0.5."""
-    import torch
     if isinstance(shape, str):
         shape = GEMMA_SHAPES[shape]
     vocab, H, L, nq, nkv, hd, I = shape[:7]
-    g = torch.Generator().manual_seed(seed)
-
-    def mat(r, c, s=std):
-        return (torch.randn(r, c, generator=g) * s).to(torch.bfloat16).float().numpy()
-
-    def vec(n):
-        return (0.1 * torch.randn(n, generator=g)).numpy().astype(np.float32)
-
+    mat, vec = seeded_mat_vec(seed, std, vec_mean=0.0)
     w = {"embed": mat(vocab, H), "final_norm": vec(H)}
     for l in range(L):
         p = f"l{l}."
@@ -241,14 +233,7 @@ def load_gemma_weights(model_dir: str):
     cfg = json.load(open(os.path.join(model_dir, "config.json")))
     dense = read_dense_modules(model_dir)
     shape = gemma_config_shape(cfg, os.path.join(model_dir, "config.json"), dense=[d.shape[0] for d in dense])
-    from safetensors.torch import load_file     # torch loader: bf16 checkpoints load too
-    files = sorted(f for f in os.listdir(model_dir) if f.endswith(".safetensors"))
-    if not files:
-        raise FileNotFoundError(f"{model_dir}: no *.safetensors file")
-    sd = {}
-    for f in files:
-        sd.update(load_file(os.path.join(model_dir, f)))
-    sd = {(k[6:] if k.startswith("model.") else k): v for k, v in sd.items()}
+    sd = read_safetensors_dir(model_dir)
     w = {"embed": sd["embed_tokens.weight"], "final_norm": sd["norm.weight"]}
     for l in range(shape[2]):
         for k, hf in HF_LAYER_NAMES.items():
@@ -278,11 +263,12 @@ def geglu_tanh_interleaved(y: "np.ndarray") -> "np.ndarray":
     return (a * g / (1.0 + np.exp(-2.0 * u))).astype(np.float32)
 
 
-class HipGemma:
+class HipGemma(HipStack):
+    family, prefix, embed_key, matrix_keys, out_name = "Gemma", "gemma", "embed", MATRIX_KEYS, "out_dim"
+
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None, dense: bool = True):
         """shape: a GEMMA_SHAPES tuple or name; weights: our names (weight_names), numpy arrays or torch tensors. dense=False leaves
         the Dense head out (the plain Gemma3 text model, mean pooled)."""
-        import torch
         if isinstance(shape, str):
             shape = GEMMA_SHAPES[shape]
         vocab, H, L, nq, nkv, hd, I, max_pos, eps, theta_g, theta_l, window, qpas, types, dense_out = shape
@@ -292,83 +278,26 @@ class HipGemma:
             raise ValueError(f"Gemma shape: {L} layers with {len(types)} layer types (at most {GEMMA_MAX_LAYERS} layers)")
         if len(dense_out) > 2:
             raise ValueError(f"Gemma shape: {len(dense_out)} Dense modules (at most 2)")
-        self._lib = _lib.init(device)
         self.shape = tuple(shape)
         self.hidden, self.layers, self.vocab, self.pooling = H, L, vocab, "mean"
         self.out_dim = dense_out[-1] if dense_out else H
         self.max_seq = min(int(max_pos), MAX_SEQ)
-        dev = torch.device("cuda", _lib.bound_device())
-        self._tensors = {}
         names = weight_names(L, len(dense_out))
-        for name in names:
-            if name not in weights:
-                raise HipBackendError(f"Gemma weight {name!r} missing")
-            arr = weights[name]
-            t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
-            is_matrix = name == "embed" or name.split(".")[-1] in MATRIX_KEYS
-            self._tensors[name] = t.to(device=dev, dtype=torch.bfloat16 if is_matrix else torch.float32).contiguous()
+        self._upload(weights, names, device)
         din = H
         for i, dout in enumerate(dense_out):
             if tuple(self._tensors[f"dense{i}"].shape) != (dout, din):
                 raise ValueError(f"Gemma weight dense{i}: shape {tuple(self._tensors[f'dense{i}'].shape)}, expected {(dout, din)}")
             din = dout
-        ptrs = [self._tensors[n].data_ptr() for n in names]
-        self._ptrs = ptrs
-        cfg = AkGemmaConfig(vocab, H, L, nq, nkv, hd, I, max_pos, eps, theta_g, theta_l, float(qpas), window // 2, 0.0, 0.0, 0, 0, 0, len(dense_out),
-                            (ctypes.c_int * 2)(*(list(dense_out) + [0, 0])[:2]), (ctypes.c_int * GEMMA_MAX_LAYERS)(*types))
-        self._cfg = cfg
-        h = ctypes.c_void_p()
-        torch.cuda.synchronize(dev)
-        arr_t = ctypes.c_void_p * len(ptrs)
-        check(self._lib.ak_gemma_create(ctypes.byref(cfg), arr_t(*ptrs), len(ptrs), ctypes.byref(h)), "ak_gemma_create")
-        self._h = h
-        self._dev = dev
+        self._create(AkGemmaConfig(vocab, H, L, nq, nkv, hd, I, max_pos, eps, theta_g, theta_l, float(qpas), window // 2, 0.0, 0.0, 0, 0, 0,
+                                   len(dense_out), (ctypes.c_int * 2)(*(list(dense_out) + [0, 0])[:2]), (ctypes.c_int * GEMMA_MAX_LAYERS)(*types)),
+                     names)
         # the rotary tables from HF's own inverse frequencies (rope_inv_freq) in place of the library's correctly rounded ones
         self._inv_freq = (rope_inv_freq(theta_g), rope_inv_freq(theta_l))
-        check(self._lib.ak_gemma_set_rope_inv_freq(h, self._inv_freq[0].ctypes.data, self._inv_freq[1].ctypes.data), "ak_gemma_set_rope_inv_freq")
+        check(self._lib.ak_gemma_set_rope_inv_freq(self._h, self._inv_freq[0].ctypes.data, self._inv_freq[1].ctypes.data), "ak_gemma_set_rope_inv_freq")
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.ak_gemma_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def forward_lens(self, stage, n_rows: int, S: int, out, pooling: Optional[str] = None, normalise: bool = True) -> None:
-        """The provider's tile layout, as HipModernBert.forward_lens: `stage` an int32 CUDA tensor [n_rows, S + 1] (S ids per row,
-        the length in column S), `out` a float32 CUDA tensor view [n_rows, out_dim]."""
-        import torch
+    def _pooling(self, pooling):
         pooling = pooling or self.pooling
         if pooling != "mean":
             raise ValueError(f"pooling {pooling!r}: Gemma embedders pool 'mean'")
-        if stage.dtype != torch.int32 or not stage.is_cuda or not stage.is_contiguous() or tuple(stage.shape) != (n_rows, S + 1):
-            raise ValueError("forward_lens: stage must be a contiguous int32 CUDA tensor [n_rows, S + 1]")
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n_rows, self.out_dim):
-            raise ValueError("forward_lens: out must be a contiguous float32 CUDA tensor [n_rows, out_dim]")
-        if S % 32 or S > self.max_seq:
-            raise ValueError(f"sequence length {S} must be a multiple of 32, <= {self.max_seq}")
-        base = stage.data_ptr()
-        check(self._lib.ak_gemma_forward_lens(self._h, ctypes.c_void_p(base), S + 1, ctypes.c_void_p(base + 4 * S), S + 1, n_rows, S,
-                                              POOLING[pooling], int(normalise), ctypes.c_void_p(out.data_ptr()),
-                                              ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)),
-              "ak_gemma_forward_lens")
-
-    def forward(self, ids, lens, pooling: Optional[str] = None, normalise: bool = True, S: Optional[int] = None):
-        """ids [B, W] (row i holds lens[i] ids), lens [B] -> [B, out_dim] float32 CUDA tensor (one tile, S = W rounded up to 32
-        unless given)."""
-        import torch
-        ids = np.asarray(ids, np.int32)
-        B, W = ids.shape
-        if S is None:
-            S = max(32, (W + 31) // 32 * 32)
-        stage = np.zeros((B, S + 1), np.int32)
-        stage[:, :min(W, S)] = ids[:, :S]
-        stage[:, S] = np.asarray(lens, np.int32)
-        st = torch.from_numpy(stage).to(self._dev)
-        out = torch.empty((B, self.out_dim), dtype=torch.float32, device=self._dev)
-        self.forward_lens(st, B, S, out, pooling=pooling, normalise=normalise)
-        return out
+        return pooling

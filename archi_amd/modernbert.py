@@ -15,8 +15,8 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import _lib
-from ._lib import MBERT_MAX_LAYERS, POOLING, AkModernBertConfig, HipBackendError, check
+from ._lib import MBERT_MAX_LAYERS, POOLING, AkModernBertConfig
+from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
 
 MAX_SEQ = 8192          # longest row the kernels take (attn_long.hip)
 HEAD_DIM = 64
@@ -75,18 +75,10 @@ def random_modernbert_weights(shape, seed: int = 0, std: float = 0.02) -> Dict[s
     """Seeded random weights of a ModernBERT shape (a MODERNBERT_SHAPES tuple or name). Matrices are drawn with `std` and ROUNDED
     TO bf16 (kept as float32 values), as random_qwen3_weights does: a float32 reference on the same values measures the kernels'
     activation rounding alone. Norm weights are drawn around 1, not set to it."""
-    import torch
     if isinstance(shape, str):
         shape = MODERNBERT_SHAPES[shape]
     vocab, H, L, heads, I = shape[:5]
-    g = torch.Generator().manual_seed(seed)
-
-    def mat(r, c):
-        return (torch.randn(r, c, generator=g) * std).to(torch.bfloat16).float().numpy()
-
-    def vec(n):
-        return (1.0 + 0.1 * torch.randn(n, generator=g)).numpy().astype(np.float32)
-
+    mat, vec = seeded_mat_vec(seed, std)
     w = {"tok_embeddings": mat(vocab, H), "emb_norm": vec(H), "final_norm": vec(H)}
     for l in range(L):
         p = f"l{l}."
@@ -176,14 +168,7 @@ def load_modernbert_weights(model_dir: str):
     our names). A "model." prefix on the tensor names is stripped; heads of a masked-LM checkpoint are ignored. No network."""
     cfg = json.load(open(os.path.join(model_dir, "config.json")))
     shape = modernbert_config_shape(cfg, os.path.join(model_dir, "config.json"))
-    from safetensors.torch import load_file     # torch loader: bf16 checkpoints load too
-    files = sorted(f for f in os.listdir(model_dir) if f.endswith(".safetensors"))
-    if not files:
-        raise FileNotFoundError(f"{model_dir}: no *.safetensors file")
-    sd = {}
-    for f in files:
-        sd.update(load_file(os.path.join(model_dir, f)))
-    sd = {(k[6:] if k.startswith("model.") else k): v for k, v in sd.items()}
+    sd = read_safetensors_dir(model_dir)
     L = shape[2]
     w = {"tok_embeddings": sd["embeddings.tok_embeddings.weight"], "emb_norm": sd["embeddings.norm.weight"],
          "final_norm": sd["final_norm.weight"]}
@@ -213,84 +198,28 @@ def geglu_interleaved(y: "np.ndarray") -> "np.ndarray":
     return (0.5 * a * (1.0 + erf) * g).astype(np.float32)
 
 
-class HipModernBert:
+class HipModernBert(HipStack):
+    family, prefix, embed_key, matrix_keys = "ModernBERT", "mbert", "tok_embeddings", MATRIX_KEYS
+
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
         """shape: a MODERNBERT_SHAPES tuple or name; weights: our names (weight_names), numpy arrays or torch tensors."""
-        import torch
         if isinstance(shape, str):
             shape = MODERNBERT_SHAPES[shape]
         vocab, H, L, heads, I, max_pos, eps, theta_g, theta_l, local, types, pooling = shape
         if L > MBERT_MAX_LAYERS or len(types) != L:
             raise ValueError(f"ModernBERT shape: {L} layers with {len(types)} layer types (at most {MBERT_MAX_LAYERS} layers)")
-        self._lib = _lib.init(device)
         self.shape = tuple(shape)
-        self.hidden, self.layers, self.vocab, self.pooling = H, L, vocab, pooling
+        self.hidden, self.layers, self.vocab, self.pooling, self.out_dim = H, L, vocab, pooling, H
         self.max_seq = min(int(max_pos), MAX_SEQ)
-        dev = torch.device("cuda", _lib.bound_device())
-        self._tensors = {}
-        for name in weight_names(L):
-            if name not in weights:
-                raise HipBackendError(f"ModernBERT weight {name!r} missing")
-            arr = weights[name]
-            t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
-            is_matrix = name == "tok_embeddings" or name.split(".")[-1] in MATRIX_KEYS
-            self._tensors[name] = t.to(device=dev, dtype=torch.bfloat16 if is_matrix else torch.float32).contiguous()
-        ptrs = [self._tensors[n].data_ptr() for n in ("tok_embeddings", "emb_norm", "final_norm")]
-        for l in range(L):
-            for k in LAYER_KEYS:        # layer 0's attn_norm is the identity: the library does not read the pointer
-                ptrs.append(self._tensors["emb_norm" if (l == 0 and k == "attn_norm") else f"l{l}.{k}"].data_ptr())
-        self._ptrs = ptrs
-        cfg = AkModernBertConfig(vocab, H, L, heads, I, max_pos, eps, theta_g, theta_l, local // 2, (ctypes.c_int * MBERT_MAX_LAYERS)(*types))
-        self._cfg = cfg
-        h = ctypes.c_void_p()
-        torch.cuda.synchronize(dev)
-        arr_t = ctypes.c_void_p * len(ptrs)
-        check(self._lib.ak_mbert_create(ctypes.byref(cfg), arr_t(*ptrs), len(ptrs), ctypes.byref(h)), "ak_mbert_create")
-        self._h = h
-        self._dev = dev
+        self._upload(weights, weight_names(L), device)
+        ptr_names = ["tok_embeddings", "emb_norm", "final_norm"]
+        for l in range(L):              # layer 0's attn_norm is the identity: the library does not read the pointer
+            ptr_names += ["emb_norm" if (l == 0 and k == "attn_norm") else f"l{l}.{k}" for k in LAYER_KEYS]
+        self._create(AkModernBertConfig(vocab, H, L, heads, I, max_pos, eps, theta_g, theta_l, local // 2, (ctypes.c_int * MBERT_MAX_LAYERS)(*types)),
+                     ptr_names)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.ak_mbert_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def forward_lens(self, stage, n_rows: int, S: int, out, pooling: Optional[str] = None, normalise: bool = True) -> None:
-        """The provider's tile layout, as HipEncoder.forward_lens: `stage` an int32 CUDA tensor [n_rows, S + 1] (S ids per row,
-        the length in column S), `out` a float32 CUDA tensor view [n_rows, hidden]."""
-        import torch
+    def _pooling(self, pooling):
         pooling = pooling or self.pooling
         if pooling not in POOLING:
             raise ValueError(f"pooling {pooling!r}: ModernBERT models pool 'mean' or 'cls'")
-        if stage.dtype != torch.int32 or not stage.is_cuda or not stage.is_contiguous() or tuple(stage.shape) != (n_rows, S + 1):
-            raise ValueError("forward_lens: stage must be a contiguous int32 CUDA tensor [n_rows, S + 1]")
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n_rows, self.hidden):
-            raise ValueError("forward_lens: out must be a contiguous float32 CUDA tensor [n_rows, hidden]")
-        if S % 32 or S > self.max_seq:
-            raise ValueError(f"sequence length {S} must be a multiple of 32, <= {self.max_seq}")
-        base = stage.data_ptr()
-        check(self._lib.ak_mbert_forward_lens(self._h, ctypes.c_void_p(base), S + 1, ctypes.c_void_p(base + 4 * S), S + 1, n_rows, S,
-                                              POOLING[pooling], int(normalise), ctypes.c_void_p(out.data_ptr()),
-                                              ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)),
-              "ak_mbert_forward_lens")
-
-    def forward(self, ids, lens, pooling: Optional[str] = None, normalise: bool = True, S: Optional[int] = None):
-        """ids [B, W] (row i holds lens[i] ids), lens [B] -> [B, hidden] float32 CUDA tensor (one tile, S = W rounded up to 32
-        unless given)."""
-        import torch
-        ids = np.asarray(ids, np.int32)
-        B, W = ids.shape
-        if S is None:
-            S = max(32, (W + 31) // 32 * 32)
-        stage = np.zeros((B, S + 1), np.int32)
-        stage[:, :min(W, S)] = ids[:, :S]
-        stage[:, S] = np.asarray(lens, np.int32)
-        st = torch.from_numpy(stage).to(self._dev)
-        out = torch.empty((B, self.hidden), dtype=torch.float32, device=self._dev)
-        self.forward_lens(st, B, S, out, pooling=pooling, normalise=normalise)
-        return out
+        return pooling

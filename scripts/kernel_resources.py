@@ -1,25 +1,65 @@
-"""Compile one .hip file of archi_amd/csrc for gfx950 with -Rpass-analysis=kernel-resource-usage and print one line per
-kernel: VGPRs, spills, scratch, SGPRs, occupancy (demangled names). python scripts/kernel_resources.py scan.hip [filter]"""
-import os, re, subprocess, sys
-root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1]; flt = sys.argv[2] if len(sys.argv) > 2 else ""
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-       "-Wno-inline-asm", "-c", src, "-o", "/tmp/_kres.o", "-Rpass-analysis=kernel-resource-usage"]
-p = subprocess.run(cmd, cwd=os.path.join(root, "archi_amd", "csrc"), stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
-if p.returncode:
-    print(p.stderr[-4000:]); sys.exit(1)
-cur = None; rows = []
-for ln in p.stderr.splitlines():
-    m = re.search(r"remark:\s+(.*?) \[-Rpass", ln)
-    if not m: continue
-    t = m.group(1).strip()
-    if t.startswith("Function Name:"):
-        cur = {"name": t.split(":", 1)[1].strip()}; rows.append(cur)
-    elif cur is not None and ":" in t:
-        k, v = t.split(":", 1); cur[k.strip()] = v.strip()
-names = subprocess.run(["/usr/bin/c++filt"] + [r["name"] for r in rows], stdout=subprocess.PIPE, text=True).stdout.splitlines()
-for r, n in zip(rows, names):
-    n = re.sub(r"\(.*", "", n)
-    if flt and flt not in n: continue
-    print(f"{n[:110]:110s} vgpr {r.get('VGPRs','?'):>3} agpr {r.get('AGPRs','?'):>3} vspill {r.get('VGPRs Spill','?'):>3} scratch {r.get('ScratchSize [bytes/lane]','?'):>4} "
-          f"sgpr {r.get('TotalSGPRs','?'):>3} sspill {r.get('SGPRs Spill','?'):>3} occ {r.get('Occupancy [waves/SIMD]','?')}")
+"""Per-kernel resource usage of one .hip file of archi_amd/csrc, compiled for gfx950 with the Makefile's FLAGS and
+-Rpass-analysis=kernel-resource-usage (no GPU needed).
+
+    from scripts.kernel_resources import kernel_resources
+    kernel_resources("mbert.hip") -> {mangled kernel name: {"VGPRs": .., "AGPRs": .., "VGPRs Spill": .., "SGPRs Spill": ..,
+                                      "ScratchSize [bytes/lane]": .., "LDS Size [bytes/block]": .., "Occupancy [waves/SIMD]": .., ...}}
+
+    python scripts/kernel_resources.py scan.hip [filter]      one line per kernel, demangled names
+"""
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "archi_amd", "csrc")
+HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+
+
+def makefile_flags():
+    """FLAGS of archi_amd/csrc/Makefile, $(ARCH) expanded."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    arch = re.search(r"^ARCH\s*:=\s*(\S+)", mk, re.M).group(1)
+    return re.search(r"^FLAGS\s*:=\s*(.*)$", mk, re.M).group(1).replace("$(ARCH)", arch).split()
+
+
+def kernel_resources(src, csrc=CSRC):
+    """src: a file name in `csrc` (or a path) -> {kernel: {field: value}}; every integer field of the compiler's remark, under the
+    compiler's names. Raises RuntimeError with the compiler's output when the file does not compile."""
+    r = subprocess.run([HIPCC] + makefile_flags() + ["--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
+                                                     os.path.join(csrc, src)], capture_output=True, text=True, cwd=csrc)
+    if r.returncode:
+        raise RuntimeError(f"{src}: hipcc failed\n{r.stderr[-4000:]}")
+    out, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+(.*?) \[-Rpass", line)
+        if not m:
+            continue
+        key, _, value = m.group(1).strip().partition(":")
+        if key == "Function Name":
+            cur = out.setdefault(value.strip(), {})
+        elif cur is not None and re.fullmatch(r"\s*\d+", value):
+            cur[key.strip()] = int(value)
+    return out
+
+
+def main():
+    src, flt = sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else ""
+    try:
+        res = kernel_resources(src)
+    except RuntimeError as e:
+        print(e)
+        sys.exit(1)
+    names = subprocess.run(["c++filt"] + list(res), stdout=subprocess.PIPE, text=True).stdout.splitlines()
+    for (_, r), n in zip(res.items(), names):
+        n = re.sub(r"\(.*", "", n)
+        if flt and flt not in n:
+            continue
+        print(f"{n[:110]:110s} vgpr {r.get('VGPRs', '?'):>3} agpr {r.get('AGPRs', '?'):>3} vspill {r.get('VGPRs Spill', '?'):>3} "
+              f"scratch {r.get('ScratchSize [bytes/lane]', '?'):>4} sgpr {r.get('TotalSGPRs', '?'):>3} sspill {r.get('SGPRs Spill', '?'):>3} "
+              f"lds {r.get('LDS Size [bytes/block]', '?'):>5} occ {r.get('Occupancy [waves/SIMD]', '?')}")
+
+
+if __name__ == "__main__":
+    main()

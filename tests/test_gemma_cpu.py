@@ -335,31 +335,14 @@ PARENT_VGPRS = {"k_gemmILi8ELi256ELb1ELb0E": 244, "k_gemmILi8ELi128ELb0ELb0E": 1
                 "k_attn_causalE": 154}
 
 
-def _resource_usage(src):
-    csrc = os.path.join(ROOT, "archi_amd", "csrc")
-    flags = re.search(r"^FLAGS\s*:=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
-                                          os.path.join(csrc, src)], capture_output=True, text=True, cwd=csrc)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(VGPRs|AGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            out.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return out
-
-
 def test_new_kernels_do_not_spill_and_the_old_ones_did_not_move():
     """-Rpass-analysis=kernel-resource-usage with the Makefile's flags: every kernel of gemma.hip, every instantiation of k_attn_gqa and
     both k_gemm MODE 9 instantiations report no spilled register and no scratch; k_attn_gqa holds 65 536 bytes of LDS; the k_gemm MODE 8,
     k_attn_long and k_attn_causal instantiations report the VGPR counts of the parent commit."""
+    from scripts.kernel_resources import kernel_resources
     srcs = ("gemma.hip", "attn_gqa.hip", "gemm.hip", "attn_long.hip", "attn_causal.hip")
     with concurrent.futures.ThreadPoolExecutor(max_workers=len(srcs)) as pool:
-        use = dict(zip(srcs, pool.map(_resource_usage, srcs)))
+        use = dict(zip(srcs, pool.map(kernel_resources, srcs)))
     new = {n: u for n, u in use["gemma.hip"].items() if "k_gm_" in n}
     new.update({n: u for n, u in use["attn_gqa.hip"].items() if "k_attn_gqa" in n})
     new.update({n: u for n, u in use["gemm.hip"].items() if "k_gemmILi9E" in n})

@@ -172,24 +172,11 @@ def test_device_bm25_refuses_an_index_without_lexical_entry_points():
 def test_lexical_kernels_have_no_spills_and_no_scratch():
     """-Rpass-analysis=kernel-resource-usage on lexical.hip with the library's flags: every kernel of the file reports 0 spilled
     registers and 0 bytes of scratch."""
-    csrc = os.path.join(ROOT, "archi_amd", "csrc")
-    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    if not os.path.exists(hipcc):
+    from scripts.kernel_resources import HIPCC, kernel_resources
+    if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I", csrc,
-                        "-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-c", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(csrc, "lexical.hip")], capture_output=True, text=True, cwd=csrc)
-    assert r.returncode == 0, r.stderr[-2000:]
-    seen, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            seen[name] = {}
-        for key in ("SGPRs Spill", "VGPRs Spill", r"ScratchSize \[bytes/lane\]"):
-            m = re.search(key + r": (\d+)", line)
-            if m and name:
-                seen[name][key] = int(m.group(1))
+    keys = ("SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]")
+    seen = {name: {key: use[key] for key in keys if key in use} for name, use in kernel_resources("lexical.hip").items()}
     kernels = ("k_lex_stats", "k_lex_compact", "k_lex_also", "k_lex_score", "k_lex_combine", "k_lex_emit", "k_lex_gather", "k_lex_scatter")
     assert all(any(k in n for n in seen) for k in kernels) and len(seen) == len(kernels), sorted(seen)
     for n, res in seen.items():

@@ -245,23 +245,12 @@ def test_fixture_is_reproduced_and_can_see_the_features(name):
 def test_new_kernels_do_not_spill():
     """-Rpass-analysis=kernel-resource-usage with the Makefile's flags: every kernel of mbert.hip, both instantiations of k_attn_long
     and every k_gemm MODE 8 instantiation report no spilled VGPRs and no scratch."""
-    import subprocess
-    csrc = os.path.join(ROOT, "archi_amd", "csrc")
-    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    from scripts.kernel_resources import kernel_resources
     seen = {}
     for src, pat in (("mbert.hip", r"k_mb_"), ("attn_long.hip", r"k_attn_long"), ("gemm.hip", r"k_gemmILi8E")):
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-inline-asm",
-                            "--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
-                            os.path.join(csrc, src)], capture_output=True, text=True, cwd=csrc)
-        assert r.returncode == 0, r.stderr[-2000:]
-        name = None
-        for line in r.stderr.splitlines():
-            m = re.search(r"Function Name: (\S+)", line)
-            if m:
-                name = m.group(1)
-            m = re.search(r"(VGPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
-            if m and name and re.search(pat, name):
-                seen[(name, m.group(1))] = int(m.group(2))
+        for name, use in kernel_resources(src).items():
+            if re.search(pat, name):
+                seen.update({(name, key): use[key] for key in ("VGPRs Spill", "ScratchSize [bytes/lane]")})
     names = {n for n, _ in seen}
     for k in ("k_mb_embed", "k_mb_add_ln", "k_mb_rope", "k_mb_pool_part", "k_mb_pool_fin", "k_attn_longILb1E", "k_attn_longILb0E",
               "k_gemmILi8ELi256ELb1E", "k_gemmILi8ELi128ELb0E"):

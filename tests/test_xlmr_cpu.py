@@ -5,7 +5,6 @@ that the fixtures' positions matter, and a compile check that the kernels the fe
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -212,23 +211,13 @@ def test_embedding_dimensions_and_routing():
 def test_touched_kernels_do_not_spill():
     """-Rpass-analysis=kernel-resource-usage on encoder.hip and encoder_f32.hip: k_positions and every embedding kernel that reads
     the position rows report `VGPRs Spill: 0` (and no scratch)."""
-    csrc = os.path.join(ROOT, "archi_amd", "csrc")
-    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    if not os.path.exists(hipcc):
+    from scripts.kernel_resources import HIPCC, kernel_resources
+    if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
     seen = {}
     for src in ("encoder.hip", "encoder_f32.hip", "attn_long.hip"):
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", csrc, "-I", os.path.join(ROOT, "include"),
-                            "--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
-                            os.path.join(csrc, src)], capture_output=True, text=True, cwd=csrc)
-        assert r.returncode == 0, r.stderr[-2000:]
-        name = None
-        for line in r.stderr.splitlines():
-            m = re.search(r"Function Name: (\S+)", line)
-            if m:
-                name = m.group(1)
-            m = re.search(r"VGPRs Spill: (\d+)", line)
-            if m and name and re.search(r"k_positions|k_embed|k32_embed|k3_embed|k_attn_long|k_pool", name):
-                seen[name] = int(m.group(1))
+        for name, use in kernel_resources(src).items():
+            if re.search(r"k_positions|k_embed|k32_embed|k3_embed|k_attn_long|k_pool", name):
+                seen[name] = use["VGPRs Spill"]
     assert all(any(k in n for n in seen) for k in ("k_positions", "k3_embed", "k_attn_long", "k_pool")) and len(seen) >= 10, seen
     assert all(v == 0 for v in seen.values()), seen
