@@ -138,6 +138,36 @@ __global__ __launch_bounds__(256) void k_dec_swiglu(const uint16_t *__restrict__
     f[i] = f32_to_bf16(g * u / (1.0f + __expf(-g)));
 }
 
+// ---- launches: the one place each kernel's grid is spelled (the forward pass below and the single-launch tests call these) ----
+int launch_dec_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                     float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st) {
+    const unsigned rows4 = (unsigned)(((int64_t)B * S + 3) / 4);
+    k_dec_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, vocab, emb, w, eps, x32, h16, lens_out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_dec_add_rmsnorm(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st) {
+    const unsigned rows4 = (unsigned)((T + 3) / 4);
+    k_dec_add_rmsnorm<<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_dec_qk_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
+                       const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *v, hipStream_t st) {
+    const int64_t T = (int64_t)B * S;
+    k_dec_qk_rope<<<(unsigned)T, 256, 0, st>>>(qkv, S, nq, nkv, qn, kn, eps, rc, rs, qscale, q, k, v);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_dec_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *out, hipStream_t st) {
+    k_dec_pool<<<B, 256, 0, st>>>(x32, lens, S, H, w, eps, normalise, out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- handle ----------------------------------------------------------------------------------------------------------------
 struct DecLayer {
     const uint16_t *wqkv, *wo, *wgu, *wd;      // wqkv [(nq + 2 nkv) 128][H] and wgu [2 I][H] (interleaved) are owned
@@ -164,22 +194,18 @@ static int dec_forward_locked(Decoder &d, const int32_t *ids, int ld_ids, const 
     const int H = c.hidden, I = c.intermediate, nq = c.q_heads, nkv = c.kv_heads, nqkv = (nq + 2 * nkv) * DEC_HD;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
     if (d.reserve(tpad, B)) return -10;
-    const unsigned rows4 = (unsigned)((T + 3) / 4);
     const float qscale = 1.4426950408889634f / sqrtf((float)DEC_HD);
-    k_dec_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.layers[0].ln_in, c.rms_eps, d.x32, d.h16, d.lens);
-    AK_HIP(hipGetLastError());
+    if (launch_dec_embed(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.layers[0].ln_in, c.rms_eps, d.x32, d.h16, d.lens, st)) return -10;
     for (size_t l = 0; l < d.layers.size(); l++) {
         const DecLayer &ly = d.layers[l];
         // q | k | v
         if (launch_gemm(3, d.gemm_bf16(tpad, d.h16, ly.wqkv, nqkv, H, d.qkv), st)) return -10;
-        k_dec_qk_rope<<<(unsigned)T, 256, 0, st>>>(d.qkv, S, nq, nkv, ly.qn, ly.kn, c.rms_eps, d.rope_c, d.rope_s, qscale, d.q, d.k, d.v);
-        AK_HIP(hipGetLastError());
+        if (launch_dec_qk_rope(d.qkv, B, S, nq, nkv, ly.qn, ly.kn, c.rms_eps, d.rope_c, d.rope_s, qscale, d.q, d.k, d.v, st)) return -10;
         CausalAttnArgs aa{d.q, d.k, d.v, d.lens, d.ctx, B, S, nq, nkv};
         if (launch_attn_causal(aa, st)) return -10;
         // x += ctx Wo^T; h = RMSNorm(x; ln_post)
         if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, nq * DEC_HD, d.y32), st)) return -10;
-        k_dec_add_rmsnorm<<<rows4, 256, 0, st>>>(d.x32, d.y32, T, H, ly.ln_post, c.rms_eps, d.h16);
-        AK_HIP(hipGetLastError());
+        if (launch_dec_add_rmsnorm(d.x32, d.y32, T, H, ly.ln_post, c.rms_eps, d.h16, st)) return -10;
         // f = silu(h Wg^T) (h Wu^T)
         if (swiglu_unfused()) {
             uint16_t *gu = d.f + tpad * I;
@@ -193,12 +219,9 @@ static int dec_forward_locked(Decoder &d, const int32_t *ids, int ld_ids, const 
         // x += f Wd^T; h = RMSNorm(x; next layer's ln_in) (after the last layer: the add only, the pool applies the final norm)
         if (launch_gemm(2, d.gemm_f32(tpad, d.f, ly.wd, H, I, d.y32), st)) return -10;
         const float *wn = l + 1 < d.layers.size() ? d.layers[l + 1].ln_in : nullptr;
-        k_dec_add_rmsnorm<<<rows4, 256, 0, st>>>(d.x32, d.y32, T, H, wn, c.rms_eps, d.h16);
-        AK_HIP(hipGetLastError());
+        if (launch_dec_add_rmsnorm(d.x32, d.y32, T, H, wn, c.rms_eps, d.h16, st)) return -10;
     }
-    k_dec_pool<<<B, 256, 0, st>>>(d.x32, d.lens, S, H, d.norm, c.rms_eps, normalise, out);
-    AK_HIP(hipGetLastError());
-    return 0;
+    return launch_dec_pool(d.x32, d.lens, B, S, H, d.norm, c.rms_eps, normalise, out, st) ? -10 : 0;
 }
 
 }  // namespace ak
@@ -277,8 +300,8 @@ extern "C" int ak_decoder_forward_lens(ak_decoder_t h, const int32_t *ids, int l
     RoctxRange range("ak_decoder_forward_lens");
     Decoder &d = *(Decoder *)h;
     if (B <= 0) return 0;
-    // (no limit on B here, unlike the other two families)
-    if (check_forward_lens("ak_decoder_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, DEC_MAX_S, d.n_pos, nullptr, 0)) return -1;
+    // at most 65535 rows: the attention launch indexes the batch row with blockIdx.z
+    if (check_forward_lens("ak_decoder_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, DEC_MAX_S, d.n_pos, nullptr, 65535)) return -1;
     std::lock_guard<std::mutex> lk(d.mu);
     return dec_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, normalise, out, (hipStream_t)stream);
 }

@@ -195,6 +195,30 @@ int launch_attn_gqa(const GqaAttnArgs &a, int half_window, hipStream_t st);
 // q scaled; q / k head-major, v transposed -- the layouts of GqaAttnArgs. rc / rs: [n_pos][128]
 int launch_gm_qk_norm_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
                            const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *vt, hipStream_t st);
+// the small kernels between the large launches of the pre-norm stacks (decoder.hip, mbert.hip, gemma.hip), each behind the one function
+// that spells its grid: the forward passes call these, and so do the single-launch tests (kernel_test.hip). Shapes are the callers'
+// business (the handles check them at create): H % 128 == 0; H <= 1024 where a row is held in registers (every mb / gm row kernel and
+// both pools' stage 1); S as check_forward_lens takes it.
+int launch_dec_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                     float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st);
+int launch_dec_add_rmsnorm(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st);
+int launch_dec_qk_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
+                       const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *v, hipStream_t st);
+int launch_dec_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *out, hipStream_t st);
+int launch_mb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                    float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, hipStream_t st);
+int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st);
+int launch_mb_rope(uint16_t *q, uint16_t *k, int64_t T, int S, int H, const float *rc, const float *rs, hipStream_t st);
+int launch_mb_pool(const float *x32, const int *lens, int B, int S, int H, float eps, const float *w, int pooling, int normalise, float *part,
+                   float *out, hipStream_t st);
+int launch_gm_fold1p(const float *w, int n, float *w1, hipStream_t st);
+int launch_gm_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                    float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st);
+int launch_gm_norm_add_norm(float *x32, const float *y32, int64_t T, int H, const float *w_post, const float *w_pre, float eps, uint16_t *h16,
+                            float *out32, hipStream_t st);
+int launch_gm_pool(const float *y32, const int *lens, int B, int S, int H, float *part, float *pooled, hipStream_t st);
+int launch_gm_dense(const float *in, const float *W, int B, int N, int K, float *out, hipStream_t st);
+int launch_gm_l2(const float *in, int B, int D, int normalise, float *out, hipStream_t st);
 bool gemm_skinny_supported(int N, int K);
 int launch_gemm_skinny(const uint16_t *X, const uint16_t *W, const float *bias, int rows, int N, int K, float *out_f32,
                        uint16_t *out_bf16, int ldo, hipStream_t st);

@@ -121,14 +121,6 @@ __global__ __launch_bounds__(256) void k_gm_norm_add_norm(float *__restrict__ x3
     }
 }
 
-int launch_gm_norm_add_norm(float *x32, const float *y32, int64_t T, int H, const float *w_post, const float *w_pre, float eps, uint16_t *h16,
-                            float *out32, hipStream_t st) {
-    const unsigned rows4 = (unsigned)((T + 3) / 4);
-    dispatch_nj(H, [&](auto nj) { k_gm_norm_add_norm<decltype(nj)::value><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); });
-    AK_HIP(hipGetLastError());
-    return 0;
-}
-
 // Workgroup (32-token block tb, head slot hs) over the QKV rows [T][(nq + 2 nkv) 256] (S % 32 == 0: a block lies inside one sequence).
 // q and k slots: 8 threads per token, thread u of them takes the 16-byte chunks 2 u, 2 u + 1 of the head and their rotate_half partners
 // 16 + 2 u, 17 + 2 u (elements d and d + 128): RMSNorm over the 256 (sum of squares over the 8 threads by shuffles), times the folded
@@ -252,6 +244,57 @@ __global__ __launch_bounds__(256) void k_gm_l2(const float *__restrict__ in, int
     for (int c = tid; c < D; c += 256) out[(int64_t)b * D + c] = x[c] * sc;
 }
 
+}  // namespace
+
+// ---- launches: the one place each kernel's grid is spelled (create, the forward pass below and the single-launch tests call these) ----
+int launch_gm_fold1p(const float *w, int n, float *w1, hipStream_t st) {
+    k_gm_fold1p<<<(n + 255) / 256, 256, 0, st>>>(w, n, w1);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gm_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                    float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st) {
+    const unsigned rows4 = (unsigned)(((int64_t)B * S + 3) / 4);
+    const float scale = sqrtf((float)H);
+    dispatch_nj(H, [&](auto nj) {
+        k_gm_embed<decltype(nj)::value><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, vocab, emb, scale, w, eps, x32, h16, lens_out);
+    });
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gm_norm_add_norm(float *x32, const float *y32, int64_t T, int H, const float *w_post, const float *w_pre, float eps, uint16_t *h16,
+                            float *out32, hipStream_t st) {
+    const unsigned rows4 = (unsigned)((T + 3) / 4);
+    dispatch_nj(H, [&](auto nj) { k_gm_norm_add_norm<decltype(nj)::value><<<rows4, 256, 0, st>>>(x32, y32, T, H, w_post, w_pre, eps, h16, out32); });
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+// both pooling stages: part [B][ceil(S / 64)][H] floats of workspace -> pooled [B][H]
+int launch_gm_pool(const float *y32, const int *lens, int B, int S, int H, float *part, float *pooled, hipStream_t st) {
+    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
+    k_gm_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(y32, lens, S, H, part);
+    AK_HIP(hipGetLastError());
+    k_gm_pool_fin<<<B, 256, 0, st>>>(part, nch, lens, H, pooled);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gm_dense(const float *in, const float *W, int B, int N, int K, float *out, hipStream_t st) {
+    k_gm_dense<<<dim3((unsigned)((N + 3) / 4), (unsigned)B), 256, 0, st>>>(in, W, N, K, out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gm_l2(const float *in, int B, int D, int normalise, float *out, hipStream_t st) {
+    k_gm_l2<<<B, 256, 0, st>>>(in, D, normalise, out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+namespace {
 struct GmLayer {
     const uint16_t *wqkv, *wo, *wgu, *wdown;       // wqkv (concatenated) and wgu (interleaved) are owned, wdown too when I is padded
     const float *input_ln, *q_norm, *k_norm, *post_attn_ln, *pre_ffn_ln, *post_ffn_ln;      // owned: 1 + w
@@ -277,13 +320,7 @@ int gm_forward_locked(Gemma &d, const int32_t *ids, int ld_ids, const int32_t *l
     const int H = c.hidden, I = d.Ip, nq = c.q_heads, nkv = c.kv_heads;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
     if (d.reserve(tpad, B)) return -10;
-    const unsigned rows4 = (unsigned)((T + 3) / 4);
-    const float scale = sqrtf((float)H);
-    dispatch_nj(H, [&](auto nj) {
-        k_gm_embed<decltype(nj)::value><<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, scale, d.layers[0].input_ln,
-                                                               c.rms_eps, d.x32, d.h16, d.lens);
-    });
-    AK_HIP(hipGetLastError());
+    if (launch_gm_embed(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.layers[0].input_ln, c.rms_eps, d.x32, d.h16, d.lens, st)) return -10;
     for (size_t l = 0; l < d.layers.size(); l++) {
         const GmLayer &ly = d.layers[l];
         const bool last = l + 1 == d.layers.size();
@@ -304,20 +341,13 @@ int gm_forward_locked(Gemma &d, const int32_t *ids, int ld_ids, const int32_t *l
                                     last ? d.y32 : nullptr, st))
             return -10;
     }
-    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
-    k_gm_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(d.y32, d.lens, S, H, d.part);
-    AK_HIP(hipGetLastError());
-    k_gm_pool_fin<<<B, 256, 0, st>>>(d.part, nch, d.lens, H, d.pool_a);
-    AK_HIP(hipGetLastError());
+    if (launch_gm_pool(d.y32, d.lens, B, S, H, d.part, d.pool_a, st)) return -10;
     float *cur = d.pool_a, *nxt = d.pool_b;
     for (int i = 0; i < c.n_dense; i++) {
-        k_gm_dense<<<dim3((unsigned)((d.dense_out[i] + 3) / 4), (unsigned)B), 256, 0, st>>>(cur, d.dense[i], d.dense_out[i], d.dense_in[i], nxt);
-        AK_HIP(hipGetLastError());
+        if (launch_gm_dense(cur, d.dense[i], B, d.dense_out[i], d.dense_in[i], nxt, st)) return -10;
         std::swap(cur, nxt);
     }
-    k_gm_l2<<<B, 256, 0, st>>>(cur, d.out_dim, normalise, out);
-    AK_HIP(hipGetLastError());
-    return 0;
+    return launch_gm_l2(cur, B, d.out_dim, normalise, out, st) ? -10 : 0;
 }
 }  // namespace
 
@@ -376,8 +406,7 @@ extern "C" int ak_gemma_create(const AkGemmaConfig *cfg, const void *const *w, i
     auto fold = [&](const void *src, int n) -> const float * {      // 1 + w
         float *p = d->dev_as<float>(n);
         if (!p) return nullptr;
-        k_gm_fold1p<<<(n + 255) / 256, 256>>>((const float *)src, n, p);
-        return hipGetLastError() == hipSuccess ? p : nullptr;
+        return launch_gm_fold1p((const float *)src, n, p, nullptr) ? nullptr : p;
     };
     if (!(d->final_norm = fold(w[1], H))) return fail("ak_gemma_create: hipMalloc failed");
     const int Ip = d->Ip = padded_intermediate(I);

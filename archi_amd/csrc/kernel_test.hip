@@ -1,4 +1,4 @@
-// kernel_test.hip -- single-launch entry points for the kernel-level tests (tests/test_kernels_gpu.py). They exist in
+// kernel_test.hip -- single-launch entry points for the kernel-level tests (tests/test_kernels_gpu.py and its siblings). They exist in
 // libarchi_hip_dbg.so only (-DAK_DBG_KERNELS=1); the product library gets an empty object from this file and exports no ak_kt_*.
 // Every wrapper fills the launcher's argument block from device pointers and calls the launcher the forward pass calls: no
 // arithmetic, no kernel selection of its own. With no AK_* switch set the instantiation that runs is the one the product launches;
@@ -224,6 +224,117 @@ extern "C" int ak_ktg_gemm_geglu_tanh(const uint16_t *X, const uint16_t *W, cons
     GemmArgs a{};
     a.X = X; a.W = W; a.bias = bias; a.T = T; a.N = N; a.K = K; a.out_bf16 = out; a.ldo = N / 2;
     return launch_gemm(9, a, (hipStream_t)stream);
+}
+
+// ---- the small kernels of the pre-norm stacks (tests/test_stack_kernels_gpu.py). Named ak_kts_*: a set of their own, like ak_ktg_*.
+// Each wrapper hands its arguments to the launch_* function the forward pass calls; it refuses only what that function's callers
+// guarantee (the shape rules of the handles' create and of check_forward_lens), so that a mistaken test shape cannot leave a buffer ----
+static bool kts_rows(long long T, int H, int max_H) { return T > 0 && T <= 0x7fffffff && H > 0 && H % 128 == 0 && (!max_H || H <= max_H); }
+static bool kts_embed(const int *ids, const int *lens, int ld_ids, int lens_stride, int B, int S, int H, int vocab, int max_H) {
+    return ids && lens && B > 0 && S > 0 && S % 32 == 0 && ld_ids >= S && lens_stride >= 1 && vocab > 0 && kts_rows((long long)B * S, H, max_H);
+}
+
+extern "C" int ak_kts_dec_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb,
+                                const float *w, float eps, float *x32, uint16_t *h16, int *lens_out, void *stream) {
+    AK_BIND();
+    if (!kts_embed(ids, lens, ld_ids, lens_stride, B, S, H, vocab, 0)) AK_FAIL(-1, "ak_kts_dec_embed: bad shape");
+    return launch_dec_embed(ids, ld_ids, lens, lens_stride, B, S, H, vocab, emb, w, eps, x32, h16, lens_out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_dec_add_rmsnorm(float *x32, const float *y32, long long T, int H, const float *w, float eps, uint16_t *h16, void *stream) {
+    AK_BIND();
+    if (!kts_rows(T, H, 0)) AK_FAIL(-1, "ak_kts_dec_add_rmsnorm: bad shape");
+    return launch_dec_add_rmsnorm(x32, y32, T, H, w, eps, h16, (hipStream_t)stream);
+}
+
+// qkv [B * S][(nq + 2 nkv) 128]; rc / rs [>= S][64]; q [B][nq][S][128], k / v [B][nkv][S][128]
+extern "C" int ak_kts_dec_qk_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
+                                  const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *v, void *stream) {
+    AK_BIND();
+    if (B <= 0 || S <= 0 || nq <= 0 || nkv <= 0 || (long long)B * S > 0x7fffffff) AK_FAIL(-1, "ak_kts_dec_qk_rope: bad shape");
+    return launch_dec_qk_rope(qkv, B, S, nq, nkv, qn, kn, eps, rc, rs, qscale, q, k, v, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_dec_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *out,
+                               void *stream) {
+    AK_BIND();
+    if (B <= 0 || S <= 0 || H <= 0) AK_FAIL(-1, "ak_kts_dec_pool: bad shape");
+    return launch_dec_pool(x32, lens, B, S, H, w, eps, normalise, out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_mb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb,
+                               const float *w, float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, void *stream) {
+    AK_BIND();
+    if (!kts_embed(ids, lens, ld_ids, lens_stride, B, S, H, vocab, 1024)) AK_FAIL(-1, "ak_kts_mb_embed: bad shape");
+    return launch_mb_embed(ids, ld_ids, lens, lens_stride, B, S, H, vocab, emb, w, eps, x32, h16, mask, lens_out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_mb_add_ln(float *x32, const float *y32, long long T, int H, const float *w, float eps, uint16_t *h16, void *stream) {
+    AK_BIND();
+    if (!kts_rows(T, H, 1024)) AK_FAIL(-1, "ak_kts_mb_add_ln: bad shape");
+    return launch_mb_add_ln(x32, y32, T, H, w, eps, h16, (hipStream_t)stream);
+}
+
+// q, k [T][H] bf16 in place; rc / rs [>= S][32]
+extern "C" int ak_kts_mb_rope(uint16_t *q, uint16_t *k, long long T, int S, int H, const float *rc, const float *rs, void *stream) {
+    AK_BIND();
+    if (!kts_rows(T, H, 0) || S <= 0 || T % S) AK_FAIL(-1, "ak_kts_mb_rope: bad shape");
+    return launch_mb_rope(q, k, T, S, H, rc, rs, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_mb_pool(const float *x32, const int *lens, int B, int S, int H, float eps, const float *w, int pooling, int normalise,
+                              float *part, float *out, void *stream) {
+    AK_BIND();
+    if (B <= 0 || B > 65535 || S <= 0 || !kts_rows(S, H, 1024) || (pooling != AK_POOL_MEAN && pooling != AK_POOL_CLS))
+        AK_FAIL(-1, "ak_kts_mb_pool: bad shape");
+    return launch_mb_pool(x32, lens, B, S, H, eps, w, pooling, normalise, part, out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_gm_fold1p(const float *w, int n, float *w1, void *stream) {
+    AK_BIND();
+    if (n <= 0) AK_FAIL(-1, "ak_kts_gm_fold1p: bad shape");
+    return launch_gm_fold1p(w, n, w1, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_gm_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb,
+                               const float *w, float eps, float *x32, uint16_t *h16, int *lens_out, void *stream) {
+    AK_BIND();
+    if (!kts_embed(ids, lens, ld_ids, lens_stride, B, S, H, vocab, 1024)) AK_FAIL(-1, "ak_kts_gm_embed: bad shape");
+    return launch_gm_embed(ids, ld_ids, lens, lens_stride, B, S, H, vocab, emb, w, eps, x32, h16, lens_out, (hipStream_t)stream);
+}
+
+// out32 != NULL: the second norm as float32 rows (out32 may be y32), h16 unused
+extern "C" int ak_kts_gm_norm_add_norm(float *x32, const float *y32, long long T, int H, const float *w_post, const float *w_pre, float eps,
+                                       uint16_t *h16, float *out32, void *stream) {
+    AK_BIND();
+    if (!kts_rows(T, H, 1024)) AK_FAIL(-1, "ak_kts_gm_norm_add_norm: bad shape");
+    return launch_gm_norm_add_norm(x32, y32, T, H, w_post, w_pre, eps, h16, out32, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_gm_pool(const float *y32, const int *lens, int B, int S, int H, float *part, float *pooled, void *stream) {
+    AK_BIND();
+    if (B <= 0 || B > 65535 || S <= 0 || !kts_rows(S, H, 1024)) AK_FAIL(-1, "ak_kts_gm_pool: bad shape");
+    return launch_gm_pool(y32, lens, B, S, H, part, pooled, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_gm_dense(const float *in, const float *W, int B, int N, int K, float *out, void *stream) {
+    AK_BIND();
+    if (B <= 0 || B > 65535 || N <= 0 || K <= 0 || K % 4) AK_FAIL(-1, "ak_kts_gm_dense: bad shape");
+    return launch_gm_dense(in, W, B, N, K, out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_gm_l2(const float *in, int B, int D, int normalise, float *out, void *stream) {
+    AK_BIND();
+    if (B <= 0 || D <= 0) AK_FAIL(-1, "ak_kts_gm_l2: bad shape");
+    return launch_gm_l2(in, B, D, normalise, out, (hipStream_t)stream);
+}
+
+// one launch_gemm(3): plain bf16 rows, X [T][K], W [N][K] -> out [T][N] (the Qwen3 and Gemma QKV projections)
+extern "C" int ak_kts_gemm_bf16(const uint16_t *X, const uint16_t *W, const float *bias, int T, int N, int K, uint16_t *out, void *stream) {
+    AK_BIND();
+    GemmArgs a{};
+    a.X = X; a.W = W; a.bias = bias; a.T = T; a.N = N; a.K = K; a.out_bf16 = out; a.ldo = N;
+    return launch_gemm(3, a, (hipStream_t)stream);
 }
 
 #endif  // AK_DBG_KERNELS

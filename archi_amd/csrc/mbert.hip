@@ -115,13 +115,6 @@ __global__ __launch_bounds__(256) void k_mb_add_ln(float *__restrict__ x32, cons
     }
 }
 
-int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st) {
-    const unsigned rows4 = (unsigned)((T + 3) / 4);
-    dispatch_nj(H, [&](auto nj) { k_mb_add_ln<decltype(nj)::value><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); });
-    AK_HIP(hipGetLastError());
-    return 0;
-}
-
 // RoPE in place on the q and k rows the QKV GEMM wrote ([T][H] bf16 each, q already scaled: the rotation is linear). One thread per
 // (token, q | k, head, 8-element chunk c < 4): it takes elements 8 c .. 8 c + 7 and their rotate_half partners 32 + 8 c .. of one head,
 // 16 bytes each: x' = x cos + rot(x) sin, rot(x)[d] = -x[d + 32], rot(x)[d + 32] = x[d], at position t % S. rc / rs: the layer's
@@ -205,6 +198,42 @@ __global__ __launch_bounds__(256) void k_mb_pool_fin(const float *__restrict__ p
     }
 }
 
+}  // namespace
+
+// ---- launches: the one place each kernel's grid is spelled (the forward pass below and the single-launch tests call these) ----
+int launch_mb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                    float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, hipStream_t st) {
+    const unsigned rows4 = (unsigned)(((int64_t)B * S + 3) / 4);
+    k_mb_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, vocab, emb, w, eps, x32, h16, mask, lens_out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st) {
+    const unsigned rows4 = (unsigned)((T + 3) / 4);
+    dispatch_nj(H, [&](auto nj) { k_mb_add_ln<decltype(nj)::value><<<rows4, 256, 0, st>>>(x32, y32, T, H, w, eps, h16); });
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_mb_rope(uint16_t *q, uint16_t *k, int64_t T, int S, int H, const float *rc, const float *rs, hipStream_t st) {
+    k_mb_rope<<<(unsigned)((T * (H / 8) + 255) / 256), 256, 0, st>>>(q, k, T, S, H, rc, rs);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+// both pooling stages: part [B][ceil(S / 64)][H] floats of workspace
+int launch_mb_pool(const float *x32, const int *lens, int B, int S, int H, float eps, const float *w, int pooling, int normalise, float *part,
+                   float *out, hipStream_t st) {
+    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
+    k_mb_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(x32, lens, S, H, eps, pooling, part);
+    AK_HIP(hipGetLastError());
+    k_mb_pool_fin<<<B, 256, 0, st>>>(part, nch, lens, H, w, pooling, normalise, out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+namespace {
 // Wi [2 I][H] -> rows interleaved: row 2 j = Wi row j (GELU input), row 2 j + 1 = Wi row I + j (gate): gemm.hip MODE 8
 struct MbLayer {
     const uint16_t *wqkv, *wo, *wi, *wo2;      // wi (interleaved) is owned, wo2 too when the intermediate size is padded
@@ -229,9 +258,7 @@ int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *l
     const int H = c.hidden, I = d.Ip, heads = c.heads;
     const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
     if (d.reserve(tpad, B)) return -10;
-    const unsigned rows4 = (unsigned)((T + 3) / 4);
-    k_mb_embed<<<rows4, 256, 0, st>>>(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.emb_norm, c.norm_eps, d.x32, d.h16, d.mask, d.lens);
-    AK_HIP(hipGetLastError());
+    if (launch_mb_embed(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.emb_norm, c.norm_eps, d.x32, d.h16, d.mask, d.lens, st)) return -10;
     for (size_t l = 0; l < d.layers.size(); l++) {
         const MbLayer &ly = d.layers[l];
         // q (scaled) | k | V^T
@@ -240,8 +267,7 @@ int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *l
         g.ldo = (int)T;                                        // MODE 0: number of real tokens (rows beyond it have no V^T slot)
         if (launch_gemm(0, g, st)) return -10;
         const int tb = ly.global ? 1 : 0;
-        k_mb_rope<<<(unsigned)((T * (H / 8) + 255) / 256), 256, 0, st>>>(d.q, d.k, T, S, H, d.rope_c[tb], d.rope_s[tb]);
-        AK_HIP(hipGetLastError());
+        if (launch_mb_rope(d.q, d.k, T, S, H, d.rope_c[tb], d.rope_s[tb], st)) return -10;
         AttnArgs a{d.q, d.k, d.vt, d.mask, d.ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, d.lens};
         if (launch_attn_window(a, ly.global ? -1 : c.half_window, st)) return -10;
         // x += ctx Wo^T; h = LayerNorm(x; mlp_norm)
@@ -254,12 +280,7 @@ int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *l
         const float *wn = l + 1 < d.layers.size() ? d.layers[l + 1].attn_norm : nullptr;
         if (launch_mb_add_ln(d.x32, d.y32, T, H, wn, c.norm_eps, d.h16, st)) return -10;
     }
-    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
-    k_mb_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(d.x32, d.lens, S, H, c.norm_eps, pooling, d.part);
-    AK_HIP(hipGetLastError());
-    k_mb_pool_fin<<<B, 256, 0, st>>>(d.part, nch, d.lens, H, d.final_norm, pooling, normalise, out);
-    AK_HIP(hipGetLastError());
-    return 0;
+    return launch_mb_pool(d.x32, d.lens, B, S, H, c.norm_eps, d.final_norm, pooling, normalise, d.part, out, st) ? -10 : 0;
 }
 }  // namespace
 
