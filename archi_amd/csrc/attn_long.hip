@@ -6,28 +6,23 @@
 // q arrives pre-scaled by log2(e) / 8 from the QKV GEMM, so the softmax runs in
 // the base-2 domain on v_exp_f32; v arrives transposed ([B][H][S], keys of every 16-group in vt_pos order) as attention.hip takes it.
 //
-// Workgroup = (128-query block, head, sequence), four waves of 32 queries. The 32-key blocks of K and V^T stream through two LDS
-// buffers: block kb + 1 is loaded into registers while block kb is computed, then written to the other buffer (one barrier per
-// block). Per wave and key block:
-//   S^T = K Q^T    4 x v_mfma_f32_32x32x16_bf16: A = K (rows = keys, from LDS), B = Q^T (16 VGPRs held for the whole loop). Keys on
-//                  M: a lane owns ONE query and 16 of the 32 keys (the other 16 in lane ^ 32): row max and sum take one cross-lane step.
-//   + mask         the block's additive mask (0 / -inf from the int mask) staged beside K: pad keys of the last block, and any hole
-//                  of an explicit mask, are excluded.
-//   online softmax in base 2 (running max / sum; a block with no real key leaves them unchanged)
-//   O^T += V^T P^T 4 MFMAs: A = V^T rows (d) from LDS, B = P^T straight from the S^T accumulators.
+// The per-key-block algorithm is flash_tile.h's; this file's own:
+//
+// Workgroup = (128-query block, head, sequence), four waves of 32 queries.
+// Staging: the 32-key blocks of K and V^T stream through two LDS buffers: block kb + 1 is loaded into registers while block kb is
+// computed, then written to the other buffer (one barrier per block); one 16-byte chunk of each tile per thread.
+// Mask: the block's additive mask (0 / -inf from the int mask) is staged beside K and added to the scores: pad keys of the last block,
+// and any hole of an explicit mask, are excluded; a block with no real key leaves the running max and sum unchanged (the guarded step).
 // Key blocks wholly past the row's length (rowlen, k_positions) are not loaded; query blocks wholly past it write zero context rows.
-// K tile [32 keys][64 d]: 128-byte rows, chunk c of key r at c ^ (r & 7); V^T tile [64 d][32 keys]: 64-byte rows, chunk c of row d at
-// c ^ ((d >> 1) & 3) (the XOR swizzles of attn_causal.hip: the lanes of a ds_read_b128 phase hit distinct bank groups).
 // LDS per workgroup: 16 640 bytes (2 x 4 KB K, 2 x 4 KB V^T, 2 x 32 mask floats), both instantiations.
-#include "encoder_kernels.h"
-#include "mfma_tile.h"
+#include "flash_tile.h"
 
 namespace ak {
-using namespace mt;
+using namespace ft;
 
 namespace {
 constexpr int AL_HD = 64, AL_QB = 128;
-constexpr int AL_K_BYTES = 32 * AL_HD * 2, AL_V_BYTES = AL_HD * 64;
+using Tile = FlashTile<AL_HD>;
 
 // WIN (ModernBERT's sliding layers, a.window = half-window w >= 1): key k is visible to query q iff |q - k| <= w. The workgroup walks
 // only the key blocks that intersect [q_begin - w, q_begin + 127 + w] (9 at most for w = 64); a wave skips the blocks that lie wholly
@@ -35,8 +30,8 @@ constexpr int AL_K_BYTES = 32 * AL_HD * 2, AL_V_BYTES = AL_HD * 64;
 // take the same instructions as WIN = false. WIN = false is the kernel as it was (every key block up to the row's length).
 template <bool WIN>
 __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
-    __shared__ __attribute__((aligned(16))) char sK[2][AL_K_BYTES];
-    __shared__ __attribute__((aligned(16))) char sV[2][AL_V_BYTES];
+    __shared__ __attribute__((aligned(16))) char sK[2][Tile::K_BYTES];
+    __shared__ __attribute__((aligned(16))) char sV[2][Tile::V_BYTES];
     __shared__ float sM[2][32];
     const int h = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -47,10 +42,7 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
     const int64_t row0 = (int64_t)b * S;
     const bool has_q = q0 < S;                                 // this wave's 32 rows exist (S % 32 == 0)
     if (q_begin >= len) {                                      // wholly past the length (uniform): zero context rows
-        if (has_q) {
-            uint16_t *crow = a.ctx + (row0 + q0 + r) * H + h * AL_HD;
-            for (int c = kh; c < AL_HD / 8; c += 2) *(uint4 *)(crow + c * 8) = uint4{0, 0, 0, 0};
-        }
+        if (has_q) Tile::zero_row(a.ctx + (row0 + q0 + r) * H + h * AL_HD, kh);
         return;
     }
     int kb_stop = (len + 31) / 32, kb_start = 0;
@@ -63,23 +55,18 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
     const uint16_t *kg = a.k + row0 * H + (int64_t)h * a.qk_hs + (int64_t)k_key * a.qk_ld + k_c * 8;
     const int c0 = kb_start & 1;                               // LDS buffer of the first block (buffers go by block parity)
     const uint16_t *vg = a.vt + ((int64_t)b * H + h * AL_HD + v_d) * S + v_c * 8;
-    const int k_dst = k_key * 128 + ((k_c ^ (k_key & 7)) << 4), v_dst = v_d * 64 + ((v_c ^ ((v_d >> 1) & 3)) << 4);
+    const int k_dst = Tile::k_off(k_key, k_c), v_dst = Tile::v_off(v_d, v_c);
     uint4 kreg = *(const uint4 *)(kg + (int64_t)kb_start * 32 * a.qk_ld), vreg = *(const uint4 *)(vg + kb_start * 32);
     float mreg = tid < 32 ? (a.mask[row0 + kb_start * 32 + tid] ? 0.f : -INFINITY) : 0.f;
     *(uint4 *)(sK[c0] + k_dst) = kreg;
     *(uint4 *)(sV[c0] + v_dst) = vreg;
     if (tid < 32) sM[c0][tid] = mreg;
 
-    uint4 qf[4];
-    {
-        const int qrow = has_q ? q0 + r : S - 1;
-        const uint16_t *qp = a.q + row0 * H + (int64_t)h * a.qk_hs + (int64_t)qrow * a.qk_ld + kh * 8;
+    uint4 qf[Tile::NC];
+    Tile::load_q(qf, a.q + row0 * H + (int64_t)h * a.qk_hs + (int64_t)(has_q ? q0 + r : S - 1) * a.qk_ld, kh);
+    f32x16 o[Tile::NDB];
 #pragma unroll
-        for (int c = 0; c < 4; c++) qf[c] = *(const uint4 *)(qp + c * 16);
-    }
-    f32x16 o[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) o[i] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < Tile::NDB; i++) o[i] = zero16();
     float m = -INFINITY, l = 0.f;
     __syncthreads();
     for (int kb = kb_start; kb < kb_stop; kb++) {
@@ -90,61 +77,25 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
             vreg = *(const uint4 *)(vg + (kb + 1) * 32);
             if (tid < 32) mreg = a.mask[row0 + (kb + 1) * 32 + tid] ? 0.f : -INFINITY;
         }
-        // the block against this wave's queries q0 .. q0 + 31 (wave-uniform): dk_hi / dk_lo = largest key - query / query - key
-        const int dk_hi = kb * 32 + 31 - q0, dk_lo = q0 + 31 - kb * 32;
-        const bool in_band = !WIN || (dk_hi - 62 <= a.window && dk_lo - 62 <= a.window);      // some (query, key) pair is visible
-        if (has_q && in_band) {
-            const char *k_t = sK[cur], *v_t = sV[cur];
-            f32x16 s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const Band band = WIN ? band_of(kb, q0, a.window) : BAND_IN;       // the block against this wave's queries (wave-uniform)
+        if (has_q && band != BAND_OUT) {
+            f32x16 s = Tile::scores(sK[cur], qf, r, kh);
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const uint4 ka = *(const uint4 *)(k_t + r * 128 + (((2 * c + kh) ^ (r & 7)) << 4));
-                s = mfma_bf16(ka, qf[c], s);
+            for (int i = 0; i < 16; i++) s[i] += sM[cur][Tile::acc_row(i, kh)];
+            if (WIN && band == BAND_EDGE) {                    // the band, per (query r, key) pair
+                const int dq = kb * 32 - (q0 + r);             // key - query of the block's first key
+#pragma unroll
+                for (int i = 0; i < 16; i++)
+                    if (band_hides(dq + Tile::acc_row(i, kh), a.window)) s[i] = -INFINITY;
             }
-            // accumulator i: key kb * 32 + 8 (i / 4) + 4 kh + i % 4 of this lane's query
-            float mb = -INFINITY;
+            float alpha;
+            s = Tile::softmax_step<true>(s, m, l, alpha);
 #pragma unroll
-            for (int i = 0; i < 16; i++) {
-                s[i] += sM[cur][8 * (i >> 2) + 4 * kh + (i & 3)];
-                if constexpr (!WIN) mb = fmaxf(mb, s[i]);
-            }
-            if constexpr (WIN) {
-                if (dk_hi > a.window || dk_lo > a.window) {    // an edge block: the band, per (query r, key) pair
-                    const int dq = kb * 32 + 4 * kh - (q0 + r);    // key - query of accumulator 0
-#pragma unroll
-                    for (int i = 0; i < 16; i++) {
-                        const int dk = dq + 8 * (i >> 2) + (i & 3);
-                        if (dk > a.window || -dk > a.window) s[i] = -INFINITY;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 16; i++) mb = fmaxf(mb, s[i]);
-            }
-            mb = fmaxf(mb, __shfl_xor(mb, 32));
-            const float mn = fmaxf(m, mb);
-            const float mref = mn == -INFINITY ? 0.f : mn;     // no real key seen yet: p = 0, nothing rescaled
-            const float alpha = exp2f(m - mref);
-            m = mn;
-            float ps = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; i++) { s[i] = exp2f(s[i] - mref); ps += s[i]; }
-            l = l * alpha + ps;
-#pragma unroll
-            for (int db = 0; db < 2; db++) o[db] = o[db] * alpha;
+            for (int db = 0; db < Tile::NDB; db++) o[db] = o[db] * alpha;
             uint4 pb[2];
+            Tile::pack_p(s, pb);
 #pragma unroll
-            for (int t = 0; t < 2; t++)
-                pb[t] = uint4{pack_bf16x2(s[8 * t + 0], s[8 * t + 1]), pack_bf16x2(s[8 * t + 2], s[8 * t + 3]),
-                              pack_bf16x2(s[8 * t + 4], s[8 * t + 5]), pack_bf16x2(s[8 * t + 6], s[8 * t + 7])};
-#pragma unroll
-            for (int db = 0; db < 2; db++) {
-                const int d = db * 32 + r;
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    const uint4 va = *(const uint4 *)(v_t + d * 64 + (((2 * t + kh) ^ ((d >> 1) & 3)) << 4));
-                    o[db] = mfma_bf16(va, pb[t], o[db]);
-                }
-            }
+            for (int db = 0; db < Tile::NDB; db++) o[db] = Tile::pv(sV[cur], pb, o[db], db, r, kh);
         }
         if (more) {                                            // the other buffer: its last readers passed the previous barrier
             *(uint4 *)(sK[cur ^ 1] + k_dst) = kreg;
@@ -157,15 +108,8 @@ __global__ __launch_bounds__(256) void k_attn_long(AttnArgs a) {
     const float lt = l + __shfl_xor(l, 32);
     const float inv = lt > 0.f ? 1.0f / lt : 0.f;
     uint16_t *crow = a.ctx + (row0 + q0 + r) * H + h * AL_HD;
-    // O^T accumulators: d = 32 db + 8 (i / 4) + 4 kh + i % 4 of this lane's query: four consecutive d per 8-byte store
 #pragma unroll
-    for (int db = 0; db < 2; db++)
-#pragma unroll
-        for (int gq = 0; gq < 4; gq++) {
-            const int d = db * 32 + 8 * gq + 4 * kh;
-            *(uint2 *)(crow + d) = uint2{pack_bf16x2(o[db][4 * gq + 0] * inv, o[db][4 * gq + 1] * inv),
-                                         pack_bf16x2(o[db][4 * gq + 2] * inv, o[db][4 * gq + 3] * inv)};
-        }
+    for (int db = 0; db < Tile::NDB; db++) Tile::store_ctx(crow, o[db], db, kh, [&](float x) { return x * inv; });
 }
 }  // namespace
 

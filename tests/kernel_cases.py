@@ -79,10 +79,11 @@ def attn_cases():
 def causal_cases():
     """launch_attn_causal: every (nq, nkv) at every S. At S = 8192 with 32 query heads the float64 reference of all heads is
     unaffordable beside the rest of the file (6 GFLOP per head and full row, three such rows): that case compares every row of the
-    first and the last query head."""
+    first and the last query head. (6, 2) is G = 3: three waves (192 threads, which do not divide the 512-chunk staging loop), at one
+    key block, at the diagonal plus one block below and at several row blocks, with a neighbouring kv head for the GQA-map probe."""
     out = []
-    for nq, nkv in ((1, 1), (2, 1), (4, 1), (16, 8), (32, 8)):
-        for S in (32, 64, 256, 2048, 8192):
+    for nq, nkv in ((1, 1), (2, 1), (4, 1), (16, 8), (32, 8), (6, 2)):
+        for S in (32, 64, 256, 2048, 8192) if nq != 6 else (32, 64, 256):
             c = dict(kernel="causal", S=S, nq=nq, nkv=nkv, heads=nq, hd=128, mask="right", window=-1, name=f"causal_q{nq}_kv{nkv}_S{S}")
             if S == 8192 and nq >= 32:
                 c["check_heads"] = [0, nq - 1]

@@ -92,7 +92,8 @@ def test_case_lists_say_what_the_issue_lists():
     a = kc.attn_cases()
     assert len(a) == 4 * 3 * 3 * 3 + 3 * 3 * 2 and len({c["name"] for c in a}) == len(a)
     c_ = kc.causal_cases()
-    assert len(c_) == 25 and {(c["nq"], c["nkv"]) for c in c_} == {(1, 1), (2, 1), (4, 1), (16, 8), (32, 8)}
+    assert len(c_) == 28 and {(c["nq"], c["nkv"]) for c in c_} == {(1, 1), (2, 1), (4, 1), (16, 8), (32, 8), (6, 2)}
+    assert sorted(c["S"] for c in c_ if c["nq"] == 6) == [32, 64, 256] and all(sum(d["nq"] == c["nq"] for d in c_) == 5 for c in c_ if c["nq"] != 6)
     g = kc.gemm_cases()
     for c in g:
         assert c["T"] % 256 == 0 and c["N"] % 128 == 0 and c["K"] % 64 == 0

@@ -79,7 +79,7 @@ def test_launch_attn_long(tmp_path):
 
 
 def test_launch_attn_causal(tmp_path):
-    """k_attn_causal at G = 1, 2, 4 and every row length: the decoder reads one row of it, here every row is checked."""
+    """k_attn_causal at G = 1, 2, 3, 4 and every row length: the decoder reads one row of it, here every row is checked."""
     _attention(tmp_path, "causal", kc.causal_cases())
 
 
