@@ -47,6 +47,7 @@ namespace {
 struct SwitchName { const char *name; std::atomic<int> Switches::*field; int dflt; bool is_flag; bool wrong_results; bool is_char; };
 const SwitchName g_switch_names[] = {
     {"AK_SCAN_CFG", &Switches::scan_cfg, 0, false, false, true},
+    {"AK_SCAN_MFMA", &Switches::scan_mfma, 0, false, false, false},
     {"AK_SCAN_BLOCKS", &Switches::scan_blocks, 0, false, false, false},
     {"AK_SCAN_NO192", &Switches::scan_no192, 0, true, false, false},
     {"AK_SEED_RATIO", &Switches::seed_ratio, 32, false, false, false},
@@ -99,6 +100,9 @@ int switches_set(const char *name, const char *value) {
             // the A/B reference tiles X and O are compiled into the dbg library only: refuse them here rather than accept the
             // switch and run the plan's own tile under a probe that believes it forced another (round-5 advisor finding)
             if (!DBG_KERNELS && n.is_char && value && (*value == 'X' || *value == 'O')) return -1;
+            // ... and so is the MFMA shape a phased tile does not ship with (AK_SCAN_MFMA = 16 / 32); 0 and a reset pass
+            if (!DBG_KERNELS && n.field == &Switches::scan_mfma && switch_value(n, value) != 0) return -1;
+            if (n.field == &Switches::scan_mfma && switch_value(n, value) != 0 && switch_value(n, value) != 16 && switch_value(n, value) != 32) return -1;
             (sw.*(n.field)).store(switch_value(n, value), std::memory_order_relaxed);
             return 0;
         }

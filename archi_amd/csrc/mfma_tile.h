@@ -1,5 +1,5 @@
 // mfma_tile.h -- shared device helpers of the MFMA kernels (scan.hip, gemm.hip, gemm_ln.hip, attention.hip):
-// LDS-DMA staging from inline asm with hand-counted vmcnt, 32x32x16 bf16/f16 MFMA wrappers.
+// LDS-DMA staging from inline asm with hand-counted vmcnt, 32x32x16 and 16x16x32 bf16/f16 MFMA wrappers.
 //
 // LDS-DMA (global_load_lds): LDS[M0 + lane*16] <- *g, 16 B per lane. Issued from inline asm so hipcc does not
 // serialise it against the ds_reads of the OTHER ring slots (it cannot prove they do not alias and would wait
@@ -67,6 +67,28 @@ __device__ inline f32x16 mfma32(uint4 a, uint4 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// 16x16x32: lane l supplies row / column l & 15 and the eight K values 8 * (l >> 4) ..; it receives column l & 15, rows 4 * (l >> 4) + j.
+// The accumulators of the kernels stay f32x16 values (one 32 x 32 block = four 16 x 16 blocks): Q names the four-float slice.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+template <bool IS_BF16>
+__device__ inline f32x4 mfma16(uint4 a, uint4 b, f32x4 c) {
+    if constexpr (IS_BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+template <int Q>
+__device__ inline f32x4 acc_slice(const f32x16 &v) {
+    return __builtin_shufflevector(v, v, 4 * Q, 4 * Q + 1, 4 * Q + 2, 4 * Q + 3);
+}
+template <int Q>
+__device__ inline void acc_set_slice(f32x16 &v, f32x4 s) {
+    const f32x16 w = __builtin_shufflevector(s, s, 0, 1, 2, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
+    if constexpr (Q == 0) v = __builtin_shufflevector(v, w, 16, 17, 18, 19, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    else if constexpr (Q == 1) v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 16, 17, 18, 19, 8, 9, 10, 11, 12, 13, 14, 15);
+    else if constexpr (Q == 2) v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 4, 5, 6, 7, 16, 17, 18, 19, 12, 13, 14, 15);
+    else v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19);
 }
 __device__ inline uint32_t pack_bf16x2(float lo, float hi) {
     typedef float f2 __attribute__((ext_vector_type(2)));

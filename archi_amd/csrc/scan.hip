@@ -15,7 +15,9 @@
 //            full-line coalesced reads). LDS rows are XOR-swizzled on the SOURCE address (chunk ^= (row>>1)&7) so
 //            the ds_read_b128 fragment reads are bank-conflict free.
 //   mfma   = v_mfma_f32_32x32x16_{bf16,f16}; A = corpus rows, B = queries, so a lane owns ONE query column (lane&31)
-//            and 16 corpus rows per 32x32 block: the top-k reduction axis is lane-local.
+//            and 16 corpus rows per 32x32 block: the top-k reduction axis is lane-local. The phased tiles also exist on
+//            v_mfma_f32_16x16x32 (ScanCfg::MFMA = 16: a lane owns two columns and 8 rows per 32x32 block; same LDS image, phases
+//            and output tile per wave) -- the chip holds a higher clock on that shape; the 256 x 256 tile ships on it.
 //   filter = per 16-row group an upper bound from precomputed per-block maxima; groups that can reach the query's
 //            threshold are scored exactly and appended to a per-(block,query) buffer in global memory (L2 resident)
 //            with an LDS counter, threshold and trigger. A wave compacts a buffer that nears capacity to
@@ -80,6 +82,13 @@ __device__ __forceinline__ void mfma_settle(f32x16 (&a)[M][N]) {
     else if constexpr (N == 3 && M == 2)
         asm volatile("s_nop 15\n\ts_nop 3" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]));
     else static_assert(M * N == 0, "unsupported accumulator shape");
+}
+
+// one 16x16x32 MFMA into slice Q of a 32 x 32 block's accumulator (zero: the block's first MFMA of a corpus tile)
+template <bool IS_BF16, int Q>
+__device__ __forceinline__ void mfma16_into(f32x16 &d, uint4 a, uint4 b, bool zero) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    acc_set_slice<Q>(d, mfma16<IS_BF16>(a, b, zero ? z : acc_slice<Q>(d)));
 }
 
 // Bitwise binary search with ballots: 32 steps over the score half of the keys and -- only when
@@ -179,10 +188,16 @@ __device__ inline int compact_wave(uint64_t *buf, int m, int k, int limit, float
 // 8-row staging pieces, chunk ^= (row>>1)&7 spreads the 16 lanes of a ds_read_b128 group over all 16 bank quads).
 // PHASED_ (the 256 x 256 tile of the MFMA-bound batches): a K-step runs as two phases of 16 MFMAs and the two waves of
 // every SIMD run them one barrier apart -- see the phased K-loop in k_scan.
-template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false>
+// MFMA_ (phased tiles only): 32 = v_mfma_f32_32x32x16, 16 = v_mfma_f32_16x16x32 on the same LDS image, phases and output tile per
+// wave -- other fragment reads, other accumulator mapping, other filter groups (k_scan, "16x16x32"). Shape32: the same tile on the
+// 32x32x16 shape, which the pre-seeding launch always runs (its group-maxima layout feeds k_seed_kth).
+template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false, int MFMA_ = 32>
 struct ScanCfg {
     static constexpr int WM = WM_, WN = WN_, MI = MI_, NI = NI_, NSTAGE = NSTAGE_, MINW = MINW_;
     static constexpr bool PHASED = PHASED_;
+    static constexpr int MFMA = MFMA_;
+    using Shape32 = ScanCfg<WM_, WN_, MI_, NI_, NSTAGE_, MINW_, PHASED_, 32>;
+    static_assert(MFMA_ == 32 || (MFMA_ == 16 && PHASED_), "the 16x16x32 shape exists for the phased tiles");
     static constexpr int AHEAD = NSTAGE_ - 1;     // ring stages issued ahead of the compute cursor
     static constexpr int BKB = 128;               // bytes per LDS row per K-step
     static constexpr int RPP = 1024 / BKB;        // rows per 1 KiB staging piece
@@ -235,6 +250,8 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
     // scans rows [row_begin, n); row_begin is a multiple of BM. thr0 (nullable): per-query initial
     // thresholds in scan-score units (from the seeding pass). Output slot: slice_off + slice.
     constexpr int BM = C::BM, BN = C::BN, NW = C::NW, MI = C::MI, NI = C::NI, NSTAGE = C::NSTAGE, CAP = C::CAP;
+    constexpr bool M16 = C::MFMA == 16;      // 16x16x32 MFMAs: a lane owns query columns 16c + (lane & 15) and rows 16h + 4 * (lane >> 4) + j
+    static_assert(!(M16 && SEED), "the pre-seeding launch runs the 32x32x16 shape (C::Shape32)");
     const int flags = INSTR ? flags_arg : 0;
     long long *const dbg = INSTR ? dbg_arg : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -400,6 +417,85 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                 for (int ni = 0; ni < NI; ni++) keep_live(acc[mi][ni]);
             return;
         }
+        if constexpr (M16) {
+            // 16x16x32 mapping: slice 2h + c of acc[mi][ni] holds, in element j, corpus row (wr*MI + mi)*32 + 16h + 4kq + j against
+            // query (wc*NI + ni)*32 + 16c + r16. A filter group is the 8 rows a lane holds of one 32-row block for one query column
+            // (h = 0, 1). All of them have row bit 2 = kq & 1, so they are a subset of the row class whose maxima t_gb keeps
+            // (computed at ingest for the 32x32x16 mapping, where the class is kh): the bound holds with no new ingest data, and
+            // a group of 8 passes it about half as often as the other shape's group of 16. 4 v_max3_f32 + fma + compare per 8
+            // values (12 VALU per 16; the 32x32x16 filter: 10 per 16). Nothing past this point knows the shape: keys carry the
+            // row, and the margin of k_query_setup (4 D 2^-24 + the operand rounding) bounds ANY summation order of the dot
+            // product, so the candidates' consumers (out_c, thr_slots, dense_cnt, dense_thr: the tails, the certificate) and
+            // the certificate itself are unchanged; ids and distances come from the exact re-rank.
+            // (the threshold is read per column block inside the loop: 2 * NI of them held across the filter, on top of 128 accumulators
+            // and a full register file, made hipcc spill two registers of the 256 x 256 tile)
+            // The lane's row / column numbers are rebuilt per tile from an opaque copy of the lane id, so no address derived from them
+            // stays live through the K-loop.
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int r16 = ln & 15, kq = ln >> 4;
+#if !AK_DBG_KERNELS
+            mfma_settle(acc);
+#endif
+#pragma unroll
+            for (int mi = 0; mi < MI; mi++) {
+                const float gea = t_gb[(wr * MI + mi) * 4 + (kq & 1)], geb = t_gb[(wr * MI + mi) * 4 + 2 + (kq & 1)];
+#pragma unroll
+                for (int ni = 0; ni < NI; ni++) {
+                    const f32x16 &a = acc[mi][ni];
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const int lo = 4 * c, hi = 8 + 4 * c;     // slices (h = 0, c) and (h = 1, c)
+#if AK_DBG_KERNELS
+                        const float dpos = fmaxf(fmaxf(fmaxf(fmaxf(a[lo], a[lo + 1]), fmaxf(a[lo + 2], a[lo + 3])),
+                                                       fmaxf(fmaxf(a[hi], a[hi + 1]), fmaxf(a[hi + 2], a[hi + 3]))), 0.f);
+#else
+                        const float dpos = max3z(max3f(max3f(a[lo], a[lo + 1], a[lo + 2]), max3f(a[lo + 3], a[hi], a[hi + 1]), a[hi + 2]), a[hi + 3]);
+#endif
+                        const float U = fmaf(dpos, gea, geb);
+                        const float thr = s_thr[(wc * NI + ni) * 32 + 16 * c + r16];
+                        if (U >= thr && !(INSTR && (flags & 16))) {
+                            if constexpr (INSTR) n_slow++;
+                            float sc[8];
+                            float mx = -__builtin_inff();
+#pragma unroll
+                            for (int h = 0; h < 2; h++) {
+                                const int base = (wr * MI + mi) * 32 + 16 * h + 4 * kq;   // rows base .. base+3 of the tile
+                                float4 e4 = *(const float4 *)&t_ea[base], b4 = *(const float4 *)&t_eb[base];
+                                if (tail) {
+                                    float *pe = (float *)&e4, *pb = (float *)&b4;
+#pragma unroll
+                                    for (int j = 0; j < 4; j++)
+                                        if (base + j >= rows_left) { pe[j] = 0.f; pb[j] = -__builtin_inff(); }
+                                }
+                                const int o = 8 * h + 4 * c;
+                                sc[4 * h + 0] = fmaf(a[o + 0], e4.x, b4.x); sc[4 * h + 1] = fmaf(a[o + 1], e4.y, b4.y);
+                                sc[4 * h + 2] = fmaf(a[o + 2], e4.z, b4.z); sc[4 * h + 3] = fmaf(a[o + 3], e4.w, b4.w);
+                                mx = fmaxf(fmaxf(mx, sc[4 * h + 0]), fmaxf(fmaxf(sc[4 * h + 1], sc[4 * h + 2]), sc[4 * h + 3]));
+                            }
+                            if (mx >= thr) {
+                                const int qcol = (wc * NI + ni) * 32 + 16 * c + r16;
+                                int nh = 0;
+#pragma unroll
+                                for (int e = 0; e < 8; e++) nh += sc[e] >= thr ? 1 : 0;
+                                int pos = atomicAdd(&s_cnt[qcol], nh);       // one LDS atomic per lane reserves room for its hits of the group
+                                if (pos + nh > s_trig[qcol]) *s_need = 1;
+                                uint64_t *dstq = my_cand + (size_t)qcol * CAP;
+                                const uint32_t rbase = (uint32_t)(tile_row0 + (wr * MI + mi) * 32 + 4 * kq);
+#pragma unroll
+                                for (int e = 0; e < 8; e++) {
+                                    if (sc[e] >= thr) {
+                                        dstq[pos] = ((uint64_t)score_key(sc[e]) << 32) | (uint64_t)(rbase + (e & 3) + 16 * (e >> 2));
+                                        pos++;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            return;
+        }
         // Common path: for the 16 rows a lane holds of a 32-row block, U = max(dot,0)*max(ea)+max(eb) is an
         // upper bound of their scores (ea >= 0); the per-block maxima are precomputed at ingest (Index::gb).
         // Only a group whose bound reaches the threshold is scored exactly -- about the true hit rate.
@@ -500,6 +596,12 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
         //        issued since in flight; every wave passes a barrier after that wait and before ANY wave's LOAD(p+1).
         // The halves stay one barrier apart across tiles (the filter of one runs under the other's MFMAs); only a compaction
         // -- rare, workgroup-uniform -- re-aligns them.
+        // 16x16x32 (C::MFMA = 16; the MFMA shape as a lever of its own in a loop whose clock the chip holds down): the same buffers, phases, barriers and 16 fragment reads per phase X (8 in Y), but a fragment is 16 rows x K32
+        // (lane: row l & 15, chunk 4s + (l >> 4) of K32 sub-step s) and a phase issues twice as many MFMAs of half the length -- the
+        // same 512 pipe cycles. The accumulators stay f32x16 per 32 x 32 block, each MFMA works on a four-float slice of one (slice
+        // 2h + c = rows 16h.., columns 16c..), so mfma_settle ties them through one statement as before. Which tile ships on which
+        // shape is decided by wall time on the benchmark's workload against the parent in the same job (docs/EXPERIMENTS.md,
+        // "16x16x32"): cycles do not rank the shapes, the clock the chip sustains on each does.
         // ------------------------------------------------------------------------------------------------------------
         constexpr int HT = 16384;                          // an A half-tile: 128 corpus rows
         // A K-tile buffer: Ah0 | B part 0 .. NI-1 | Ah1. Half h of A holds, per wave row, its AH = MI / 2 blocks h*AH ..; a B part
@@ -540,12 +642,25 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                     voB[t][p] = (uint32_t)qrow * (uint32_t)D * 2u + ((schunk ^ swz(lr)) << 4);
                 }
             // fragment read offsets: A rows wr*AH*32 + m*32 + r of a half-tile, B rows wc*32 + r of a part; chunk (2*k2 + kh) ^ swz(row)
+            // 16x16x32: fragment f = 2 * b + s is the 16-row block b (A: h, B: c) of a 32-row block at K32 sub-step s: rows 16b + r16,
+            // chunk (4s + kq) ^ swz(row) -- swz(16b + r16) = swz(r16), the source-side swizzle stands. The 16 lanes ds_read_b128
+            // serves together ({0-3, 12-15, 20-27}, ...) hold 16 rows and, with kq and the swizzle, 16 distinct bank quads.
+            if constexpr (M16) {
+                const int r6 = ln & 15, k6 = ln >> 4;
+#pragma unroll
+                for (int f = 0; f < 4; f++) {
+                    const int coff = ((4 * (f & 1) + k6) ^ swz(r6)) << 4;
+                    ra[f] = (wr * AH * 32 + 16 * (f >> 1) + r6) * BKB + coff;
+                    rb[f] = (wc * 32 + 16 * (f >> 1) + r6) * BKB + coff;
+                }
+            } else {
             const int cc0 = kk ^ swz(rr);
 #pragma unroll
             for (int k2 = 0; k2 < 4; k2++) {
                 const int coff = (cc0 ^ (k2 << 1)) << 4;
                 ra[k2] = (wr * AH * 32 + rr) * BKB + coff;
                 rb[k2] = (wc * 32 + rr) * BKB + coff;
+            }
             }
         };
         lane_consts(lane);
@@ -653,6 +768,24 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
             const long long ts3 = TICK();
             __builtin_amdgcn_s_setprio(1);
             constexpr int MB = Y ? AH : 0;                  // 32-row blocks MB .. MB + AH - 1
+            if constexpr (M16) {
+                // the same 512 pipe cycles as twice as many MFMAs of half the length: per K32 sub-step s and 32 x 32 block its four
+                // 16 x 16 blocks (h, c) = slice 2h + c of the block's accumulator, from fragments fa[m][2h + s], fb[nb][2c + s]
+#pragma unroll
+                for (int s = 0; s < 2; s++)
+#pragma unroll
+                    for (int m = 0; m < AH; m++)
+#pragma unroll
+                        for (int e = 0; e < NI; e++) {
+                            const int nb = Y ? NI - 1 - e : e;
+                            const bool zero = FIRST && s == 0;
+                            f32x16 &d = acc[MB + m][nb];
+                            mfma16_into<IS_BF16, 0>(d, fa[m][s], fb[nb][s], zero);
+                            mfma16_into<IS_BF16, 1>(d, fa[m][s], fb[nb][2 + s], zero);
+                            mfma16_into<IS_BF16, 2>(d, fa[m][2 + s], fb[nb][s], zero);
+                            mfma16_into<IS_BF16, 3>(d, fa[m][2 + s], fb[nb][2 + s], zero);
+                        }
+            } else
 #pragma unroll
             for (int k2 = 0; k2 < 4; k2++)
 #pragma unroll
@@ -1258,8 +1391,16 @@ __global__ __launch_bounds__(64) void k_finalize(const uint64_t *__restrict__ to
 // host side: configuration table, plan, launch
 // ---------------------------------------------------------------------------
 //                      WM WN MI NI ring minw
-using CfgP = ScanCfg<2, 4, 4, 2, 2, 2, true>;   // 256 x 256, 8 waves (128x64 each), phased K-loop, SIMD partners one barrier apart : MFMA-bound batches
-using CfgQ = ScanCfg<2, 4, 4, 1, 2, 2, true>;   // 256 x 128, 8 waves (128x32 each), phased K-loop (three half-tiles per K-step) : 128-query groups of MFMA-bound batches
+// MFMA shape of the phased tiles in the product library: the winner by wall time on the benchmark's own workload, parent and variant
+// alternating in one job, every run of the winner above every run of the other (docs/EXPERIMENTS.md "16x16x32": P +6.0 % at Q = 1024,
+// R +5.7 % at 384, Q +3.0 % at 256 queries/s). libarchi_hip_dbg.so instantiates both shapes of each and AK_SCAN_MFMA = 16 / 32
+// picks one there.
+constexpr int SHIP_P = 16, SHIP_Q = 16, SHIP_R = 16;
+template <int S> using CfgPs = ScanCfg<2, 4, 4, 2, 2, 2, true, S>;
+template <int S> using CfgQs = ScanCfg<2, 4, 4, 1, 2, 2, true, S>;
+template <int S> using CfgRs = ScanCfg<4, 2, 2, 3, 2, 2, true, S>;
+using CfgP = CfgPs<SHIP_P>;                     // 256 x 256, 8 waves (128x64 each), phased K-loop, SIMD partners one barrier apart : MFMA-bound batches
+using CfgQ = CfgQs<SHIP_Q>;                     // 256 x 128, 8 waves (128x32 each), phased K-loop (three half-tiles per K-step) : 128-query groups of MFMA-bound batches
 using CfgX = ScanCfg<2, 4, 4, 2, 2, 2>;   // the same tile with the in-step K-loop of rounds 1-2 (2-slot ring, one barrier per K-step): A/B reference
 // Measured and not kept (round 1-2; docs/EXPERIMENTS.md has the numbers): an L2 prefetch of the corpus lines three K-steps
 // ahead of the staging cursor (the prefetch instruction costs half of what a wave's staging instructions issue per K-step:
@@ -1271,7 +1412,7 @@ using CfgL = ScanCfg<4, 2, 2, 2, 3, 2>;   // 256 x 128, 8 waves (64x64 each), 3-
 using CfgM = ScanCfg<4, 1, 2, 2, 3, 1>;   // 256 x 64 , 4 waves, 3-slot ring : HBM-bound, Q <= 64
 using CfgS = ScanCfg<4, 1, 2, 1, 3, 1>;   // 256 x 32 , 4 waves, 3-slot ring : HBM-bound, Q <= 32
 using CfgO = ScanCfg<2, 2, 2, 2, 2, 2>;   // 128 x 128, 4 waves, 2-slot ring, 2 blocks/CU (first version; A/B reference)
-using CfgR = ScanCfg<4, 2, 2, 3, 2, 2, true>;   // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
+using CfgR = CfgRs<SHIP_R>;                     // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
 
 struct CfgInfo { int bm, bn, cap, threads, lds, blocks_per_cu; };
 template <class C> constexpr CfgInfo info_of(int bpc) { return CfgInfo{C::BM, C::BN, C::CAP, C::THREADS, C::LDS_BYTES, bpc}; }
@@ -1518,15 +1659,26 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
 #define SCAN(CFG, R0, R1, NS, THR, SOFF, DBG, SP)                                                                    \
     rc = bf ? launch_scan<true, CFG, false, SP>(ix, filter_dev, R0, R1, qs, nq, NS, nqg, k, kp, THR, mar, SOFF, ns_tot, cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr) \
             : launch_scan<false, CFG, false, SP>(ix, filter_dev, R0, R1, qs, nq, NS, nqg, k, kp, THR, mar, SOFF, ns_tot, cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
+    // phased tiles: the shipped shape; the dbg library carries both and honours AK_SCAN_MFMA (the product library's ak_debug_set
+    // refuses it, and a value in its environment is ignored, like a forced X / O tile)
+#if AK_DBG_KERNELS
+    const int mfma_forced = switches().scan_mfma.load(std::memory_order_relaxed);
+#define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)                         \
+    if (mfma_forced == 16) { SCAN(T<16>, R0, R1, NS, THR, SOFF, DBG, SP); }             \
+    else if (mfma_forced == 32) { SCAN(T<32>, R0, R1, NS, THR, SOFF, DBG, SP); }        \
+    else { SCAN(SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP); }
+#else
+#define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP) SCAN(SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)
+#endif
 #define SCAN_ANY(R0, R1, NS, THR, SOFF, DBG, SP)                         \
     switch (plan.cfg) {                                          \
         case CFG_L: SCAN(CfgL, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
         case CFG_M: SCAN(CfgM, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
         case CFG_S: SCAN(CfgS, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
         AK_SCAN_XO_CASES(SCAN, R0, R1, NS, THR, SOFF, DBG, SP)            \
-        case CFG_P: SCAN(CfgP, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_Q: SCAN(CfgQ, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_R: SCAN(CfgR, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
+        case CFG_P: SCAN_SHAPED(CfgPs, CfgP, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
+        case CFG_Q: SCAN_SHAPED(CfgQs, CfgQ, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
+        case CFG_R: SCAN_SHAPED(CfgRs, CfgR, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
         default: AK_FAIL(-1, "scan: tile configuration not in this library (X and O: libarchi_hip_dbg.so)"); \
     }
     long long *dbg0 = nullptr, *dbg1 = nullptr;
@@ -1553,9 +1705,9 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
                 case CFG_X: PRE(CfgX); break;
                 case CFG_O: PRE(CfgO); break;
 #endif
-                case CFG_P: PRE(CfgP); break;
-                case CFG_Q: PRE(CfgQ); break;
-                case CFG_R: PRE(CfgR); break;
+                case CFG_P: PRE(CfgP::Shape32); break;      // the pre-seeding launch stays on 32x32x16 whatever the tile ships
+                case CFG_Q: PRE(CfgQ::Shape32); break;
+                case CFG_R: PRE(CfgR::Shape32); break;
                 default: AK_FAIL(-1, "scan: tile configuration not in this library (X and O: libarchi_hip_dbg.so)");
             }
 #undef PRE
@@ -1595,6 +1747,7 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
     if (ev0) AK_HIP(hipEventRecord(ev0, st));   // the timed "dominant kernel" is the main-pass launch
     SCAN_ANY(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false);
 #undef SCAN_ANY
+#undef SCAN_SHAPED
 #undef SCAN
     if (rc) return rc;
     if (ev1) AK_HIP(hipEventRecord(ev1, st));
