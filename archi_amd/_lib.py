@@ -118,6 +118,20 @@ class AkGemmaConfig(ctypes.Structure):
     ]
 
 
+class AkNomicBertConfig(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("heads", ctypes.c_int),
+        ("intermediate", ctypes.c_int),
+        ("type_vocab", ctypes.c_int),
+        ("max_position", ctypes.c_int),
+        ("ln_eps", ctypes.c_float),
+        ("rope_theta", ctypes.c_float),
+    ]
+
+
 _lock = threading.Lock()
 _lib = None
 _inited_device = None
@@ -186,6 +200,9 @@ SYMBOLS = [
     ("ak_gemma_destroy", _I, [_P]),
     ("ak_gemma_set_rope_inv_freq", _I, [_P, _P, _P]),
     ("ak_gemma_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("ak_nomic_create", _I, [ctypes.POINTER(AkNomicBertConfig), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_nomic_destroy", _I, [_P]),
+    ("ak_nomic_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_create_ex", _I, [ctypes.c_char_p, _I, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.POINTER(ctypes.c_char_p), _I, ctypes.POINTER(_P)]),
@@ -274,6 +291,14 @@ KTS_SYMBOLS = [
     ("ak_kts_gemm_bf16", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 ]
 
+# NomicBERT's row kernels (csrc/nomic.hip), one launch each (tests/test_nomic_kernels_gpu.py): libarchi_hip_dbg.so only, a fourth
+# set of its own (ak_ktn_*)
+KTN_SYMBOLS = [
+    ("ak_ktn_embed", _I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
+    ("ak_ktn_add_ln", _I, [_P, _P, _I64, _I, _P, _P, _F, _P, _P]),
+    ("ak_ktn_pool", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+]
+
 
 def load() -> ctypes.CDLL:
     """dlopen the library and bind every declared symbol (no GPU needed)."""
@@ -302,7 +327,7 @@ def load() -> ctypes.CDLL:
                 fn.restype = res
                 fn.argtypes = args
             if path != LIB_PATH:
-                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS + KTS_SYMBOLS:
+                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS + KTS_SYMBOLS + KTN_SYMBOLS:
                     fn = getattr(lib, name)
                     fn.restype = res
                     fn.argtypes = args

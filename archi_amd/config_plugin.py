@@ -35,6 +35,10 @@ EMBEDDING_DIMENSIONS = {
     "lightonai/modernbert-embed-large": 1024,
     "answerdotai/ModernBERT-base": 768,
     "answerdotai/ModernBERT-large": 1024,
+    "nomic-ai/nomic-embed-text-v1": 768,
+    "nomic-ai/nomic-embed-text-v1.5": 768,
+    "nomic-ai/nomic-embed-text-v1-unsupervised": 768,
+    "Snowflake/snowflake-arctic-embed-m-long": 768,
 }
 
 

@@ -195,9 +195,9 @@ int launch_attn_gqa(const GqaAttnArgs &a, int half_window, hipStream_t st);
 // q scaled; q / k head-major, v transposed -- the layouts of GqaAttnArgs. rc / rs: [n_pos][128]
 int launch_gm_qk_norm_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
                            const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *vt, hipStream_t st);
-// the small kernels between the large launches of the pre-norm stacks (decoder.hip, mbert.hip, gemma.hip), each behind the one function
+// the small kernels between the large launches of the stacks (decoder.hip, mbert.hip, gemma.hip, nomic.hip), each behind the one function
 // that spells its grid: the forward passes call these, and so do the single-launch tests (kernel_test.hip). Shapes are the callers'
-// business (the handles check them at create): H % 128 == 0; H <= 1024 where a row is held in registers (every mb / gm row kernel and
+// business (the handles check them at create): H % 128 == 0; H <= 1024 where a row is held in registers (every mb / gm / nb row kernel and
 // both pools' stage 1); S as check_forward_lens takes it.
 int launch_dec_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
                      float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st);
@@ -211,6 +211,12 @@ int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float
 int launch_mb_rope(uint16_t *q, uint16_t *k, int64_t T, int S, int H, const float *rc, const float *rs, hipStream_t st);
 int launch_mb_pool(const float *x32, const int *lens, int B, int S, int H, float eps, const float *w, int pooling, int normalise, float *part,
                    float *out, hipStream_t st);
+// nomic.hip (the post-norm stack; its RoPE launch is launch_mb_rope): type0 = row 0 of the float32 token-type table; g / b the LayerNorm's
+// weight and bias. launch_nb_add_ln writes the NORMALISED row back to x32 (launch_mb_add_ln: the sum).
+int launch_nb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *word,
+                    const float *type0, const float *g, const float *b, float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, hipStream_t st);
+int launch_nb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *g, const float *b, float eps, uint16_t *h16, hipStream_t st);
+int launch_nb_pool(const float *x32, const int *lens, int B, int S, int H, int pooling, int normalise, float *part, float *out, hipStream_t st);
 int launch_gm_fold1p(const float *w, int n, float *w1, hipStream_t st);
 int launch_gm_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
                     float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st);

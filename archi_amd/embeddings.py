@@ -15,7 +15,8 @@ Host side (this file): text normalisation, WordPiece tokenisation, length-sorted
 Device side: archi_amd.encoder.HipEncoder (hand-written HIP). No CPU fallback.
 Qwen3-Embedding checkpoints (config.json model_type "qwen3") run on archi_amd.decoder.HipDecoder instead, tokenised by the
 checkpoint's own tokenizer.json, pooled on the last token; ModernBERT checkpoints (model_type "modernbert") run on
-archi_amd.modernbert.HipModernBert; the same batching harness drives all of them.
+archi_amd.modernbert.HipModernBert, NomicBERT checkpoints (model_type "nomic_bert") on archi_amd.nomic.HipNomicBert with the BERT
+WordPiece tokenizer of their vocab.txt; the same batching harness drives all of them.
 """
 from __future__ import annotations
 
@@ -38,6 +39,8 @@ from .modernbert import MODERNBERT_SHAPES, HipModernBert, load_modernbert_weight
 from .modernbert import MAX_SEQ as MODERNBERT_MAX_SEQ
 from .gemma import GEMMA_SHAPES, HipGemma, load_gemma_weights, random_gemma_weights
 from .gemma import MAX_SEQ as GEMMA_MAX_SEQ
+from .nomic import NOMIC_SHAPES, HipNomicBert, load_nomic_weights, nomic_config_info, random_nomic_weights
+from .nomic import MAX_SEQ as NOMIC_MAX_SEQ
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
 # special tokens by name: (cls, sep, unk, the strings the full tokenizer matches in raw text)
@@ -199,6 +202,15 @@ def _is_gemma(model_name: str) -> bool:
     return model_name in GEMMA_SHAPES
 
 
+def _is_nomic(model_name: str) -> bool:
+    """A NomicBERT checkpoint directory (config.json model_type "nomic_bert") or one of the named NomicBERT shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "nomic_bert"
+    return model_name in NOMIC_SHAPES
+
+
 def _is_mpnet(model_name: str) -> bool:
     """An MPNet checkpoint directory (config.json model_type "mpnet") or one of the named MPNet shapes."""
     import json
@@ -234,6 +246,8 @@ class _StackFamily(NamedTuple):
     random: Callable            # (shape, model_kwargs) -> seeded random weights
     pooling: Callable           # (model_name, shape, model_kwargs, the checkpoint's pooling | None) -> pooling
     handle: Callable            # the HipStack subclass
+    wordpiece: bool = False     # a vocab.txt beside the weights (or model_kwargs["vocab_file"]) is the tokenizer: BERT WordPiece
+    precheck: Optional[Callable] = None      # (checkpoint directory, model_kwargs): refusals the config alone decides, before any GPU work
 
 
 def _seed_std(kw):
@@ -262,6 +276,25 @@ _GEMMA = _StackFamily("Gemma embedders", "an EmbeddingGemma", "tokenizer", GEMMA
                       read_sentence_transformers_config, lambda shape, kw: random_gemma_weights(shape, **_seed_std(kw)), _gemma_pooling, HipGemma)
 
 
+def _nomic_precheck(model_dir, kw):
+    """A dynamic-NTK RoPE checkpoint equals the default RoPE up to its trained length and nothing computes it beyond: a larger
+    explicit max_seq_length is refused, not truncated."""
+    import json
+    cj = os.path.join(model_dir, "config.json")
+    shape, dynamic = nomic_config_info(json.load(open(cj)), cj)
+    if dynamic and "max_seq_length" in kw and int(kw["max_seq_length"]) > shape[6]:
+        raise ValueError(f"{model_dir}: max_seq_length {int(kw['max_seq_length'])} is past the trained length {shape[6]} of a dynamic-NTK "
+                         f"RoPE checkpoint (rows up to {shape[6]} tokens equal the default RoPE; longer rows are not implemented)")
+
+
+# NomicBERT (nomic-ai/nomic-embed-text-v1 / -v1.5 / -v1-unsupervised, Snowflake/snowflake-arctic-embed-m-long): mean or cls pooling as the
+# checkpoint or the named shape says, rows up to 8192 tokens (a dynamic-NTK checkpoint: up to its trained length), BERT WordPiece
+_NOMIC = _StackFamily("NomicBERT models", "a NomicBERT", "vocab.txt or tokenizer.json", NOMIC_SHAPES, 6, NOMIC_MAX_SEQ, load_nomic_weights,
+                      read_sentence_transformers_config, lambda shape, kw: random_nomic_weights(shape, **_seed_std(kw)),
+                      lambda name, shape, kw, st_pool: kw.get("pooling", st_pool or shape[9]), HipNomicBert, wordpiece=True,
+                      precheck=_nomic_precheck)
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -283,7 +316,7 @@ class ArchiHipEmbeddings:
         device = int(dev.split(":")[1]) if ":" in dev else None
         self._stage = self._stage_out = None
         self._stage_lock = threading.Lock()
-        for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA)):
+        for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA), (_is_nomic, _NOMIC)):
             if is_family(model_name):
                 self._init_stack(family, model_name, device)
                 return
@@ -406,21 +439,24 @@ class ArchiHipEmbeddings:
         return vocab, H, L, heads, I, max_pos, weights, eps, mpnet_rel_bias_table(rel_w, max_pos)
 
     def _init_stack(self, fam: "_StackFamily", model_name: str, device: Optional[int]) -> None:
-        """A pre-norm stack (Qwen3-Embedding, ModernBERT, EmbeddingGemma; the _StackFamily records below): a local checkpoint
-        directory (config.json of the family's model_type, safetensors, tokenizer.json, the sentence-transformers files) or a named
-        shape with synthetic_seed. bf16 only. Query / document prompts stay with the caller, as the reference's retrievers handle
+        """A stack family (Qwen3-Embedding, ModernBERT, EmbeddingGemma, NomicBERT; the _StackFamily records above): a local checkpoint
+        directory (config.json of the family's model_type, safetensors, tokenizer.json -- NomicBERT: vocab.txt first --, the
+        sentence-transformers files) or a named shape with synthetic_seed. bf16 only. Query / document prompts stay with the caller, as the reference's retrievers handle
         instructions themselves."""
         precision = str(self.model_kwargs.get("precision", "bf16"))
         if precision != "bf16":
             raise ValueError(f"precision {precision!r}: {fam.models} run in bf16 only")
         if os.path.isdir(model_name):
-            tf = os.path.join(model_name, "tokenizer.json")
-            if not os.path.exists(tf):
+            tf, vf = os.path.join(model_name, "tokenizer.json"), os.path.join(model_name, "vocab.txt")
+            use_vocab = fam.wordpiece and os.path.exists(vf)
+            if not use_vocab and not os.path.exists(tf):
                 raise FileNotFoundError(f"{model_name}: tokenizer.json not found -- {fam.checkpoint} checkpoint needs its {fam.tokenizer}")
+            if fam.precheck:
+                fam.precheck(model_name, self.model_kwargs)
             shape, weights = fam.load(model_name)
             st_pool, st_len, st_norm = fam.st_config(model_name)
             self.normalize = self.normalize or st_norm
-            self.tokenizer = BpeTokenizer(tf)
+            self.tokenizer = NativeWordPiece(vf, lowercase=_do_lower_case(model_name)) if use_vocab else BpeTokenizer(tf)
         else:
             if "synthetic_seed" not in self.model_kwargs:
                 raise FileNotFoundError(f"{model_name!r}: no local checkpoint directory (offline image). Pass {fam.checkpoint} checkpoint "
@@ -429,8 +465,8 @@ class ArchiHipEmbeddings:
             weights = fam.random(shape, self.model_kwargs)
             st_pool, st_len = None, None
             self.normalize = True                      # the released sentence-transformers models carry a Normalize module
-            tf = self.model_kwargs.get("tokenizer_file")
-            self.tokenizer = BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
+            tf, vf = self.model_kwargs.get("tokenizer_file"), self.model_kwargs.get("vocab_file") if fam.wordpiece else None
+            self.tokenizer = NativeWordPiece(vf) if vf else BpeTokenizer(tf) if tf else HashWordPiece(shape[0])
         self.pooling = fam.pooling(model_name, shape, self.model_kwargs, st_pool)
         max_pos = int(shape[fam.max_position])
         self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, fam.max_seq)

@@ -548,6 +548,44 @@ int ak_gemma_set_rope_inv_freq(ak_gemma_t h, const float *global_inv, const floa
 int ak_gemma_forward_lens(ak_gemma_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
                           int pooling, int normalise, float *out_dev, void *stream);
 
+/* ---- NomicBERT encoders (nomic-ai/nomic-embed-text-v1 / -v1.5 / -v1-unsupervised, Snowflake/snowflake-arctic-embed-m-long) ---- */
+/* The forward pass of HF NomicBertModel, the model behind Embeddings.embed_documents (manager.py:373) when embedding_class_map names a
+ * NomicBERT checkpoint: word embedding + token-type row 0 + LayerNorm (no position table), POST-norm layers -- x = LayerNorm(x +
+ * sub-layer(x)): the residual stream is the LayerNorm output -- with separate q / k / v projections, rotate_half RoPE at head size 64
+ * with one theta over the whole head, bidirectional attention scaled by 1 / 8, a SwiGLU MLP (silu(gate) * up); no final norm; then
+ * mean / cls pooling over the valid tokens and L2 normalisation. No bias in any Linear; every LayerNorm carries a weight and a bias.
+ * bf16 MFMA GEMMs, float32 residual stream / norms / softmax. */
+typedef void *ak_nomic_t;
+typedef struct AkNomicBertConfig {
+    int vocab_size;     /* 30528 */
+    int hidden;         /* 768; a multiple of 128, <= 1024 */
+    int layers;         /* 12; <= AK_MBERT_MAX_LAYERS */
+    int heads;          /* 12; hidden / heads must be 64 */
+    int intermediate;   /* 3072; a multiple of 64 */
+    int type_vocab;     /* 2: rows of the token-type table (row 0 is the one read) */
+    int max_position;   /* 8192 (rows are limited to min(max_position, 8192) tokens) */
+    float ln_eps;       /* 1e-12 */
+    float rope_theta;   /* 1000 (default RoPE: a dynamic-NTK checkpoint equals it up to its trained length, which max_position states) */
+} AkNomicBertConfig;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] as torch.nn.Linear.weight, vectors float32):
+ *   0 word_emb [vocab][H] bf16, 1 type_emb [type_vocab][H] float32, 2 emb_ln_g [H], 3 emb_ln_b [H],
+ *   per layer l (base 4 + 11 * l):
+ *     +0 wq [H][H] +1 wk [H][H] +2 wv [H][H] +3 wo [H][H] +4 ln1_g [H] +5 ln1_b [H] (post_attention_layernorm)
+ *     +6 w_gate [I][H] +7 w_up [I][H] +8 w_down [H][I] +9 ln2_g [H] +10 ln2_b [H] (post_mlp_layernorm)
+ * The library copies wq | wk | wv into one matrix and interleaves the gate and up rows at create (row 2 j = gate row j, row 2 j + 1 =
+ * up row j; when 2 I is not a multiple of 256 it also pads them with zero rows and copies w_down with zero columns to match); the
+ * other pointers must stay valid until the handle is destroyed. Refused (non-zero, message in the last-error string): head size != 64,
+ * hidden % 128 or > 1024, intermediate % 64, layers > AK_MBERT_MAX_LAYERS, a non-positive size, ln_eps or rope_theta, a weight count
+ * other than 4 + 11 * layers. */
+int ak_nomic_create(const AkNomicBertConfig *cfg, const void *const *weights_dev, int n_weights, ak_nomic_t *out);
+int ak_nomic_destroy(ak_nomic_t h);
+/* One tile of the embedding step of manager.py:373, in the tile layout of ak_encoder_forward_lens: B right-padded rows of S token ids
+ * `ld_ids` int32 apart, lengths `lens_stride` apart (clamped to [0, S]; ids past a row's length are ignored; a row of length 0 embeds
+ * to zeros). pooling: AK_POOL_MEAN / AK_POOL_CLS over the last layer's rows of the valid tokens; out_dev [B][H] float32, L2-normalised
+ * when `normalise` != 0. S a multiple of 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
+int ak_nomic_forward_lens(ak_nomic_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                          int pooling, int normalise, float *out_dev, void *stream);
+
 /* ---- host tokenizer: the tokenisation step inside Embeddings.embed_documents -------- */
 /* manager.py:373 -> HuggingFaceEmbeddings -> sentence-transformers' BERT WordPiece tokenizer [upstream]. Pure host
  * code (no GPU work): multi-threaded, so that text -> token ids keeps up with ak_encoder_forward at ingestion.
