@@ -269,7 +269,7 @@ KTG_SYMBOLS = [
     ("ak_ktg_gemm_geglu_tanh", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 ]
 
-# the small kernels of the pre-norm stacks (decoder.hip, mbert.hip, gemma.hip) and k_gemm MODE 3, one launch each
+# the small kernels of the stacks (decoder.hip, mbert.hip, nomic.hip, gemma.hip) and k_gemm MODE 3, one launch each
 # (tests/test_stack_kernels_gpu.py): libarchi_hip_dbg.so only, a third set of its own (ak_kts_*)
 _F = ctypes.c_float
 _EMBED = [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P]
@@ -282,6 +282,9 @@ KTS_SYMBOLS = [
     ("ak_kts_mb_add_ln", _I, [_P, _P, _I64, _I, _P, _F, _P, _P]),
     ("ak_kts_mb_rope", _I, [_P, _P, _I64, _I, _I, _P, _P, _P]),
     ("ak_kts_mb_pool", _I, [_P, _P, _I, _I, _I, _F, _P, _I, _I, _P, _P, _P]),
+    ("ak_kts_nb_embed", _I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
+    ("ak_kts_nb_add_ln", _I, [_P, _P, _I64, _I, _P, _P, _F, _P, _P]),
+    ("ak_kts_nb_pool", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     ("ak_kts_gm_fold1p", _I, [_P, _I, _P, _P]),
     ("ak_kts_gm_embed", _I, _EMBED + [_P, _P]),
     ("ak_kts_gm_norm_add_norm", _I, [_P, _P, _I64, _I, _P, _P, _F, _P, _P, _P]),
@@ -289,14 +292,6 @@ KTS_SYMBOLS = [
     ("ak_kts_gm_dense", _I, [_P, _P, _I, _I, _I, _P, _P]),
     ("ak_kts_gm_l2", _I, [_P, _I, _I, _I, _P, _P]),
     ("ak_kts_gemm_bf16", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
-]
-
-# NomicBERT's row kernels (csrc/nomic.hip), one launch each (tests/test_nomic_kernels_gpu.py): libarchi_hip_dbg.so only, a fourth
-# set of its own (ak_ktn_*)
-KTN_SYMBOLS = [
-    ("ak_ktn_embed", _I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
-    ("ak_ktn_add_ln", _I, [_P, _P, _I64, _I, _P, _P, _F, _P, _P]),
-    ("ak_ktn_pool", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
 ]
 
 
@@ -327,7 +322,7 @@ def load() -> ctypes.CDLL:
                 fn.restype = res
                 fn.argtypes = args
             if path != LIB_PATH:
-                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS + KTS_SYMBOLS + KTN_SYMBOLS:
+                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS + KTS_SYMBOLS:
                     fn = getattr(lib, name)
                     fn.restype = res
                     fn.argtypes = args

@@ -1,6 +1,6 @@
-"""What the Python handles of the pre-norm stacks share (HipDecoder, HipModernBert, HipGemma; csrc/stack.h is the library's side):
-weight upload, the pointer array, create / close, the tile layout of forward_lens and its validation, forward. Also the safetensors
-directory reader and the seeded weight generators of the three families' loaders.
+"""What the Python handles of the stacks share (HipDecoder, HipModernBert, HipGemma, HipNomicBert; csrc/stack.h is the library's side):
+weight upload, the pointer array, create / close, the pooling rule, the tile layout of forward_lens and its validation, forward. Also
+the safetensors directory reader and the seeded weight generators of the families' loaders.
 """
 from __future__ import annotations
 
@@ -45,7 +45,7 @@ def seeded_mat_vec(seed: int, std: float = 0.02, vec_mean: float = 1.0):
 
 
 class HipStack:
-    """Base of the three handles. PyTorch-ROCm only HOLDS the weights in HBM (bf16 matrices, fp32 vectors) and hands raw device
+    """Base of the four handles. PyTorch-ROCm only HOLDS the weights in HBM (bf16 matrices, fp32 vectors) and hands raw device
     pointers to the C ABI. A subclass states what differs:"""
     family = ""                 # as the "weight missing" message names the model family
     prefix = ""                 # the library symbols: ak_<prefix>_create / _destroy / _forward_lens
@@ -53,6 +53,8 @@ class HipStack:
     matrix_keys = frozenset()
     abi_pooling = True          # ak_<prefix>_forward_lens takes a pooling argument
     out_name = "hidden"         # how forward_lens' message names the output width (self.out_dim)
+    poolings = ("mean", "cls")  # what _pooling accepts; None stands for self.pooling, the model's own
+    pooling_noun = ""           # as _pooling's message names the family: "<noun> pool 'mean' or 'cls'"
 
     def _upload(self, weights, names: Iterable[str], device: Optional[int]) -> None:
         """Binds the library and the device; the weights `names` (numpy arrays or torch tensors) -> self._tensors on the device."""
@@ -92,7 +94,10 @@ class HipStack:
 
     def _pooling(self, pooling: Optional[str]) -> str:
         """The pooling a call runs with; a ValueError for one the family does not implement."""
-        raise NotImplementedError
+        pooling = pooling or self.pooling
+        if pooling not in self.poolings:
+            raise ValueError(f"pooling {pooling!r}: {self.pooling_noun} pool " + " or ".join(repr(p) for p in self.poolings))
+        return pooling
 
     def forward_lens(self, stage, n_rows: int, S: int, out, pooling: Optional[str] = None, normalise: bool = True) -> None:
         """The provider's tile layout, as HipEncoder.forward_lens: `stage` an int32 CUDA tensor [n_rows, S + 1] (S ids per row,

@@ -226,7 +226,7 @@ extern "C" int ak_ktg_gemm_geglu_tanh(const uint16_t *X, const uint16_t *W, cons
     return launch_gemm(9, a, (hipStream_t)stream);
 }
 
-// ---- the small kernels of the pre-norm stacks (tests/test_stack_kernels_gpu.py). Named ak_kts_*: a set of their own, like ak_ktg_*.
+// ---- the small kernels of the stacks, NomicBERT's among them (tests/test_stack_kernels_gpu.py). Named ak_kts_*: a set of their own, like ak_ktg_*.
 // Each wrapper hands its arguments to the launch_* function the forward pass calls; it refuses only what that function's callers
 // guarantee (the shape rules of the handles' create and of check_forward_lens), so that a mistaken test shape cannot leave a buffer ----
 static bool kts_rows(long long T, int H, int max_H) { return T > 0 && T <= 0x7fffffff && H > 0 && H % 128 == 0 && (!max_H || H <= max_H); }
@@ -290,6 +290,31 @@ extern "C" int ak_kts_mb_pool(const float *x32, const int *lens, int B, int S, i
     return launch_mb_pool(x32, lens, B, S, H, eps, w, pooling, normalise, part, out, (hipStream_t)stream);
 }
 
+// NomicBERT's row kernels. type0: row 0 of the float32 token-type table; g / b: the LayerNorm's weight and bias
+extern "C" int ak_kts_nb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *word,
+                               const float *type0, const float *g, const float *b, float eps, float *x32, uint16_t *h16, int *mask, int *lens_out,
+                               void *stream) {
+    AK_BIND();
+    if (!kts_embed(ids, lens, ld_ids, lens_stride, B, S, H, vocab, 1024)) AK_FAIL(-1, "ak_kts_nb_embed: bad shape");
+    return launch_nb_embed(ids, ld_ids, lens, lens_stride, B, S, H, vocab, word, type0, g, b, eps, x32, h16, mask, lens_out, (hipStream_t)stream);
+}
+
+extern "C" int ak_kts_nb_add_ln(float *x32, const float *y32, long long T, int H, const float *g, const float *b, float eps, uint16_t *h16,
+                                void *stream) {
+    AK_BIND();
+    if (!kts_rows(T, H, 1024)) AK_FAIL(-1, "ak_kts_nb_add_ln: bad shape");
+    return launch_nb_add_ln(x32, y32, T, H, g, b, eps, h16, (hipStream_t)stream);
+}
+
+// part: [B][ceil(S / 64)][H] floats of workspace
+extern "C" int ak_kts_nb_pool(const float *x32, const int *lens, int B, int S, int H, int pooling, int normalise, float *part, float *out,
+                              void *stream) {
+    AK_BIND();
+    if (B <= 0 || B > 65535 || S <= 0 || !kts_rows(S, H, 1024) || (pooling != AK_POOL_MEAN && pooling != AK_POOL_CLS))
+        AK_FAIL(-1, "ak_kts_nb_pool: bad shape");
+    return launch_nb_pool(x32, lens, B, S, H, pooling, normalise, part, out, (hipStream_t)stream);
+}
+
 extern "C" int ak_kts_gm_fold1p(const float *w, int n, float *w1, void *stream) {
     AK_BIND();
     if (n <= 0) AK_FAIL(-1, "ak_kts_gm_fold1p: bad shape");
@@ -335,30 +360,6 @@ extern "C" int ak_kts_gemm_bf16(const uint16_t *X, const uint16_t *W, const floa
     GemmArgs a{};
     a.X = X; a.W = W; a.bias = bias; a.T = T; a.N = N; a.K = K; a.out_bf16 = out; a.ldo = N;
     return launch_gemm(3, a, (hipStream_t)stream);
-}
-
-// ---- NomicBERT's row kernels (tests/test_nomic_kernels_gpu.py). Named ak_ktn_*: a fourth set of its own. The same rules as ak_kts_* ----
-// type0: row 0 of the float32 token-type table; g / b: the embedding LayerNorm
-extern "C" int ak_ktn_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *word,
-                            const float *type0, const float *g, const float *b, float eps, float *x32, uint16_t *h16, int *mask, int *lens_out,
-                            void *stream) {
-    AK_BIND();
-    if (!kts_embed(ids, lens, ld_ids, lens_stride, B, S, H, vocab, 1024)) AK_FAIL(-1, "ak_ktn_embed: bad shape");
-    return launch_nb_embed(ids, ld_ids, lens, lens_stride, B, S, H, vocab, word, type0, g, b, eps, x32, h16, mask, lens_out, (hipStream_t)stream);
-}
-
-extern "C" int ak_ktn_add_ln(float *x32, const float *y32, long long T, int H, const float *g, const float *b, float eps, uint16_t *h16, void *stream) {
-    AK_BIND();
-    if (!kts_rows(T, H, 1024)) AK_FAIL(-1, "ak_ktn_add_ln: bad shape");
-    return launch_nb_add_ln(x32, y32, T, H, g, b, eps, h16, (hipStream_t)stream);
-}
-
-// part: [B][ceil(S / 64)][H] floats of workspace
-extern "C" int ak_ktn_pool(const float *x32, const int *lens, int B, int S, int H, int pooling, int normalise, float *part, float *out, void *stream) {
-    AK_BIND();
-    if (B <= 0 || B > 65535 || S <= 0 || !kts_rows(S, H, 1024) || (pooling != AK_POOL_MEAN && pooling != AK_POOL_CLS))
-        AK_FAIL(-1, "ak_ktn_pool: bad shape");
-    return launch_nb_pool(x32, lens, B, S, H, pooling, normalise, part, out, (hipStream_t)stream);
 }
 
 #endif  // AK_DBG_KERNELS

@@ -13,37 +13,27 @@
 //   x += f Wo^T; h = LayerNorm(x; next attn_norm)      k_gemm MODE 2 + k_mb_add_ln
 // then final_norm per token, mean / cls pooling over the valid tokens and L2 normalisation in float32 (k_mb_pool_part, k_mb_pool_fin).
 // The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in decoder.hip.
-// Here: the config checks, the layer struct, the layer loop and the family's own kernels and formulas. The plumbing shared with decoder.hip
-// and gemma.hip is stack.h / stack.hip: the token-slot prologue and the row helpers of k_mb_embed, the body of k_mb_pool_part (here: its
-// per-token transform), the L2 tail of k_mb_pool_fin, the NJ dispatch, the workspace, the weight preparation at create (interleave, the
-// pad-to-256 rule), the rotary tables, the GemmArgs of the launches.
+// Here: the config struct's own checks, the layer struct, the order of a layer (block, join, block, join) and the family's kernels: the
+// embedding, the join k_mb_add_ln (x32 keeps the SUM), k_mb_rope, the per-token transform of the pool. stack.h holds the token-slot
+// prologue, the LayerNorm of a row in registers, both pooling bodies and the NJ dispatch; enc64.h (shared with nomic.hip) the handle's
+// workspace, the common create steps, the attention and FFN blocks and the body of ak_mbert_forward_lens.
 // LDS per workgroup: k_mb_embed / k_mb_add_ln / k_mb_rope none; k_mb_pool_part 4 * H * 4 bytes (dynamic: 12 KB at H = 768, 16 KB at
 // 1024); k_mb_pool_fin 16 bytes; the GEMMs and the attention kernel as their files state.
-#include <algorithm>
-#include <cmath>
-
-#include "stack.h"
+#include "enc64.h"
 
 namespace ak {
 
 namespace {
-constexpr int MB_HD = 64, MB_MAX_S = ATTN_LONG_MAX_S, MB_MAX_H = POOL_MAX_H;
+constexpr int MB_HD = Enc64::HD;
 
 // LayerNorm statistics of one float32 row held in memory (H % 4 == 0), by one wave: mean, then the variance about it (two passes,
 // as torch's float32 kernel -- not E[x^2] - mean^2)
 __device__ inline void mb_row_stats(const float *__restrict__ xr, int H, int lane, float eps, float &mean, float &rstd) {
     float s = 0.f;
-    for (int c = lane * 4; c < H; c += 256) {
-        const float4 f = *(const float4 *)(xr + c);
-        s += (f.x + f.y) + (f.z + f.w);
-    }
+    for (int c = lane * 4; c < H; c += 256) s += row_sum4(*(const float4 *)(xr + c));
     mean = wave_sum(s) / (float)H;
     float q = 0.f;
-    for (int c = lane * 4; c < H; c += 256) {
-        const float4 f = *(const float4 *)(xr + c);
-        const float a = f.x - mean, b = f.y - mean, cc = f.z - mean, d = f.w - mean;
-        q += (a * a + b * b) + (cc * cc + d * d);
-    }
+    for (int c = lane * 4; c < H; c += 256) q += row_sq4(*(const float4 *)(xr + c), mean);
     rstd = rsqrtf(wave_sum(q) / (float)H + eps);
 }
 
@@ -71,39 +61,18 @@ __global__ __launch_bounds__(256) void k_mb_embed(const int *__restrict__ ids, i
 
 // one wave per token t < T: x32 += y32 (the sub-layer's float32 GEMM output), then h16 = LayerNorm(x32; w) (w == NULL: the add only).
 // The LayerNorm twin of k_dec_add_rmsnorm. The row stays in registers between the add, the two reductions and the store (NJ float4 per
-// lane, NJ = ceil(H / 256)): one pass over memory. Mean, then the variance about it, as mb_row_stats.
+// lane, NJ = ceil(H / 256)): one pass over memory. The statistics: row_ln_stats (stack.h), as mb_row_stats.
 template <int NJ>
 __global__ __launch_bounds__(256) void k_mb_add_ln(float *__restrict__ x32, const float *__restrict__ y32, int64_t T, int H, const float *__restrict__ w,
                                                    float eps, uint16_t *__restrict__ h16) {
     const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (t >= T) return;
-    float *xr = x32 + t * H;
-    const float *yr = y32 + t * H;
     float4 f[NJ];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; j++) {
-        const int c = lane * 4 + j * 256;
-        f[j] = float4{0.f, 0.f, 0.f, 0.f};
-        if (c < H) {
-            f[j] = *(const float4 *)(xr + c);
-            const float4 y = *(const float4 *)(yr + c);
-            f[j].x += y.x; f[j].y += y.y; f[j].z += y.z; f[j].w += y.w;
-            *(float4 *)(xr + c) = f[j];
-            s += (f[j].x + f[j].y) + (f[j].z + f[j].w);
-        }
-    }
+    const float s = row_load_sum<true>(x32 + t * H, y32 + t * H, H, lane, f);
     if (!w) return;
-    const float mean = wave_sum(s) / (float)H;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; j++)
-        if (lane * 4 + j * 256 < H) {
-            const float a = f[j].x - mean, b = f[j].y - mean, cc = f[j].z - mean, d = f[j].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
+    float mean, rstd;
+    row_ln_stats(f, s, H, lane, eps, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
         const int c = lane * 4 + j * 256;
@@ -153,7 +122,7 @@ struct MbFinalNorm {
         float mean, rstd;
         __device__ float apply(float x) const { return (x - mean) * rstd; }
     };
-    __device__ int count(int len) const { return len <= 0 ? 0 : (pooling == AK_POOL_CLS ? 1 : len); }
+    __device__ int count(int len) const { return pooled_count(len, pooling); }
     __device__ Token begin(const float *xr, int H, int lane) const {
         Token t;
         mb_row_stats(xr, H, lane, eps, t.mean, t.rstd);
@@ -165,37 +134,10 @@ __global__ __launch_bounds__(256) void k_mb_pool_part(const float *__restrict__ 
     pool_part(x32, lens, S, H, MbFinalNorm{eps, pooling}, part);
 }
 
-// Pooling, stage 2. One workgroup per row b: the chunk sums added in chunk order, * w / n, then the L2 normalisation. A row of length 0
-// embeds to zeros.
+// Pooling, stage 2 (pool_fin of stack.h) with the final LayerNorm's weight: sum * w / n, then the L2 normalisation
 __global__ __launch_bounds__(256) void k_mb_pool_fin(const float *__restrict__ part, int nch, const int *__restrict__ lens, int H, const float *__restrict__ w,
                                                      int pooling, int normalise, float *__restrict__ out) {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int len = lens[b];
-    float *o = out + (int64_t)b * H;
-    if (len <= 0) {
-        for (int c = tid; c < H; c += 256) o[c] = 0.f;
-        return;
-    }
-    const int n = pooling == AK_POOL_CLS ? 1 : len, used = (n + POOL_CHUNK - 1) / POOL_CHUNK;
-    const float inv_n = 1.0f / (float)n;
-    float y[MB_MAX_H / 256];
-    float s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < MB_MAX_H / 256; j++) {
-        const int c = tid + j * 256;
-        y[j] = 0.f;
-        if (c < H) {
-            for (int ck = 0; ck < used; ck++) y[j] += part[((int64_t)b * nch + ck) * H + c];
-            y[j] = y[j] * w[c] * inv_n;
-            s2 += y[j] * y[j];
-        }
-    }
-    const float sc = block_l2_scale(s2, lane, wave, normalise);
-#pragma unroll
-    for (int j = 0; j < MB_MAX_H / 256; j++) {
-        const int c = tid + j * 256;
-        if (c < H) o[c] = y[j] * sc;
-    }
+    pool_fin<true>(part, nch, lens, H, w, pooling, normalise, out);
 }
 
 }  // namespace
@@ -225,12 +167,9 @@ int launch_mb_rope(uint16_t *q, uint16_t *k, int64_t T, int S, int H, const floa
 // both pooling stages: part [B][ceil(S / 64)][H] floats of workspace
 int launch_mb_pool(const float *x32, const int *lens, int B, int S, int H, float eps, const float *w, int pooling, int normalise, float *part,
                    float *out, hipStream_t st) {
-    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
-    k_mb_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(x32, lens, S, H, eps, pooling, part);
-    AK_HIP(hipGetLastError());
-    k_mb_pool_fin<<<B, 256, 0, st>>>(part, nch, lens, H, w, pooling, normalise, out);
-    AK_HIP(hipGetLastError());
-    return 0;
+    return launch_pool_stages(
+        B, S, H, [&](dim3 grid, size_t lds) { k_mb_pool_part<<<grid, 256, lds, st>>>(x32, lens, S, H, eps, pooling, part); },
+        [&](int nch) { k_mb_pool_fin<<<B, 256, 0, st>>>(part, nch, lens, H, w, pooling, normalise, out); });
 }
 
 namespace {
@@ -240,48 +179,33 @@ struct MbLayer {
     const float *attn_norm, *mlp_norm;         // attn_norm of layer 0: not read
     bool global;
 };
-struct MBert : Stack {
+struct MBert : Enc64 {
     AkModernBertConfig cfg;
     const uint16_t *emb = nullptr; const float *emb_norm = nullptr, *final_norm = nullptr;
     std::vector<MbLayer> layers;
     float *rope_c[2] = {nullptr, nullptr}, *rope_s[2] = {nullptr, nullptr};      // [0] local theta, [1] global theta
-    int Ip = 0;                                // intermediate size as the GEMMs see it (padded_intermediate)
-    float *x32 = nullptr, *y32 = nullptr;
-    uint16_t *h16 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *f = nullptr;
-    float *part = nullptr;                     // pooling: chunk sums [B][ceil(S / 64)][H]
-    int *mask = nullptr, *lens = nullptr;
-};
 
-int mb_forward_locked(MBert &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling, int normalise,
-                      float *out, hipStream_t st) {
-    const AkModernBertConfig &c = d.cfg;
-    const int H = c.hidden, I = d.Ip, heads = c.heads;
-    const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
-    if (d.reserve(tpad, B)) return -10;
-    if (launch_mb_embed(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.emb_norm, c.norm_eps, d.x32, d.h16, d.mask, d.lens, st)) return -10;
-    for (size_t l = 0; l < d.layers.size(); l++) {
-        const MbLayer &ly = d.layers[l];
-        // q (scaled) | k | V^T
-        GemmArgs g = d.gemm(tpad, d.h16, ly.wqkv, 3 * H, H);
-        g.q = d.q; g.k = d.k; g.vt = d.vt; g.H = H; g.S = S; g.qscale = 1.4426950408889634f / sqrtf((float)MB_HD);
-        g.ldo = (int)T;                                        // MODE 0: number of real tokens (rows beyond it have no V^T slot)
-        if (launch_gemm(0, g, st)) return -10;
-        const int tb = ly.global ? 1 : 0;
-        if (launch_mb_rope(d.q, d.k, T, S, H, d.rope_c[tb], d.rope_s[tb], st)) return -10;
-        AttnArgs a{d.q, d.k, d.vt, d.mask, d.ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, d.lens};
-        if (launch_attn_window(a, ly.global ? -1 : c.half_window, st)) return -10;
-        // x += ctx Wo^T; h = LayerNorm(x; mlp_norm)
-        if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, H, d.y32), st)) return -10;
-        if (launch_mb_add_ln(d.x32, d.y32, T, H, ly.mlp_norm, c.norm_eps, d.h16, st)) return -10;
-        // f = gelu(h Wi_a^T) (h Wi_g^T)
-        if (launch_gemm(8, d.gemm_gated(tpad, d.h16, ly.wi, I, H, d.f), st)) return -10;
-        // x += f Wo^T; h = LayerNorm(x; next layer's attn_norm) (after the last layer: the add only, the pool applies final_norm)
-        if (launch_gemm(2, d.gemm_f32(tpad, d.f, ly.wo2, H, I, d.y32), st)) return -10;
-        const float *wn = l + 1 < d.layers.size() ? d.layers[l + 1].attn_norm : nullptr;
-        if (launch_mb_add_ln(d.x32, d.y32, T, H, wn, c.norm_eps, d.h16, st)) return -10;
+    int forward(const int32_t *ids, int ld_ids, const int32_t *lens_in, int lens_stride, int B, int S, int pooling, int normalise, float *out,
+                hipStream_t st) {
+        const float eps = cfg.norm_eps;
+        const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
+        if (reserve(tpad, B)) return -10;
+        if (launch_mb_embed(ids, ld_ids, lens_in, lens_stride, B, S, H, cfg.vocab_size, emb, emb_norm, eps, x32, h16, mask, lens, st)) return -10;
+        for (size_t l = 0; l < layers.size(); l++) {
+            const MbLayer &ly = layers[l];
+            const int tb = ly.global ? 1 : 0;
+            // x += attention(h) Wo^T; h = LayerNorm(x; mlp_norm)
+            if (attention_block(tpad, B, S, ly.wqkv, ly.wo, rope_c[tb], rope_s[tb], ly.global ? -1 : cfg.half_window, st)) return -10;
+            if (launch_mb_add_ln(x32, y32, T, H, ly.mlp_norm, eps, h16, st)) return -10;
+            // x += (gelu(h Wi_a^T) (h Wi_g^T)) Wo^T; h = LayerNorm(x; next layer's attn_norm) (after the last layer: the add only, the
+            // pool applies final_norm)
+            if (ffn_block(8, tpad, ly.wi, ly.wo2, st)) return -10;
+            const float *wn = l + 1 < layers.size() ? layers[l + 1].attn_norm : nullptr;
+            if (launch_mb_add_ln(x32, y32, T, H, wn, eps, h16, st)) return -10;
+        }
+        return launch_mb_pool(x32, lens, B, S, H, eps, final_norm, pooling, normalise, part, out, st) ? -10 : 0;
     }
-    return launch_mb_pool(d.x32, d.lens, B, S, H, c.norm_eps, d.final_norm, pooling, normalise, d.part, out, st) ? -10 : 0;
-}
+};
 }  // namespace
 
 }  // namespace ak
@@ -296,10 +220,7 @@ extern "C" int ak_mbert_create(const AkModernBertConfig *cfg, const void *const 
     *out = nullptr;
     const AkModernBertConfig c = *cfg;
     const int H = c.hidden, I = c.intermediate, L = c.layers;
-    if (L <= 0 || c.vocab_size <= 0 || c.heads <= 0 || H <= 0 || I <= 0 || c.max_position <= 0) AK_FAIL(-1, "ak_mbert_create: sizes must be positive");
-    if (L > AK_MBERT_MAX_LAYERS) AK_FAIL(-1, "ak_mbert_create: more than AK_MBERT_MAX_LAYERS layers");
-    if (H != c.heads * MB_HD) AK_FAIL(-1, "ak_mbert_create: head size (hidden / heads) must be 64");
-    if (H % 128 || H > MB_MAX_H || I % 64) AK_FAIL(-1, "ak_mbert_create: hidden must be a multiple of 128 (<= 1024), intermediate a multiple of 64");
+    if (Enc64::check_sizes("ak_mbert_create", H, I, c.heads, L, c.vocab_size, c.max_position, true)) return -1;
     if (c.half_window < 1) AK_FAIL(-1, "ak_mbert_create: half_window must be >= 1");
     if (!(c.norm_eps > 0.f) || !(c.global_rope_theta > 0.f) || !(c.local_rope_theta > 0.f)) AK_FAIL(-1, "ak_mbert_create: norm_eps and the rope thetas must be positive");
     if (n_weights != 3 + 6 * L) AK_FAIL(-1, "ak_mbert_create: expected 3 + 6 * layers weight pointers");
@@ -310,49 +231,25 @@ extern "C" int ak_mbert_create(const AkModernBertConfig *cfg, const void *const 
     d->emb = (const uint16_t *)w[0];
     d->emb_norm = (const float *)w[1];
     d->final_norm = (const float *)w[2];
-    auto fail = [&](const char *what) { set_error(what); ak_mbert_destroy(d); return -10; };
-    const int Ip = d->Ip = padded_intermediate(I);             // large: 2624 -> 2688
-    d->zero_bias = d->dev_as<float>(std::max<size_t>((size_t)3 * H, (size_t)2 * Ip), true);
-    if (!d->zero_bias) return fail("ak_mbert_create: hipMalloc failed");
-    // the two rotary tables, positions 0 .. min(max_position, 8192) - 1, at head size 64
-    d->n_pos = c.max_position < MB_MAX_S ? c.max_position : MB_MAX_S;
+    auto fail = [&](const char *what) { return enc64_create_failed(d, "ak_mbert_create", what); };
+    if (const char *what = d->init(H, c.heads, I, c.max_position)) return fail(what);
     for (int tb = 0; tb < 2; tb++)
-        if (!d->rope_tables(tb ? c.global_rope_theta : c.local_rope_theta, MB_HD, &d->rope_c[tb], &d->rope_s[tb]))
-            return fail("ak_mbert_create: rotary table upload failed");
+        if (!d->rope_table(tb ? c.global_rope_theta : c.local_rope_theta, &d->rope_c[tb], &d->rope_s[tb])) return fail("rotary table upload failed");
     for (int l = 0; l < L; l++) {
         const void *const *p = w + 3 + 6 * l;      // attn_norm wqkv wo mlp_norm wi mlp_wo
         MbLayer ly{};
-        uint16_t *wi = d->dev_as<uint16_t>((size_t)2 * Ip * H, Ip != I);
-        if (!wi) return fail("ak_mbert_create: hipMalloc failed");
-        // row 2 j = Wi row j, row 2 j + 1 = Wi row I + j (gemm.hip MODE 8)
-        if (!d->interleave_rows(wi, p[4], (const uint16_t *)p[4] + (size_t)I * H, I, H)) return fail("ak_mbert_create: Wi interleave failed");
+        if (const char *what = d->prepare_gated(p[4], (const uint16_t *)p[4] + (size_t)I * H, I, p[5], &ly.wi, &ly.wo2)) return fail(what);
         ly.attn_norm = (const float *)p[0]; ly.wqkv = (const uint16_t *)p[1]; ly.wo = (const uint16_t *)p[2];
-        ly.mlp_norm = (const float *)p[3]; ly.wi = wi; ly.wo2 = (const uint16_t *)p[5];
-        if (Ip != I && !(ly.wo2 = d->pad_cols(p[5], H, I, Ip))) return fail("ak_mbert_create: mlp.Wo padding failed");
+        ly.mlp_norm = (const float *)p[3];
         ly.global = c.layer_global[l] != 0;
         d->layers.push_back(ly);
     }
-    const size_t row16 = (size_t)H * 2;
-    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, row16);
-    d->buffer(&d->q, row16); d->buffer(&d->k, row16); d->buffer(&d->vt, row16); d->buffer(&d->ctx, row16);
-    d->buffer(&d->f, (size_t)Ip * 2); d->buffer(&d->mask, 4); d->buffer(&d->lens, 0, 4);
-    d->buffer(&d->part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
-    if (hipDeviceSynchronize() != hipSuccess) return fail("ak_mbert_create: weight preparation failed");
+    if (hipDeviceSynchronize() != hipSuccess) return fail("weight preparation failed");
     *out = d;
     return 0;
 }
 
 extern "C" int ak_mbert_forward_lens(ak_mbert_t h, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling,
                                      int normalise, float *out, void *stream) {
-    AK_BIND();
-    if (!h) AK_FAIL(-1, "ak_mbert_forward_lens: NULL handle");
-    RoctxRange range("ak_mbert_forward_lens");
-    MBert &d = *(MBert *)h;
-    if (B <= 0) return 0;
-    const bool pool_ok = pooling == AK_POOL_MEAN || pooling == AK_POOL_CLS;
-    if (check_forward_lens("ak_mbert_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, MB_MAX_S, d.n_pos,
-                           pool_ok ? nullptr : "pooling must be AK_POOL_MEAN or AK_POOL_CLS", 65535))
-        return -1;
-    std::lock_guard<std::mutex> lk(d.mu);
-    return mb_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, (hipStream_t)stream);
+    return enc64_forward_lens<MBert>("ak_mbert_forward_lens", h, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, stream);
 }

@@ -12,33 +12,25 @@
 // then mean / cls pooling over the valid tokens of x (no final norm) and L2 normalisation in float32 (k_nb_pool_part, k_nb_pool_fin).
 // The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in mbert.hip.
 // What differs from mbert.hip's k_mb_add_ln is the post-norm: the NORMALISED row goes back to x32 (there: the sum), and the
-// LayerNorms carry a bias. The plumbing is stack.h / stack.hip. Nothing here reads the environment.
+// LayerNorms carry a bias. Here: the config struct's own checks, the layer struct, the order of a layer (block, join, block, join)
+// and the family's kernels: the embedding, the join k_nb_add_ln, the identity transform of the pool. stack.h holds the token-slot
+// prologue, the LayerNorm of a row in registers, both pooling bodies and the NJ dispatch; enc64.h (shared with mbert.hip) the handle's
+// workspace, the common create steps, the attention and FFN blocks and the body of ak_nomic_forward_lens. Nothing here reads the
+// environment.
 // LDS per workgroup: k_nb_embed / k_nb_add_ln none; k_nb_pool_part 4 * H * 4 bytes (dynamic: 12 KB at H = 768); k_nb_pool_fin 16 bytes.
-#include <algorithm>
-#include <cmath>
-
-#include "stack.h"
+#include "enc64.h"
 
 namespace ak {
 
 namespace {
-constexpr int NB_HD = 64, NB_MAX_S = ATTN_LONG_MAX_S, NB_MAX_H = POOL_MAX_H;
-
 // The tail both row kernels share, one wave per row held in registers (NJ float4 per lane, feature c = 4 lane + 256 j; lanes at or
-// past H hold zeros and store nothing): s = the lane's share of the row's sum. Mean, then the variance about it (two passes, as
-// torch's float32 kernel and mb_row_stats -- not E[x^2] - mean^2); x32 row = (f - mean) rstd g + b in float32, h16 row = bf16 of it.
+// past H hold zeros and store nothing): s = the lane's share of the row's sum. The statistics: row_ln_stats (stack.h); x32 row =
+// (f - mean) rstd g + b in float32, h16 row = bf16 of it.
 template <int NJ>
 __device__ inline void nb_ln_store(float4 (&f)[NJ], float s, int H, int lane, const float *__restrict__ g, const float *__restrict__ b, float eps,
                                    float *__restrict__ xr, uint16_t *__restrict__ hr) {
-    const float mean = wave_sum(s) / (float)H;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; j++)
-        if (lane * 4 + j * 256 < H) {
-            const float a = f[j].x - mean, bb = f[j].y - mean, cc = f[j].z - mean, d = f[j].w - mean;
-            q += (a * a + bb * bb) + (cc * cc + d * d);
-        }
-    const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
+    float mean, rstd;
+    row_ln_stats(f, s, H, lane, eps, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
         const int c = lane * 4 + j * 256;
@@ -63,20 +55,8 @@ __global__ __launch_bounds__(256) void k_nb_embed(const int *__restrict__ ids, i
     const int lane = threadIdx.x & 63;
     if (t >= (int64_t)B * S) return;
     const int id = token_slot<true>(ids, ld_ids, lens, lens_stride, S, vocab, t, lane, mask, lens_out);
-    const uint16_t *e = word + (int64_t)id * H;
     float4 f[NJ];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; j++) {
-        const int c = lane * 4 + j * 256;
-        f[j] = float4{0.f, 0.f, 0.f, 0.f};
-        if (c < H) {
-            f[j] = load_bf16x4(e + c);
-            const float4 ty = *(const float4 *)(type0 + c);
-            f[j].x += ty.x; f[j].y += ty.y; f[j].z += ty.z; f[j].w += ty.w;
-            s += (f[j].x + f[j].y) + (f[j].z + f[j].w);
-        }
-    }
+    const float s = row_load_sum<false>(word + (int64_t)id * H, type0, H, lane, f);
     nb_ln_store<NJ>(f, s, H, lane, g, b, eps, x32 + t * H, h16 + t * H);
 }
 
@@ -89,20 +69,8 @@ __global__ __launch_bounds__(256) void k_nb_add_ln(float *__restrict__ x32, cons
     const int lane = threadIdx.x & 63;
     if (t >= T) return;
     float *xr = x32 + t * H;
-    const float *yr = y32 + t * H;
     float4 f[NJ];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; j++) {
-        const int c = lane * 4 + j * 256;
-        f[j] = float4{0.f, 0.f, 0.f, 0.f};
-        if (c < H) {
-            f[j] = *(const float4 *)(xr + c);
-            const float4 y = *(const float4 *)(yr + c);
-            f[j].x += y.x; f[j].y += y.y; f[j].z += y.z; f[j].w += y.w;
-            s += (f[j].x + f[j].y) + (f[j].z + f[j].w);
-        }
-    }
+    const float s = row_load_sum<false>(xr, y32 + t * H, H, lane, f);
     nb_ln_store<NJ>(f, s, H, lane, g, b, eps, xr, h16 + t * H);
 }
 
@@ -113,7 +81,7 @@ struct NbIdentity {
     struct Token {
         __device__ float apply(float x) const { return x; }
     };
-    __device__ int count(int len) const { return len <= 0 ? 0 : (pooling == AK_POOL_CLS ? 1 : len); }
+    __device__ int count(int len) const { return pooled_count(len, pooling); }
     __device__ Token begin(const float *, int, int) const { return Token{}; }
 };
 __global__ __launch_bounds__(256) void k_nb_pool_part(const float *__restrict__ x32, const int *__restrict__ lens, int S, int H, int pooling,
@@ -121,37 +89,10 @@ __global__ __launch_bounds__(256) void k_nb_pool_part(const float *__restrict__ 
     pool_part(x32, lens, S, H, NbIdentity{pooling}, part);
 }
 
-// Pooling, stage 2. One workgroup per row b: the chunk sums added in chunk order, / n, then the L2 normalisation. A row of length 0
-// embeds to zeros.
+// Pooling, stage 2 (pool_fin of stack.h) without a weight: sum / n, then the L2 normalisation
 __global__ __launch_bounds__(256) void k_nb_pool_fin(const float *__restrict__ part, int nch, const int *__restrict__ lens, int H, int pooling,
                                                      int normalise, float *__restrict__ out) {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int len = lens[b];
-    float *o = out + (int64_t)b * H;
-    if (len <= 0) {
-        for (int c = tid; c < H; c += 256) o[c] = 0.f;
-        return;
-    }
-    const int n = pooling == AK_POOL_CLS ? 1 : len, used = (n + POOL_CHUNK - 1) / POOL_CHUNK;
-    const float inv_n = 1.0f / (float)n;
-    float y[NB_MAX_H / 256];
-    float s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NB_MAX_H / 256; j++) {
-        const int c = tid + j * 256;
-        y[j] = 0.f;
-        if (c < H) {
-            for (int ck = 0; ck < used; ck++) y[j] += part[((int64_t)b * nch + ck) * H + c];
-            y[j] = y[j] * inv_n;
-            s2 += y[j] * y[j];
-        }
-    }
-    const float sc = block_l2_scale(s2, lane, wave, normalise);
-#pragma unroll
-    for (int j = 0; j < NB_MAX_H / 256; j++) {
-        const int c = tid + j * 256;
-        if (c < H) o[c] = y[j] * sc;
-    }
+    pool_fin<false>(part, nch, lens, H, nullptr, pooling, normalise, out);
 }
 
 }  // namespace
@@ -177,12 +118,9 @@ int launch_nb_add_ln(float *x32, const float *y32, int64_t T, int H, const float
 
 // both pooling stages: part [B][ceil(S / 64)][H] floats of workspace
 int launch_nb_pool(const float *x32, const int *lens, int B, int S, int H, int pooling, int normalise, float *part, float *out, hipStream_t st) {
-    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
-    k_nb_pool_part<<<dim3((unsigned)nch, (unsigned)B), 256, (size_t)4 * H * 4, st>>>(x32, lens, S, H, pooling, part);
-    AK_HIP(hipGetLastError());
-    k_nb_pool_fin<<<B, 256, 0, st>>>(part, nch, lens, H, pooling, normalise, out);
-    AK_HIP(hipGetLastError());
-    return 0;
+    return launch_pool_stages(
+        B, S, H, [&](dim3 grid, size_t lds) { k_nb_pool_part<<<grid, 256, lds, st>>>(x32, lens, S, H, pooling, part); },
+        [&](int nch) { k_nb_pool_fin<<<B, 256, 0, st>>>(part, nch, lens, H, pooling, normalise, out); });
 }
 
 namespace {
@@ -190,47 +128,30 @@ struct NbLayer {
     const uint16_t *wqkv, *wo, *wgu, *wdown;   // wqkv (concatenated) and wgu (gate / up interleaved) are owned, wdown too when I is padded
     const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
 };
-struct Nomic : Stack {
+struct Nomic : Enc64 {
     AkNomicBertConfig cfg;
     const uint16_t *word = nullptr; const float *type0 = nullptr, *emb_g = nullptr, *emb_b = nullptr;
     std::vector<NbLayer> layers;
     float *rope_c = nullptr, *rope_s = nullptr;
-    int Ip = 0;                                // intermediate size as the GEMMs see it (padded_intermediate)
-    float *x32 = nullptr, *y32 = nullptr;
-    uint16_t *h16 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *f = nullptr;
-    float *part = nullptr;                     // pooling: chunk sums [B][ceil(S / 64)][H]
-    int *mask = nullptr, *lens = nullptr;
-};
 
-int nb_forward_locked(Nomic &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling, int normalise,
-                      float *out, hipStream_t st) {
-    const AkNomicBertConfig &c = d.cfg;
-    const int H = c.hidden, I = d.Ip, heads = c.heads;
-    const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
-    if (d.reserve(tpad, B)) return -10;
-    if (launch_nb_embed(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.word, d.type0, d.emb_g, d.emb_b, c.ln_eps, d.x32, d.h16, d.mask,
-                        d.lens, st))
-        return -10;
-    for (const NbLayer &ly : d.layers) {
-        // q (scaled) | k | V^T
-        GemmArgs g = d.gemm(tpad, d.h16, ly.wqkv, 3 * H, H);
-        g.q = d.q; g.k = d.k; g.vt = d.vt; g.H = H; g.S = S; g.qscale = 1.4426950408889634f / sqrtf((float)NB_HD);
-        g.ldo = (int)T;                                        // MODE 0: number of real tokens (rows beyond it have no V^T slot)
-        if (launch_gemm(0, g, st)) return -10;
-        if (launch_mb_rope(d.q, d.k, T, S, H, d.rope_c, d.rope_s, st)) return -10;
-        AttnArgs a{d.q, d.k, d.vt, d.mask, d.ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, d.lens};
-        if (launch_attn_window(a, -1, st)) return -10;
-        // x = LayerNorm(x + ctx Wo^T; ln1)
-        if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, H, d.y32), st)) return -10;
-        if (launch_nb_add_ln(d.x32, d.y32, T, H, ly.ln1_g, ly.ln1_b, c.ln_eps, d.h16, st)) return -10;
-        // f = silu(h Wgate^T) (h Wup^T)
-        if (launch_gemm(7, d.gemm_gated(tpad, d.h16, ly.wgu, I, H, d.f), st)) return -10;
-        // x = LayerNorm(x + f Wdown^T; ln2)
-        if (launch_gemm(2, d.gemm_f32(tpad, d.f, ly.wdown, H, I, d.y32), st)) return -10;
-        if (launch_nb_add_ln(d.x32, d.y32, T, H, ly.ln2_g, ly.ln2_b, c.ln_eps, d.h16, st)) return -10;
+    int forward(const int32_t *ids, int ld_ids, const int32_t *lens_in, int lens_stride, int B, int S, int pooling, int normalise, float *out,
+                hipStream_t st) {
+        const float eps = cfg.ln_eps;
+        const int64_t T = (int64_t)B * S, tpad = (T + 255) / 256 * 256;
+        if (reserve(tpad, B)) return -10;
+        if (launch_nb_embed(ids, ld_ids, lens_in, lens_stride, B, S, H, cfg.vocab_size, word, type0, emb_g, emb_b, eps, x32, h16, mask, lens, st))
+            return -10;
+        for (const NbLayer &ly : layers) {
+            // x = LayerNorm(x + attention(h) Wo^T; ln1), every key
+            if (attention_block(tpad, B, S, ly.wqkv, ly.wo, rope_c, rope_s, -1, st)) return -10;
+            if (launch_nb_add_ln(x32, y32, T, H, ly.ln1_g, ly.ln1_b, eps, h16, st)) return -10;
+            // x = LayerNorm(x + (silu(h Wgate^T) (h Wup^T)) Wdown^T; ln2)
+            if (ffn_block(7, tpad, ly.wgu, ly.wdown, st)) return -10;
+            if (launch_nb_add_ln(x32, y32, T, H, ly.ln2_g, ly.ln2_b, eps, h16, st)) return -10;
+        }
+        return launch_nb_pool(x32, lens, B, S, H, pooling, normalise, part, out, st) ? -10 : 0;
     }
-    return launch_nb_pool(d.x32, d.lens, B, S, H, pooling, normalise, d.part, out, st) ? -10 : 0;
-}
+};
 }  // namespace
 
 }  // namespace ak
@@ -245,11 +166,7 @@ extern "C" int ak_nomic_create(const AkNomicBertConfig *cfg, const void *const *
     *out = nullptr;
     const AkNomicBertConfig c = *cfg;
     const int H = c.hidden, I = c.intermediate, L = c.layers;
-    if (L <= 0 || c.vocab_size <= 0 || c.heads <= 0 || H <= 0 || I <= 0 || c.type_vocab <= 0 || c.max_position <= 0)
-        AK_FAIL(-1, "ak_nomic_create: sizes must be positive");
-    if (L > AK_MBERT_MAX_LAYERS) AK_FAIL(-1, "ak_nomic_create: more than AK_MBERT_MAX_LAYERS layers");
-    if (H != c.heads * NB_HD) AK_FAIL(-1, "ak_nomic_create: head size (hidden / heads) must be 64");
-    if (H % 128 || H > NB_MAX_H || I % 64) AK_FAIL(-1, "ak_nomic_create: hidden must be a multiple of 128 (<= 1024), intermediate a multiple of 64");
+    if (Enc64::check_sizes("ak_nomic_create", H, I, c.heads, L, c.vocab_size, c.max_position, c.type_vocab > 0)) return -1;
     if (!(c.ln_eps > 0.f) || !(c.rope_theta > 0.f)) AK_FAIL(-1, "ak_nomic_create: ln_eps and rope_theta must be positive");
     if (n_weights != 4 + 11 * L) AK_FAIL(-1, "ak_nomic_create: expected 4 + 11 * layers weight pointers");
     for (int i = 0; i < n_weights; i++)
@@ -260,48 +177,26 @@ extern "C" int ak_nomic_create(const AkNomicBertConfig *cfg, const void *const *
     d->type0 = (const float *)w[1];            // row 0 of [type_vocab][H]: single sentences only
     d->emb_g = (const float *)w[2];
     d->emb_b = (const float *)w[3];
-    auto fail = [&](const char *what) { set_error(what); ak_nomic_destroy(d); return -10; };
-    const int Ip = d->Ip = padded_intermediate(I);
-    d->zero_bias = d->dev_as<float>(std::max<size_t>((size_t)3 * H, (size_t)2 * Ip), true);
-    if (!d->zero_bias) return fail("ak_nomic_create: hipMalloc failed");
-    // one rotary table, positions 0 .. min(max_position, 8192) - 1, at head size 64
-    d->n_pos = c.max_position < NB_MAX_S ? c.max_position : NB_MAX_S;
-    if (!d->rope_tables(c.rope_theta, NB_HD, &d->rope_c, &d->rope_s)) return fail("ak_nomic_create: rotary table upload failed");
+    auto fail = [&](const char *what) { return enc64_create_failed(d, "ak_nomic_create", what); };
+    if (const char *what = d->init(H, c.heads, I, c.max_position)) return fail(what);
+    if (!d->rope_table(c.rope_theta, &d->rope_c, &d->rope_s)) return fail("rotary table upload failed");
     for (int l = 0; l < L; l++) {
         const void *const *p = w + 4 + 11 * l;     // wq wk wv wo ln1_g ln1_b w_gate w_up w_down ln2_g ln2_b
         NbLayer ly{};
         uint16_t *wqkv = d->dev_as<uint16_t>((size_t)3 * H * H);
-        uint16_t *wgu = d->dev_as<uint16_t>((size_t)2 * Ip * H, Ip != I);
-        if (!wqkv || !wgu) return fail("ak_nomic_create: hipMalloc failed");
-        if (!d->concat_rows(wqkv, H, {{p[0], (size_t)H}, {p[1], (size_t)H}, {p[2], (size_t)H}})) return fail("ak_nomic_create: QKV concatenation failed");
-        // row 2 j = gate row j, row 2 j + 1 = up row j (gemm.hip MODE 7)
-        if (!d->interleave_rows(wgu, p[6], p[7], I, H)) return fail("ak_nomic_create: gate / up interleave failed");
+        if (!wqkv) return fail("hipMalloc failed");
+        if (!d->concat_rows(wqkv, H, {{p[0], (size_t)H}, {p[1], (size_t)H}, {p[2], (size_t)H}})) return fail("QKV concatenation failed");
+        if (const char *what = d->prepare_gated(p[6], p[7], I, p[8], &ly.wgu, &ly.wdown)) return fail(what);
         ly.wqkv = wqkv; ly.wo = (const uint16_t *)p[3]; ly.ln1_g = (const float *)p[4]; ly.ln1_b = (const float *)p[5];
-        ly.wgu = wgu; ly.wdown = (const uint16_t *)p[8]; ly.ln2_g = (const float *)p[9]; ly.ln2_b = (const float *)p[10];
-        if (Ip != I && !(ly.wdown = d->pad_cols(p[8], H, I, Ip))) return fail("ak_nomic_create: w_down padding failed");
+        ly.ln2_g = (const float *)p[9]; ly.ln2_b = (const float *)p[10];
         d->layers.push_back(ly);
     }
-    const size_t row16 = (size_t)H * 2;
-    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, row16);
-    d->buffer(&d->q, row16); d->buffer(&d->k, row16); d->buffer(&d->vt, row16); d->buffer(&d->ctx, row16);
-    d->buffer(&d->f, (size_t)Ip * 2); d->buffer(&d->mask, 4); d->buffer(&d->lens, 0, 4);
-    d->buffer(&d->part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
-    if (hipDeviceSynchronize() != hipSuccess) return fail("ak_nomic_create: weight preparation failed");
+    if (hipDeviceSynchronize() != hipSuccess) return fail("weight preparation failed");
     *out = d;
     return 0;
 }
 
 extern "C" int ak_nomic_forward_lens(ak_nomic_t h, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling,
                                      int normalise, float *out, void *stream) {
-    AK_BIND();
-    if (!h) AK_FAIL(-1, "ak_nomic_forward_lens: NULL handle");
-    RoctxRange range("ak_nomic_forward_lens");
-    Nomic &d = *(Nomic *)h;
-    if (B <= 0) return 0;
-    const bool pool_ok = pooling == AK_POOL_MEAN || pooling == AK_POOL_CLS;
-    if (check_forward_lens("ak_nomic_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, NB_MAX_S, d.n_pos,
-                           pool_ok ? nullptr : "pooling must be AK_POOL_MEAN or AK_POOL_CLS", 65535))
-        return -1;
-    std::lock_guard<std::mutex> lk(d.mu);
-    return nb_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, (hipStream_t)stream);
+    return enc64_forward_lens<Nomic>("ak_nomic_forward_lens", h, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, stream);
 }

@@ -1,9 +1,12 @@
-// stack.h -- what the pre-norm stacks (decoder.hip: Qwen3, mbert.hip: ModernBERT, gemma.hip: EmbeddingGemma) share: a float32
-// residual stream feeding bf16 GEMM rows, one wave per token in the row kernels, pooling in chunks of 64 tokens. Plumbing only:
-// each family keeps its own formulas (the order of its sums is part of what it computes) and its own kernels.
-//   device: wave_sum, token_slot, load_bf16x4 / store_bf16x4, block_l2_scale, pool_part
-//   host:   dispatch_nj, Stack (owned device memory, weight preparation, workspace, rotary tables, GemmArgs), stack_destroy,
-//           check_forward_lens (stack.hip holds what is better not inlined)
+// stack.h -- what the stacks (decoder.hip: Qwen3, mbert.hip: ModernBERT, gemma.hip: EmbeddingGemma, nomic.hip: NomicBERT) share: a
+// float32 residual stream feeding bf16 GEMM rows, one wave per token in the row kernels, pooling in chunks of 64 tokens. Plumbing
+// only: each family keeps its own kernels, and where a formula is stated here (the LayerNorm statistics of a row in registers, the
+// pooling stages) the order of its sums is part of the statement.
+//   device: wave_sum, token_slot, load_bf16x4 / store_bf16x4, row_sum4 / row_sq4, row_load_sum / row_ln_stats (the LayerNorm
+//           families: mbert.hip, nomic.hip), block_l2_scale, pooled_count, pool_part, pool_fin
+//   host:   dispatch_nj, launch_pool_stages, Stack (owned device memory, weight preparation, workspace, rotary tables, GemmArgs),
+//           stack_destroy, check_forward_lens (stack.hip holds what is better not inlined)
+// enc64.h builds the head-64 encoder base of mbert.hip and nomic.hip on Stack.
 #pragma once
 #include <mutex>
 #include <type_traits>
@@ -50,6 +53,46 @@ __device__ inline void store_bf16x4(uint16_t *p, float x, float y, float z, floa
     *(uint2 *)p = uint2{mt::pack_bf16x2(x, y), mt::pack_bf16x2(z, w)};
 }
 
+// ---- a LayerNorm row in registers: NJ float4 per lane, feature c = 4 lane + 256 j; lanes at or past H hold zeros ----
+__device__ inline float4 load_row4(const float *p) { return *(const float4 *)p; }
+__device__ inline float4 load_row4(const uint16_t *p) { return load_bf16x4(p); }
+// one float4's share of a row's sum, and of its sum of squares about `mean`: the pairing is part of the statement
+__device__ inline float row_sum4(const float4 &f) { return (f.x + f.y) + (f.z + f.w); }
+__device__ inline float row_sq4(const float4 &f, float mean) {
+    const float a = f.x - mean, b = f.y - mean, c = f.z - mean, d = f.w - mean;
+    return (a * a + b * b) + (c * c + d * d);
+}
+// f = row a (float32, or bf16 widened) + row b, one float32 add per feature; STORE: the sum goes back to a. Returns the lane's share
+// of the row's sum.
+template <bool STORE, int NJ, class A>
+__device__ inline float row_load_sum(A *__restrict__ ar, const float *__restrict__ br, int H, int lane, float4 (&f)[NJ]) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int c = lane * 4 + j * 256;
+        f[j] = float4{0.f, 0.f, 0.f, 0.f};
+        if (c < H) {
+            f[j] = load_row4(ar + c);
+            const float4 y = *(const float4 *)(br + c);
+            f[j].x += y.x; f[j].y += y.y; f[j].z += y.z; f[j].w += y.w;
+            if constexpr (STORE) *(float4 *)(ar + c) = f[j];
+            s += row_sum4(f[j]);
+        }
+    }
+    return s;
+}
+// s = the lane's share of the row's sum -> mean, then the variance about it (two passes, as torch's float32 kernel -- not
+// E[x^2] - mean^2), rstd = rsqrt(var + eps)
+template <int NJ>
+__device__ inline void row_ln_stats(const float4 (&f)[NJ], float s, int H, int lane, float eps, float &mean, float &rstd) {
+    mean = wave_sum(s) / (float)H;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+        if (lane * 4 + j * 256 < H) q += row_sq4(f[j], mean);
+    rstd = rsqrtf(wave_sum(q) / (float)H + eps);
+}
+
 // The L2 tail of a 4-wave workgroup (thread = 64 wave + lane): s2 = each thread's share of a row's sum of squares; the wave sums
 // meet in wave order through 16 bytes of LDS. Returns 1 / max(|row|, 1e-12) (torch.nn.functional.normalize's eps), or 1 when normalise == 0.
 __device__ inline float block_l2_scale(float s2, int lane, int wave, int normalise) {
@@ -60,6 +103,9 @@ __device__ inline float block_l2_scale(float s2, int lane, int wave, int normali
     const float tot = ((red[0] + red[1]) + red[2]) + red[3];
     return normalise ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 1.0f;
 }
+
+// tokens that mean / cls pooling sums in a row of length len
+__device__ inline int pooled_count(int len, int pooling) { return len <= 0 ? 0 : (pooling == AK_POOL_CLS ? 1 : len); }
 
 // Pooling, stage 1, of workgroup (chunk ck = blockIdx.x, row b = blockIdx.y), 4 waves: tokens 64 ck .. 64 ck + 63 below n of row b,
 // each through the per-token transform, summed: wave v takes tokens v, v + 4, ...; the four wave partials are added in wave order
@@ -98,6 +144,39 @@ __device__ inline void pool_part(const float *x32, const int *lens, int S, int H
     for (int c = tid; c < H; c += 256) o[c] = ((lds[c] + lds[H + c]) + lds[2 * H + c]) + lds[3 * H + c];
 }
 
+// Pooling, stage 2, of workgroup b = blockIdx.x (256 threads) behind pool_part on pooled_count tokens: the chunk sums added in chunk
+// order, WEIGHT: * w[c], / n, then the L2 normalisation. A row of length 0 embeds to zeros.
+template <bool WEIGHT>
+__device__ inline void pool_fin(const float *part, int nch, const int *lens, int H, const float *w, int pooling, int normalise, float *out) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len = lens[b];
+    float *o = out + (int64_t)b * H;
+    if (len <= 0) {
+        for (int c = tid; c < H; c += 256) o[c] = 0.f;
+        return;
+    }
+    const int n = pooled_count(len, pooling), used = (n + POOL_CHUNK - 1) / POOL_CHUNK;
+    const float inv_n = 1.0f / (float)n;
+    float y[POOL_MAX_H / 256];
+    float s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < POOL_MAX_H / 256; j++) {
+        const int c = tid + j * 256;
+        y[j] = 0.f;
+        if (c < H) {
+            for (int ck = 0; ck < used; ck++) y[j] += part[((int64_t)b * nch + ck) * H + c];
+            y[j] = WEIGHT ? y[j] * w[c] * inv_n : y[j] * inv_n;
+            s2 += y[j] * y[j];
+        }
+    }
+    const float sc = block_l2_scale(s2, lane, wave, normalise);
+#pragma unroll
+    for (int j = 0; j < POOL_MAX_H / 256; j++) {
+        const int c = tid + j * 256;
+        if (c < H) o[c] = y[j] * sc;
+    }
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------
 // The row kernels that hold a row in registers are templates over NJ = ceil(H / 256) float4 per lane, H <= 1024:
 // f(std::integral_constant<int, NJ>)
@@ -109,6 +188,18 @@ inline void dispatch_nj(int H, F &&f) {
         case 3: f(std::integral_constant<int, 3>{}); break;
         default: f(std::integral_constant<int, 4>{}); break;
     }
+}
+
+// Both stages of a pool_part / pool_fin pair: part(grid, lds_bytes) launches stage 1 on (chunk, row) workgroups with its [4][H]
+// floats of dynamic LDS, fin(nch) stage 2 on the nch = ceil(S / 64) chunk sums per row
+template <class P, class F>
+inline int launch_pool_stages(int B, int S, int H, P &&part, F &&fin) {
+    const int nch = (S + POOL_CHUNK - 1) / POOL_CHUNK;
+    part(dim3((unsigned)nch, (unsigned)B), (size_t)4 * H * 4);
+    AK_HIP(hipGetLastError());
+    fin(nch);
+    AK_HIP(hipGetLastError());
+    return 0;
 }
 
 // 2 I off the wide GEMM tile (ModernBERT large: 5248 = 41 x 128): the interleaved gate / up matrix gets zero rows up to a multiple

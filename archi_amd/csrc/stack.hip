@@ -1,9 +1,11 @@
 // stack.hip -- the host side of stack.h: rotary tables, owned device memory and weight preparation, the workspace, the argument
-// checks of the ak_*_forward_lens entry points. No kernels.
+// checks of the ak_*_forward_lens entry points, and of enc64.h: the create steps and the two forward blocks of the head-64 encoders.
+// No kernels.
+#include <algorithm>
 #include <cmath>
 #include <string>
 
-#include "stack.h"
+#include "enc64.h"
 
 namespace ak {
 
@@ -115,6 +117,59 @@ int check_forward_lens(const char *fn, const void *ids, const void *lens, const 
     if (S > n_pos) AK_FAIL(-1, f + "S exceeds max_position");
     if (max_B && B > max_B) AK_FAIL(-1, f + "at most " + std::to_string(max_B) + " rows per call");
     return 0;
+}
+
+// ---- the head-64 encoder base (enc64.h) --------------------------------------------------------------------------------------
+int Enc64::check_sizes(const char *fn, int H, int I, int heads, int L, int vocab, int max_position, bool others_positive) {
+    const std::string f = std::string(fn) + ": ";
+    if (L <= 0 || vocab <= 0 || heads <= 0 || H <= 0 || I <= 0 || max_position <= 0 || !others_positive) AK_FAIL(-1, f + "sizes must be positive");
+    if (L > AK_MBERT_MAX_LAYERS) AK_FAIL(-1, f + "more than AK_MBERT_MAX_LAYERS layers");
+    if (H != heads * HD) AK_FAIL(-1, f + "head size (hidden / heads) must be 64");
+    if (H % 128 || H > MAX_H || I % 64) AK_FAIL(-1, f + "hidden must be a multiple of 128 (<= 1024), intermediate a multiple of 64");
+    return 0;
+}
+
+const char *Enc64::init(int hidden, int n_heads, int I, int max_position) {
+    H = hidden; heads = n_heads;
+    Ip = padded_intermediate(I);               // ModernBERT large: 2624 -> 2688
+    zero_bias = dev_as<float>(std::max<size_t>((size_t)3 * H, (size_t)2 * Ip), true);
+    if (!zero_bias) return "hipMalloc failed";
+    n_pos = max_position < MAX_S ? max_position : MAX_S;
+    const size_t row16 = (size_t)H * 2;
+    buffer(&x32, (size_t)H * 4); buffer(&y32, (size_t)H * 4); buffer(&h16, row16);
+    buffer(&q, row16); buffer(&k, row16); buffer(&vt, row16); buffer(&ctx, row16);
+    buffer(&f, (size_t)Ip * 2); buffer(&mask, 4); buffer(&lens, 0, 4);
+    buffer(&part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
+    return nullptr;
+}
+
+const char *Enc64::prepare_gated(const void *a, const void *b, int I, const void *down, const uint16_t **wgu, const uint16_t **wdown) {
+    uint16_t *w = dev_as<uint16_t>((size_t)2 * Ip * H, Ip != I);
+    if (!w) return "hipMalloc failed";
+    if (!interleave_rows(w, a, b, I, H)) return "gate / up interleave failed";
+    *wgu = w;
+    *wdown = (const uint16_t *)down;
+    if (Ip != I && !(*wdown = pad_cols(down, H, I, Ip))) return "down projection padding failed";
+    return nullptr;
+}
+
+int Enc64::attention_block(int64_t tpad, int B, int S, const uint16_t *wqkv, const uint16_t *wo, const float *rc, const float *rs, int half_window,
+                           hipStream_t st) {
+    const int64_t T = (int64_t)B * S;
+    // q (scaled) | k | V^T
+    GemmArgs g = gemm(tpad, h16, wqkv, 3 * H, H);
+    g.q = q; g.k = k; g.vt = vt; g.H = H; g.S = S; g.qscale = 1.4426950408889634f / sqrtf((float)HD);
+    g.ldo = (int)T;                                            // MODE 0: number of real tokens (rows beyond it have no V^T slot)
+    if (launch_gemm(0, g, st)) return -10;
+    if (launch_mb_rope(q, k, T, S, H, rc, rs, st)) return -10;
+    AttnArgs a{q, k, vt, mask, ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, lens};
+    if (launch_attn_window(a, half_window, st)) return -10;
+    return launch_gemm(2, gemm_f32(tpad, ctx, wo, H, H, y32), st) ? -10 : 0;
+}
+
+int Enc64::ffn_block(int mode, int64_t tpad, const uint16_t *wgu, const uint16_t *wdown, hipStream_t st) {
+    if (launch_gemm(mode, gemm_gated(tpad, h16, wgu, Ip, H, f), st)) return -10;
+    return launch_gemm(2, gemm_f32(tpad, f, wdown, H, Ip, y32), st) ? -10 : 0;
 }
 
 }  // namespace ak

@@ -265,6 +265,7 @@ def geglu_tanh_interleaved(y: "np.ndarray") -> "np.ndarray":
 
 class HipGemma(HipStack):
     family, prefix, embed_key, matrix_keys, out_name = "Gemma", "gemma", "embed", MATRIX_KEYS, "out_dim"
+    poolings, pooling_noun = ("mean",), "Gemma embedders"
 
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None, dense: bool = True):
         """shape: a GEMMA_SHAPES tuple or name; weights: our names (weight_names), numpy arrays or torch tensors. dense=False leaves
@@ -295,9 +296,3 @@ class HipGemma(HipStack):
         # the rotary tables from HF's own inverse frequencies (rope_inv_freq) in place of the library's correctly rounded ones
         self._inv_freq = (rope_inv_freq(theta_g), rope_inv_freq(theta_l))
         check(self._lib.ak_gemma_set_rope_inv_freq(self._h, self._inv_freq[0].ctypes.data, self._inv_freq[1].ctypes.data), "ak_gemma_set_rope_inv_freq")
-
-    def _pooling(self, pooling):
-        pooling = pooling or self.pooling
-        if pooling != "mean":
-            raise ValueError(f"pooling {pooling!r}: Gemma embedders pool 'mean'")
-        return pooling

@@ -15,7 +15,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import MBERT_MAX_LAYERS, POOLING, AkModernBertConfig
+from ._lib import MBERT_MAX_LAYERS, AkModernBertConfig
 from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
 
 MAX_SEQ = 8192          # longest row the kernels take (attn_long.hip)
@@ -199,7 +199,7 @@ def geglu_interleaved(y: "np.ndarray") -> "np.ndarray":
 
 
 class HipModernBert(HipStack):
-    family, prefix, embed_key, matrix_keys = "ModernBERT", "mbert", "tok_embeddings", MATRIX_KEYS
+    family, prefix, embed_key, matrix_keys, pooling_noun = "ModernBERT", "mbert", "tok_embeddings", MATRIX_KEYS, "ModernBERT models"
 
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
         """shape: a MODERNBERT_SHAPES tuple or name; weights: our names (weight_names), numpy arrays or torch tensors."""
@@ -217,9 +217,3 @@ class HipModernBert(HipStack):
             ptr_names += ["emb_norm" if (l == 0 and k == "attn_norm") else f"l{l}.{k}" for k in LAYER_KEYS]
         self._create(AkModernBertConfig(vocab, H, L, heads, I, max_pos, eps, theta_g, theta_l, local // 2, (ctypes.c_int * MBERT_MAX_LAYERS)(*types)),
                      ptr_names)
-
-    def _pooling(self, pooling):
-        pooling = pooling or self.pooling
-        if pooling not in POOLING:
-            raise ValueError(f"pooling {pooling!r}: ModernBERT models pool 'mean' or 'cls'")
-        return pooling

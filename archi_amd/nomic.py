@@ -15,7 +15,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import MBERT_MAX_LAYERS, POOLING, AkNomicBertConfig
+from ._lib import MBERT_MAX_LAYERS, AkNomicBertConfig
 from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
 
 MAX_SEQ = 8192          # longest row the kernels take (attn_long.hip)
@@ -237,7 +237,7 @@ def load_nomic_weights(model_dir: str):
 
 
 class HipNomicBert(HipStack):
-    family, prefix, embed_key, matrix_keys = "nomic", "nomic", "word_emb", MATRIX_KEYS
+    family, prefix, embed_key, matrix_keys, pooling_noun = "nomic", "nomic", "word_emb", MATRIX_KEYS, "NomicBERT models"
 
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
         """shape: a NOMIC_SHAPES tuple or name; weights: our names (weight_names), numpy arrays or torch tensors."""
@@ -252,9 +252,3 @@ class HipNomicBert(HipStack):
         names = weight_names(L)
         self._upload(weights, names, device)
         self._create(AkNomicBertConfig(vocab, H, L, heads, I, types, max_pos, eps, theta), names)
-
-    def _pooling(self, pooling):
-        pooling = pooling or self.pooling
-        if pooling not in POOLING:
-            raise ValueError(f"pooling {pooling!r}: NomicBERT models pool 'mean' or 'cls'")
-        return pooling

@@ -3,7 +3,7 @@
 TFLOP/s and share of the 2.5 PF bf16 peak; beside them in the same run the bge-base forward at 128 x 512 (the project's flagship
 encoder on the same token count) and transformers NomicBertModel bf16 + SDPA on the same GPU and ids; per-launch times of the three new
 launches (k_nb_embed, k_nb_add_ln, k_nb_pool_part + k_nb_pool_fin) at both workloads' token counts with their GB/s and share of the
-8 TB/s HBM peak, measured in a child process on libarchi_hip_dbg.so through the ak_ktn_* wrappers; then a check of the timed outputs
+8 TB/s HBM peak, measured in a child process on libarchi_hip_dbg.so through the ak_kts_nb_* wrappers; then a check of the timed outputs
 against float32 NomicBertModel on the CPU on sampled rows of the 512-token workload (exit status 1 on a mismatch; 8192-token rows are
 checked by tests/test_nomic_gpu.py on a small shape). Prints ONE JSON line and writes it to --out.
 
@@ -89,16 +89,16 @@ def launches(iters, warmup, seed):
 
         def embed():
             for _ in range(rep):
-                _lib.check(lib.ak_ktn_embed(P(stage), S + 1, ctypes.c_void_p(stage.data_ptr() + 4 * S), S + 1, B, S, H, vocab, P(word), P(typ), P(gam),
-                                            P(bet), eps, P(x32), P(h16), P(mask), P(lens), None), "ak_ktn_embed")
+                _lib.check(lib.ak_kts_nb_embed(P(stage), S + 1, ctypes.c_void_p(stage.data_ptr() + 4 * S), S + 1, B, S, H, vocab, P(word), P(typ), P(gam),
+                                            P(bet), eps, P(x32), P(h16), P(mask), P(lens), None), "ak_kts_nb_embed")
 
         def add_ln():
             for _ in range(rep):
-                _lib.check(lib.ak_ktn_add_ln(P(x32), P(y32), T, H, P(gam), P(bet), eps, P(h16), None), "ak_ktn_add_ln")
+                _lib.check(lib.ak_kts_nb_add_ln(P(x32), P(y32), T, H, P(gam), P(bet), eps, P(h16), None), "ak_kts_nb_add_ln")
 
         def pool():
             for _ in range(rep):
-                _lib.check(lib.ak_ktn_pool(P(x32), P(lens), B, S, H, 0, 1, P(part), P(pooled), None), "ak_ktn_pool")
+                _lib.check(lib.ak_kts_nb_pool(P(x32), P(lens), B, S, H, 0, 1, P(part), P(pooled), None), "ak_kts_nb_pool")
 
         for name, fn, bytes_tok in (("k_nb_embed", embed, 8 * H), ("k_nb_add_ln", add_ln, 14 * H), ("k_nb_pool_part+fin", pool, 4 * H)):
             ms, _ = timed(fn, iters, warmup)

@@ -1,5 +1,5 @@
 """Cases, inputs, float64 statements, derived bounds, float32 emulations and mutants of NomicBERT's three row kernels (csrc/nomic.hip:
-k_nb_embed, k_nb_add_ln, k_nb_pool_part + k_nb_pool_fin), one launch each through ak_ktn_*. Plain numpy, written from the mathematics,
+k_nb_embed, k_nb_add_ln, k_nb_pool_part + k_nb_pool_fin), one launch each through ak_kts_nb_*: family `nb` of tests/test_stack_kernels_gpu.py. Plain numpy, written from the mathematics,
 on the conventions of tests/stack_kernel_refs.py (its module docstring derives the pieces used here: the summation trees, store16, the
 LayerNorm bound, the pooling bound, the L2 tail); nothing here goes through the library or tests/nomic_ref.py.
 
@@ -58,7 +58,7 @@ def embed_cases():
     out = []
     for H in HS:
         for S in SS:
-            out.append(dict(H=H, S=S, B=7, ld_ids=S + 7, lens_stride=2, vocab=VOCAB, eps=EPS[len(out) % 2], name=f"embed_nb_H{H}_S{S}"))
+            out.append(dict(fam="nb", H=H, S=S, B=7, ld_ids=S + 7, lens_stride=2, vocab=VOCAB, eps=EPS[len(out) % 2], name=f"embed_nb_H{H}_S{S}"))
     return out
 
 
@@ -91,7 +91,7 @@ def addnorm_cases():
     out = []
     for H in HS:
         for T in (1, 5, 127, 384):
-            out.append(dict(H=H, T=T, eps=EPS[len(out) % 2], name=f"addnorm_nb_H{H}_T{T}"))
+            out.append(dict(fam="nb", H=H, T=T, eps=EPS[len(out) % 2], name=f"addnorm_nb_H{H}_T{T}"))
     return out
 
 

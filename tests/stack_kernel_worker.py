@@ -1,6 +1,7 @@
 """Child of tests/test_stack_kernels_gpu.py, in the manner of tests/gemma_kernel_worker.py: runs every case of one group through its
 ak_kts_* wrapper (libarchi_hip_dbg.so; the parent sets ARCHI_HIP_DBG=1), each case ONCE, and writes the raw outputs to one .npz
-("<case>:<output>"). The float64 references are the parent's work. Any launcher error or HIP error ends the process with a non-zero
+("<case>:<output>"); NomicBERT's cases (tests/nomic_kernel_refs.py, family `nb`) run in the embed, addnorm and pool groups behind the
+other families'. The float64 references are the parent's work. Any launcher error or HIP error ends the process with a non-zero
 status. Every output buffer is prefilled: NaN where the kernel must write, the sentinel where it must not.
 
     stack_kernel_worker.py <group> <out.npz>      group: embed | addnorm | rope | pool | tail | gemm3"""
@@ -15,6 +16,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 from tests import kernel_cases as kc  # noqa: E402
 from tests import kernel_refs as kr  # noqa: E402
+from tests import nomic_kernel_refs as nk  # noqa: E402
 from tests import stack_kernel_cases as sc  # noqa: E402
 from tests.kernel_worker import NAN_BITS, _check, _dev, _host16, _ptr  # noqa: E402
 
@@ -44,17 +46,19 @@ def _host(t):
 
 
 def run_embed(lib, res):
-    for c in sc.embed_cases():
-        inp = sc.embed_inputs(c)
+    for c in sc.embed_cases() + nk.embed_cases():
+        inp = nk.embed_inputs(c) if c["fam"] == "nb" else sc.embed_inputs(c)
         B, S, H, T = c["B"], c["S"], c["H"], c["B"] * c["S"]
-        ids, lens, emb, w = _dev(inp["ids"]), _dev(inp["lens"]), _dev(inp["emb"]), _dev(inp["w"])
+        ids, lens, emb = _dev(inp["ids"]), _dev(inp["lens"]), _dev(inp["emb"])
+        norm = [_dev(inp[k]) for k in (("type", "g", "b") if c["fam"] == "nb" else ("w",))]      # the table and norm operands behind emb
         x32, h16 = _buf32(T + G, H, T), _buf16(T + G, H, T)
         lens_out = _dev(np.full(B, sc.SENT_I, np.int32))
-        head = (_ptr(ids), c["ld_ids"], _ptr(lens), c["lens_stride"], B, S, H, c["vocab"], _ptr(emb), _ptr(w), _f(c["eps"]), _ptr(x32), _ptr(h16))
+        head = (_ptr(ids), c["ld_ids"], _ptr(lens), c["lens_stride"], B, S, H, c["vocab"], _ptr(emb), *map(_ptr, norm), _f(c["eps"]), _ptr(x32),
+                _ptr(h16))
         n = c["name"]
-        if c["fam"] == "mb":
+        if c["fam"] in ("mb", "nb"):
             mask = _dev(np.full(T + G, sc.SENT_I, np.int32))
-            _check(lib, lib.ak_kts_mb_embed(*head, _ptr(mask), _ptr(lens_out), None), n)
+            _check(lib, getattr(lib, f"ak_kts_{c['fam']}_embed")(*head, _ptr(mask), _ptr(lens_out), None), n)
             m = _host(mask)
             assert (m[T:] == sc.SENT_I).all(), n + ": mask written past B * S"
             res[n + ":mask"] = m[:T]
@@ -66,22 +70,28 @@ def run_embed(lib, res):
 
 
 def run_addnorm(lib, res):
-    for c in sc.addnorm_cases():
-        inp = sc.addnorm_inputs(c)
-        T, H, fam, form, n = c["T"], c["H"], c["fam"], c["form"], c["name"]
+    for c in sc.addnorm_cases() + nk.addnorm_cases():
+        fam, n = c["fam"], c["name"]
+        inp = nk.addnorm_inputs(c) if fam == "nb" else sc.addnorm_inputs(c)
+        T, H, form = c["T"], c["H"], c.get("form", "norm")
         x32, y32 = _buf32(T + G, H, T), _buf32(T + G, H, T)
         x32[:T] = _dev(inp["x"])
         y32[:T] = _dev(inp["y"])
         h16 = _buf16(T + G, H, 0 if form in ("add", "out32") else T)
-        w = _dev(inp["w"])
-        if fam == "gm":
-            wp = _dev(inp["w_post"])
+        if fam == "nb":
+            g, b = _dev(inp["g"]), _dev(inp["b"])
+            _check(lib, lib.ak_kts_nb_add_ln(_ptr(x32), _ptr(y32), T, H, _ptr(g), _ptr(b), _f(c["eps"]), _ptr(h16), None), n)
+        elif fam == "gm":
+            w, wp = _dev(inp["w"]), _dev(inp["w_post"])
             _check(lib, lib.ak_kts_gm_norm_add_norm(_ptr(x32), _ptr(y32), T, H, _ptr(wp), _ptr(w), _f(c["eps"]), _ptr(h16),
                                                     _ptr(y32) if form == "out32" else None, None), n)
         else:
+            w = _dev(inp["w"])
             fn = lib.ak_kts_dec_add_rmsnorm if fam == "dec" else lib.ak_kts_mb_add_ln
             _check(lib, fn(_ptr(x32), _ptr(y32), T, H, None if form == "add" else _ptr(w), _f(c["eps"]), _ptr(h16), None), n)
         x, y, h = _host(x32), _host(y32), _host16(h16)
+        if fam == "nb":
+            assert np.array_equal(y[:T].view(np.uint32), inp["y"].view(np.uint32)) and (y[T:] == nk.SENT).all(), n + ": y32 written"
         res[n + ":x32"], res[n + ":x32_guard"] = x[:T], x[T:]
         if form == "add":
             res[n + ":h16"] = h
@@ -129,18 +139,20 @@ def run_rope(lib, res):
 
 
 def run_pool(lib, res):
-    for c in sc.pool_cases():
-        inp = sc.pool_inputs(c)
+    for c in sc.pool_cases() + nk.pool_cases():
+        inp = nk.pool_inputs(c) if c["fam"] == "nb" else sc.pool_inputs(c)
         B, S, H, fam, n = len(c["lens"]), c["S"], c["H"], c["fam"], c["name"]
         x, lens, w = _dev(inp["x"]), _dev(inp["lens"]), _dev(inp["w"])
         nch = -(-S // 64)
-        for suffix, pooling, normalise in sc.pool_modes(c):
+        for suffix, pooling, normalise in (nk.POOL_MODES if fam == "nb" else sc.pool_modes(c)):
             out = _buf32(B + 1, H, B)
             part = _buf32(B * nch + 1, H, B * nch)
             if fam == "dec":
                 rc = lib.ak_kts_dec_pool(_ptr(x), _ptr(lens), B, S, H, _ptr(w), _f(c["eps"]), normalise, _ptr(out), None)
             elif fam == "mb":
                 rc = lib.ak_kts_mb_pool(_ptr(x), _ptr(lens), B, S, H, _f(c["eps"]), _ptr(w), pooling, normalise, _ptr(part), _ptr(out), None)
+            elif fam == "nb":
+                rc = lib.ak_kts_nb_pool(_ptr(x), _ptr(lens), B, S, H, pooling, normalise, _ptr(part), _ptr(out), None)
             else:
                 rc = lib.ak_kts_gm_pool(_ptr(x), _ptr(lens), B, S, H, _ptr(part), _ptr(out), None)
             _check(lib, rc, n + ":" + suffix)

@@ -333,22 +333,24 @@ def test_config_struct_matches_header():
 
 
 def test_nomic_wrappers_stay_out_of_the_product_library():
-    """ak_ktn_* (csrc/kernel_test.hip) exist in libarchi_hip_dbg.so only, are exactly _lib.KTN_SYMBOLS, and none of them is in the
-    other three sets."""
+    """ak_kts_nb_* (csrc/kernel_test.hip) exist in libarchi_hip_dbg.so only, are exactly the nb entries of _lib.KTS_SYMBOLS, and none
+    of them is in the other two sets; no library exports a wrapper under the earlier ak_ktn_* names."""
     from archi_amd import _lib
 
     def exported(name):
         out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "archi_amd", "lib", name)], stdout=subprocess.PIPE,
                              check=True).stdout.decode()
-        return set(re.findall(r"\b(ak_ktn_[a-z0-9_]+)\b", out))
+        return set(re.findall(r"\b(ak_kts_nb_[a-z0-9_]+|ak_ktn_[a-z0-9_]+)\b", out))
 
     _lib.load()
     assert exported("libarchi_hip.so") == set()
-    names = {n for n, _, _ in _lib.KTN_SYMBOLS}
-    assert exported("libarchi_hip_dbg.so") == names == {"ak_ktn_embed", "ak_ktn_add_ln", "ak_ktn_pool"} and len(_lib.KTN_SYMBOLS) == 3
-    others = {n for n, _, _ in _lib.KT_SYMBOLS + _lib.KTG_SYMBOLS + _lib.KTS_SYMBOLS}
-    assert not names & others and not any(n.startswith(("ak_kt_", "ak_ktg_", "ak_kts_")) for n in names)
-    assert not any(n.startswith("ak_ktn_") for n in others)
+    names = {n for n, _, _ in _lib.KTS_SYMBOLS if n.startswith("ak_kts_nb_")}
+    assert exported("libarchi_hip_dbg.so") == names == {"ak_kts_nb_embed", "ak_kts_nb_add_ln", "ak_kts_nb_pool"}
+    assert sum(n.startswith("ak_kts_nb_") for n, _, _ in _lib.KTS_SYMBOLS) == 3 and not hasattr(_lib, "KTN_SYMBOLS")
+    others = {n for n, _, _ in _lib.KT_SYMBOLS + _lib.KTG_SYMBOLS}
+    assert not names & others and not any(n.startswith(("ak_kt_", "ak_ktg_")) for n in names)
+    header = open(os.path.join(ROOT, "include", "archi_knn.h")).read()
+    assert "ak_kts_" not in header and "ak_ktn_" not in header
 
 
 def test_new_kernels_do_not_spill_and_read_no_environment():
@@ -371,7 +373,7 @@ def test_new_kernels_do_not_spill_and_read_no_environment():
 
 # ---- kernel references -------------------------------------------------------------------------------------------------------------
 def _groups():
-    """{group: [(case, expect(mut), emulate())]} over every GPU case of tests/test_nomic_kernels_gpu.py."""
+    """{group: [(case, expect(mut), emulate())]} over every nb case of tests/test_stack_kernels_gpu.py."""
     out = {"embed": [], "addnorm": [], "pool": []}
     for c in nk.embed_cases():
         out["embed"].append((c, lambda mut=None, c=c: nk.embed_expect(c, nk.embed_inputs(c), mut), lambda c=c: nk.embed_emulate(c, nk.embed_inputs(c))))

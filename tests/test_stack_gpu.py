@@ -1,4 +1,4 @@
-"""GPU tests of what the three pre-norm stacks share (csrc/stack.h, archi_amd/_stack.py), on the tiny shapes: the workspace that
+"""GPU tests of what the four stacks share (csrc/stack.h, archi_amd/_stack.py), on the tiny shapes: the workspace that
 regrows between calls, and the zero padding of an intermediate size off the wide GEMM tile. Both compare bit for bit, so there is no
 tolerance to choose."""
 import numpy as np
@@ -7,6 +7,7 @@ import pytest
 from archi_amd.decoder import QWEN3_SHAPES, HipDecoder, random_qwen3_weights
 from archi_amd.gemma import GEMMA_SHAPES, HipGemma, random_gemma_weights
 from archi_amd.modernbert import MODERNBERT_SHAPES, HipModernBert, random_modernbert_weights
+from archi_amd.nomic import NOMIC_SHAPES, HipNomicBert, random_nomic_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -14,6 +15,7 @@ FAMILIES = {
     "qwen3-tiny-g2": (HipDecoder, QWEN3_SHAPES, lambda s: random_qwen3_weights(s, seed=11)),
     "modernbert-tiny-mix": (HipModernBert, MODERNBERT_SHAPES, lambda s: random_modernbert_weights(s, seed=12, std=0.1)),
     "gm-tiny": (HipGemma, GEMMA_SHAPES, lambda s: random_gemma_weights(s, seed=13, std=0.1)),
+    "nomic-tiny-mean": (HipNomicBert, NOMIC_SHAPES, lambda s: random_nomic_weights(s, seed=14, std=0.1)),
 }
 
 
@@ -84,7 +86,21 @@ def _padded_gemma():
     return HipGemma, shape, w, wide, wp
 
 
-@pytest.mark.parametrize("family", [_padded_modernbert, _padded_gemma], ids=["modernbert", "gemma"])
+def _padded_nomic():
+    """nomic-tiny-mean (I = 192: the library pads 2 I = 384 to 512) and the same model given as I = 256: 64 zero rows behind every
+    w_gate and w_up, 64 zero columns behind every w_down."""
+    shape = NOMIC_SHAPES["nomic-tiny-mean"]
+    I, pad = shape[4], 256 - shape[4]
+    assert I == 192
+    w = random_nomic_weights(shape, seed=23, std=0.1)
+    wp = dict(w)
+    for l in range(shape[2]):
+        wp[f"l{l}.w_gate"], wp[f"l{l}.w_up"] = _zero_rows(w[f"l{l}.w_gate"], pad), _zero_rows(w[f"l{l}.w_up"], pad)
+        wp[f"l{l}.w_down"] = _zero_cols(w[f"l{l}.w_down"], pad)
+    return HipNomicBert, shape, w, shape[:4] + (256,) + shape[5:], wp
+
+
+@pytest.mark.parametrize("family", [_padded_modernbert, _padded_gemma, _padded_nomic], ids=["modernbert", "gemma", "nomic"])
 def test_library_padding_equals_explicit_zero_padding(hip, family):
     """The library must build the very matrices the test builds by hand: results are equal bit for bit."""
     cls, shape, w, shape_padded, w_padded = family()
