@@ -17,7 +17,7 @@ DTYPES = {"f32": 0, "bf16": 1, "f16": 2}
 # store-level metric names (postgres_vectorstore.py:74-78) -> AK_METRIC_*
 METRICS = {"cosine": 0, "l2": 1, "inner_product": 2}
 SEARCH_MODES = {"auto": 0, "exact": 1, "fast_only": 2}
-POOLING = {"mean": 0, "cls": 1}
+POOLING = {"mean": 0, "cls": 1, "last": 2}      # AK_POOL_*; "last": ak_llama_forward_lens only
 
 
 class HipBackendError(RuntimeError):
@@ -132,6 +132,23 @@ class AkNomicBertConfig(ctypes.Structure):
     ]
 
 
+class AkLlamaConfig(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("q_heads", ctypes.c_int),
+        ("kv_heads", ctypes.c_int),
+        ("head_dim", ctypes.c_int),
+        ("intermediate", ctypes.c_int),
+        ("max_position", ctypes.c_int),
+        ("rms_eps", ctypes.c_float),
+        ("rope_theta", ctypes.c_float),
+        ("sliding_window", ctypes.c_int),
+        ("bidirectional", ctypes.c_int),
+    ]
+
+
 _lock = threading.Lock()
 _lib = None
 _inited_device = None
@@ -203,6 +220,10 @@ SYMBOLS = [
     ("ak_nomic_create", _I, [ctypes.POINTER(AkNomicBertConfig), _P, _I, ctypes.POINTER(_P)]),
     ("ak_nomic_destroy", _I, [_P]),
     ("ak_nomic_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("ak_llama_create", _I, [ctypes.POINTER(AkLlamaConfig), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_llama_destroy", _I, [_P]),
+    ("ak_llama_set_rope_inv_freq", _I, [_P, _P]),
+    ("ak_llama_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_create_ex", _I, [ctypes.c_char_p, _I, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.POINTER(ctypes.c_char_p), _I, ctypes.POINTER(_P)]),
@@ -269,8 +290,8 @@ KTG_SYMBOLS = [
     ("ak_ktg_gemm_geglu_tanh", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 ]
 
-# the small kernels of the stacks (decoder.hip, mbert.hip, nomic.hip, gemma.hip) and k_gemm MODE 3, one launch each
-# (tests/test_stack_kernels_gpu.py): libarchi_hip_dbg.so only, a third set of its own (ak_kts_*)
+# the small kernels of the stacks (decoder.hip, mbert.hip, nomic.hip, gemma.hip, llama.hip) and k_gemm MODE 3, one launch each
+# (tests/test_stack_kernels_gpu.py, tests/test_llama_kernels_gpu.py): libarchi_hip_dbg.so only, a third set of its own (ak_kts_*)
 _F = ctypes.c_float
 _EMBED = [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P]
 KTS_SYMBOLS = [
@@ -292,6 +313,9 @@ KTS_SYMBOLS = [
     ("ak_kts_gm_dense", _I, [_P, _P, _I, _I, _I, _P, _P]),
     ("ak_kts_gm_l2", _I, [_P, _I, _I, _I, _P, _P]),
     ("ak_kts_gemm_bf16", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    ("ak_kts_ll_attn", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    ("ak_kts_ll_pool", _I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _P]),
+    ("ak_kts_ll_rope", _I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
 ]
 
 

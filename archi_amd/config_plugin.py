@@ -30,6 +30,9 @@ EMBEDDING_DIMENSIONS = {
     "Qwen/Qwen3-Embedding-0.6B": 1024,
     "Qwen/Qwen3-Embedding-4B": 2560,
     "Qwen/Qwen3-Embedding-8B": 4096,
+    "intfloat/e5-mistral-7b-instruct": 4096,
+    "Salesforce/SFR-Embedding-Mistral": 4096,
+    "Linq-AI-Research/Linq-Embed-Mistral": 4096,
     "nomic-ai/modernbert-embed-base": 768,
     "Alibaba-NLP/gte-modernbert-base": 768,
     "lightonai/modernbert-embed-large": 1024,

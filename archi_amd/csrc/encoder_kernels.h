@@ -174,6 +174,10 @@ struct CausalAttnArgs {
     const int *lens;
     uint16_t *ctx;
     int B, S, nq, nkv;
+    // sliding window (llama.hip; Mistral's sliding_window): key k visible to query q iff k <= q and q - k <= window - 1. 0: no band
+    // (Qwen3: the kernel it ran before the band existed)
+    int window = 0;
+    int bidirectional = 0;       // != 0 (llama.hip): every key below the row's length, for every query below it; the window is ignored
 };
 bool attn_causal_supported(int nq, int nkv, int head_dim, int S);
 int launch_attn_causal(const CausalAttnArgs &a, hipStream_t st);
@@ -205,6 +209,14 @@ int launch_dec_add_rmsnorm(float *x32, const float *y32, int64_t T, int H, const
 int launch_dec_qk_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
                        const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *v, hipStream_t st);
 int launch_dec_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *out, hipStream_t st);
+// llama.hip (Mistral / Llama: its embed, residual norms and last-token pool are the launch_dec_* above): q | k | v rows
+// [B * S][(nq + 2 nkv) 128] -> rotate_half RoPE of the q and k heads (no per-head norm), q scaled; the layouts of CausalAttnArgs
+int launch_ll_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *rc, const float *rs, float qscale, uint16_t *q, uint16_t *k,
+                   uint16_t *v, hipStream_t st);
+// mean over t < len of RMSNorm(x_t) (the norm per token, before the mean), times the final norm's weight, then the optional L2: any
+// H % 128 == 0 (pool_part in column slices of 1024); part [B][ceil(S / 64)][H] floats of workspace
+int launch_ll_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *part, float *out,
+                   hipStream_t st);
 int launch_mb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
                     float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, hipStream_t st);
 int launch_mb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *w, float eps, uint16_t *h16, hipStream_t st);

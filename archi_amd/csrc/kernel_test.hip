@@ -262,6 +262,30 @@ extern "C" int ak_kts_dec_pool(const float *x32, const int *lens, int B, int S, 
     return launch_dec_pool(x32, lens, B, S, H, w, eps, normalise, out, (hipStream_t)stream);
 }
 
+// launch_attn_causal through the new arguments (llama.hip): window 0 = the plain causal kernel, w > 0 the sliding window; bidirectional != 0: every key below the length
+extern "C" int ak_kts_ll_attn(const uint16_t *q, const uint16_t *k, const uint16_t *v, const int *lens, uint16_t *ctx, int B, int S, int nq,
+                              int nkv, int window, int bidirectional, void *stream) {
+    AK_BIND();
+    CausalAttnArgs a{};
+    a.q = q; a.k = k; a.v = v; a.lens = lens; a.ctx = ctx;
+    a.B = B; a.S = S; a.nq = nq; a.nkv = nkv; a.window = window; a.bidirectional = bidirectional;
+    return launch_attn_causal(a, (hipStream_t)stream);
+}
+
+// qkv [B * S][(nq + 2 nkv) 128]; rc / rs [>= S][64]; q [B][nq][S][128], k / v [B][nkv][S][128]
+extern "C" int ak_kts_ll_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *rc, const float *rs, float qscale, uint16_t *q,
+                              uint16_t *k, uint16_t *v, void *stream) {
+    AK_BIND();
+    return launch_ll_rope(qkv, B, S, nq, nkv, rc, rs, qscale, q, k, v, (hipStream_t)stream);
+}
+
+// part: [B][ceil(S / 64)][H] floats of workspace
+extern "C" int ak_kts_ll_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *part,
+                              float *out, void *stream) {
+    AK_BIND();
+    return launch_ll_pool(x32, lens, B, S, H, w, eps, normalise, part, out, (hipStream_t)stream);
+}
+
 extern "C" int ak_kts_mb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb,
                                const float *w, float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, void *stream) {
     AK_BIND();

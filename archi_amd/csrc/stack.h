@@ -110,12 +110,14 @@ __device__ inline int pooled_count(int len, int pooling) { return len <= 0 ? 0 :
 // Pooling, stage 1, of workgroup (chunk ck = blockIdx.x, row b = blockIdx.y), 4 waves: tokens 64 ck .. 64 ck + 63 below n of row b,
 // each through the per-token transform, summed: wave v takes tokens v, v + 4, ...; the four wave partials are added in wave order
 // -> part[b][ck][H]. Chunks at or past n write nothing (stage 2 does not read them). Which tokens meet in which sum depends on n
-// alone, not on S or the batch around it. Row: n = count(the row's length); tok = begin(xr, H, lane) once per token row, then
+// alone, not on S or the batch around it. A row wider than POOL_MAX_H is pooled in column slices of POOL_MAX_H, slice blockIdx.z
+// (gridDim.z = ceil(H / 1024); the per-token transform still sees the whole row). Row: n = count(the row's length); tok = begin(xr, H, lane) once per token row, then
 // tok.apply(x) per feature.
 template <class Row>
 __device__ inline void pool_part(const float *x32, const int *lens, int S, int H, Row row, float *part) {
-    extern __shared__ float lds[];                             // [4][H]: the launch's dynamic LDS
+    extern __shared__ float lds[];                             // [4][W]: the launch's dynamic LDS
     const int ck = blockIdx.x, b = blockIdx.y, nch = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c0 = blockIdx.z * POOL_MAX_H, W = min(H - c0, POOL_MAX_H);      // the workgroup's columns (H <= 1024: all of them)
     const int n = row.count(lens[b]);
     if (ck * POOL_CHUNK >= n) return;
     const int stop = min(n, (ck + 1) * POOL_CHUNK);
@@ -128,8 +130,8 @@ __device__ inline void pool_part(const float *x32, const int *lens, int S, int H
 #pragma unroll
         for (int j = 0; j < POOL_MAX_H / 256; j++) {
             const int c = lane * 4 + j * 256;
-            if (c < H) {
-                const float4 f = *(const float4 *)(xr + c);
+            if (c < W) {
+                const float4 f = *(const float4 *)(xr + c0 + c);
                 acc[j].x += tok.apply(f.x); acc[j].y += tok.apply(f.y); acc[j].z += tok.apply(f.z); acc[j].w += tok.apply(f.w);
             }
         }
@@ -137,11 +139,11 @@ __device__ inline void pool_part(const float *x32, const int *lens, int S, int H
 #pragma unroll
     for (int j = 0; j < POOL_MAX_H / 256; j++) {
         const int c = lane * 4 + j * 256;
-        if (c < H) *(float4 *)(lds + wave * H + c) = acc[j];
+        if (c < W) *(float4 *)(lds + wave * W + c) = acc[j];
     }
     __syncthreads();
-    float *o = part + ((int64_t)b * nch + ck) * H;
-    for (int c = tid; c < H; c += 256) o[c] = ((lds[c] + lds[H + c]) + lds[2 * H + c]) + lds[3 * H + c];
+    float *o = part + ((int64_t)b * nch + ck) * H + c0;
+    for (int c = tid; c < W; c += 256) o[c] = ((lds[c] + lds[W + c]) + lds[2 * W + c]) + lds[3 * W + c];
 }
 
 // Pooling, stage 2, of workgroup b = blockIdx.x (256 threads) behind pool_part on pooled_count tokens: the chunk sums added in chunk

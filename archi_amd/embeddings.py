@@ -16,7 +16,8 @@ Device side: archi_amd.encoder.HipEncoder (hand-written HIP). No CPU fallback.
 Qwen3-Embedding checkpoints (config.json model_type "qwen3") run on archi_amd.decoder.HipDecoder instead, tokenised by the
 checkpoint's own tokenizer.json, pooled on the last token; ModernBERT checkpoints (model_type "modernbert") run on
 archi_amd.modernbert.HipModernBert, NomicBERT checkpoints (model_type "nomic_bert") on archi_amd.nomic.HipNomicBert with the BERT
-WordPiece tokenizer of their vocab.txt; the same batching harness drives all of them.
+WordPiece tokenizer of their vocab.txt, Mistral / Llama checkpoints (model_type "mistral" | "llama") on archi_amd.llama.HipLlama; the
+same batching harness drives all of them.
 """
 from __future__ import annotations
 
@@ -41,6 +42,8 @@ from .gemma import GEMMA_SHAPES, HipGemma, load_gemma_weights, random_gemma_weig
 from .gemma import MAX_SEQ as GEMMA_MAX_SEQ
 from .nomic import NOMIC_SHAPES, HipNomicBert, load_nomic_weights, nomic_config_info, random_nomic_weights
 from .nomic import MAX_SEQ as NOMIC_MAX_SEQ
+from .llama import LLAMA_SHAPES, HipLlama, apply_mode, load_llama_weights, random_llama_weights, read_llama_st_config, resolve_mode
+from .llama import MAX_SEQ as LLAMA_MAX_SEQ
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
 # special tokens by name: (cls, sep, unk, the strings the full tokenizer matches in raw text)
@@ -211,6 +214,15 @@ def _is_nomic(model_name: str) -> bool:
     return model_name in NOMIC_SHAPES
 
 
+def _is_llama(model_name: str) -> bool:
+    """A Mistral / Llama checkpoint directory (config.json model_type "mistral" | "llama") or one of the named shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") in ("mistral", "llama")
+    return model_name in LLAMA_SHAPES
+
+
 def _is_mpnet(model_name: str) -> bool:
     """An MPNet checkpoint directory (config.json model_type "mpnet") or one of the named MPNet shapes."""
     import json
@@ -248,6 +260,7 @@ class _StackFamily(NamedTuple):
     handle: Callable            # the HipStack subclass
     wordpiece: bool = False     # a vocab.txt beside the weights (or model_kwargs["vocab_file"]) is the tokenizer: BERT WordPiece
     precheck: Optional[Callable] = None      # (checkpoint directory, model_kwargs): refusals the config alone decides, before any GPU work
+    reshape: Optional[Callable] = None       # (shape, model_kwargs) -> the shape the handle is built from (a mode the caller states)
 
 
 def _seed_std(kw):
@@ -295,6 +308,23 @@ _NOMIC = _StackFamily("NomicBERT models", "a NomicBERT", "vocab.txt or tokenizer
                       precheck=_nomic_precheck)
 
 
+def _llama_precheck(model_dir, kw):
+    """What the sentence-transformers files and the keywords alone decide (an attention mode or a pooling that does not exist), before
+    the weights are read."""
+    st_pool, _, _ = read_llama_st_config(model_dir)
+    resolve_mode(model_dir, None, kw, st_pool)
+
+
+# Mistral / Llama embedders (intfloat/e5-mistral-7b-instruct, Salesforce/SFR-Embedding-Mistral, Linq-AI-Research/Linq-Embed-Mistral, the
+# Llama-3.1-8B based ones): causal attention with the config's sliding window and lasttoken pooling, or -- model_kwargs["attention"] =
+# "bidirectional", the caller's statement of how the checkpoint was trained -- every key below the length and mean pooling
+# (llama.resolve_mode; model_kwargs["pooling"] overrides); rows up to 8192 tokens; the special tokens are whatever the tokenizer.json's
+# post-processor adds. LLAMA_SHAPES also names the small shapes of the test fixtures (synthetic_seed only), as the other families' do
+_LLAMA = _StackFamily("Mistral / Llama embedders", "a Mistral or Llama", "tokenizer", LLAMA_SHAPES, 6, LLAMA_MAX_SEQ, load_llama_weights,
+                      read_llama_st_config, lambda shape, kw: random_llama_weights(shape, **_seed_std(kw)), resolve_mode, HipLlama,
+                      precheck=_llama_precheck, reshape=apply_mode)
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -316,7 +346,8 @@ class ArchiHipEmbeddings:
         device = int(dev.split(":")[1]) if ":" in dev else None
         self._stage = self._stage_out = None
         self._stage_lock = threading.Lock()
-        for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA), (_is_nomic, _NOMIC)):
+        for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA), (_is_nomic, _NOMIC),
+                                  (_is_llama, _LLAMA)):
             if is_family(model_name):
                 self._init_stack(family, model_name, device)
                 return
@@ -470,6 +501,8 @@ class ArchiHipEmbeddings:
         self.pooling = fam.pooling(model_name, shape, self.model_kwargs, st_pool)
         max_pos = int(shape[fam.max_position])
         self.max_seq_length = min(int(self.model_kwargs.get("max_seq_length", st_len or max_pos)), max_pos, fam.max_seq)
+        if fam.reshape:
+            shape = fam.reshape(shape, self.model_kwargs)
         self.encoder = fam.handle(shape, weights, device=device)
         self.dimensions = int(self.encoder.out_dim)
 

@@ -59,6 +59,7 @@ extern "C" {
 /* encoder pooling (sentence-transformers Pooling module [upstream]) */
 #define AK_POOL_MEAN 0 /* all-MiniLM-L6-v2 */
 #define AK_POOL_CLS 1  /* bge-base-en */
+#define AK_POOL_LAST 2 /* e5-mistral-7b-instruct: the last valid token (ak_llama_forward_lens only) */
 
 typedef void *ak_index_t;
 typedef void *ak_encoder_t;
@@ -584,6 +585,51 @@ int ak_nomic_destroy(ak_nomic_t h);
  * to zeros). pooling: AK_POOL_MEAN / AK_POOL_CLS over the last layer's rows of the valid tokens; out_dev [B][H] float32, L2-normalised
  * when `normalise` != 0. S a multiple of 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
 int ak_nomic_forward_lens(ak_nomic_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                          int pooling, int normalise, float *out_dev, void *stream);
+
+/* ---- Mistral / Llama decoder embedders (intfloat/e5-mistral-7b-instruct, Salesforce/SFR-Embedding-Mistral,
+ * Linq-AI-Research/Linq-Embed-Mistral, the Llama-3.1-8B based embedders) ---- */
+/* The other instruction-aware embedders the reference's retrievers single out (retrievers/utils.py:7-19), loaded by name through
+ * HuggingFaceEmbeddings. The forward pass of HF MistralModel / LlamaModel: RMSNorm, rotate_half RoPE at head dim 128 WITHOUT a per-head
+ * q / k norm, grouped-query causal attention -- with sliding_window = w > 0 key k is visible to query q iff k <= q and q - k <= w - 1
+ * (HF's sliding_window_overlay), or bidirectional attention for the embedders trained without the causal mask --, SwiGLU MLP; then the
+ * final norm of each row's LAST valid token, or the mean of the final norm over the valid tokens, and L2 normalisation
+ * (sentence-transformers' lasttoken / mean Pooling + Normalize). No bias anywhere. bf16 MFMA GEMMs, float32 residual stream / norms / softmax. */
+typedef void *ak_llama_t;
+typedef struct AkLlamaConfig {
+    int vocab_size;     /* 32000 (Mistral) / 128256 (Llama 3.1) */
+    int hidden;         /* 4096; a multiple of 128 */
+    int layers;         /* 32 */
+    int q_heads;        /* 32 */
+    int kv_heads;       /* 8; q_heads % kv_heads == 0, at most 4 query heads per kv head */
+    int head_dim;       /* 128 (the only head size implemented) */
+    int intermediate;   /* 14336; a multiple of 64 */
+    int max_position;   /* 32768 / 131072 (rows are limited to min(max_position, 8192) tokens) */
+    float rms_eps;      /* 1e-5 */
+    float rope_theta;   /* 1e4 / 5e5: the default rotary table (ak_llama_set_rope_inv_freq replaces it, e.g. for rope_type llama3) */
+    int sliding_window; /* 4096 (Mistral-7B-v0.1); 0 = none; < 0 is refused */
+    int bidirectional;  /* 0 = causal (with the window); 1 = every key below the row's length for every query below it, the window ignored */
+} AkLlamaConfig;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] exactly as torch.nn.Linear.weight, vectors float32):
+ *   0 embed_tokens [vocab][H] bf16, 1 final norm [H],
+ *   per layer l (base 2 + 9 * l):
+ *     +0 wq [q_heads 128][H] +1 wk [kv_heads 128][H] +2 wv [kv_heads 128][H] +3 wo [H][q_heads 128]
+ *     +4 ln_in [H] (input_layernorm) +5 ln_post [H] (post_attention_layernorm) +6 w_gate [I][H] +7 w_up [I][H] +8 w_down [H][I]
+ * The library copies wq | wk | wv into one matrix and interleaves the gate and up rows at create; the other pointers must stay valid
+ * until ak_llama_destroy. Refused (non-zero, message naming the field in the last-error string): head_dim != 128, q_heads % kv_heads,
+ * more than 4 query heads per kv head, hidden % 128, intermediate % 64, sliding_window < 0, bidirectional other than 0 / 1, a non-positive size,
+ * rms_eps or rope_theta, a weight count other than 2 + 9 * layers. */
+int ak_llama_create(const AkLlamaConfig *cfg, const void *const *weights_dev, int n_weights, ak_llama_t *out);
+int ak_llama_destroy(ak_llama_t h);
+/* Replace the rotary table ak_llama_create built from rope_theta by the table of GIVEN inverse frequencies (ak_decoder_rope_table_inv):
+ * inv_freq, 64 host floats -- the HF model's own inv_freq buffer (archi_amd.llama.rope_inv_freq restates HF's float32 expressions for
+ * the default and the llama3 rope types). Waits for the handle's work in flight. */
+int ak_llama_set_rope_inv_freq(ak_llama_t h, const float *inv_freq);
+/* The tile layout and the argument checks of ak_decoder_forward_lens. pooling: AK_POOL_LAST (the final norm of token len - 1 of each
+ * row) or AK_POOL_MEAN (the mean over t < len of the final norm of token t: the norm per token, before the mean; what the embedders
+ * trained without the causal mask pair with bidirectional = 1); anything else is refused. out_dev [B][H] float32, L2-normalised when
+ * `normalise` != 0. S a multiple of 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
+int ak_llama_forward_lens(ak_llama_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
                           int pooling, int normalise, float *out_dev, void *stream);
 
 /* ---- host tokenizer: the tokenisation step inside Embeddings.embed_documents -------- */
