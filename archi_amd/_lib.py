@@ -183,6 +183,7 @@ SYMBOLS = [
     ("ak_index_slots", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_U64)]),
     ("ak_index_compact", _I, [_P, ctypes.POINTER(_I64)]),
     ("ak_index_scan_plan", _I, [_P, _I, _I, _P]),
+    ("ak_index_i8_info", _I, [_P, _P]),
     ("ak_index_debug_read", _I, [_P, _P, _I]),
     ("ak_index_profile", _I, [_P, _I]),
     ("ak_index_profile_read", _I, [_P, _P, _I, ctypes.POINTER(_I)]),

@@ -13,6 +13,7 @@
 //   lex_off [cap] i64, lex_cnt [cap] i32, lex_len [cap] i32   the row's sorted (term id, tf) list in the entry arena and its length in
 //                     tokens (lexical.hip: the BM25 leg of the hybrid query); a row without a list has cnt = len = 0
 #pragma once
+#include <atomic>
 #include <condition_variable>
 #include <mutex>
 #include <shared_mutex>
@@ -58,6 +59,18 @@ struct Index : IndexBook {
     hipEvent_t lex_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // ak_index_profile: stage boundaries of the hybrid query
     float max_na = 0.f;  // max over rows of na (for the ip / l2 error bound)
     float max_rho = 0.f; // f32 corpora: max over rows of |a - shadow(a)| / |a| (measured at ingest; certificate term rho_c)
+    // ---- int8 shadow of a 16-bit corpus (the i8 scan plan, scan.hip): rows8 [cap in whole tiles][dim] int8 with one scale per
+    // row, ea8 = scale * ea (the scan-side term), gb8 the filter's per-32-row-block maxima of ea8 / eb. Built lazily by the first
+    // search whose plan asks for it (ensure_shadow8), extended for appended rows, dropped when rows moved (a reclaim of tombstones renumbers the slots) or the
+    // buffers grew. Removed rows need nothing: the scan takes eb (-inf for a tombstone) from the index itself.
+    int8_t *rows8 = nullptr;
+    float *ea8 = nullptr, *gb8 = nullptr;
+    int64_t s8_n = 0, s8_cap = 0;          // rows covered / rows allocated
+    uint64_t s8_epoch = 0;                 // the layout it was built for: IndexBook::reclaims, the epoch changes that renumbered slots
+    float max_rho8 = 0.f;                  // max over rows of |a - scale * a8| / |a|, rounded up
+    int64_t s8_builds = 0;                 // full builds so far (ak_index_i8_info)
+    std::atomic<int64_t> s8_searches{0};   // searches that ran the i8 plan
+    std::mutex s8_mu;
     Coalescer co;
     std::shared_mutex mu;
     Workspace ws_dev;     // workspace of ak_index_search_dev (one call at a time: ws_mu + ws_event order its users)
@@ -158,10 +171,16 @@ struct FastPlan {
     int pre_slices;     // workgroups along the sample
     int pre_stride;
     int nqg;        // query groups
+    int i8;         // 1 = the main and seeding pass scan the int8 shadow (tile P on v_mfma_i32_16x16x64_i8, k' = 512 dense tail)
     size_t bytes;   // workspace bytes
 };
+// int8 shadow (index.hip): make it cover rows [0, ix.n) of the current layout; synchronises `st` when it had to build
+// AK_SHADOW8_NOMEM: the device has no room for it (nothing is left allocated; the caller runs the 16-bit plan)
+constexpr int AK_SHADOW8_NOMEM = -1008;
+int ensure_shadow8(Index &ix, hipStream_t st);
+void release_shadow8(Index &ix);
 bool fast_supported(const Index &ix, int nq, int k);
-FastPlan fast_plan(const Index &ix, int nq, int k, bool widest = false);
+FastPlan fast_plan(const Index &ix, int nq, int k, bool widest = false, bool allow_i8 = true);
 // Candidate scan + select + exact re-rank + certification, all on `st`.
 // cert_dev [nq] int32: 1 = top-k proven identical to the exact path.
 // nb_dev [nq]: the queries' sums of squares in the reference arithmetic -- an INPUT when nb_ready, otherwise computed here

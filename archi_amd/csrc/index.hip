@@ -48,6 +48,7 @@ struct SwitchName { const char *name; std::atomic<int> Switches::*field; int dfl
 const SwitchName g_switch_names[] = {
     {"AK_SCAN_CFG", &Switches::scan_cfg, 0, false, false, true},
     {"AK_SCAN_MFMA", &Switches::scan_mfma, 0, false, false, false},
+    {"AK_SCAN_I8", &Switches::scan_i8, AK_SCAN_I8_DEFAULT, false, false, false},
     {"AK_SCAN_BLOCKS", &Switches::scan_blocks, 0, false, false, false},
     {"AK_SCAN_NO192", &Switches::scan_no192, 0, true, false, false},
     {"AK_SEED_RATIO", &Switches::seed_ratio, 32, false, false, false},
@@ -461,6 +462,120 @@ static int finish_rows(Index &ix, int64_t slot0, int64_t n, hipStream_t st) {
     return 0;
 }
 
+// ---- int8 shadow of a 16-bit corpus (the i8 scan plan) -----------------------
+// One wave per row: scale = max|a| / 127, a8 = round(a / scale) (four values per lane and step, one 32-bit store), the scan-side
+// term ea8 = scale * ea, and rho = |a - scale * a8| / |a| in double, maximum over the rows as the float bits of a non-negative
+// value (k_shadow_rho's method, rounded up the same way). A row of zeros has scale 0 and an all-zero shadow; a row with a
+// non-finite value gets one too and its rho is skipped -- such a row has no finite score in any plan.
+template <int DT>
+__global__ __launch_bounds__(256) void k_shadow8(const typename Store<DT>::T *__restrict__ rows, const float *__restrict__ ea, int64_t slot0,
+                                                 int64_t n, int dim, int8_t *__restrict__ rows8, float *__restrict__ ea8,
+                                                 unsigned int *__restrict__ out_bits) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= n) return;
+    const typename Store<DT>::T *a = rows + (slot0 + r) * (int64_t)dim;
+    float mx = 0.f;
+    bool bad = false;
+    for (int i = lane * 4; i < dim; i += 256)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float ax = fabsf(Store<DT>::load(a, i + j));
+            if (!(ax < INFINITY)) bad = true;
+            else if (ax > mx) mx = ax;
+        }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    bad = __any(bad);
+    const float s = bad ? 0.f : mx / 127.f;
+    const float inv = s > 0.f ? 1.f / s : 0.f;
+    double e2 = 0.0, a2 = 0.0;
+    uint32_t *dst = (uint32_t *)(rows8 + (slot0 + r) * (int64_t)dim);
+    for (int i = lane * 4; i < dim; i += 256) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float x = Store<DT>::load(a, i + j);
+            float v = rintf(x * inv);
+            v = v > 127.f ? 127.f : (v < -127.f ? -127.f : v);
+            if (!(v == v)) v = 0.f;
+            const double d = (double)x - (double)s * (double)v;
+            e2 += d * d; a2 += (double)x * (double)x;
+            w |= ((uint32_t)(int)v & 0xffu) << (8 * j);
+        }
+        dst[i >> 2] = w;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { e2 += __shfl_xor(e2, off); a2 += __shfl_xor(a2, off); }
+    if (lane == 0) {
+        ea8[slot0 + r] = s * ea[slot0 + r];
+        if (!bad && a2 > 0.0 && e2 == e2 && a2 < 1e300) {
+            const float rho = (float)(sqrt(e2 / a2) * 1.0001) + 1e-9f;
+            atomicMax(out_bits, __float_as_uint(rho));
+        }
+    }
+}
+
+void release_shadow8(Index &ix) {
+    if (ix.rows8) hipFree(ix.rows8);
+    if (ix.ea8) hipFree(ix.ea8);
+    if (ix.gb8) hipFree(ix.gb8);
+    ix.rows8 = nullptr; ix.ea8 = nullptr; ix.gb8 = nullptr;
+    ix.s8_n = 0; ix.s8_cap = 0; ix.s8_epoch = 0; ix.max_rho8 = 0.f;
+}
+
+// Called by a search whose plan scans the int8 shadow, under the index's shared lock: rows, n, cap and the epoch stand still, and
+// s8_mu orders the searches among themselves. The stream is synchronised before the state is published, so a search on another
+// stream that finds the shadow complete never reads rows still being written. Paid once per ingest, not per search.
+int ensure_shadow8(Index &ix, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(ix.s8_mu);
+    if (ix.dtype == AK_DTYPE_F32 || ix.dim % 4 != 0) AK_FAIL(-1, "int8 shadow: 16-bit corpora with dim % 4 == 0 only");
+    if (ix.rows8 && ix.s8_epoch == ix.reclaims && ix.s8_cap == ix.cap && ix.s8_n == ix.n) return 0;
+    if (!ix.rows8 || ix.s8_epoch != ix.reclaims || ix.s8_cap != ix.cap || ix.s8_n > ix.n) {
+        // rows moved (compaction / reclaim) or the buffers grew: nothing of the old shadow is kept
+        AK_HIP(hipStreamSynchronize(st));
+        release_shadow8(ix);
+        const size_t cap_t = ((size_t)ix.cap + 255) / 256 * 256;     // whole tiles, like the 16-bit rows (alloc_buffers)
+        hipError_t e = hipMalloc((void **)&ix.rows8, cap_t * ix.dim + 256);
+        if (e == hipSuccess) e = hipMalloc((void **)&ix.ea8, (size_t)ix.cap * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&ix.gb8, (((size_t)ix.cap + 31) / 32) * 16 + 256);
+        if (e != hipSuccess) {
+            release_shadow8(ix);
+            (void)hipGetLastError();               // the failed allocation is this function's to report, not the next launch's
+            return AK_SHADOW8_NOMEM;
+        }
+        ix.s8_cap = ix.cap; ix.s8_epoch = ix.reclaims; ix.s8_n = 0;
+        ix.s8_builds++;
+    }
+    const int64_t slot0 = ix.s8_n, n = ix.n - slot0;
+    if (n > 0) {
+        unsigned int *bits = nullptr;
+        AK_HIP(hipMalloc((void **)&bits, 4));
+        hipError_t e = hipMemsetAsync(bits, 0, 4, st);
+        const unsigned grid = (unsigned)((n + 3) / 4);
+        if (e == hipSuccess) {
+            if (ix.dtype == AK_DTYPE_BF16)
+                k_shadow8<AK_DTYPE_BF16><<<grid, 256, 0, st>>>((const Store<AK_DTYPE_BF16>::T *)ix.rows, ix.ea, slot0, n, ix.dim, ix.rows8, ix.ea8, bits);
+            else
+                k_shadow8<AK_DTYPE_F16><<<grid, 256, 0, st>>>((const Store<AK_DTYPE_F16>::T *)ix.rows, ix.ea, slot0, n, ix.dim, ix.rows8, ix.ea8, bits);
+            const int64_t blk0 = slot0 / 32, nblk = (ix.n + 31) / 32 - blk0;
+            k_group_bounds<<<(unsigned)((nblk * 2 + 255) / 256), 256, 0, st>>>(ix.ea8, ix.eb, ix.n, blk0, nblk, ix.gb8);
+            e = hipGetLastError();
+        }
+        float rho = 0.f;
+        if (e == hipSuccess) e = hipMemcpyAsync(&rho, bits, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        hipFree(bits);
+        if (e != hipSuccess) {
+            release_shadow8(ix);
+            AK_FAIL(-10, std::string("int8 shadow: build failed: ") + hipGetErrorString(e));
+        }
+        ix.max_rho8 = std::max(ix.max_rho8, rho);
+        ix.s8_n = ix.n;
+    }
+    return 0;
+}
+
 // ---- compaction / growth ---------------------------------------------------
 // dst row i <- src row src[i]: one wave per row, 16-byte pieces (row bytes are a multiple of 2; the tail goes by 2 bytes)
 __global__ __launch_bounds__(256) void k_gather_rows(const char *__restrict__ src_rows, const int64_t *__restrict__ src, int64_t m,
@@ -583,6 +698,9 @@ static void take_buffers(Index &ix, IndexBuffers &b) {   // ix <- b, b <- what i
 // replaces its chunks (ON CONFLICT, postgres_vectorstore.py:168-182 / manager.py:192-211), so a long-running data manager
 // would otherwise run an append-only index into "capacity exceeded" with few live rows. Caller holds the unique lock.
 static int rebuild(Index &ix, int64_t new_cap, bool compact, hipStream_t st) {
+    // the int8 shadow describes the old buffers (slot numbers, capacity): free it BEFORE the new ones are allocated, the next
+    // eligible search builds it anew (the callers have fenced the asynchronous searches)
+    { std::lock_guard<std::mutex> sl(ix.s8_mu); release_shadow8(ix); }
     IndexBuffers nb;
     hipError_t e = alloc_buffers(nb, new_cap, ix.dim, ix.dtype);
     if (e != hipSuccess) AK_FAIL(-10, std::string("index growth / compaction: hipMalloc failed: ") + hipGetErrorString(e));
@@ -739,6 +857,7 @@ int ak_index_destroy(ak_index_t h) {
     lex_release(*ix);
     if (ix->ws_event) hipEventDestroy(ix->ws_event);
     if (ix->dbg_dev) hipFree(ix->dbg_dev);
+    release_shadow8(*ix);
     if (switches().coalesce_stats.load(std::memory_order_relaxed) && ix->co.n_launch)
         fprintf(stderr, "ak_index_search coalescing: %lld requests in %lld launches (%.1f per launch), %lld gather waits\n",
                 (long long)ix->co.n_req, (long long)ix->co.n_launch, (double)ix->co.n_req / ix->co.n_launch, (long long)ix->co.n_wait);
@@ -1120,7 +1239,7 @@ static int search_host(Index &ix, const float *queries, int nq, int k, int mode,
         int first_kprime = 0;
         if (fast) {
             FastPlan plan = fast_plan(ix, nq, k);
-            first_kprime = plan.kprime;
+            first_kprime = plan.i8 ? TAIL_KP : plan.kprime;      // the second chance of an int8 plan is the widest 16-bit scan
             if (scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, plan.bytes, false)) { rc = -10; break; }
             if ((rc = fast_search(ix, dq, dnb, false, nq, k, dfl, doi, dod, dct, dce, dst, t_ctx.ws, plan, st))) break;
             if (hipMemcpyAsync(pin_out, blk + off_oi, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = -10; break; }
@@ -1283,7 +1402,7 @@ int ak::search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, in
     if (!todo.empty()) {
         auto reserve = [&](size_t bytes) -> void * { return ix.ws_fb.reserve(bytes) ? nullptr : ix.ws_fb.buf; };
         if ((rc = rerun_uncertified(ix, queries_dev, dnb, nq, k, row_filter_dev, out_ids_dev, out_dist_dev, dct, dce, todo, true,
-                                    plan.kprime, reserve, st, nullptr))) return rc;
+                                    plan.i8 ? TAIL_KP : plan.kprime, reserve, st, nullptr))) return rc;
         AK_HIP(hipStreamSynchronize(st));
     }
     guard.armed = false;      // the stream was synchronised after the last kernel: nothing of this call is in flight
@@ -1312,6 +1431,16 @@ int ak_index_scan_plan(ak_index_t h, int nq, int k, int64_t *out8) {
     FastPlan p = fast_plan(ix, nq, k);
     out8[0] = 1; out8[1] = p.cfg; out8[2] = p.kprime; out8[3] = p.nslices; out8[4] = p.nqg; out8[5] = p.ns_seed;
     out8[6] = p.seed_rows; out8[7] = p.qtile;
+    return 0;
+}
+
+// {rows the int8 shadow covers, full builds so far, searches that ran the int8 plan, max_rho8 in units of 1e-9}
+int ak_index_i8_info(ak_index_t h, int64_t *out4) {
+    if (!h || !out4) AK_FAIL(-1, "ak_index_i8_info: NULL argument");
+    Index &ix = *(Index *)h;
+    std::shared_lock<std::shared_mutex> lk(ix.mu);
+    std::lock_guard<std::mutex> sl(ix.s8_mu);
+    out4[0] = ix.rows8 ? ix.s8_n : 0; out4[1] = ix.s8_builds; out4[2] = ix.s8_searches.load(std::memory_order_relaxed); out4[3] = (int64_t)((double)ix.max_rho8 * 1e9);
     return 0;
 }
 

@@ -28,6 +28,7 @@ struct IndexBook {
     // count grows) and every reclaim of tombstones (slots are renumbered). A tombstone alone does not change it: a mask that
     // still lets a deleted row pass is harmless, the row is dead in `alive`.
     uint64_t epoch = 1;
+    uint64_t reclaims = 0;                             // the epoch changes that RENUMBERED slots (what a per-slot shadow is keyed on)
     std::vector<int64_t> h_ids;                        // [n] id of every slot
     std::vector<uint8_t> h_alive;                      // [n] 0 = tombstone
     std::unordered_map<int64_t, int64_t> id2slot;      // alive ids only
@@ -106,7 +107,7 @@ struct IndexBook {
             h_alive.assign((size_t)m, 1);
             id2slot.clear();
             if (had_map) for (int64_t i = 0; i < m; i++) id2slot.emplace(h_ids[i], i);
-            if (m != n) epoch++;            // tombstones reclaimed: every surviving row has a new slot number
+            if (m != n) { epoch++; reclaims++; }      // tombstones reclaimed: every surviving row has a new slot number
             n = m;
         }
         cap = new_cap;

@@ -91,6 +91,18 @@ __device__ __forceinline__ void mfma16_into(f32x16 &d, uint4 a, uint4 b, bool ze
     acc_set_slice<Q>(d, mfma16<IS_BF16>(a, b, zero ? z : acc_slice<Q>(d)));
 }
 
+// ... and its int8 form, v_mfma_i32_16x16x64_i8: twice the K in the same pipe cycles. A lane supplies 16 consecutive bytes of row /
+// column l & 15, K-group l >> 4 -- the bytes the 16x16x32 fragment read already fetches -- and receives the same four results. The
+// accumulators keep their f32x16 type and hold int32 BITS (a register is a register; nothing but the filter below reads them).
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+template <int Q>
+__device__ __forceinline__ void mfma16_i8_into(f32x16 &d, uint4 a, uint4 b, bool zero) {
+    const i32x4 z = {0, 0, 0, 0};
+    const i32x4 c = zero ? z : __builtin_bit_cast(i32x4, acc_slice<Q>(d));
+    acc_set_slice<Q>(d, __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0)));
+}
+
 // Bitwise binary search with ballots: 32 steps over the score half of the keys and -- only when
 // equal scores straddle the cut -- 32 more over the row half of the tied keys. Needs >= kk valid keys.
 template <int NS>
@@ -196,6 +208,7 @@ struct ScanCfg {
     static constexpr int WM = WM_, WN = WN_, MI = MI_, NI = NI_, NSTAGE = NSTAGE_, MINW = MINW_;
     static constexpr bool PHASED = PHASED_;
     static constexpr int MFMA = MFMA_;
+    static constexpr bool I8 = false;             // int8 operands (one byte per element, K-step 128): CfgP8 below
     using Shape32 = ScanCfg<WM_, WN_, MI_, NI_, NSTAGE_, MINW_, PHASED_, 32>;
     static_assert(MFMA_ == 32 || (MFMA_ == 16 && PHASED_), "the 16x16x32 shape exists for the phased tiles");
     static constexpr int AHEAD = NSTAGE_ - 1;     // ring stages issued ahead of the compute cursor
@@ -250,6 +263,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
     // scans rows [row_begin, n); row_begin is a multiple of BM. thr0 (nullable): per-query initial
     // thresholds in scan-score units (from the seeding pass). Output slot: slice_off + slice.
     constexpr int BM = C::BM, BN = C::BN, NW = C::NW, MI = C::MI, NI = C::NI, NSTAGE = C::NSTAGE, CAP = C::CAP;
+    constexpr bool I8 = C::I8;               // int8 shadow rows and int8 queries: K-step 128 elements, int32 accumulator bits
+    constexpr int EB = I8 ? 1 : 2;           // bytes per element of rows / qs
+    static_assert(!I8 || (C::MFMA == 16 && C::PHASED && !SEED), "the int8 scan is the phased tile on the 16x16 shape; its pre-seeding stays on 16 bits");
     constexpr bool M16 = C::MFMA == 16;      // 16x16x32 MFMAs: a lane owns query columns 16c + (lane & 15) and rows 16h + 4 * (lane >> 4) + j
     static_assert(!(M16 && SEED), "the pre-seeding launch runs the 32x32x16 shape (C::Shape32)");
     const int flags = INSTR ? flags_arg : 0;
@@ -292,7 +308,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
     const int64_t tmul = SEED ? tstride : 1;
     const int ntiles = (int)(tb + ntiles_all * (slice + 1) / nslices - t0);
     constexpr int BKB = C::BKB, CPR = C::CPR, RPP = C::RPP;
-    const int KS = D * 2 / BKB;
+    const int KS = D * EB / BKB;
     const int nsteps = ntiles * KS;
     const int q0 = qg * BN;
 
@@ -446,12 +462,23 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
 #pragma unroll
                     for (int c = 0; c < 2; c++) {
                         const int lo = 4 * c, hi = 8 + 4 * c;     // slices (h = 0, c) and (h = 1, c)
+                        // int8: the group maximum is taken on the integers and only the maximum is converted (|dot| <= 127^2 D < 2^24
+                        // up to D = 1040 and the conversion is monotone beyond: the bound holds either way); plain integer max, which
+                        // the compiler sees -- no inline-asm read of accumulators on this path
+                        const i32x16 ia = __builtin_bit_cast(i32x16, a);
+                        auto imax = [](int x, int y) { return x > y ? x : y; };
+                        float dpos;
+                        if constexpr (I8) {
+                            dpos = (float)imax(imax(imax(imax(ia[lo], ia[lo + 1]), imax(ia[lo + 2], ia[lo + 3])),
+                                                    imax(imax(ia[hi], ia[hi + 1]), imax(ia[hi + 2], ia[hi + 3]))), 0);
+                        } else {
 #if AK_DBG_KERNELS
-                        const float dpos = fmaxf(fmaxf(fmaxf(fmaxf(a[lo], a[lo + 1]), fmaxf(a[lo + 2], a[lo + 3])),
-                                                       fmaxf(fmaxf(a[hi], a[hi + 1]), fmaxf(a[hi + 2], a[hi + 3]))), 0.f);
+                            dpos = fmaxf(fmaxf(fmaxf(fmaxf(a[lo], a[lo + 1]), fmaxf(a[lo + 2], a[lo + 3])),
+                                               fmaxf(fmaxf(a[hi], a[hi + 1]), fmaxf(a[hi + 2], a[hi + 3]))), 0.f);
 #else
-                        const float dpos = max3z(max3f(max3f(a[lo], a[lo + 1], a[lo + 2]), max3f(a[lo + 3], a[hi], a[hi + 1]), a[hi + 2]), a[hi + 3]);
+                            dpos = max3z(max3f(max3f(a[lo], a[lo + 1], a[lo + 2]), max3f(a[lo + 3], a[hi], a[hi + 1]), a[hi + 2]), a[hi + 3]);
 #endif
+                        }
                         const float U = fmaf(dpos, gea, geb);
                         const float thr = s_thr[(wc * NI + ni) * 32 + 16 * c + r16];
                         if (U >= thr && !(INSTR && (flags & 16))) {
@@ -469,8 +496,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                                         if (base + j >= rows_left) { pe[j] = 0.f; pb[j] = -__builtin_inff(); }
                                 }
                                 const int o = 8 * h + 4 * c;
-                                sc[4 * h + 0] = fmaf(a[o + 0], e4.x, b4.x); sc[4 * h + 1] = fmaf(a[o + 1], e4.y, b4.y);
-                                sc[4 * h + 2] = fmaf(a[o + 2], e4.z, b4.z); sc[4 * h + 3] = fmaf(a[o + 3], e4.w, b4.w);
+                                const float d0 = I8 ? (float)ia[o + 0] : a[o + 0], d1 = I8 ? (float)ia[o + 1] : a[o + 1],
+                                            d2 = I8 ? (float)ia[o + 2] : a[o + 2], d3 = I8 ? (float)ia[o + 3] : a[o + 3];
+                                sc[4 * h + 0] = fmaf(d0, e4.x, b4.x); sc[4 * h + 1] = fmaf(d1, e4.y, b4.y);
+                                sc[4 * h + 2] = fmaf(d2, e4.z, b4.z); sc[4 * h + 3] = fmaf(d3, e4.w, b4.w);
                                 mx = fmaxf(fmaxf(mx, sc[4 * h + 0]), fmaxf(fmaxf(sc[4 * h + 1], sc[4 * h + 2]), sc[4 * h + 3]));
                             }
                             if (mx >= thr) {
@@ -631,7 +660,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                 for (int p = 0; p < 2; p++) {
                     const int lr = (wave * 2 + p) * RPP + srow;                                 // row of the A half-tile
                     const int trow = ((lr / (AH * 32)) * MI + AH * h + ((lr >> 5) % AH)) * 32 + (lr & 31);   // corpus row of the tile
-                    voA[h][p] = (uint32_t)trow * (uint32_t)D * 2u + ((schunk ^ swz(lr)) << 4);
+                    voA[h][p] = (uint32_t)trow * (uint32_t)D * (uint32_t)EB + ((schunk ^ swz(lr)) << 4);
                 }
 #pragma unroll
             for (int t = 0; t < NI; t++)
@@ -639,7 +668,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                 for (int p = 0; p < BPP; p++) {
                     const int lr = (wave * BPP + p) * RPP + srow;                               // row of the B part
                     const int qrow = ((lr >> 5) * NI + t) * 32 + (lr & 31);                      // query of the block
-                    voB[t][p] = (uint32_t)qrow * (uint32_t)D * 2u + ((schunk ^ swz(lr)) << 4);
+                    voB[t][p] = (uint32_t)qrow * (uint32_t)D * (uint32_t)EB + ((schunk ^ swz(lr)) << 4);
                 }
             // fragment read offsets: A rows wr*AH*32 + m*32 + r of a half-tile, B rows wc*32 + r of a part; chunk (2*k2 + kh) ^ swz(row)
             // 16x16x32: fragment f = 2 * b + s is the 16-row block b (A: h, B: c) of a 32-row block at K32 sub-step s: rows 16b + r16,
@@ -665,7 +694,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
         };
         lane_consts(lane);
         const char *const rows_b = (const char *)rows;
-        const char *const qs_b = (const char *)qs + (int64_t)q0 * D * 2;
+        const char *const qs_b = (const char *)qs + (int64_t)q0 * D * EB;
         int c_kk = 0, c_tile = 0;                          // staging cursor (K-tile), clamped to the last K-tile: past the
         auto c_adv = [&]() {                               // end it re-stages that K-tile into slots nobody reads any more
             if (c_kk + 1 < KS) c_kk++;
@@ -676,7 +705,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
             const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
             return ((uint64_t)hi << 32) | lo;
         };
-        auto c_pa = [&]() { return sgpr64(rows_b + ((t0 + c_tile) * tmul * BM * D + (int64_t)c_kk * 64) * 2); };
+        auto c_pa = [&]() { return sgpr64(rows_b + (t0 + c_tile) * tmul * BM * D * EB + (int64_t)c_kk * 128); };
         auto c_pb = [&]() { return sgpr64(qs_b + c_kk * 128); };
         const uint32_t lds_w = lds_addr(smem) + wave * 2048;      // this wave's two pieces of an A half-tile
         const uint32_t lds_wb = lds_addr(smem) + wave * (BPP * 1024);   // ... and its piece(s) of a B part
@@ -780,6 +809,13 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                             const int nb = Y ? NI - 1 - e : e;
                             const bool zero = FIRST && s == 0;
                             f32x16 &d = acc[MB + m][nb];
+                            if constexpr (I8) {
+                                mfma16_i8_into<0>(d, fa[m][s], fb[nb][s], zero);
+                                mfma16_i8_into<1>(d, fa[m][s], fb[nb][2 + s], zero);
+                                mfma16_i8_into<2>(d, fa[m][2 + s], fb[nb][s], zero);
+                                mfma16_i8_into<3>(d, fa[m][2 + s], fb[nb][2 + s], zero);
+                                continue;
+                            }
                             mfma16_into<IS_BF16, 0>(d, fa[m][s], fb[nb][s], zero);
                             mfma16_into<IS_BF16, 1>(d, fa[m][s], fb[nb][2 + s], zero);
                             mfma16_into<IS_BF16, 2>(d, fa[m][2 + s], fb[nb][s], zero);
@@ -1205,6 +1241,184 @@ __global__ __launch_bounds__(64) void k_query_setup(const float *__restrict__ q,
     }
 }
 
+// ---------------------------------------------------------------------------
+// The int8 plan (AK_SCAN_I8): seeding and main pass read an int8 shadow of the 16-bit corpus and int8 queries, each with one
+// scale per row / per query. The kernel's score is s' = dot_i32 * ea8[row] (ea8 = row scale * ea); with the query's scale folded
+// into QPrep::a the true-unit score is a * s' + b as for every other plan, so thresholds, keys and margins of ONE query live in
+// that query's own units and QPrep is the only place that converts (lists are per query: nothing compares across queries).
+//   eps: |a.q - (s_r a8).(s_q q8)| <= (rho_q + rho_c + rho_q rho_c) |a| |q| with rho_c the measured maximum over the rows
+//   (Index::max_rho8) and rho_q measured here; the integer dot product is exact, the one float multiply and the stored terms are
+//   covered by the 4 gamma the 16-bit plans carry. At D = 768 on unit Gaussian rows eps ~ 0.6 sigma of the scores, ten times the
+//   bf16 scan's: the plan therefore re-ranks k' = 512 candidates and starts the main pass from an EXACT seed threshold.
+// ---------------------------------------------------------------------------
+__device__ inline float f32_round_down(double s) {
+    float f = (float)s;
+    if ((double)f > s) {
+        uint32_t u = f32_bits(f);
+        f = f > 0.f ? bits_f32(u - 1) : (f < 0.f ? bits_f32(u + 1) : -1.0e-45f);
+    }
+    return f;
+}
+
+__global__ __launch_bounds__(64) void k_query_setup8(const float *__restrict__ q, const float *__restrict__ nb, int nq, int D, int metric,
+                                                     float max_na, float corpus_rho, int8_t *__restrict__ qs8, QPrep *__restrict__ prep,
+                                                     float *__restrict__ mar) {
+    const int qi = blockIdx.x, lane = threadIdx.x;
+    uint32_t *dst = (uint32_t *)(qs8 + (int64_t)qi * D);
+    if (qi >= nq) {
+        for (int i = lane; i < D / 4; i += 64) dst[i] = 0u;
+        return;
+    }
+    const float *v = q + (int64_t)qi * D;
+    float mx = 0.f;
+    for (int i = lane; i < D; i += 64) {
+        const float ax = fabsf(v[i]);
+        if (ax < __builtin_inff() && ax > mx) mx = ax;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    const float sq = mx / 127.f, inv = sq > 0.f ? 1.f / sq : 0.f;
+    double err2 = 0.0;
+    for (int i = lane * 4; i < D; i += 256) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float x = v[i + j];
+            float y = rintf(x * inv);
+            y = y > 127.f ? 127.f : (y < -127.f ? -127.f : y);
+            if (!(y == y)) y = 0.f;
+            const double d = (double)x - (double)sq * (double)y;
+            err2 += d * d;
+            w |= ((uint32_t)(int)y & 0xffu) << (8 * j);
+        }
+        dst[i >> 2] = w;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) err2 += __shfl_xor(err2, off);
+    if (lane == 0) {
+        const double nq2 = (double)nb[qi], qn = sqrt(nq2);
+        const double gamma = (double)D * 5.9604644775390625e-08;           // D * 2^-24
+        const double rho_q = qn > 0 ? sqrt(err2) / qn : 0.0, rho_c = (double)corpus_rho;
+        const double erel = 4.0 * gamma + rho_q + rho_c + rho_q * rho_c + 1e-6;
+        const double maxn = sqrt((double)max_na) * (1.0 + gamma);
+        QPrep p;
+        if (metric == AK_METRIC_COSINE) {
+            p.eps = erel + 4.0 * gamma;
+            p.a = qn > 0 ? (double)sq / qn : 0.0;
+        } else {                                   // inner product (l2 never takes this plan: its additive row term)
+            p.eps = erel * qn * maxn;
+            p.a = (double)sq;
+        }
+        p.b = 0.0;
+        if (!(p.eps == p.eps) || !(p.a == p.a)) { p.eps = __builtin_inf(); p.a = 0.0; }
+        prep[qi] = p;
+        mar[qi] = p.a > 0.0 ? (float)(3.0 * p.eps / p.a * 1.0001) : 3.0e38f;   // 3 eps in this query's scan units
+    }
+}
+
+// A threshold of the 16-bit pre-seeding launch -> the int8 scan's units. t16 is already three eps16 below a k-th best, so
+// a16 t16 + b is a lower bound L of the exact k-th best; a row of the exact top-k has a8 s8 + b >= exact - eps8 >= L - eps8.
+__global__ void k_thr_to_i8(const QPrep *__restrict__ p16, const QPrep *__restrict__ p8, int nq, float *__restrict__ thr0) {
+    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= nq) return;
+    const float t16 = thr0[qi];
+    float t = -3.4028234663852886e38f;
+    const QPrep a = p16[qi], b = p8[qi];
+    if (t16 > -3.0e38f && t16 == t16 && b.a > 0.0) {
+        const float f = f32_round_down((a.a * (double)t16 + a.b - b.eps - b.b) / b.a);
+        if (f == f && f > t) t = f;
+    }
+    thr0[qi] = t;
+}
+
+// The exact seed threshold: dist [nq][k] are the exact distances of the k best of the seed candidates' best 64, re-ranked by the
+// fused tail. The exact k-th best of ANY k rows is a lower bound of the global exact k-th best, whether or not that list
+// certified; theta = (it - eps) in the query's scan units is where the main pass starts (raises thr0 only).
+__global__ void k_seed_exact_thr(const double *__restrict__ dist, const int *__restrict__ cnt, const QPrep *__restrict__ prep, int nq, int k,
+                                 int metric, bool keep, float *__restrict__ thr0) {
+    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= nq) return;
+    float t0 = keep ? thr0[qi] : -3.4028234663852886e38f;      // keep: the pre-seeding threshold stands where it is higher
+    if (!(t0 == t0)) t0 = -3.4028234663852886e38f;
+    const QPrep p = prep[qi];
+    if (cnt[qi] == k && p.a > 0.0) {
+        const double dk = dist[(int64_t)qi * k + (k - 1)];
+        const double t = metric == AK_METRIC_COSINE ? 1.0 - dk : -dk;
+        const float f = f32_round_down((t - p.eps - p.b) / p.a);
+        if (dk == dk && f == f && f > t0) t0 = f;
+    }
+    thr0[qi] = t0;
+}
+
+// Tail selection of the int8 plan: the dense per-query list -> drop what lies below the cut (the main pass's starting threshold
+// and the max-reduced workgroup thresholds, as k_tail does) -> the best kp (512) keys by a bitwise binary search over the 64-bit
+// keys (distinct: they carry the row), unordered except that a full selection ends with its worst key, which is what
+// k_finalize's list-full rule reads. The keys stay in registers, 16 per thread of a 1024-thread workgroup: the int8 margin lets
+// 3-6 k keys per query through at 10M rows, more than an LDS array of the size k_tail sorts would hold. thr_fin[q]: the cut, for
+// the certificate; +inf (never certified) when the list is longer than the workgroup holds.
+constexpr int SD_THREADS = 1024, SD_EPT = 16, SD_CAP = SD_THREADS * SD_EPT, SD_WAVES = SD_THREADS / 64;
+__global__ __launch_bounds__(SD_THREADS) void k_select_dense(const uint64_t *__restrict__ list, int64_t lcap, const int *__restrict__ cnt_g,
+                                                             const unsigned int *__restrict__ thr_g, const float *__restrict__ thr0, int kp,
+                                                             uint64_t *__restrict__ top, float *__restrict__ thr_fin) {
+    __shared__ int s_pos;
+    __shared__ int s_c[2][SD_WAVES];
+    const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float theta = thr0 ? thr0[qi] : -__builtin_inff();
+    if (!(theta == theta)) theta = -__builtin_inff();
+    const unsigned int tg = thr_g[qi];
+    const float tmax = tg ? key_score(~tg) : -__builtin_inff();
+    const float cutoff = tmax > theta ? tmax : theta;
+    const uint32_t cut_key = score_key(cutoff);
+    int64_t n = cnt_g[qi];
+    if (n > lcap) n = lcap;
+    const bool overflow = n > SD_CAP;
+    if (overflow) n = SD_CAP;
+    if (tid == 0) {
+        s_pos = 0;
+        thr_fin[qi] = overflow ? __builtin_inff() : (cutoff > -3.0e38f ? cutoff : -3.4028234663852886e38f);
+    }
+    const uint64_t *lst = list + (int64_t)qi * lcap;
+    uint64_t key[SD_EPT];
+    int c = 0;
+#pragma unroll
+    for (int e = 0; e < SD_EPT; e++) {
+        const int idx = e * SD_THREADS + tid;
+        uint64_t k = idx < n ? lst[idx] : KEY_INVALID;
+        if ((uint32_t)(k >> 32) > cut_key) k = KEY_INVALID;
+        key[e] = k;
+        c += __popcll(__ballot(k != KEY_INVALID));
+    }
+    auto block_sum = [&](int v, int par) {          // v is wave-uniform; one barrier, the two parities alternate
+        if (lane == 0) s_c[par][wave] = v;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < SD_WAVES; w++) tot += s_c[par][w];
+        return tot;
+    };
+    const int have = block_sum(c, 0);
+    uint64_t *dst = top + (int64_t)qi * kp;
+    uint64_t th = KEY_INVALID;                       // keep every key below th; th itself goes last
+    if (have >= kp) {                                // (exactly kp survivors: all are kept, the search finds the worst of them)
+        th = 0;
+        for (int bit = 63; bit >= 0; bit--) {
+            const uint64_t test = th | ((1ull << bit) - 1ull);
+            int cc = 0;
+#pragma unroll
+            for (int e = 0; e < SD_EPT; e++) cc += __popcll(__ballot(key[e] <= test));
+            if (block_sum(cc, bit & 1) < kp) th |= (1ull << bit);      // bit 63 takes parity 1: the count above took 0
+        }
+        // th = the kp-th smallest key: kp - 1 keys lie below it
+    }
+#pragma unroll
+    for (int e = 0; e < SD_EPT; e++) {
+        if (key[e] < th) dst[atomicAdd(&s_pos, 1)] = key[e];
+        else if (key[e] == th && have >= kp) dst[kp - 1] = key[e];
+    }
+    if (have < kp)
+        for (int i = have + tid; i < kp; i += SD_THREADS) dst[i] = KEY_INVALID;
+}
+
 // Seeding pass -> per-query initial threshold for the main pass, in scan-score units:
 // (k-th best approximate score of the seed rows) - 3 eps'. The k-th best of a subset is a lower
 // bound of the global k-th best, so no row that could reach the exact top-k is discarded.
@@ -1412,6 +1626,8 @@ using CfgL = ScanCfg<4, 2, 2, 2, 3, 2>;   // 256 x 128, 8 waves (64x64 each), 3-
 using CfgM = ScanCfg<4, 1, 2, 2, 3, 1>;   // 256 x 64 , 4 waves, 3-slot ring : HBM-bound, Q <= 64
 using CfgS = ScanCfg<4, 1, 2, 1, 3, 1>;   // 256 x 32 , 4 waves, 3-slot ring : HBM-bound, Q <= 32
 using CfgO = ScanCfg<2, 2, 2, 2, 2, 2>;   // 128 x 128, 4 waves, 2-slot ring, 2 blocks/CU (first version; A/B reference)
+// the 256 x 256 phased tile on int8 operands (v_mfma_i32_16x16x64_i8): a type of its own, so the names of the 16-bit kernels stand
+struct CfgP8 : CfgPs<16> { static constexpr bool I8 = true; };
 using CfgR = CfgRs<SHIP_R>;                     // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
 
 struct CfgInfo { int bm, bn, cap, threads, lds, blocks_per_cu; };
@@ -1443,6 +1659,9 @@ enum { CFG_L = 0, CFG_M = 1, CFG_S = 2, CFG_O = 3, CFG_X = 4, CFG_P = 5, CFG_Q =
 // group costs ~0.62 of a 256-query group. Between the regimes -- Q in (256, 384], (768, 896] ... -- the narrower tile
 // wastes less. Small shards (1M x 384 f32, Q = 256: L 0.455, Q 0.455, P 0.509 ms; 1.25M x 768 bf16: L 0.864, Q 0.872,
 // P 0.759; Q = 1024: Q 2.15, P 1.91): the wide tile needs long rows and enough tiles per workgroup to pay.
+// long rows and many tiles: where the wide tiles pay and the scan is bound by the matrix pipe (pick_cfg, the int8 plan's eligibility)
+static bool big_shard(const Index &ix) { return ix.dim >= 768 && (ix.n + 255) / 256 >= 4096; }
+
 static int pick_cfg(int nq, const Index &ix) {
     if (const int forced = switches().scan_cfg.load(std::memory_order_relaxed)) {
         switch (forced) { case 'L': return CFG_L; case 'M': return CFG_M; case 'S': return CFG_S;
@@ -1455,9 +1674,8 @@ static int pick_cfg(int nq, const Index &ix) {
     if (nq <= 64) return CFG_M;
     if (nq <= 128) return CFG_L;          // HBM-bound: the in-step loop with its three-slot ring
     if (ix.dim < 128) return CFG_L;       // one K-step per tile: the phased loop wants two (its compaction-request sampling)
-    const int64_t ntiles = (ix.n + 255) / 256;
     const int g128 = (nq + 127) / 128, g192 = (nq + 191) / 192, g256 = (nq + 255) / 256;
-    const bool big = ix.dim >= 768 && ntiles >= 4096;
+    const bool big = big_shard(ix);
     // A query group is a full pass over the slice's tiles whatever it holds; relative cost of a pass: 256-query group 1,
     // 192-query group 0.85, 128-query group 0.62. Long rows and many tiles: the cheapest padded batch. Small or short-row shards:
     // the wide tile pays later (two 128-groups at Q <= 256, the measured 1.62 rule above), the 192 tile when it beats that choice
@@ -1474,6 +1692,8 @@ static int pick_cfg(int nq, const Index &ix) {
     return cr < (base == CFG_P ? cp : cq) ? CFG_R : base;
 }
 
+constexpr int I8_KP = 512;      // candidates the int8 plan re-ranks per query (k_finalize<8>; the append buffers' limit)
+
 bool fast_supported(const Index &ix, int nq, int k) {
     if (ix.dim % BK != 0) return false;
     if (ix.n < 4096) return false;                          // tiny index: exact path is cheaper
@@ -1483,11 +1703,22 @@ bool fast_supported(const Index &ix, int nq, int k) {
 
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-FastPlan fast_plan(const Index &ix, int nq, int k, bool widest) {
+FastPlan fast_plan(const Index &ix, int nq, int k, bool widest, bool allow_i8) {
     FastPlan p;
     p.cfg = pick_cfg(nq, ix);
     const CfgInfo &c = g_cfgs[p.cfg];
     p.kprime = k <= 16 ? 64 : (k <= 48 ? 128 : 256);
+    // the int8 plan: tile P, cosine / inner product (no additive row term), a 16-bit corpus, rows of >= two 128-element K-steps,
+    // the common k' (k <= 16); by its own choice (AK_SCAN_I8 = 1) only where the scan is bound by the matrix pipe -- a big shard
+    // and at least two 256-query groups. AK_SCAN_I8 = 2 takes every shape the kernel allows (tests, A/B runs).
+    p.i8 = 0;
+    if (const int i8m = switches().scan_i8.load(std::memory_order_relaxed)) {
+        const bool shape_ok = allow_i8 && !widest && p.cfg == CFG_P && ix.metric != AK_METRIC_L2 && ix.dtype != AK_DTYPE_F32 && ix.dim % 128 == 0 &&
+                              ix.dim >= 256 && ix.dim <= TAIL_MAX_DIM && k <= 16;
+        const bool big = big_shard(ix);
+        if (shape_ok && (i8m >= 2 || (big && nq > 256))) p.i8 = 1;
+    }
+    if (p.i8) p.kprime = I8_KP;
     // second-chance plan (AUTO mode, queries the first pass could not certify): the widest candidate lists the
     // append buffers and k_finalize<8> allow, so a pile-up of up to 512 equal scores still certifies
     if (widest) p.kprime = 512;
@@ -1560,6 +1791,11 @@ FastPlan fast_plan(const Index &ix, int nq, int k, bool widest) {
     bytes += al((size_t)nq * k * 8) * 2;                                    // final keys + ids
     bytes += al(select_scratch_bytes(nq, (int64_t)ns_tot * p.kprime, p.kprime) +
                 select_keys_scratch_bytes(nq, (int64_t)ns_tot * p.kprime, p.kprime));
+    if (p.i8) {
+        bytes += al((size_t)nq_pad * ix.dim);                                // int8 queries
+        bytes += al((size_t)nq * sizeof(QPrep));                             // their prep
+        bytes += al((size_t)nq * 4) * 4;                                     // margins, final cut, seed re-rank counts + flags
+    }
     bytes += 4096;
     p.bytes = bytes;
     return p;
@@ -1582,7 +1818,8 @@ static int launch_scan(const Index &ix, const uint8_t *filter_dev, int64_t row_b
             AK_HIP(hipFuncSetAttribute((const void *)k_scan<BF, C, SEED, true, SEEDPASS>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
         attr_set = true;
     }
-    const uint16_t *rows16 = (const uint16_t *)(ix.dtype == AK_DTYPE_F32 ? ix.shadow : ix.rows);
+    const uint16_t *rows16 = (const uint16_t *)(C::I8 ? (const void *)ix.rows8 : (ix.dtype == AK_DTYPE_F32 ? ix.shadow : ix.rows));
+    const float *ea = C::I8 ? ix.ea8 : ix.ea, *gb = C::I8 ? ix.gb8 : ix.gb;      // int8: the scale-folded terms; eb (0 / -inf) is the index's own
     const int64_t gbb = (ix.n + 31) / 32;
     bool instr = false;
     if constexpr (!SEED) instr = scan_instrumented();
@@ -1590,11 +1827,11 @@ static int launch_scan(const Index &ix, const uint8_t *filter_dev, int64_t row_b
         if constexpr (!DBG_KERNELS) AK_FAIL(-1, "AK_SCAN_DBG and the scan ablation switch need libarchi_hip_dbg.so (make -C archi_amd/csrc dbg): the product library carries no instrumented scan kernels");
         if constexpr (!SEED && DBG_KERNELS)
             k_scan<BF, C, SEED, true, SEEDPASS><<<(unsigned)(ns * nqg), C::THREADS, C::LDS_BYTES, st>>>(
-                rows16, ix.ea, ix.eb, ix.gb, gbb, filter_dev, row_begin, row_end, ix.dim, qs, nq, ns, nqg, k, kp, thr0, mar, slice_off,
+                rows16, ea, ix.eb, gb, gbb, filter_dev, row_begin, row_end, ix.dim, qs, nq, ns, nqg, k, kp, thr0, mar, slice_off,
                 ns_total, cand, out_c, thr_slots, scan_ablate_flags(), dbg, sample_tiles, tstride, dense_cnt, dense_thr);
     } else {
         k_scan<BF, C, SEED, false, SEEDPASS><<<(unsigned)(ns * nqg), C::THREADS, LDSB, st>>>(
-            rows16, ix.ea, ix.eb, ix.gb, gbb, filter_dev, row_begin, row_end, ix.dim, qs, nq, ns, nqg, k, kp, thr0, mar, slice_off,
+            rows16, ea, ix.eb, gb, gbb, filter_dev, row_begin, row_end, ix.dim, qs, nq, ns, nqg, k, kp, thr0, mar, slice_off,
             ns_total, cand, out_c, thr_slots, 0, nullptr, sample_tiles, tstride, dense_cnt, dense_thr);
     }
     AK_HIP(hipGetLastError());
@@ -1604,6 +1841,18 @@ static int launch_scan(const Index &ix, const uint8_t *filter_dev, int64_t row_b
 int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_ready, int nq, int k, const uint8_t *filter_dev,
                 int64_t *out_ids_dev, double *out_dist_dev, int *out_cnt_dev, int *cert_dev, int64_t *stats_dev,
                 void *ws, const FastPlan &plan, hipStream_t st) {
+    if (plan.i8) {
+        // the shadow is +50 % of the corpus: on a device too full for it the search runs the 16-bit plan it ran before the int8
+        // plan existed (same tile and slices, k' = 64: every part of its workspace is no larger than this plan's)
+        const int src = ensure_shadow8(ix, st);
+        if (src == AK_SHADOW8_NOMEM) {
+            const FastPlan alt = fast_plan(ix, nq, k, false, false);
+            if (alt.bytes > plan.bytes) AK_FAIL(-10, "fast_search: no memory for the int8 shadow and the workspace does not hold the 16-bit plan");
+            return fast_search(ix, queries_dev, nb_dev, nb_ready, nq, k, filter_dev, out_ids_dev, out_dist_dev, out_cnt_dev, cert_dev,
+                               stats_dev, ws, alt, st);
+        }
+        if (src) return src;
+    }
     const CfgInfo &c = g_cfgs[plan.cfg];
     const int kp = plan.kprime, ns = plan.nslices, nss = plan.ns_seed, ns_tot = ns + nss, nqg = plan.nqg,
               nq_pad = nqg * c.bn;
@@ -1622,12 +1871,24 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
     int64_t *top_i = (int64_t *)p; p += al((size_t)nq * kp * 8);
     uint64_t *rr_k = (uint64_t *)p; p += al((size_t)nq * kp * 8);
     int64_t *rr_i = (int64_t *)p; p += al((size_t)nq * kp * 8);
-    p += 2 * al((size_t)nq * k * 8);
+    int64_t *fin_i = (int64_t *)p; p += al((size_t)nq * k * 8);        // (the int8 plan parks its seed re-rank here)
+    double *fin_d = (double *)p; p += al((size_t)nq * k * 8);
+    const bool i8 = plan.i8 != 0;
+    int8_t *qs8 = nullptr; QPrep *prep8 = nullptr; float *mar8 = nullptr, *thr_fin = nullptr; int *sd_cnt = nullptr, *sd_cert = nullptr;
+    if (i8) {
+        qs8 = (int8_t *)p; p += al((size_t)nq_pad * ix.dim);
+        prep8 = (QPrep *)p; p += al((size_t)nq * sizeof(QPrep));
+        mar8 = (float *)p; p += al((size_t)nq * 4);
+        thr_fin = (float *)p; p += al((size_t)nq * 4);
+        sd_cnt = (int *)p; p += al((size_t)nq * 4);
+        sd_cert = (int *)p; p += al((size_t)nq * 4);
+        if (plan.cfg != CFG_P || kp != I8_KP) AK_FAIL(-1, "fast_search: the int8 plan is tile P with k' = 512");
+    }
     void *scratch = p;
 
     // The common plan (k' = 64, i.e. k <= 16) runs with dense candidate lists and the fused tail kernel; the wide plans
     // (k' = 128 / 256 / 512: large k, second-chance scans) keep the slot layout and the three-kernel tail.
-    const bool dense = kp == TAIL_KP && ix.dim <= TAIL_MAX_DIM && !switches().tail_old.load(std::memory_order_relaxed);
+    const bool dense = i8 || (kp == TAIL_KP && ix.dim <= TAIL_MAX_DIM && !switches().tail_old.load(std::memory_order_relaxed));
     int *dcnt = dense ? d_cnt : nullptr;
     unsigned int *dthr = dense ? d_thr : nullptr;
 
@@ -1638,6 +1899,7 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
                                                        shadowed ? ix.max_rho : 0.f, qs, prep, mar, stats_dev, dcnt, dthr);
     else k_query_setup<false><<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, nb_ready ? 0 : 1, nq, nq_pad, ix.dim, ix.metric, ix.max_na, 0.f,
                                                      qs, prep, mar, stats_dev, dcnt, dthr);
+    if (i8) k_query_setup8<<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, nq, ix.dim, ix.metric, ix.max_na, ix.max_rho8, qs8, prep8, mar8);
     AK_HIP(hipGetLastError());
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1681,6 +1943,10 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
         case CFG_R: SCAN_SHAPED(CfgRs, CfgR, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
         default: AK_FAIL(-1, "scan: tile configuration not in this library (X and O: libarchi_hip_dbg.so)"); \
     }
+    // the int8 plan: one tile, one element type
+#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP)                                                                                     \
+    rc = launch_scan<true, CfgP8, false, SP>(ix, filter_dev, R0, R1, (const uint16_t *)qs8, nq, NS, nqg, k, kp, THR, mar8, SOFF, ns_tot, \
+                                             cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
     long long *dbg0 = nullptr, *dbg1 = nullptr;
     if (want_dbg) {
         if (!ix.dbg_dev) { AK_HIP(hipMalloc((void **)&ix.dbg_dev, 2 * 65536 * 8)); }
@@ -1713,12 +1979,26 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
 #undef PRE
             if (rc) return rc;
             k_seed_kth<<<nq, 64, 0, st>>>(gmax, plan.pre_slices * (c.bm / 16), prep, k, thr0);
+            if (i8) k_thr_to_i8<<<(nq + 63) / 64, 64, 0, st>>>(prep, prep8, nq, thr0);      // the 16-bit sample's threshold in int8 units
             AK_HIP(hipGetLastError());
             thr_seed = thr0;
             thr_main = thr0;
         }
     }
-    if (nss > 0) {
+    if (nss > 0 && i8) {
+        // int8 seeding pass, then the exact seed threshold: the fused tail re-ranks the best 64 seed candidates of every query
+        // in the reference arithmetic (its usual work, on the lists as they stand before the main pass) and k_seed_exact_thr
+        // turns their exact k-th best into theta. "k-th best approximate score - 3 eps" with the int8 eps lets 10-20 k rows
+        // per query through the main pass (docs/EXPERIMENTS.md, "int8 shadow"); this one about as many as the bf16 plan.
+        SCAN8(0, plan.seed_rows, nss, thr_seed, 0, dbg0, true);
+        if (rc) return rc;
+        rc = fused_tail(ix, queries_dev, nb_dev, nq, k, out_c, (int64_t)ns_tot * kp, d_cnt, d_thr, thr_seed, prep8, fin_i, fin_d, sd_cnt,
+                        sd_cert, nullptr, st);
+        if (rc) return rc;
+        k_seed_exact_thr<<<(nq + 63) / 64, 64, 0, st>>>(fin_d, sd_cnt, prep8, nq, k, ix.metric, thr_seed != nullptr, thr0);
+        AK_HIP(hipGetLastError());
+        thr_main = thr0;
+    } else if (nss > 0) {
         // seeding pass over rows [0, seed_rows) -> per-query thresholds for the main pass
         SCAN_ANY(0, plan.seed_rows, nss, thr_seed, 0, dbg0, true);
         if (rc) return rc;
@@ -1745,13 +2025,28 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
         thr_main = thr0;
     }
     if (ev0) AK_HIP(hipEventRecord(ev0, st));   // the timed "dominant kernel" is the main-pass launch
-    SCAN_ANY(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false);
+    if (i8) { SCAN8(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false); }
+    else { SCAN_ANY(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false); }
+#undef SCAN8
 #undef SCAN_ANY
 #undef SCAN_SHAPED
 #undef SCAN
     if (rc) return rc;
     if (ev1) AK_HIP(hipEventRecord(ev1, st));
 
+    if (i8) {
+        // the int8 tail: best 512 of the dense list -> exact re-rank against the stored 16-bit rows -> top-k + certificate with
+        // the int8 eps (one cut for the whole query where the slot layout had one threshold per slice)
+        ix.s8_searches.fetch_add(1, std::memory_order_relaxed);
+        k_select_dense<<<nq, SD_THREADS, 0, st>>>(out_c, (int64_t)ns_tot * kp, d_cnt, d_thr, thr_main, kp, top_k, thr_fin);
+        AK_HIP(hipGetLastError());
+        rc = rerank(ix, queries_dev, nb_dev, nq, kp, top_k, rr_k, rr_i, st);
+        if (rc) return rc;
+        k_finalize<8><<<nq, 64, 0, st>>>(top_k, rr_k, rr_i, prep8, nb_dev, thr_fin, 1, k, kp, ix.metric, out_ids_dev, out_dist_dev,
+                                         out_cnt_dev, cert_dev, stats_dev);
+        AK_HIP(hipGetLastError());
+        return 0;
+    }
     if (dense)
         return fused_tail(ix, queries_dev, nb_dev, nq, k, out_c, (int64_t)ns_tot * kp, d_cnt, d_thr, thr_main, prep, out_ids_dev,
                           out_dist_dev, out_cnt_dev, cert_dev, stats_dev, st);

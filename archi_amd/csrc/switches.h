@@ -10,11 +10,15 @@
 
 namespace ak {
 
+// default of AK_SCAN_I8, decided by the alternating same-job A/B against the parent build (docs/EXPERIMENTS.md, "int8 shadow")
+constexpr int AK_SCAN_I8_DEFAULT = 1;
+
 struct Switches {
     // scan plan (scan.hip)
     std::atomic<int> scan_cfg{0};        // AK_SCAN_CFG: forced tile, its letter (0 = the plan's choice)
     std::atomic<int> scan_mfma{0};       // AK_SCAN_MFMA: MFMA shape of the phased tiles P / Q / R, 16 (16x16x32) or 32 (32x32x16); 0 = the shape that
                                          // ships for the tile. Both shapes exist in the dbg library only: the product library refuses 16 / 32
+    std::atomic<int> scan_i8{AK_SCAN_I8_DEFAULT};   // AK_SCAN_I8: the int8 scan plan. 0 = off, 1 = where the plan finds it eligible, 2 = wherever the shape allows (tests)
     std::atomic<int> scan_blocks{0};     // AK_SCAN_BLOCKS: workgroups per launch (0 = resident count)
     std::atomic<int> scan_r192_pm{850};  // AK_SCAN_R192: relative cost of a 192-query pass, per mille
     std::atomic<int> scan_no192{0};      // AK_SCAN_NO192

@@ -281,6 +281,12 @@ class HipIndex:
         d["cfg_name"] = ["256x128", "256x64", "256x32", "128x128", "256x256 in-step", "256x256", "256x128 phased", "256x192 phased"][d["cfg"]] if d["fast"] else None
         return d
 
+    def i8_info(self) -> dict:
+        """State of the int8 shadow the AK_SCAN_I8 plan scans: rows covered, full builds, searches that ran on it, max row rho."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.ak_index_i8_info(self._h, _ptr(out)), "ak_index_i8_info")
+        return {"rows": int(out[0]), "builds": int(out[1]), "searches": int(out[2]), "max_rho": float(out[3]) * 1e-9}
+
     def debug_read(self) -> np.ndarray:
         """[2 launches][8192 waves][8] phase cycle counters (needs AK_SCAN_DBG=1 during the search)."""
         out = np.zeros(2 * 65536, dtype=np.int64)

@@ -235,6 +235,9 @@ int ak_index_search_dev(ak_index_t h, const float *queries_dev, int nq, int k, i
  * slices, query groups, seed-pass slices, seed-pass rows, queries per workgroup}. The main scan
  * launch covers rows [seed_rows, count).                                                      */
 int ak_index_scan_plan(ak_index_t h, int nq, int k, int64_t *out8);
+/* int8 shadow of a 16-bit corpus (AK_SCAN_I8): out4 = {rows covered, full builds so far, searches that ran the int8 plan,
+ * largest relative rounding error of a row in units of 1e-9} */
+int ak_index_i8_info(ak_index_t h, int64_t *out4);
 
 /* Developer aid: per-wave phase cycle counters of the last search's two scan launches (seed pass at
  * [0,65536), main pass at [65536,131072), 8 int64 per wave: k-loop, filter, sync, compaction, final,
