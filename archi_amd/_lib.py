@@ -17,7 +17,7 @@ DTYPES = {"f32": 0, "bf16": 1, "f16": 2}
 # store-level metric names (postgres_vectorstore.py:74-78) -> AK_METRIC_*
 METRICS = {"cosine": 0, "l2": 1, "inner_product": 2}
 SEARCH_MODES = {"auto": 0, "exact": 1, "fast_only": 2}
-POOLING = {"mean": 0, "cls": 1, "last": 2}      # AK_POOL_*; "last": ak_llama_forward_lens only
+POOLING = {"mean": 0, "cls": 1, "last": 2}      # AK_POOL_*; "last": ak_llama_forward_lens and ak_qwen2_forward_lens only
 
 
 class HipBackendError(RuntimeError):
@@ -149,6 +149,22 @@ class AkLlamaConfig(ctypes.Structure):
     ]
 
 
+class AkQwen2Config(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("q_heads", ctypes.c_int),
+        ("kv_heads", ctypes.c_int),
+        ("head_dim", ctypes.c_int),
+        ("intermediate", ctypes.c_int),
+        ("max_position", ctypes.c_int),
+        ("rms_eps", ctypes.c_float),
+        ("rope_theta", ctypes.c_float),
+        ("bidirectional", ctypes.c_int),
+    ]
+
+
 _lock = threading.Lock()
 _lib = None
 _inited_device = None
@@ -225,6 +241,10 @@ SYMBOLS = [
     ("ak_llama_destroy", _I, [_P]),
     ("ak_llama_set_rope_inv_freq", _I, [_P, _P]),
     ("ak_llama_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("ak_qwen2_create", _I, [ctypes.POINTER(AkQwen2Config), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_qwen2_destroy", _I, [_P]),
+    ("ak_qwen2_set_rope_inv_freq", _I, [_P, _P]),
+    ("ak_qwen2_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_wordpiece_create", _I, [ctypes.c_char_p, _I, ctypes.POINTER(_P)]),
     ("ak_wordpiece_create_ex", _I, [ctypes.c_char_p, _I, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.POINTER(ctypes.c_char_p), _I, ctypes.POINTER(_P)]),
@@ -317,6 +337,7 @@ KTS_SYMBOLS = [
     ("ak_kts_ll_attn", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     ("ak_kts_ll_pool", _I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _P]),
     ("ak_kts_ll_rope", _I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
+    ("ak_kts_q2_attn", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),      # launch_attn_causal_split (tests/test_qwen2_kernels_gpu.py)
 ]
 
 

@@ -33,6 +33,8 @@ EMBEDDING_DIMENSIONS = {
     "intfloat/e5-mistral-7b-instruct": 4096,
     "Salesforce/SFR-Embedding-Mistral": 4096,
     "Linq-AI-Research/Linq-Embed-Mistral": 4096,
+    "Alibaba-NLP/gte-Qwen2-1.5B-instruct": 1536,
+    "Alibaba-NLP/gte-Qwen2-7B-instruct": 3584,
     "nomic-ai/modernbert-embed-base": 768,
     "Alibaba-NLP/gte-modernbert-base": 768,
     "lightonai/modernbert-embed-large": 1024,

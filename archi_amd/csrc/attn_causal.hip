@@ -23,6 +23,8 @@
 // row's length for every query below it. The workgroup walks the blocks that hold such a key and no others; inside the last partial
 // block the keys at or past the length are masked (the causal mask hid them for free). Key 0 is below the length of a live row, so the
 // step needs no guard. Rows at or past the length are stored as zeros.
+// SPLIT (k_attn_causal_gs, k_attn_bidir_gs; launch_attn_causal_split: Qwen2's 5 to 8 query heads per kv head): the same wave, one
+// 32-row query block per workgroup, the group's heads in two workgroups of 3 or 4 waves (attn_causal_body.h says how).
 #include "flash_tile.h"
 
 namespace ak {
@@ -48,6 +50,19 @@ using Tile = FlashTile<CA_HD>;
 #include "attn_causal_body.h"
 #undef AK_CAUSAL_KERNEL
 #undef AK_CAUSAL_VIS
+// the kv group split over workgroups (5 to 8 query heads per kv head: Qwen2), causal and bidirectional; no banded variant
+#define AK_CAUSAL_SPLIT 1
+#define AK_CAUSAL_KERNEL k_attn_causal_gs
+#define AK_CAUSAL_VIS 0
+#include "attn_causal_body.h"
+#undef AK_CAUSAL_KERNEL
+#undef AK_CAUSAL_VIS
+#define AK_CAUSAL_KERNEL k_attn_bidir_gs
+#define AK_CAUSAL_VIS 2
+#include "attn_causal_body.h"
+#undef AK_CAUSAL_KERNEL
+#undef AK_CAUSAL_VIS
+#undef AK_CAUSAL_SPLIT
 }  // namespace
 
 bool attn_causal_supported(int nq, int nkv, int head_dim, int S) {
@@ -64,6 +79,28 @@ int launch_attn_causal(const CausalAttnArgs &a, hipStream_t st) {
     if (a.bidirectional) k_attn_bidir<<<grid, 64 * G * R, 0, st>>>(a);        // ignores the window
     else if (a.window > 0) k_attn_causal_band<<<grid, 64 * G * R, 0, st>>>(a);      // (a window >= S hides nothing; the rows past a length are still zeroed)
     else k_attn_causal<<<grid, 64 * G * R, 0, st>>>(a);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+
+// 5 to 8 query heads per kv head (Qwen2-1.5B: 6, Qwen2-7B: 7, Qwen2.5-3B: 8, Qwen2.5-14B: 5): the group in P = ceil(G / 4) workgroups of
+// GP = ceil(G / P) waves (3 + 2, 3 + 3, 4 + 3, 4 + 4 heads), grid (S / 32, nkv * P, B); each workgroup stages the K / V blocks it walks
+// once for its 3 or 4 heads
+bool attn_causal_split_supported(int nq, int nkv, int head_dim, int S) {
+    if (head_dim != CA_HD || nkv <= 0 || nq <= 0 || nq % nkv) return false;
+    const int G = nq / nkv;
+    return G >= 5 && G <= 8 && S % 32 == 0 && S > 0 && S <= 8192;
+}
+
+int launch_attn_causal_split(const CausalAttnArgs &a, hipStream_t st) {
+    if (!attn_causal_split_supported(a.nq, a.nkv, CA_HD, a.S))
+        AK_FAIL(-1, "attn_causal_split: 5 to 8 query heads per kv head, S a multiple of 32 up to 8192");
+    if (a.window != 0) AK_FAIL(-1, "attn_causal_split: no sliding window (window must be 0)");
+    if (a.B <= 0 || a.B > 65535) AK_FAIL(-1, "attn_causal_split: 1 to 65535 rows");
+    const int G = a.nq / a.nkv, P = (G + 3) / 4, GP = (G + P - 1) / P;
+    const dim3 grid(a.S / 32, a.nkv * P, a.B);
+    if (a.bidirectional) k_attn_bidir_gs<<<grid, 64 * GP, 0, st>>>(a);
+    else k_attn_causal_gs<<<grid, 64 * GP, 0, st>>>(a);
     AK_HIP(hipGetLastError());
     return 0;
 }

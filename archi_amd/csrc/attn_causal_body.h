@@ -2,23 +2,44 @@
 // CA_HD and Tile): AK_CAUSAL_KERNEL names the kernel, AK_CAUSAL_VIS its visibility: 0 causal, 1 causal + sliding window, 2 bidirectional
 // (every key below the row's length). Three kernels of one text rather than instantiations of a template or callers of an inlined body: k_attn_causal keeps its name and, compiled as a plain
 // kernel, the register allocation it had before the band existed (153 VGPRs; through an inlined body: 154). No include guard on purpose.
+// AK_CAUSAL_SPLIT (k_attn_causal_gs, k_attn_bidir_gs: 5 to 8 query heads per kv head, Qwen2): the group's G heads are split over
+// P = ceil(G / 4) workgroups of GP = ceil(G / P) waves, blockIdx.y = kvh * P + part, one 32-row query block per workgroup; wave w of
+// part p computes head p * GP + w of the group. The last part of G = 5 and G = 7 has one wave more than heads: that wave owns no
+// head -- it stages and meets every barrier, loads no q and stores nothing. Both split kernels store zeros for every query at or past
+// the length (k_attn_causal leaves those of a live row block finite but unspecified). Without the macro the text below is what it was.
 __global__ __launch_bounds__(256) void AK_CAUSAL_KERNEL(CausalAttnArgs a) {
     constexpr bool BAND = AK_CAUSAL_VIS == 1, BIDIR = AK_CAUSAL_VIS == 2;
     __shared__ __attribute__((aligned(16))) char sK[Tile::K_BYTES];
     __shared__ __attribute__((aligned(16))) char sV[Tile::V_BYTES];
+#if AK_CAUSAL_SPLIT
+    const int G = a.nq / a.nkv, P = (G + 3) / 4, GP = (G + P - 1) / P, QR = 32;
+    const int kvh = blockIdx.y / P, part = blockIdx.y % P, b = blockIdx.z;
+#else
     const int G = a.nq / a.nkv, R = rows_per_group(G), QR = 32 * R;
     const int kvh = blockIdx.y, b = blockIdx.z;
+#endif
     const int qblk = gridDim.x - 1 - blockIdx.x;              // the longest causal rows first
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#if AK_CAUSAL_SPLIT
+    const int g = part * GP + wave, j = 0;
+    const bool owns = g < G;                                   // false: the surplus wave of the last part
+    const int h = kvh * G + (owns ? g : G - 1);                // (a surplus wave's addresses stay inside its own group; it uses none of them)
+#else
     const int g = wave % G, j = wave / G, h = kvh * G + g;
+#endif
     const int S = a.S, len = a.lens[b];
     const int q_begin = qblk * QR, q0 = q_begin + 32 * j;
     const int r = lane & 31, kh = lane >> 5;
     const int ldc = a.nq * CA_HD;
     uint16_t *ctx_row = a.ctx + ((int64_t)b * S + q0 + r) * ldc + h * CA_HD;
+#if AK_CAUSAL_SPLIT
+    const bool live = owns && q0 < S && q0 < len;              // this wave has a head and its 32 rows hold a valid query
+    if (owns && q0 < S && !live) Tile::zero_row(ctx_row, kh);  // wholly past the length
+#else
     const bool live = q0 < S && q0 < len;                      // this wave's 32 rows hold a valid query
     if (q0 < S && !live) Tile::zero_row(ctx_row, kh);          // wholly past the length
+#endif
     if (q_begin >= len) return;                                // (uniform over the workgroup: no barrier below is skipped by some waves only)
     // key blocks the workgroup stages: up to the diagonal of its last row block, and not past the row's length
     int q_end = q_begin + QR;
@@ -94,7 +115,11 @@ __global__ __launch_bounds__(256) void AK_CAUSAL_KERNEL(CausalAttnArgs a) {
     }
     if (!live) return;
     float inv = 1.0f / (l + __shfl_xor(l, 32));
+#if AK_CAUSAL_SPLIT
+    if (q0 + r >= len) inv = 0.f;                                         // a query past the length: o is finite, the row is stored as zeros (causal too)
+#else
     if ((BAND || BIDIR) && q0 + r >= len) inv = 0.f;                      // a query past the length: o is finite, the row is stored as zeros
+#endif
 #pragma unroll
     for (int db = 0; db < Tile::NDB; db++) Tile::store_ctx(ctx_row, o[db], db, kh, [&](float x) { return x * inv; });
 }

@@ -181,6 +181,10 @@ struct CausalAttnArgs {
 };
 bool attn_causal_supported(int nq, int nkv, int head_dim, int S);
 int launch_attn_causal(const CausalAttnArgs &a, hipStream_t st);
+// the same attention at 5 to 8 query heads per kv head (qwen2.hip), a kv group split over two workgroups: causal or bidirectional,
+// window must be 0; S % 32 == 0, S <= 8192
+bool attn_causal_split_supported(int nq, int nkv, int head_dim, int S);
+int launch_attn_causal_split(const CausalAttnArgs &a, hipStream_t st);
 // bidirectional grouped-query attention at head dim 256 with an optional band (attn_gqa.hip; EmbeddingGemma, gemma.hip): q
 // [B][nq][S][256] pre-scaled by log2(e) * scalar^-0.5, k [B][nkv][S][256], vt [B][nkv][256][S] (keys of a 16-group in vt_pos order),
 // ctx [B * S][nq * 256]; lens [B]. nq / nkv in 1 .. 4, S % 32 == 0, S <= ATTN_GQA_MAX_S.

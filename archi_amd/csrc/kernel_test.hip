@@ -272,6 +272,17 @@ extern "C" int ak_kts_ll_attn(const uint16_t *q, const uint16_t *k, const uint16
     return launch_attn_causal(a, (hipStream_t)stream);
 }
 
+// launch_attn_causal_split (qwen2.hip: 5 to 8 query heads per kv head), the arguments of ak_kts_ll_attn without the window.
+// Named ak_kts_q2_*: the ak_kts_ll_* set stays the three it is
+extern "C" int ak_kts_q2_attn(const uint16_t *q, const uint16_t *k, const uint16_t *v, const int *lens, uint16_t *ctx, int B, int S, int nq,
+                              int nkv, int bidirectional, void *stream) {
+    AK_BIND();
+    CausalAttnArgs a{};
+    a.q = q; a.k = k; a.v = v; a.lens = lens; a.ctx = ctx;
+    a.B = B; a.S = S; a.nq = nq; a.nkv = nkv; a.bidirectional = bidirectional;
+    return launch_attn_causal_split(a, (hipStream_t)stream);
+}
+
 // qkv [B * S][(nq + 2 nkv) 128]; rc / rs [>= S][64]; q [B][nq][S][128], k / v [B][nkv][S][128]
 extern "C" int ak_kts_ll_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *rc, const float *rs, float qscale, uint16_t *q,
                               uint16_t *k, uint16_t *v, void *stream) {

@@ -13,18 +13,17 @@
 // + Normalize; or (AK_POOL_MEAN) the mean over the valid tokens of the final norm per token, k_ll_pool_part / _fin on stack.h's pool body.
 // The residual stream x is float32 throughout; GEMM operands are bf16. The rotary table comes from rope_theta (HF's default
 // rotary embedding) or from inverse frequencies the caller hands over (ak_llama_set_rope_inv_freq: rope_type llama3).
-// Here: the config checks, the layer struct, the layer loop and k_ll_rope. Everything else is stack.h / stack.hip and the launches
+// Here: ak_llama_*'s config checks, the layer loop (llama_impl.h: qwen2.hip builds its handle on it, with q / k / v biases and the split
+// attention launch) and k_ll_rope. Everything else is stack.h / stack.hip and the launches
 // decoder.hip spells (launch_dec_embed, launch_dec_add_rmsnorm, launch_dec_pool).
 #include <algorithm>
 #include <cmath>
 
-#include "stack.h"
+#include "llama_impl.h"
 
 namespace ak {
 
 namespace {
-constexpr int LL_HD = 128, LL_MAX_S = 8192;
-
 // one workgroup (4 waves) per token t < B * S; a wave takes one head slot of the QKV row at a time (nq query heads, nkv key heads,
 // nkv value heads), a lane the pair (d, d + 64) that rotate_half couples: q and k get RoPE at position t % S --
 // x'[d] = x[d] cos - x[d + 64] sin, x'[d + 64] = x[d + 64] cos + x[d] sin --, q then the scale log2(e) / sqrt(128); v is copied.
@@ -126,22 +125,7 @@ int launch_ll_pool(const float *x32, const int *lens, int B, int S, int H, const
     return 0;
 }
 
-namespace {
-struct LlLayer {
-    const uint16_t *wqkv, *wo, *wgu, *wd;      // wqkv [(nq + 2 nkv) 128][H] and wgu [2 I][H] (interleaved) are owned
-    const float *ln_in, *ln_post;
-};
-struct Llama : Stack {
-    AkLlamaConfig cfg;
-    const uint16_t *emb = nullptr; const float *norm = nullptr;
-    std::vector<LlLayer> layers;
-    float *rope_c = nullptr, *rope_s = nullptr;
-    float *x32 = nullptr, *y32 = nullptr, *part = nullptr;
-    uint16_t *h16 = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *ctx = nullptr, *f = nullptr;
-    int *lens = nullptr;
-};
-
-int ll_forward_locked(Llama &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling, int normalise, float *out,
+static int ll_forward_locked(Llama &d, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling, int normalise, float *out,
                       hipStream_t st) {
     const AkLlamaConfig &c = d.cfg;
     const int H = c.hidden, I = c.intermediate, nq = c.q_heads, nkv = c.kv_heads, nqkv = (nq + 2 * nkv) * LL_HD;
@@ -151,13 +135,15 @@ int ll_forward_locked(Llama &d, const int32_t *ids, int ld_ids, const int32_t *l
     if (launch_dec_embed(ids, ld_ids, lens, lens_stride, B, S, H, c.vocab_size, d.emb, d.layers[0].ln_in, c.rms_eps, d.x32, d.h16, d.lens, st)) return -10;
     for (size_t l = 0; l < d.layers.size(); l++) {
         const LlLayer &ly = d.layers[l];
-        // q | k | v
-        if (launch_gemm(3, d.gemm_bf16(tpad, d.h16, ly.wqkv, nqkv, H, d.qkv), st)) return -10;
+        // q | k | v (+ the layer's q | k | v bias in float32 before the bf16 store: Qwen2)
+        GemmArgs gq = d.gemm_bf16(tpad, d.h16, ly.wqkv, nqkv, H, d.qkv);
+        if (ly.bqkv) gq.bias = ly.bqkv;
+        if (launch_gemm(3, gq, st)) return -10;
         if (launch_ll_rope(d.qkv, B, S, nq, nkv, d.rope_c, d.rope_s, qscale, d.q, d.k, d.v, st)) return -10;
         CausalAttnArgs aa{d.q, d.k, d.v, d.lens, d.ctx, B, S, nq, nkv};
         aa.window = c.sliding_window;
         aa.bidirectional = c.bidirectional;
-        if (launch_attn_causal(aa, st)) return -10;
+        if (d.split_attn ? launch_attn_causal_split(aa, st) : launch_attn_causal(aa, st)) return -10;
         // x += ctx Wo^T; h = RMSNorm(x; ln_post)
         if (launch_gemm(2, d.gemm_f32(tpad, d.ctx, ly.wo, H, nq * LL_HD, d.y32), st)) return -10;
         if (launch_dec_add_rmsnorm(d.x32, d.y32, T, H, ly.ln_post, c.rms_eps, d.h16, st)) return -10;
@@ -171,7 +157,77 @@ int ll_forward_locked(Llama &d, const int32_t *ids, int ld_ids, const int32_t *l
     if (pooling == AK_POOL_MEAN) return launch_ll_pool(d.x32, d.lens, B, S, H, d.norm, c.rms_eps, normalise, d.part, out, st) ? -10 : 0;
     return launch_dec_pool(d.x32, d.lens, B, S, H, d.norm, c.rms_eps, normalise, out, st) ? -10 : 0;
 }
-}  // namespace
+
+// The handle of a checked config (the caller's create has refused what it refuses; n_weights = 2 + (qkv_bias ? 12 : 9) * layers):
+// the concatenated / interleaved matrices, the rotary table, the workspace
+int ll_create(const char *fn, const AkLlamaConfig &c, const void *const *w, bool qkv_bias, bool split_attn, void **out) {
+    const std::string f = std::string(fn) + ": ";
+    const int H = c.hidden, I = c.intermediate, L = c.layers, nq = c.q_heads, nkv = c.kv_heads;
+    Llama *d = new Llama();
+    d->cfg = c;
+    d->split_attn = split_attn;
+    d->emb = (const uint16_t *)w[0];
+    d->norm = (const float *)w[1];
+    auto fail = [&](const char *what) { set_error(f + what); stack_destroy<Llama>(d); return -10; };
+    const size_t qrows = (size_t)nq * LL_HD, kvrows = (size_t)nkv * LL_HD, nqkv = qrows + 2 * kvrows;
+    d->zero_bias = d->dev_as<float>(std::max<size_t>({nqkv, (size_t)2 * I, (size_t)H}), true);
+    if (!d->zero_bias) return fail("hipMalloc failed");
+    // RoPE table, positions 0 .. min(max_position, 8192) - 1
+    d->n_pos = c.max_position < LL_MAX_S ? c.max_position : LL_MAX_S;
+    if (!d->rope_tables(c.rope_theta, LL_HD, &d->rope_c, &d->rope_s)) return fail("RoPE table upload failed");
+    const int per_layer = qkv_bias ? 12 : 9, o = qkv_bias ? 3 : 0;
+    for (int l = 0; l < L; l++) {
+        const void *const *p = w + 2 + per_layer * l;       // wq wk wv [bq bk bv] wo ln_in ln_post w_gate w_up w_down
+        LlLayer ly{};
+        uint16_t *wqkv = d->dev_as<uint16_t>(nqkv * H), *wgu = d->dev_as<uint16_t>((size_t)2 * I * H);
+        if (!wqkv || !wgu) return fail("hipMalloc failed");
+        if (!d->concat_rows(wqkv, H, {{p[0], qrows}, {p[1], kvrows}, {p[2], kvrows}})) return fail("QKV concatenation failed");
+        if (qkv_bias) {                                     // bq | bk | bv in the row order of wqkv
+            float *b = d->dev_as<float>(nqkv);
+            if (!b) return fail("hipMalloc failed");
+            if (hipMemcpyAsync(b, p[3], qrows * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                hipMemcpyAsync(b + qrows, p[4], kvrows * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                hipMemcpyAsync(b + qrows + kvrows, p[5], kvrows * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                return fail("QKV bias concatenation failed");
+            ly.bqkv = b;
+        }
+        if (!d->interleave_rows(wgu, p[o + 6], p[o + 7], I, H)) return fail("gate / up interleave failed");      // gemm.hip MODE 7
+        ly.wqkv = wqkv; ly.wgu = wgu;
+        ly.wo = (const uint16_t *)p[o + 3];
+        ly.ln_in = (const float *)p[o + 4]; ly.ln_post = (const float *)p[o + 5];
+        ly.wd = (const uint16_t *)p[o + 8];
+        d->layers.push_back(ly);
+    }
+    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, (size_t)H * 2);
+    d->buffer(&d->qkv, nqkv * 2); d->buffer(&d->q, qrows * 2); d->buffer(&d->k, kvrows * 2); d->buffer(&d->v, kvrows * 2);
+    d->buffer(&d->ctx, qrows * 2); d->buffer(&d->f, (size_t)I * 2); d->buffer(&d->lens, 0, 4);
+    d->buffer(&d->part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
+    if (hipDeviceSynchronize() != hipSuccess) return fail("weight preparation failed");
+    *out = d;
+    return 0;
+}
+
+int ll_set_rope_inv_freq(const char *fn, void *h, const float *inv_freq) {
+    if (!h || !inv_freq) AK_FAIL(-1, std::string(fn) + ": NULL argument");
+    Llama &d = *(Llama *)h;
+    std::lock_guard<std::mutex> lk(d.mu);
+    AK_HIP(hipDeviceSynchronize());                            // no forward of this handle reads the table while it changes
+    return d.rope_tables_set_inv(inv_freq, LL_HD / 2, d.rope_c, d.rope_s) ? -10 : 0;
+}
+
+int ll_forward_lens(const char *fn, void *h, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling,
+                    int normalise, float *out, void *stream) {
+    if (!h) AK_FAIL(-1, std::string(fn) + ": NULL handle");
+    RoctxRange range(fn);
+    Llama &d = *(Llama *)h;
+    if (B <= 0) return 0;
+    // at most 65535 rows: the attention launch indexes the batch row with blockIdx.z
+    if (check_forward_lens(fn, ids, lens, out, ld_ids, lens_stride, B, S, LL_MAX_S, d.n_pos,
+                           pooling == AK_POOL_LAST || pooling == AK_POOL_MEAN ? nullptr : "pooling must be AK_POOL_LAST or AK_POOL_MEAN", 65535))
+        return -1;
+    std::lock_guard<std::mutex> lk(d.mu);
+    return ll_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, (hipStream_t)stream);
+}
 
 }  // namespace ak
 
@@ -196,59 +252,16 @@ extern "C" int ak_llama_create(const AkLlamaConfig *cfg, const void *const *w, i
     if (n_weights != 2 + 9 * L) AK_FAIL(-1, "ak_llama_create: expected 2 + 9 * layers weight pointers");
     for (int i = 0; i < n_weights; i++)
         if (!w[i]) AK_FAIL(-1, "ak_llama_create: NULL weight pointer");
-    Llama *d = new Llama();
-    d->cfg = c;
-    d->emb = (const uint16_t *)w[0];
-    d->norm = (const float *)w[1];
-    auto fail = [&](const char *what) { set_error(what); ak_llama_destroy(d); return -10; };
-    const size_t qrows = (size_t)nq * LL_HD, kvrows = (size_t)nkv * LL_HD, nqkv = qrows + 2 * kvrows;
-    d->zero_bias = d->dev_as<float>(std::max<size_t>({nqkv, (size_t)2 * I, (size_t)H}), true);
-    if (!d->zero_bias) return fail("ak_llama_create: hipMalloc failed");
-    // RoPE table, positions 0 .. min(max_position, 8192) - 1
-    d->n_pos = c.max_position < LL_MAX_S ? c.max_position : LL_MAX_S;
-    if (!d->rope_tables(c.rope_theta, LL_HD, &d->rope_c, &d->rope_s)) return fail("ak_llama_create: RoPE table upload failed");
-    for (int l = 0; l < L; l++) {
-        const void *const *p = w + 2 + 9 * l;       // wq wk wv wo ln_in ln_post w_gate w_up w_down
-        LlLayer ly{};
-        uint16_t *wqkv = d->dev_as<uint16_t>(nqkv * H), *wgu = d->dev_as<uint16_t>((size_t)2 * I * H);
-        if (!wqkv || !wgu) return fail("ak_llama_create: hipMalloc failed");
-        if (!d->concat_rows(wqkv, H, {{p[0], qrows}, {p[1], kvrows}, {p[2], kvrows}})) return fail("ak_llama_create: QKV concatenation failed");
-        if (!d->interleave_rows(wgu, p[6], p[7], I, H)) return fail("ak_llama_create: gate / up interleave failed");      // gemm.hip MODE 7
-        ly.wqkv = wqkv; ly.wgu = wgu;
-        ly.wo = (const uint16_t *)p[3];
-        ly.ln_in = (const float *)p[4]; ly.ln_post = (const float *)p[5];
-        ly.wd = (const uint16_t *)p[8];
-        d->layers.push_back(ly);
-    }
-    d->buffer(&d->x32, (size_t)H * 4); d->buffer(&d->y32, (size_t)H * 4); d->buffer(&d->h16, (size_t)H * 2);
-    d->buffer(&d->qkv, nqkv * 2); d->buffer(&d->q, qrows * 2); d->buffer(&d->k, kvrows * 2); d->buffer(&d->v, kvrows * 2);
-    d->buffer(&d->ctx, qrows * 2); d->buffer(&d->f, (size_t)I * 2); d->buffer(&d->lens, 0, 4);
-    d->buffer(&d->part, (size_t)H * 4 / POOL_CHUNK, (size_t)H * 4);      // B ceil(S / 64) <= T / 64 + B rows of H floats
-    if (hipDeviceSynchronize() != hipSuccess) return fail("ak_llama_create: weight preparation failed");
-    *out = d;
-    return 0;
+    return ll_create("ak_llama_create", c, w, false, false, out);
 }
 
 extern "C" int ak_llama_set_rope_inv_freq(ak_llama_t h, const float *inv_freq) {
     AK_BIND();
-    if (!h || !inv_freq) AK_FAIL(-1, "ak_llama_set_rope_inv_freq: NULL argument");
-    Llama &d = *(Llama *)h;
-    std::lock_guard<std::mutex> lk(d.mu);
-    AK_HIP(hipDeviceSynchronize());                            // no forward of this handle reads the table while it changes
-    return d.rope_tables_set_inv(inv_freq, LL_HD / 2, d.rope_c, d.rope_s) ? -10 : 0;
+    return ll_set_rope_inv_freq("ak_llama_set_rope_inv_freq", h, inv_freq);
 }
 
 extern "C" int ak_llama_forward_lens(ak_llama_t h, const int32_t *ids, int ld_ids, const int32_t *lens, int lens_stride, int B, int S, int pooling,
                                      int normalise, float *out, void *stream) {
     AK_BIND();
-    if (!h) AK_FAIL(-1, "ak_llama_forward_lens: NULL handle");
-    RoctxRange range("ak_llama_forward_lens");
-    Llama &d = *(Llama *)h;
-    if (B <= 0) return 0;
-    // at most 65535 rows: the attention launch indexes the batch row with blockIdx.z
-    if (check_forward_lens("ak_llama_forward_lens", ids, lens, out, ld_ids, lens_stride, B, S, LL_MAX_S, d.n_pos,
-                           pooling == AK_POOL_LAST || pooling == AK_POOL_MEAN ? nullptr : "pooling must be AK_POOL_LAST or AK_POOL_MEAN", 65535))
-        return -1;
-    std::lock_guard<std::mutex> lk(d.mu);
-    return ll_forward_locked(d, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, (hipStream_t)stream);
+    return ll_forward_lens("ak_llama_forward_lens", h, ids, ld_ids, lens, lens_stride, B, S, pooling, normalise, out, stream);
 }

@@ -16,8 +16,8 @@ Device side: archi_amd.encoder.HipEncoder (hand-written HIP). No CPU fallback.
 Qwen3-Embedding checkpoints (config.json model_type "qwen3") run on archi_amd.decoder.HipDecoder instead, tokenised by the
 checkpoint's own tokenizer.json, pooled on the last token; ModernBERT checkpoints (model_type "modernbert") run on
 archi_amd.modernbert.HipModernBert, NomicBERT checkpoints (model_type "nomic_bert") on archi_amd.nomic.HipNomicBert with the BERT
-WordPiece tokenizer of their vocab.txt, Mistral / Llama checkpoints (model_type "mistral" | "llama") on archi_amd.llama.HipLlama; the
-same batching harness drives all of them.
+WordPiece tokenizer of their vocab.txt, Mistral / Llama checkpoints (model_type "mistral" | "llama") on archi_amd.llama.HipLlama, Qwen2 checkpoints
+(model_type "qwen2") on archi_amd.qwen2.HipQwen2; the same batching harness drives all of them.
 """
 from __future__ import annotations
 
@@ -44,6 +44,8 @@ from .nomic import NOMIC_SHAPES, HipNomicBert, load_nomic_weights, nomic_config_
 from .nomic import MAX_SEQ as NOMIC_MAX_SEQ
 from .llama import LLAMA_SHAPES, HipLlama, apply_mode, load_llama_weights, random_llama_weights, read_llama_st_config, resolve_mode
 from .llama import MAX_SEQ as LLAMA_MAX_SEQ
+from .qwen2 import QWEN2_SHAPES, HipQwen2, load_qwen2_weights, qwen2_config_shape, random_qwen2_weights
+from .qwen2 import apply_mode as qwen2_apply_mode
 
 CLS, SEP, PAD, UNK = 101, 102, 0, 100
 # special tokens by name: (cls, sep, unk, the strings the full tokenizer matches in raw text)
@@ -223,6 +225,15 @@ def _is_llama(model_name: str) -> bool:
     return model_name in LLAMA_SHAPES
 
 
+def _is_qwen2(model_name: str) -> bool:
+    """A Qwen2 checkpoint directory (config.json model_type "qwen2") or one of the named Qwen2 shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "qwen2"
+    return model_name in QWEN2_SHAPES
+
+
 def _is_mpnet(model_name: str) -> bool:
     """An MPNet checkpoint directory (config.json model_type "mpnet") or one of the named MPNet shapes."""
     import json
@@ -325,6 +336,27 @@ _LLAMA = _StackFamily("Mistral / Llama embedders", "a Mistral or Llama", "tokeni
                       precheck=_llama_precheck, reshape=apply_mode)
 
 
+def _qwen2_precheck(model_dir, kw):
+    """What config.json, the sentence-transformers files and the keywords alone decide, before the weights are read."""
+    import json
+    cj = os.path.join(model_dir, "config.json")
+    shape = qwen2_config_shape(json.load(open(cj)), cj)
+    st_pool, _, _ = read_llama_st_config(model_dir)
+    resolve_mode(model_dir, shape, kw, st_pool)
+
+
+def _qwen2_random(shape, kw):
+    return random_qwen2_weights(shape, bias_std=float(kw.get("synthetic_bias_std", 2.0)), **_seed_std(kw))
+
+
+# Qwen2 / Qwen2.5 embedders (Alibaba-NLP/gte-Qwen2-1.5B-instruct and -7B-instruct, gte-Qwen1.5-7B-instruct, infly/inf-retriever-v1): q / k / v
+# biases and up to 8 query heads per kv head; causal attention and lasttoken pooling unless config.json says is_causal: false or
+# model_kwargs["attention"] = "bidirectional" (the keyword wins; llama.resolve_mode, model_kwargs["pooling"] overrides); rows up to 8192
+# tokens; prompts and special tokens stay with the caller and the tokenizer.json's post-processor, as for the Llama family
+_QWEN2 = _StackFamily("Qwen2 embedders", "a Qwen2", "byte-level BPE tokenizer", QWEN2_SHAPES, 6, LLAMA_MAX_SEQ, load_qwen2_weights,
+                      read_llama_st_config, _qwen2_random, resolve_mode, HipQwen2, precheck=_qwen2_precheck, reshape=qwen2_apply_mode)
+
+
 class ArchiHipEmbeddings:
     def __init__(self, model_name: str = "sentence-transformers/all-MiniLM-L6-v2",
                  model_kwargs: Optional[Dict[str, Any]] = None, encode_kwargs: Optional[Dict[str, Any]] = None,
@@ -347,7 +379,7 @@ class ArchiHipEmbeddings:
         self._stage = self._stage_out = None
         self._stage_lock = threading.Lock()
         for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA), (_is_nomic, _NOMIC),
-                                  (_is_llama, _LLAMA)):
+                                  (_is_llama, _LLAMA), (_is_qwen2, _QWEN2)):
             if is_family(model_name):
                 self._init_stack(family, model_name, device)
                 return

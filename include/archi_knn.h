@@ -59,7 +59,7 @@ extern "C" {
 /* encoder pooling (sentence-transformers Pooling module [upstream]) */
 #define AK_POOL_MEAN 0 /* all-MiniLM-L6-v2 */
 #define AK_POOL_CLS 1  /* bge-base-en */
-#define AK_POOL_LAST 2 /* e5-mistral-7b-instruct: the last valid token (ak_llama_forward_lens only) */
+#define AK_POOL_LAST 2 /* e5-mistral-7b-instruct: the last valid token (ak_llama_ / ak_qwen2_forward_lens only) */
 
 typedef void *ak_index_t;
 typedef void *ak_encoder_t;
@@ -633,6 +633,48 @@ int ak_llama_set_rope_inv_freq(ak_llama_t h, const float *inv_freq);
  * trained without the causal mask pair with bidirectional = 1); anything else is refused. out_dev [B][H] float32, L2-normalised when
  * `normalise` != 0. S a multiple of 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
 int ak_llama_forward_lens(ak_llama_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                          int pooling, int normalise, float *out_dev, void *stream);
+
+/* ---- Qwen2 / Qwen2.5 decoder embedders (Alibaba-NLP/gte-Qwen2-1.5B-instruct, gte-Qwen2-7B-instruct, gte-Qwen1.5-7B-instruct,
+ * infly/inf-retriever-v1 and -1.5b) ---- */
+/* Instruction-aware embedders of the kind the reference's retrievers single out (retrievers/utils.py:7-19), loaded by name through
+ * HuggingFaceEmbeddings. The forward pass of HF Qwen2Model: the Mistral / Llama layer above (RMSNorm, rotate_half RoPE at head dim 128,
+ * grouped-query attention, SwiGLU MLP) WITH a bias on the q, k and v projections -- added in float32 to the projection's accumulator
+ * before its bf16 store -- and with up to 8 query heads per kv head (Qwen2-1.5B: 6, Qwen2-7B: 7, Qwen2.5-3B: 8, Qwen2.5-14B: 5). Causal
+ * attention without a window, or bidirectional attention for the embedders trained without the causal mask; then the final norm of
+ * each row's LAST valid token, or the mean of the final norm over the valid tokens, and L2 normalisation (sentence-transformers'
+ * lasttoken / mean Pooling + Normalize). bf16 MFMA GEMMs, float32 residual stream / norms / softmax / biases. */
+typedef void *ak_qwen2_t;
+typedef struct AkQwen2Config {
+    int vocab_size;     /* 151646 (gte-Qwen2) */
+    int hidden;         /* 1536 / 3584; a multiple of 128 */
+    int layers;         /* 28 */
+    int q_heads;        /* 12 / 28 */
+    int kv_heads;       /* 2 / 4; q_heads % kv_heads == 0, at most 8 query heads per kv head */
+    int head_dim;       /* 128 (the only head size implemented) */
+    int intermediate;   /* 8960 / 18944; a multiple of 64 */
+    int max_position;   /* 131072 (rows are limited to min(max_position, 8192) tokens) */
+    float rms_eps;      /* 1e-6 */
+    float rope_theta;   /* 1e6: the default rotary table (ak_qwen2_set_rope_inv_freq replaces it) */
+    int bidirectional;  /* 0 = causal; 1 = every key below the row's length for every query below it */
+} AkQwen2Config;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] exactly as torch.nn.Linear.weight, vectors and biases float32):
+ *   0 embed_tokens [vocab][H] bf16, 1 final norm [H],
+ *   per layer l (base 2 + 12 * l):
+ *     +0 wq [q_heads 128][H] +1 wk [kv_heads 128][H] +2 wv [kv_heads 128][H] +3 bq [q_heads 128] +4 bk [kv_heads 128] +5 bv [kv_heads 128]
+ *     +6 wo [H][q_heads 128] +7 ln_in [H] (input_layernorm) +8 ln_post [H] (post_attention_layernorm) +9 w_gate [I][H] +10 w_up [I][H]
+ *     +11 w_down [H][I]
+ * The library copies wq | wk | wv into one matrix and bq | bk | bv into one vector and interleaves the gate and up rows at create; the
+ * other pointers must stay valid until ak_qwen2_destroy. Refused (non-zero, message naming the field in the last-error string):
+ * head_dim != 128, q_heads % kv_heads, more than 8 query heads per kv head, hidden % 128, intermediate % 64, bidirectional other than
+ * 0 / 1, a non-positive size, rms_eps or rope_theta, a weight count other than 2 + 12 * layers, a NULL pointer. */
+int ak_qwen2_create(const AkQwen2Config *cfg, const void *const *weights_dev, int n_weights, ak_qwen2_t *out);
+int ak_qwen2_destroy(ak_qwen2_t h);
+/* ak_llama_set_rope_inv_freq for a Qwen2 handle: the rotary table of GIVEN inverse frequencies (64 host floats; rope_type llama3). */
+int ak_qwen2_set_rope_inv_freq(ak_qwen2_t h, const float *inv_freq);
+/* The tile layout, the argument checks and the poolings (AK_POOL_LAST / AK_POOL_MEAN) of ak_llama_forward_lens. out_dev [B][H] float32,
+ * L2-normalised when `normalise` != 0. S a multiple of 32, <= 8192 and <= max_position. Asynchronous on `stream`. */
+int ak_qwen2_forward_lens(ak_qwen2_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
                           int pooling, int normalise, float *out_dev, void *stream);
 
 /* ---- host tokenizer: the tokenisation step inside Embeddings.embed_documents -------- */
