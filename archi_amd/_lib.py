@@ -132,6 +132,22 @@ class AkNomicBertConfig(ctypes.Structure):
     ]
 
 
+class AkT5Config(ctypes.Structure):
+    _fields_ = [
+        ("vocab_size", ctypes.c_int),
+        ("hidden", ctypes.c_int),
+        ("layers", ctypes.c_int),
+        ("heads", ctypes.c_int),
+        ("head_dim", ctypes.c_int),
+        ("d_ff", ctypes.c_int),
+        ("gated", ctypes.c_int),
+        ("max_distance", ctypes.c_int),
+        ("ln_eps", ctypes.c_float),
+        ("n_dense", ctypes.c_int),
+        ("dense_out", ctypes.c_int * 2),
+    ]
+
+
 class AkLlamaConfig(ctypes.Structure):
     _fields_ = [
         ("vocab_size", ctypes.c_int),
@@ -237,6 +253,9 @@ SYMBOLS = [
     ("ak_nomic_create", _I, [ctypes.POINTER(AkNomicBertConfig), _P, _I, ctypes.POINTER(_P)]),
     ("ak_nomic_destroy", _I, [_P]),
     ("ak_nomic_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("ak_t5_create", _I, [ctypes.POINTER(AkT5Config), _P, _I, ctypes.POINTER(_P)]),
+    ("ak_t5_destroy", _I, [_P]),
+    ("ak_t5_forward_lens", _I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("ak_llama_create", _I, [ctypes.POINTER(AkLlamaConfig), _P, _I, ctypes.POINTER(_P)]),
     ("ak_llama_destroy", _I, [_P]),
     ("ak_llama_set_rope_inv_freq", _I, [_P, _P]),
@@ -338,6 +357,8 @@ KTS_SYMBOLS = [
     ("ak_kts_ll_pool", _I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _P]),
     ("ak_kts_ll_rope", _I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
     ("ak_kts_q2_attn", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),      # launch_attn_causal_split (tests/test_qwen2_kernels_gpu.py)
+    ("ak_kts_t5_attn", _I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),      # launch_attn_relbias (tests/test_t5_kernels_gpu.py)
+    ("ak_kts_t5_gemm_relu", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),                              # launch_gemm(10)
 ]
 
 

@@ -44,6 +44,10 @@ EMBEDDING_DIMENSIONS = {
     "nomic-ai/nomic-embed-text-v1.5": 768,
     "nomic-ai/nomic-embed-text-v1-unsupervised": 768,
     "Snowflake/snowflake-arctic-embed-m-long": 768,
+    "sentence-transformers/gtr-t5-base": 768,
+    "sentence-transformers/gtr-t5-large": 768,
+    "sentence-transformers/sentence-t5-base": 768,
+    "sentence-transformers/sentence-t5-large": 768,
 }
 
 

@@ -2,6 +2,8 @@
 // residual stream x32, bf16 GEMM rows, and per layer
 //   attention_block: k_gemm MODE 0 (q scaled | k | V^T) -> k_mb_rope -> k_attn_long<WIN> -> k_gemm MODE 2 into y32
 //   ffn_block:       the gated k_gemm (MODE 7 SwiGLU / 8 GeGLU) -> k_gemm MODE 2 into y32
+// T5 (t5.hip) takes the two other forms: attention_block_relbias (no RoPE launch, the caller's q scale, k_attn_long_relbias with
+// the clamped relative bias) and ffn_block_plain (an un-gated activation mode, no interleaving),
 // with the family's own join kernel (what becomes of x32 + y32) behind each block. Here: the workspace, the create steps both
 // families make and the body of ak_*_forward_lens. A family keeps its config struct and that struct's own checks, its layers' norm
 // pointers, the rotary table / window of a layer, its embed, join and pooling kernels. stack.hip holds the bodies.
@@ -34,6 +36,17 @@ struct Enc64 : Stack {
     int attention_block(int64_t tpad, int B, int S, const uint16_t *wqkv, const uint16_t *wo, const float *rc, const float *rs, int half_window,
                         hipStream_t st);
     int ffn_block(int mode, int64_t tpad, const uint16_t *wgu, const uint16_t *wdown, hipStream_t st);
+    // no RoPE; q scaled by qscale (the softmax runs in base 2: log2(e) times the model's scale); rbias [heads][2 D + 1]: the bias of
+    // clamp(key - query, -D, D), in the base-2 domain (AttnArgs::rbias)
+    int attention_block_relbias(int64_t tpad, int B, int S, const uint16_t *wqkv, const uint16_t *wo, float qscale, const float *rbias, int D,
+                                hipStream_t st);
+    // the un-gated pair f = act(h wi^T) (mode 10: ReLU), y32 = f wo^T on what prepare_plain left: *wi_out [Ip][H] with zero rows past I,
+    // *wo_out [H][Ip] with zero columns past I (the given matrices themselves when Ip == I). NULL, or what failed.
+    const char *prepare_plain(const void *wi, int I, const void *wo, const uint16_t **wi_out, const uint16_t **wo_out);
+    int ffn_block_plain(int mode, int64_t tpad, const uint16_t *wi, const uint16_t *wo, hipStream_t st);
+
+private:
+    int qkv_gemm(int64_t tpad, int64_t T, int S, const uint16_t *wqkv, float qscale, hipStream_t st);      // MODE 0: q (scaled) | k | V^T
 };
 
 // what a create says and does when a step after `new T` failed

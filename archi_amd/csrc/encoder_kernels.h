@@ -46,6 +46,11 @@ struct AttnArgs {
     const int *rowlen = nullptr;
     // half-window of the banded instantiation (launch_attn_window sets it): key k visible to query q iff |q - k| <= window
     int window = -1;
+    // additive relative-position bias at any S (T5; launch_attn_relbias): rbias[h * (2 D + 1) + clamp(key - query, -D, D) + D], D =
+    // rbias_D >= 1, base-2 domain like q. The bias saturates at distance D on either side, so one row of 2 D + 1 floats per head
+    // covers every row length. NULL: no bias
+    const float *rbias = nullptr;
+    int rbias_D = 0;
 };
 // rows longer than 512 tokens (encoders given ak_encoder_set_positions_from_ids(max_seq > 512); bf16, head size 64): attn_long.hip,
 // 512 < S <= ATTN_LONG_MAX_S. Tiles with S <= 512 always run the kernels of attention.hip.
@@ -53,6 +58,9 @@ constexpr int ATTN_LONG_MAX_S = 8192;
 int launch_attn_long(const AttnArgs &a, hipStream_t st);
 // the long-row kernel at any S % 32 == 0 in [32, 8192] with a band of half-width `window` (< 0 or >= S: none): ModernBERT (mbert.hip)
 int launch_attn_window(const AttnArgs &a, int window, hipStream_t st);
+// the long-row kernel at any S % 32 == 0 in [32, 8192], every key, with the clamped relative bias a.rbias / a.rbias_D (T5, t5.hip)
+constexpr int ATTN_RELBIAS_MAX_D = 4096;
+int launch_attn_relbias(const AttnArgs &a, hipStream_t st);
 // layout of the library's per-distance bias tables (ak_encoder_set_rel_bias): one row of REL_ROW floats per head, distance d at
 // REL_MID + d. Any (key, query) pair of a 32-query block of a wave / workgroup, S <= 512, lands inside the row.
 constexpr int REL_ROW = 2048, REL_MID = 1024;
@@ -233,6 +241,13 @@ int launch_nb_embed(const int *ids, int ld_ids, const int *lens, int lens_stride
                     const float *type0, const float *g, const float *b, float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, hipStream_t st);
 int launch_nb_add_ln(float *x32, const float *y32, int64_t T, int H, const float *g, const float *b, float eps, uint16_t *h16, hipStream_t st);
 int launch_nb_pool(const float *x32, const int *lens, int B, int S, int H, int pooling, int normalise, float *part, float *out, hipStream_t st);
+// t5.hip (its residual joins are launch_dec_add_rmsnorm, its Dense head launch_gm_dense / launch_gm_l2): x32 = shared[id] (no scale, no
+// position), h16 = bf16(RMSNorm(x32; w)), the int key mask and the clamped lengths; the pool is the mean (or token 0) of the final
+// RMSNorm per token times its weight, NOT normalised: pooled [B][H]. H <= 1024.
+int launch_t5_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
+                    float eps, float *x32, uint16_t *h16, int *mask, int *lens_out, hipStream_t st);
+int launch_t5_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int pooling, float *part, float *pooled,
+                   hipStream_t st);
 int launch_gm_fold1p(const float *w, int n, float *w1, hipStream_t st);
 int launch_gm_embed(const int *ids, int ld_ids, const int *lens, int lens_stride, int B, int S, int H, int vocab, const uint16_t *emb, const float *w,
                     float eps, float *x32, uint16_t *h16, int *lens_out, hipStream_t st);

@@ -22,6 +22,8 @@
 //           row 2 j + 1 = row j of its second half, the gate g_j); it stores gelu_erf(a) g as bf16, N / 2 columns wide
 //   MODE 9  GeGLU with the TANH GELU (EmbeddingGemma's gate / up projection, gemma.hip: gelu_pytorch_tanh): MODE 8's layout with
 //           row 2 j = gate_proj row j (the GELU input), row 2 j + 1 = up_proj row j; it stores gelu_tanh(a) g
+//   MODE 10 bf16 output with ReLU, max(acc + bias, 0) (T5 v1.0's un-gated wi, t5.hip): MODE 3's store path, no table of any kind; on the
+//           narrow tile and the wide phased tile
 // Replaces the torch CPU GEMMs behind SentenceTransformer.encode as called at
 // /root/reference/src/data_manager/vectorstore/manager.py:373.
 //
@@ -300,6 +302,8 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
             const float u0 = 0.7978845608028654f * (o.x + 0.044715f * o.x * o.x * o.x), u1 = 0.7978845608028654f * (o.z + 0.044715f * o.z * o.z * o.z);
             const float s0 = o.x * o.y / (1.0f + __expf(-2.0f * u0)), s1 = o.z * o.w / (1.0f + __expf(-2.0f * u1));
             *(uint32_t *)(a.out_bf16 + (int64_t)t * a.ldo + (n >> 1)) = pack_bf16x2(s0, s1);
+        } else if constexpr (MODE == 10) {
+            *(uint2 *)(a.out_bf16 + (int64_t)t * a.ldo + n) = cvt_bf16x4(f32x4{fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f)});
         } else {
             *(uint2 *)(a.out_bf16 + (int64_t)t * a.ldo + n) = cvt_bf16x4(o);
         }
@@ -349,6 +353,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
                                  fmaf(a_rs, v[4 * g + 2], fmaf(a_nm, cc.z, bi.z)), fmaf(a_rs, v[4 * g + 3], fmaf(a_nm, cc.w, bi.w))};
                         } else o = {v[4 * g + 0] + bi.x, v[4 * g + 1] + bi.y, v[4 * g + 2] + bi.z, v[4 * g + 3] + bi.w};
                         if constexpr (MODE == 1 && !GTAB) o = gelu_erf4(o);
+                        if constexpr (MODE == 10) o = f32x4{fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f)};
                         if constexpr (MODE == 0) o = o * scale;
                         if constexpr (F32T) *(f32x4 *)(scr + r * 256 + (((mi * 8 + 2 * g + kh) ^ ((r & 7) << 1)) << 4)) = o;
                         else *(uint2 *)(scr + r * 128 + (((mi * 4 + g) ^ (r & 7)) << 4) + kh * 8) = GTAB ? f_gelu_tab4(o) : cvt_bf16x4(o);
@@ -584,7 +589,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm(GemmArgs a) {
     };
     // the finished tile (p_tn, p_tt, p_par set) through the wave's 4 KB scratch
     auto tile_out = [&](char *scr, int tn) {
-        if constexpr (MODE == 1 || MODE == 3 || MODE == 4) rows_out(scr, a.out_bf16, a.ldo, tn * G_BN, 1.0f);
+        if constexpr (MODE == 1 || MODE == 3 || MODE == 4 || MODE == 10) rows_out(scr, a.out_bf16, a.ldo, tn * G_BN, 1.0f);
         else if constexpr (MODE == 6) rows_out_split(scr, tn * G_BN);
         else if constexpr (MODE == 7 || MODE == 8 || MODE == 9) all_pieces();
         else if constexpr (MODE == 0 && G_BN == 256) {     // H % 256 == 0: a tile is all Q, all K or all V
@@ -870,6 +875,7 @@ static int launch_gemm_bn(int mode, const GemmArgs &a, hipStream_t st) {
         if constexpr (BN == 128 || PH) {
             AK_HIP(hipFuncSetAttribute((const void *)k_gemm<8, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
             AK_HIP(hipFuncSetAttribute((const void *)k_gemm<9, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
+            AK_HIP(hipFuncSetAttribute((const void *)k_gemm<10, BN, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<BN>::LDS));
         }
         attr = true;
     }
@@ -888,6 +894,10 @@ static int launch_gemm_bn(int mode, const GemmArgs &a, hipStream_t st) {
         case 9:       // the tanh twin of MODE 8, on the same two tiles
             if constexpr (BN == 128 || PH) k_gemm<9, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a);
             else AK_FAIL(-1, "gemm: MODE 9 runs on the narrow tile or the wide phased tile");
+            break;
+        case 10:      // ReLU (T5 v1.0's wi): instantiated where MODE 8 / 9 are
+            if constexpr (BN == 128 || PH) k_gemm<10, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a);
+            else AK_FAIL(-1, "gemm: MODE 10 runs on the narrow tile or the wide phased tile");
             break;
         default: k_gemm<3, BN, PH><<<grid, G_THREADS, GCfg<BN>::LDS, st>>>(a); break;
     }
@@ -1057,7 +1067,7 @@ int launch_gemm(int mode, const GemmArgs &a_in, hipStream_t st) {
     if (force_bn == 128) wide = false;
     if (force_bn == 256 && a.N % 256 == 0 && (mode != 0 || a.H % 256 == 0)) wide = true;
     static const int phased = env_get("AK_GEMM_PHASED") ? atoi(env_get("AK_GEMM_PHASED")) : 1;      // A/B: 0 = the in-step loop on the wide tile
-    if ((mode == 8 || mode == 9) && !(phased && a.K >= 192)) wide = false;      // MODE 8 / 9 have no wide in-step instantiation (it would spill)
+    if ((mode == 8 || mode == 9 || mode == 10) && !(phased && a.K >= 192)) wide = false;      // MODE 8 / 9 have no wide in-step instantiation (it would spill), MODE 10 none either
     if (wide) a.fb = gemm_fb(a.N / 256);
     if (wide && phased && a.K >= 192) return launch_gemm_bn<256, true>(mode, a, st);
     return wide ? launch_gemm_bn<256>(mode, a, st) : launch_gemm_bn<128>(mode, a, st);

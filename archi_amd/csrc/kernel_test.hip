@@ -397,4 +397,23 @@ extern "C" int ak_kts_gemm_bf16(const uint16_t *X, const uint16_t *W, const floa
     return launch_gemm(3, a, (hipStream_t)stream);
 }
 
+// ---- T5 (tests/test_t5_kernels_gpu.py). Named ak_kts_t5_*: the other ak_kts_* subsets stay what they are ----
+// one launch_attn_relbias: k_attn_long_relbias, every key below the length, rbias [heads][2 D + 1] floats (base-2 domain)
+extern "C" int ak_kts_t5_attn(const uint16_t *q, const uint16_t *k, const uint16_t *vt, const int *mask, const int *rowlen, uint16_t *ctx, int B,
+                              int S, int H, int heads, int qk_ld, int qk_hs, const float *rbias, int D, void *stream) {
+    AK_BIND();
+    AttnArgs a = kt_attn_args(q, k, vt, mask, ctx, B, S, H, heads, qk_ld, qk_hs);
+    a.rowlen = rowlen;
+    a.rbias = rbias; a.rbias_D = D;
+    return launch_attn_relbias(a, (hipStream_t)stream);
+}
+
+// one launch_gemm(10): the ReLU epilogue; X [T][K], W [N][K] -> out [T][N] bf16
+extern "C" int ak_kts_t5_gemm_relu(const uint16_t *X, const uint16_t *W, const float *bias, int T, int N, int K, uint16_t *out, void *stream) {
+    AK_BIND();
+    GemmArgs a{};
+    a.X = X; a.W = W; a.bias = bias; a.T = T; a.N = N; a.K = K; a.out_bf16 = out; a.ldo = N;
+    return launch_gemm(10, a, (hipStream_t)stream);
+}
+
 #endif  // AK_DBG_KERNELS

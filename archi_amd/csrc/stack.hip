@@ -153,18 +153,47 @@ const char *Enc64::prepare_gated(const void *a, const void *b, int I, const void
     return nullptr;
 }
 
+const char *Enc64::prepare_plain(const void *wi, int I, const void *wo, const uint16_t **wi_out, const uint16_t **wo_out) {
+    *wi_out = (const uint16_t *)wi;
+    *wo_out = (const uint16_t *)wo;
+    if (Ip == I) return nullptr;
+    uint16_t *w = dev_as<uint16_t>((size_t)Ip * H, true);
+    if (!w) return "hipMalloc failed";
+    if (!concat_rows(w, H, {{wi, (size_t)I}})) return "input projection padding failed";
+    *wi_out = w;
+    if (!(*wo_out = pad_cols(wo, H, I, Ip))) return "output projection padding failed";
+    return nullptr;
+}
+
+int Enc64::qkv_gemm(int64_t tpad, int64_t T, int S, const uint16_t *wqkv, float qscale, hipStream_t st) {
+    GemmArgs g = gemm(tpad, h16, wqkv, 3 * H, H);
+    g.q = q; g.k = k; g.vt = vt; g.H = H; g.S = S; g.qscale = qscale;
+    g.ldo = (int)T;                                            // MODE 0: number of real tokens (rows beyond it have no V^T slot)
+    return launch_gemm(0, g, st);
+}
+
 int Enc64::attention_block(int64_t tpad, int B, int S, const uint16_t *wqkv, const uint16_t *wo, const float *rc, const float *rs, int half_window,
                            hipStream_t st) {
     const int64_t T = (int64_t)B * S;
-    // q (scaled) | k | V^T
-    GemmArgs g = gemm(tpad, h16, wqkv, 3 * H, H);
-    g.q = q; g.k = k; g.vt = vt; g.H = H; g.S = S; g.qscale = 1.4426950408889634f / sqrtf((float)HD);
-    g.ldo = (int)T;                                            // MODE 0: number of real tokens (rows beyond it have no V^T slot)
-    if (launch_gemm(0, g, st)) return -10;
+    if (qkv_gemm(tpad, T, S, wqkv, 1.4426950408889634f / sqrtf((float)HD), st)) return -10;
     if (launch_mb_rope(q, k, T, S, H, rc, rs, st)) return -10;
     AttnArgs a{q, k, vt, mask, ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, lens};
     if (launch_attn_window(a, half_window, st)) return -10;
     return launch_gemm(2, gemm_f32(tpad, ctx, wo, H, H, y32), st) ? -10 : 0;
+}
+
+int Enc64::attention_block_relbias(int64_t tpad, int B, int S, const uint16_t *wqkv, const uint16_t *wo, float qscale, const float *rbias, int D,
+                                   hipStream_t st) {
+    if (qkv_gemm(tpad, (int64_t)B * S, S, wqkv, qscale, st)) return -10;
+    AttnArgs a{q, k, vt, mask, ctx, B, S, H, heads, nullptr, nullptr, 0, 0, nullptr, lens};
+    a.rbias = rbias; a.rbias_D = D;
+    if (launch_attn_relbias(a, st)) return -10;
+    return launch_gemm(2, gemm_f32(tpad, ctx, wo, H, H, y32), st) ? -10 : 0;
+}
+
+int Enc64::ffn_block_plain(int mode, int64_t tpad, const uint16_t *wi, const uint16_t *wo, hipStream_t st) {
+    if (launch_gemm(mode, gemm_bf16(tpad, h16, wi, Ip, H, f), st)) return -10;
+    return launch_gemm(2, gemm_f32(tpad, f, wo, H, Ip, y32), st) ? -10 : 0;
 }
 
 int Enc64::ffn_block(int mode, int64_t tpad, const uint16_t *wgu, const uint16_t *wdown, hipStream_t st) {

@@ -17,7 +17,7 @@ Qwen3-Embedding checkpoints (config.json model_type "qwen3") run on archi_amd.de
 checkpoint's own tokenizer.json, pooled on the last token; ModernBERT checkpoints (model_type "modernbert") run on
 archi_amd.modernbert.HipModernBert, NomicBERT checkpoints (model_type "nomic_bert") on archi_amd.nomic.HipNomicBert with the BERT
 WordPiece tokenizer of their vocab.txt, Mistral / Llama checkpoints (model_type "mistral" | "llama") on archi_amd.llama.HipLlama, Qwen2 checkpoints
-(model_type "qwen2") on archi_amd.qwen2.HipQwen2; the same batching harness drives all of them.
+(model_type "qwen2") on archi_amd.qwen2.HipQwen2, T5 checkpoints (model_type "t5": gtr-t5, sentence-t5) on archi_amd.t5.HipT5; the same batching harness drives all of them.
 """
 from __future__ import annotations
 
@@ -42,6 +42,8 @@ from .gemma import GEMMA_SHAPES, HipGemma, load_gemma_weights, random_gemma_weig
 from .gemma import MAX_SEQ as GEMMA_MAX_SEQ
 from .nomic import NOMIC_SHAPES, HipNomicBert, load_nomic_weights, nomic_config_info, random_nomic_weights
 from .nomic import MAX_SEQ as NOMIC_MAX_SEQ
+from .t5 import T5_SHAPES, HipT5, load_t5_weights, random_t5_weights
+from .t5 import MAX_SEQ as T5_MAX_SEQ
 from .llama import LLAMA_SHAPES, HipLlama, apply_mode, load_llama_weights, random_llama_weights, read_llama_st_config, resolve_mode
 from .llama import MAX_SEQ as LLAMA_MAX_SEQ
 from .qwen2 import QWEN2_SHAPES, HipQwen2, load_qwen2_weights, qwen2_config_shape, random_qwen2_weights
@@ -216,6 +218,15 @@ def _is_nomic(model_name: str) -> bool:
     return model_name in NOMIC_SHAPES
 
 
+def _is_t5(model_name: str) -> bool:
+    """A T5 checkpoint directory (config.json model_type "t5") or one of the named T5 shapes."""
+    import json
+    if os.path.isdir(model_name):
+        cj = os.path.join(model_name, "config.json")
+        return os.path.exists(cj) and json.load(open(cj)).get("model_type") == "t5"
+    return model_name in T5_SHAPES
+
+
 def _is_llama(model_name: str) -> bool:
     """A Mistral / Llama checkpoint directory (config.json model_type "mistral" | "llama") or one of the named shapes."""
     import json
@@ -319,6 +330,30 @@ _NOMIC = _StackFamily("NomicBERT models", "a NomicBERT", "vocab.txt or tokenizer
                       precheck=_nomic_precheck)
 
 
+def _t5_st_config(model_dir):
+    """read_sentence_transformers_config, and the refusal of a pool that leaves the prompt's tokens out (instructor's 1_Pooling):
+    prompts stay with the caller, so the pool cannot know how many tokens one holds."""
+    import json
+    pj = os.path.join(model_dir, "1_Pooling", "config.json")
+    if os.path.exists(pj) and json.load(open(pj)).get("include_prompt", True) is False:
+        raise ValueError(f"{pj}: include_prompt false is not supported (the pool would leave the prompt's tokens out, and prompts stay "
+                         "with the caller: the provider cannot know their length)")
+    return read_sentence_transformers_config(model_dir)
+
+
+def _t5_random(shape, kw):
+    return random_t5_weights(shape, seed=int(kw["synthetic_seed"]), std=float(kw.get("synthetic_std", 0.05)),
+                             bias_std=float(kw.get("synthetic_bias_std", 2.0)))
+
+
+# T5 encoders (sentence-transformers/gtr-t5-base / -large, sentence-t5-base / -large, instructor directories whose pool includes the
+# prompt): mean or cls pooling as the checkpoint or the named shape says, the Dense modules come with the weights, rows up to 8192
+# tokens (the model has no position limit); the checkpoint's own tokenizer.json (Unigram), whose post-processor appends </s>
+_T5 = _StackFamily("T5 embedders", "a T5", "tokenizer.json (its post-processor appends </s>)", T5_SHAPES, 10, T5_MAX_SEQ, load_t5_weights,
+                   _t5_st_config, _t5_random, lambda name, shape, kw, st_pool: kw.get("pooling", st_pool or shape[11]), HipT5,
+                   precheck=lambda model_dir, kw: _t5_st_config(model_dir))
+
+
 def _llama_precheck(model_dir, kw):
     """What the sentence-transformers files and the keywords alone decide (an attention mode or a pooling that does not exist), before
     the weights are read."""
@@ -379,7 +414,7 @@ class ArchiHipEmbeddings:
         self._stage = self._stage_out = None
         self._stage_lock = threading.Lock()
         for is_family, family in ((_is_qwen3, _QWEN3), (_is_modernbert, _MODERNBERT), (_is_gemma, _GEMMA), (_is_nomic, _NOMIC),
-                                  (_is_llama, _LLAMA), (_is_qwen2, _QWEN2)):
+                                  (_is_llama, _LLAMA), (_is_qwen2, _QWEN2), (_is_t5, _T5)):
             if is_family(model_name):
                 self._init_stack(family, model_name, device)
                 return

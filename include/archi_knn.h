@@ -590,6 +590,50 @@ int ak_nomic_destroy(ak_nomic_t h);
 int ak_nomic_forward_lens(ak_nomic_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
                           int pooling, int normalise, float *out_dev, void *stream);
 
+/* ---- T5 encoders (sentence-transformers/gtr-t5-base / -large, sentence-t5-base / -large, GTR-initialised instructor models) ---- */
+/* The forward pass of HF T5EncoderModel: the shared embedding (no scale, no position table), pre-norm layers with T5LayerNorm
+ * (x * rsqrt(mean(x^2) + eps) * w, float32), separate q / k / v projections, bidirectional attention WITHOUT a 1 / sqrt(d) scale whose
+ * only position signal is the learned per-head bias of the T5 bucket of key - query (one table for all layers), an un-gated ReLU
+ * feed-forward (T5 v1.0) or the gated gelu_new one (T5 v1.1); the final_layer_norm per token; mean / cls pooling over the valid
+ * tokens; the 0 - 2 bias-free Dense matrices of the sentence-transformers tail in float32; L2 normalisation. No bias in any Linear.
+ * bf16 MFMA GEMMs, float32 residual stream / norms / softmax. */
+typedef void *ak_t5_t;
+typedef struct AkT5Config {
+    int vocab_size;     /* 32128 */
+    int hidden;         /* d_model 768 / 1024; a multiple of 128, <= 1024 */
+    int layers;         /* 12 / 24; <= AK_MBERT_MAX_LAYERS */
+    int heads;          /* 12 / 16; heads * 64 == hidden */
+    int head_dim;       /* d_kv; 64 */
+    int d_ff;           /* 3072 / 4096 (relu), 2048 / 2816 (gated-gelu); a multiple of 64 */
+    int gated;          /* 0: wo(relu(wi(x))); 1: wo(gelu_new(wi_0(x)) * wi_1(x)) */
+    int max_distance;   /* relative_attention_max_distance D (128): the bias table holds 2 D + 1 floats per head; 1 .. 4096 */
+    float ln_eps;       /* layer_norm_epsilon 1e-6 */
+    int n_dense;        /* Dense modules behind the pool: 0, 1 or 2 */
+    int dense_out[2];   /* their output widths: multiples of 4, <= 4096 */
+} AkT5Config;
+/* Weight order (device pointers; matrices bf16 row-major [out][in] as torch.nn.Linear.weight, vectors float32):
+ *   0 shared [vocab][H] bf16,
+ *   1 rel_table [heads][2 D + 1] float32: entry [h][clamp(key - query, -D, D) + D] = block 0's relative_attention_bias weight at the
+ *     T5 bucket of that distance, TIMES log2(e) (the softmax runs in base 2). The bidirectional bucket saturates at D on either
+ *     side, so the clamped table is the whole bias at any row length; the caller builds it (archi_amd.t5.t5_rel_table evaluates
+ *     HF's own float32 expression for the bucket) -- the library does not derive buckets,
+ *   2 final_layer_norm [H],
+ *   per layer l (base 3 + (8 + gated) * l):
+ *     +0 ln0 [H] (layer.0.layer_norm), +1 wq, +2 wk, +3 wv, +4 wo [H][H], +5 ln1 [H] (layer.1.layer_norm),
+ *     gated == 0: +6 wi [d_ff][H], +7 wo_ff [H][d_ff];   gated == 1: +6 wi_0 [d_ff][H], +7 wi_1 [d_ff][H], +8 wo_ff [H][d_ff],
+ *   then the n_dense Dense matrices, float32 [out][in].
+ * The library copies what it re-lays out (QKV concatenated, wi_0 / wi_1 interleaved, d_ff padded to the GEMM tile); every other
+ * pointer must stay valid until the handle is destroyed. Refused (non-zero, message in the last-error string): head_dim != 64,
+ * heads * 64 != hidden, hidden % 128 or > 1024, d_ff % 64, layers > AK_MBERT_MAX_LAYERS, a non-positive size, max_distance < 1 or
+ * > 4096, ln_eps <= 0, gated other than 0 / 1, a Dense width out of range, a weight count other than 3 + (8 + gated) * layers + n_dense. */
+int ak_t5_create(const AkT5Config *cfg, const void *const *weights_dev, int n_weights, ak_t5_t *out);
+int ak_t5_destroy(ak_t5_t h);
+/* One tile in the layout of ak_nomic_forward_lens. pooling: AK_POOL_MEAN / AK_POOL_CLS over the final_layer_norm rows of the valid
+ * tokens; out_dev [B][out_dim] float32 (out_dim = the last Dense width, or hidden), L2-normalised when `normalise` != 0. S a multiple
+ * of 32, <= 8192 (the model has no position limit of its own). Asynchronous on `stream`. */
+int ak_t5_forward_lens(ak_t5_t h, const int32_t *ids_dev, int ld_ids, const int32_t *lens_dev, int lens_stride, int B, int S,
+                       int pooling, int normalise, float *out_dev, void *stream);
+
 /* ---- Mistral / Llama decoder embedders (intfloat/e5-mistral-7b-instruct, Salesforce/SFR-Embedding-Mistral,
  * Linq-AI-Research/Linq-Embed-Mistral, the Llama-3.1-8B based embedders) ---- */
 /* The other instruction-aware embedders the reference's retrievers single out (retrievers/utils.py:7-19), loaded by name through
