@@ -359,6 +359,9 @@ KTS_SYMBOLS = [
     ("ak_kts_q2_attn", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),      # launch_attn_causal_split (tests/test_qwen2_kernels_gpu.py)
     ("ak_kts_t5_attn", _I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),      # launch_attn_relbias (tests/test_t5_kernels_gpu.py)
     ("ak_kts_t5_gemm_relu", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),                              # launch_gemm(10)
+    # query_norms + one re-rank launch, which = 0 thread-per-candidate / 1 panel (tests/test_rerank_panel_gpu.py); the kernel rerank() picks
+    ("ak_kts_rr_rerank", _I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    ("ak_kts_rr_choice", _I, [_P]),
 ]
 
 

@@ -35,6 +35,17 @@ __device__ inline void load8(const typename Store<DT>::T *row, int i, float (&v)
     }
 }
 
+// The finish of one (query,row) distance: the float32 accumulator of the sequential chain -> float8 distance. One function for
+// exact_distance and the panel re-rank, so that the two kernels cannot drift apart.
+__device__ inline double exact_finish(float acc, int metric, float na, float nb) {
+    if (metric == AK_METRIC_L2) return sqrt((double)acc);
+    if (metric == AK_METRIC_IP) return (double)(-acc);
+    double sim = (double)acc / sqrt((double)na * (double)nb);
+    if (sim > 1.0) sim = 1.0;
+    else if (sim < -1.0) sim = -1.0;
+    return 1.0 - sim;
+}
+
 // One (query,row) distance in the oracle's arithmetic. `na` is the row's
 // precomputed pgvector-order sum of squares, `nb` the query's.
 template <int DT>
@@ -59,7 +70,7 @@ __device__ inline double exact_distance(const typename Store<DT>::T *row, const 
             float diff = __fsub_rn(S::load(row, i), q[i]);
             acc = __fadd_rn(acc, __fmul_rn(diff, diff));
         }
-        return sqrt((double)acc);
+        return exact_finish(acc, metric, na, nb);
     }
     int i = 0;
     if (vec)
@@ -70,11 +81,7 @@ __device__ inline double exact_distance(const typename Store<DT>::T *row, const 
             for (int j = 0; j < 8; j++) acc = __fadd_rn(acc, __fmul_rn(v[j], q[i + j]));
         }
     for (; i < dim; i++) acc = __fadd_rn(acc, __fmul_rn(S::load(row, i), q[i]));
-    if (metric == AK_METRIC_IP) return (double)(-acc);
-    double sim = (double)acc / sqrt((double)na * (double)nb);
-    if (sim > 1.0) sim = 1.0;
-    else if (sim < -1.0) sim = -1.0;
-    return 1.0 - sim;
+    return exact_finish(acc, metric, na, nb);
 }
 
 // Thread per row, QB queries per pass (row element loaded once, reused QB times).
@@ -169,7 +176,9 @@ int query_norms(const float *queries_dev, int nq, int dim, float *nb_dev, hipStr
     return 0;
 }
 
-// Re-rank kernel used by the fast path: thread per candidate.
+// Re-rank kernel of the fast path as it was: thread per candidate, each lane walking its own row with dependent 16-byte loads.
+// The fallback for rows the panel kernel below does not take (dim % 64 != 0, dim > TAIL_MAX_DIM), AK_RERANK_OLD = 1, and the
+// reference the panel kernel is held to bit for bit (tests/test_rerank_panel_gpu.py).
 // cand [nq][kp] approx keys with the row slot in the low 32 bits.
 template <int DT>
 __global__ void k_rerank(const typename Store<DT>::T *__restrict__ rows, const float *__restrict__ na,
@@ -189,8 +198,160 @@ __global__ void k_rerank(const typename Store<DT>::T *__restrict__ rows, const f
     oids[t] = ids[r];
 }
 
-int rerank(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int kp, const uint64_t *cand,
-           uint64_t *okeys, int64_t *oids, hipStream_t st) {
+// ---------------------------------------------------------------------------
+// Panel re-rank: the same chains, fed from coalesced loads (k_tail's scheme, for any k'). A workgroup is four waves of ONE query;
+// each wave owns 64 consecutive candidates of that query's list end to end: it fetches their rows itself -- 8 neighbouring lanes
+// take the 128 contiguous bytes of one row's panel, every load of a super-panel (3 panels, 24 KB per wave) issued before
+// anything waits and parked in registers --, passes them panel by panel through its own padded LDS image (144-byte row stride:
+// the 64 lanes' 16-byte fragment reads of 64 different rows are conflict-free), and each lane then walks its candidate's row in
+// element order with the roundings of exact_distance. No workgroup barrier after the query row is staged: the image is
+// wave-private, a wave's LDS instructions execute in order, and one image (9 216 B per wave) is enough -- the loader and the
+// chains are the same wave, so there is nothing for a second buffer to overlap with. 36 KB + the query row per workgroup:
+// four workgroups (16 waves) fit a CU at dim 768. Every wave of a workgroup runs chains; a wave whose 64 candidates are all
+// invalid writes its padding and leaves.
+// ---------------------------------------------------------------------------
+constexpr int RP_WAVES = 4, RP_THREADS = RP_WAVES * WAVE;
+constexpr int RP_ROWB = 128;                          // panel bytes per row: 64 elements (16-bit) / 32 (f32)
+constexpr int RP_STRIDE = RP_ROWB + 16;               // + one chunk: consecutive rows start 4 banks apart
+constexpr int RP_CPR = RP_ROWB / 16;                  // 16-byte chunks per panel row: 8 lanes per row
+constexpr int RP_CPL = WAVE * RP_CPR / WAVE;          // chunks per lane per panel (64 rows x 8 chunks over 64 lanes): 8
+constexpr int RP_SPP = 24 / RP_CPL;                   // panels per super-panel: 3 (24 uint4 = 96 VGPRs parked)
+constexpr int RP_IMAGE = WAVE * RP_STRIDE;            // one wave's LDS image
+
+template <int DT>
+__global__ __launch_bounds__(RP_THREADS) void k_rerank_panel(const typename Store<DT>::T *__restrict__ rows, const float *__restrict__ na,
+                                                             const int64_t *__restrict__ ids, int dim, int metric,
+                                                             const float *__restrict__ queries, const float *__restrict__ nb, int kp,
+                                                             int gpq, const uint64_t *__restrict__ cand, uint64_t *__restrict__ okeys,
+                                                             int64_t *__restrict__ oids) {
+    using S = Store<DT>;
+    constexpr int ES = (int)sizeof(typename S::T), PW = RP_ROWB / ES;     // panel width in elements
+    extern __shared__ __attribute__((aligned(16))) char s_dyn[];          // [dim] float32 query row, then RP_WAVES images
+    float *s_q = (float *)s_dyn;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int qi = blockIdx.x / gpq, grp = blockIdx.x % gpq;             // gpq workgroups per query
+    for (int i = tid; i < dim; i += RP_THREADS) s_q[i] = queries[(int64_t)qi * dim + i];
+    __syncthreads();                                  // the only workgroup barrier: waves part ways below
+    const int c0 = (grp * RP_WAVES + wave) * WAVE;    // this wave's first candidate
+    if (c0 >= kp) return;
+    const int ci = c0 + lane;
+    const int64_t t = (int64_t)qi * kp + ci;
+    const uint64_t key = ci < kp ? cand[t] : KEY_INVALID;
+    const bool valid = key != KEY_INVALID;
+    const uint64_t vmask = __ballot(valid);
+    if (!vmask) {                                     // wave-uniform
+        if (ci < kp) { okeys[t] = KEY_INVALID; oids[t] = -1; }
+        return;
+    }
+    // a missing candidate's loads go to the row of the wave's first valid one (never used: its chain does not run); nothing
+    // is read at slot 0xffffffff
+    const int slot = (int)(uint32_t)key;
+    const int spare = __shfl(slot, __builtin_ctzll(vmask));          // (every lane takes part in the shuffle)
+    const int fslot = valid ? slot : spare;
+    // loader role: chunk c = lane + 64 j of the panel is row (lane / 8 + 8 j), 16-byte piece (lane % 8)
+    const char *rbase[RP_CPL];
+#pragma unroll
+    for (int j = 0; j < RP_CPL; j++)
+        rbase[j] = (const char *)rows + (int64_t)(uint32_t)__shfl(fslot, (lane >> 3) + 8 * j) * dim * ES + (lane & 7) * 16;
+    char *img = s_dyn + (size_t)dim * 4 + wave * RP_IMAGE;
+    char *wr = img + (lane >> 3) * RP_STRIDE + (lane & 7) * 16;
+    const char *row = img + lane * RP_STRIDE;
+    float acc = 0.0f;
+    const int npanels = dim / PW;                     // dim % 64 == 0 (rerank_panel_supported)
+    for (int p0 = 0; p0 < npanels; p0 += RP_SPP) {
+        const int np = npanels - p0 < RP_SPP ? npanels - p0 : RP_SPP;
+        // as in k_tail: inline asm, or hipcc sinks the loads to their LDS writes and exposes one round trip per panel
+        uint4 park[RP_SPP][RP_CPL];
+#pragma unroll
+        for (int pp = 0; pp < RP_SPP; pp++)
+#pragma unroll
+            for (int j = 0; j < RP_CPL; j++) {
+                const char *g = rbase[j] + (int64_t)(p0 + (pp < np ? pp : np - 1)) * RP_ROWB;
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(park[pp][j]) : "v"(g) : "memory");
+            }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // (volatile asm statements keep their order: nothing reads a parked register before the wait)
+#pragma unroll
+        for (int pp = 0; pp < RP_SPP; pp++)
+#pragma unroll
+            for (int j = 0; j < RP_CPL; j++)
+                asm volatile("" : "+v"(park[pp][j].x), "+v"(park[pp][j].y), "+v"(park[pp][j].z), "+v"(park[pp][j].w));
+#pragma unroll
+        for (int pp = 0; pp < RP_SPP; pp++) {
+            if (pp < np) {                            // wave-uniform
+#pragma unroll
+                for (int j = 0; j < RP_CPL; j++) *(uint4 *)(wr + 8 * j * RP_STRIDE) = park[pp][j];
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes have landed
+                if (valid) {
+                    const float *qq = s_q + (p0 + pp) * PW;
+#pragma unroll
+                    for (int i = 0; i < PW; i += 8) {
+                        float v[8];
+                        if constexpr (DT == AK_DTYPE_F32) {
+                            const float4 a = *(const float4 *)(row + i * 4), b = *(const float4 *)(row + i * 4 + 16);
+                            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+                        } else {
+                            const uint4 u = *(const uint4 *)(row + i * 2);
+                            const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+                            for (int e = 0; e < 4; e++) {
+                                const uint16_t lo = (uint16_t)(w[e] & 0xffffu), hi = (uint16_t)(w[e] >> 16);
+                                v[2 * e] = DT == AK_DTYPE_BF16 ? bf16_to_f32(lo) : f16_to_f32(lo);
+                                v[2 * e + 1] = DT == AK_DTYPE_BF16 ? bf16_to_f32(hi) : f16_to_f32(hi);
+                            }
+                        }
+                        if (metric == AK_METRIC_L2) {
+#pragma unroll
+                            for (int e = 0; e < 8; e++) {
+                                const float diff = __fsub_rn(v[e], qq[i + e]);
+                                acc = __fadd_rn(acc, __fmul_rn(diff, diff));
+                            }
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; e++) acc = __fadd_rn(acc, __fmul_rn(v[e], qq[i + e]));
+                        }
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();      // the next panel overwrites the image
+            }
+        }
+    }
+    if (ci >= kp) return;
+    if (valid) {
+        const int64_t r = (int64_t)(uint32_t)key;
+        okeys[t] = dist_key(exact_finish(acc, metric, na[r], nb[qi]));
+        oids[t] = ids[r];
+    } else {
+        okeys[t] = KEY_INVALID;
+        oids[t] = -1;
+    }
+}
+
+bool rerank_panel_supported(const Index &ix) { return ix.dim > 0 && ix.dim % 64 == 0 && ix.dim <= TAIL_MAX_DIM; }
+bool rerank_takes_panel(const Index &ix) {
+    return rerank_panel_supported(ix) && !switches().rerank_old.load(std::memory_order_relaxed);
+}
+
+int rerank_with(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int kp, const uint64_t *cand, uint64_t *okeys,
+                int64_t *oids, bool panel, hipStream_t st) {
+    if (nq <= 0 || kp <= 0) return 0;
+    if ((int64_t)nq * kp > 0x7fffffff) AK_FAIL(-1, "rerank: more than 2^31 candidates");
+    if (panel) {
+        if (!rerank_panel_supported(ix)) AK_FAIL(-1, "rerank: the panel kernel takes dim % 64 == 0, dim <= 4096");
+        const int gpq = (kp + RP_WAVES * WAVE - 1) / (RP_WAVES * WAVE);
+        if ((int64_t)nq * gpq > 0x7fffffff) AK_FAIL(-1, "rerank: too many workgroups");
+        const size_t lds = (size_t)ix.dim * 4 + RP_WAVES * RP_IMAGE;       // <= 53 248 B
+#define LAUNCH(DT)                                                                                                      \
+    k_rerank_panel<DT><<<nq * gpq, RP_THREADS, lds, st>>>((const Store<DT>::T *)ix.rows, ix.na, ix.ids, ix.dim, ix.metric, \
+                                                          queries_dev, nb_dev, kp, gpq, cand, okeys, oids)
+        if (ix.dtype == AK_DTYPE_F32) LAUNCH(AK_DTYPE_F32);
+        else if (ix.dtype == AK_DTYPE_BF16) LAUNCH(AK_DTYPE_BF16);
+        else LAUNCH(AK_DTYPE_F16);
+#undef LAUNCH
+        AK_HIP(hipGetLastError());
+        return 0;
+    }
     int total = nq * kp;
     int grid = (total + 127) / 128;
 #define LAUNCH(DT)                                                                                   \
@@ -202,6 +363,11 @@ int rerank(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int
 #undef LAUNCH
     AK_HIP(hipGetLastError());
     return 0;
+}
+
+int rerank(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int kp, const uint64_t *cand,
+           uint64_t *okeys, int64_t *oids, hipStream_t st) {
+    return rerank_with(ix, queries_dev, nb_dev, nq, kp, cand, okeys, oids, rerank_takes_panel(ix), st);
 }
 
 // ---------------------------------------------------------------------------

@@ -120,8 +120,15 @@ int select_keys_topk(const uint64_t *keys, int nq, int64_t n_in, int64_t in_stri
 
 // exact re-rank of candidates: cand [nq][kp] approx keys (row slot in the low
 // 32 bits) -> exact distance keys + global ids, same layout.
+// Two kernels: the panel kernel (coalesced row fetch through wave-private LDS images; dim % 64 == 0, dim <= TAIL_MAX_DIM) and the
+// thread-per-candidate one (every shape; AK_RERANK_OLD = 1). Same bits from both.
 int rerank(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int kp, const uint64_t *cand,
            uint64_t *okeys, int64_t *oids, hipStream_t st);
+bool rerank_panel_supported(const Index &ix);
+bool rerank_takes_panel(const Index &ix);          // what rerank() launches for this index under the current switches
+// one named kernel (kernel-level tests); panel on a shape it does not take is an error, not a fallback
+int rerank_with(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int kp, const uint64_t *cand, uint64_t *okeys,
+                int64_t *oids, bool panel, hipStream_t st);
 
 // per-query preparation: nb (pgvector-order sum of squares)
 int query_norms(const float *queries_dev, int nq, int dim, float *nb_dev, hipStream_t st);

@@ -57,6 +57,7 @@ const SwitchName g_switch_names[] = {
     {"AK_SCAN_NOSEED", &Switches::scan_noseed, 0, true, false, false},
     {"AK_SCAN_NOPRE", &Switches::scan_nopre, 0, true, false, false},
     {"AK_TAIL_OLD", &Switches::tail_old, 0, true, false, false},
+    {"AK_RERANK_OLD", &Switches::rerank_old, 0, false, false, false},
     {"AK_SCAN_DBG", &Switches::scan_dbg, 0, true, false, false},
     {"AK_COALESCE_STATS", &Switches::coalesce_stats, 0, true, false, false},
     {"AK_SHARD_INJECT", &Switches::shard_inject, 0, false, false, false},

@@ -4,6 +4,7 @@
 // arithmetic, no kernel selection of its own. With no AK_* switch set the instantiation that runs is the one the product launches;
 // a shape the launcher refuses comes back as its error code (ak_last_error has the text).
 #include "encoder_kernels.h"
+#include "index.h"
 
 #if AK_DBG_KERNELS
 
@@ -414,6 +415,26 @@ extern "C" int ak_kts_t5_gemm_relu(const uint16_t *X, const uint16_t *W, const f
     GemmArgs a{};
     a.X = X; a.W = W; a.bias = bias; a.T = T; a.N = N; a.K = K; a.out_bf16 = out; a.ldo = N;
     return launch_gemm(10, a, (hipStream_t)stream);
+}
+
+// ---- the re-rank kernels of the kNN fast path (tests/test_rerank_panel_gpu.py). Named ak_kts_rr_*: the other subsets stay what they are ----
+// query_norms, then ONE re-rank launch on a caller-built candidate array cand [nq][kp] (approximate keys, row slot in the low 32
+// bits, KEY_INVALID padding) -> okeys / oids [nq][kp]. which = 0: the thread-per-candidate kernel, 1: the panel kernel (an error on a
+// shape it does not take, never the other kernel). nb [nq] floats is workspace. The caller keeps writers away from the index.
+extern "C" int ak_kts_rr_rerank(void *index, const float *queries, int nq, int kp, const uint64_t *cand, uint64_t *okeys, int64_t *oids,
+                                float *nb, int which, void *stream) {
+    AK_BIND();
+    if (!index || !queries || !cand || !okeys || !oids || !nb) AK_FAIL(-1, "ak_kts_rr_rerank: NULL argument");
+    if (nq <= 0 || kp <= 0 || (which != 0 && which != 1)) AK_FAIL(-1, "ak_kts_rr_rerank: nq, kp > 0, which 0 or 1");
+    Index &ix = *(Index *)index;
+    std::shared_lock<std::shared_mutex> lk(ix.mu);
+    if (int rc = query_norms(queries, nq, ix.dim, nb, (hipStream_t)stream)) return rc;
+    return rerank_with(ix, queries, nb, nq, kp, cand, okeys, oids, which == 1, (hipStream_t)stream);
+}
+// the kernel rerank() launches for this index under the current switches (AK_RERANK_OLD): 0 thread-per-candidate, 1 panel
+extern "C" int ak_kts_rr_choice(void *index) {
+    if (!index) AK_FAIL(-1, "ak_kts_rr_choice: NULL argument");
+    return rerank_takes_panel(*(Index *)index) ? 1 : 0;
 }
 
 #endif  // AK_DBG_KERNELS

@@ -28,6 +28,7 @@ struct Switches {
     std::atomic<int> scan_noseed{0};     // AK_SCAN_NOSEED
     std::atomic<int> scan_nopre{0};      // AK_SCAN_NOPRE
     std::atomic<int> tail_old{0};        // AK_TAIL_OLD: the three-kernel tail
+    std::atomic<int> rerank_old{0};      // AK_RERANK_OLD: rerank() on the thread-per-candidate kernel (0 = the panel kernel where it takes the shape)
     std::atomic<int> scan_dbg{0};        // AK_SCAN_DBG: cycle stamps (instrumented kernels: dbg library)
     std::atomic<int> coalesce_stats{0};  // AK_COALESCE_STATS
     std::atomic<int> query_fused{0};     // AK_QUERY_FUSED: 1 = embed_query through query_forward.hip's single launch (measured SLOWER than the 47
