@@ -211,6 +211,7 @@ SYMBOLS = [
     ("ak_index_lex_scores", _I, [_P, _P, _I, _D, _D, _D, _P, _P, _P]),
     ("ak_index_hybrid_search", _I, [_P, _P, _P, _I, _D, _D, _D, _D, _D, _P, _I64, _P, _I64, _U64, _I, _P, _P, ctypes.POINTER(_I),
                                     _P, _P, ctypes.POINTER(_I), _P]),
+    ("ak_index_hybrid_search_batch", _I, [_P, _P, _I, _P, _P, _D, _D, _D, _D, _D, _P, _I64, _P, _I64, _U64, _I, _P, _P, _P, _P, _P, _P, _P]),
     ("ak_index_search_dev", _I, [_P, _P, _I, _I, _I, _P, _I64, _U64, _P, _P, _P, _P]),
     ("ak_index_slots", _I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_U64)]),
     ("ak_index_compact", _I, [_P, ctypes.POINTER(_I64)]),

@@ -54,6 +54,7 @@ struct Index : IndexBook {
     std::vector<int32_t> h_lex_cnt;              // host mirror of lex_cnt (shorter than n: the missing slots hold 0)
     std::vector<uint8_t> h_lex_att;              // 1 = a list was attached to the slot (an empty text attaches an empty list)
     Workspace ws_lex;                            // workspace of the lexical / hybrid query (one at a time: lex_mu)
+    Workspace ws_lexb;                           // the batch call's [queries][rows of U] arrays, sized after |U| is known (lex_mu)
     std::mutex lex_mu;
     char *lex_pin = nullptr; size_t lex_pin_cap = 0;       // pinned landing pad of the query's small copies
     hipEvent_t lex_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // ak_index_profile: stage boundaries of the hybrid query
@@ -72,6 +73,7 @@ struct Index : IndexBook {
     std::atomic<int64_t> s8_searches{0};   // searches that ran the i8 plan
     std::mutex s8_mu;
     Coalescer co;
+    HybridCoalescer hco;  // concurrent ak_index_hybrid_search calls (lexical_batch.hip)
     std::shared_mutex mu;
     Workspace ws_dev;     // workspace of ak_index_search_dev (one call at a time: ws_mu + ws_event order its users)
     Workspace ws_fb;      // ak_index_search_dev, AUTO mode: workspace of the re-run of uncertified queries (rare, grow-only)
@@ -153,6 +155,19 @@ int lex_rebuild(Index &ix, const LexMove &to, const std::vector<int64_t> *src, h
 void lex_rebuilt(Index &ix, const std::vector<int64_t> *src, uint2 *new_arena, int64_t new_cap, int64_t new_used);
 void lex_removed(Index &ix, const std::vector<int64_t> &slots);
 void lex_release(Index &ix);
+// pieces of lexical.hip the batch call (lexical_batch.hip) builds on
+int lex_unique_terms(const int32_t *terms, int T, std::vector<uint32_t> &out, const char *who);      // distinct, first-occurrence order
+int lex_pin_reserve(Index &ix, size_t need);
+hipEvent_t *lex_events(Index &ix);                    // ix.lex_ev when ak_index_profile is on, else NULL
+void lex_also_slots(const Index &ix, const int64_t *also_ids, int64_t n_also, std::vector<int64_t> &also);
+// ak_index_hybrid_search behind its argument checks and locks (ix.mu shared, ix.lex_mu)
+int lex_hybrid_one(Index &ix, const float *query, const std::vector<uint32_t> &uq, double k1, double b, double sign, double w_s,
+                   double w_b, const std::vector<int64_t> &also, const uint8_t *row_filter, int k, int64_t *out_hit_ids,
+                   double *out_hit_combined, int *n_hit, int64_t *out_scan_ids, double *out_scan_dist, int *n_scan, int64_t *out_info);
+// ak_index_hybrid_search: the call itself (uncoalesced) -- what a group of one runs
+int lex_hybrid_single(Index &ix, const HybridReq &r);
+// lexical_batch.hip: one group of same-keyed concurrent calls as one batch call; fills every request's outputs, rc and err
+void lex_hybrid_group(Index &ix, std::vector<HybridReq *> &g);
 
 // ---- fast path (scan.hip) ----------------------------------------------------
 // per-query certificate terms: s~_units = a * s~' + b where s~' is the scan's score; eps in score units

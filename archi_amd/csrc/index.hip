@@ -60,6 +60,9 @@ const SwitchName g_switch_names[] = {
     {"AK_RERANK_OLD", &Switches::rerank_old, 0, false, false, false},
     {"AK_SCAN_DBG", &Switches::scan_dbg, 0, true, false, false},
     {"AK_COALESCE_STATS", &Switches::coalesce_stats, 0, true, false, false},
+    {"AK_COALESCE", &Switches::coalesce, 1, false, false, false},
+    {"AK_LEX_BATCH_PAIRS", &Switches::lex_batch_pairs, 1 << 24, false, false, false},
+    {"AK_LEX_BATCH_TERMS", &Switches::lex_batch_terms, 0, false, false, false},
     {"AK_SHARD_INJECT", &Switches::shard_inject, 0, false, false, false},
     {"AK_QUERY_FUSED", &Switches::query_fused, 0, false, false, false},
 #if AK_DBG_KERNELS      // WRONG RESULTS: the product library does not even know the names
@@ -1277,10 +1280,7 @@ static int search_host(Index &ix, const float *queries, int nq, int k, int mode,
 // under ThreadSanitizer / AddressSanitizer in the CPU suite). Here: what a group's search is. AK_COALESCE=0 turns it off.
 namespace ak {
 constexpr int COALESCE_MAX_NQ = 16;
-static bool coalesce_enabled() {
-    static const bool v = !(env_get("AK_COALESCE") && atoi(env_get("AK_COALESCE")) == 0);
-    return v;
-}
+static bool coalesce_enabled() { return switches().coalesce.load(std::memory_order_relaxed) != 0; }
 static void run_group(Index &ix, std::vector<SearchReq *> &g) {
     if (g.size() == 1) {
         SearchReq &r = *g[0];

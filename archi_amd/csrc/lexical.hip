@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "index.h"
+#include "switches.h"
 
 namespace ak {
 
@@ -325,6 +326,7 @@ void lex_release(Index &ix) {
     if (ix.lex_arena) hipFree(ix.lex_arena);
     ix.lex_arena = nullptr; ix.lex_arena_cap = ix.lex_used = 0;
     ix.ws_lex.release();
+    ix.ws_lexb.release();
     if (ix.lex_pin) hipHostFree(ix.lex_pin);
     ix.lex_pin = nullptr; ix.lex_pin_cap = 0;
     for (auto &e : ix.lex_ev) if (e) { hipEventDestroy(e); e = nullptr; }
@@ -353,8 +355,10 @@ struct QueryTable {       // the query's terms as the kernels read them
     size_t bytes() const { return sorted.size() * 8; }
 };
 
+}  // namespace
+
 // the query's distinct terms in first-occurrence order
-int unique_terms(const int32_t *terms, int T, std::vector<uint32_t> &out, const char *who) {
+int lex_unique_terms(const int32_t *terms, int T, std::vector<uint32_t> &out, const char *who) {
     out.clear();
     if (T < 0 || (T > 0 && !terms)) AK_FAIL(-1, std::string(who) + ": bad terms");
     std::unordered_set<uint32_t> seen;
@@ -365,7 +369,7 @@ int unique_terms(const int32_t *terms, int T, std::vector<uint32_t> &out, const 
     return 0;
 }
 
-int pin_reserve(Index &ix, size_t need) {
+int lex_pin_reserve(Index &ix, size_t need) {
     if (need <= ix.lex_pin_cap) return 0;
     if (ix.lex_pin) hipHostFree(ix.lex_pin);
     ix.lex_pin = nullptr; ix.lex_pin_cap = 0;
@@ -374,6 +378,8 @@ int pin_reserve(Index &ix, size_t need) {
     ix.lex_pin_cap = need;
     return 0;
 }
+
+namespace {
 
 struct LexPlan {          // workspace of one query; every array sized for the worst case so that nothing grows after the counts are known
     uint8_t *match, *mask, *filter;
@@ -439,7 +445,7 @@ int lex_passes(Index &ix, LexPlan &p, const std::vector<uint32_t> &terms, const 
     AK_HIP(hipGetLastError());
     if (ev) AK_HIP(hipEventRecord(ev[1], st));
     // the one small copy: df [T] | n | sum_len | hits
-    if (pin_reserve(ix, tq * 4 + 32 + 4096)) return -10;
+    if (lex_pin_reserve(ix, tq * 4 + 32 + 4096)) return -10;
     AK_HIP(hipMemcpyAsync(ix.lex_pin, p.df, tq * 4 + 32, hipMemcpyDeviceToHost, st));
     AK_HIP(hipStreamSynchronize(st));
     const unsigned int *df = (const unsigned int *)ix.lex_pin;
@@ -469,6 +475,8 @@ int lex_passes(Index &ix, LexPlan &p, const std::vector<uint32_t> &terms, const 
     return 0;
 }
 
+}  // namespace
+
 hipEvent_t *lex_events(Index &ix) {
     if (!ix.profile) return nullptr;
     for (auto &e : ix.lex_ev)
@@ -476,7 +484,24 @@ hipEvent_t *lex_events(Index &ix) {
     return ix.lex_ev;
 }
 
-}  // namespace
+// also_ids -> the distinct live slots they name: a const look at the id map (the shared lock allows no lazy build; generated rows
+// go by the id array)
+void lex_also_slots(const Index &ix, const int64_t *also_ids, int64_t n_also, std::vector<int64_t> &also) {
+    also.clear();
+    const int64_t n = ix.n;
+    std::unordered_set<int64_t> seen;
+    for (int64_t i = 0; i < n_also; i++) {
+        int64_t s = -1;
+        if (ix.map_built) {
+            auto it = ix.id2slot.find(also_ids[i]);
+            if (it != ix.id2slot.end()) s = it->second;
+        } else {
+            for (int64_t r = 0; r < n; r++) if (ix.h_ids[r] == also_ids[i] && ix.h_alive[r]) { s = r; break; }
+        }
+        if (s >= 0 && ix.h_alive[s] && seen.insert(s).second) also.push_back(s);
+    }
+}
+
 }  // namespace ak
 
 using namespace ak;
@@ -603,7 +628,7 @@ int ak_index_lex_scores(ak_index_t h, const int32_t *terms, int T, double k1, do
     Index &ix = *(Index *)h;
     if (out_info) memset(out_info, 0, 4 * sizeof(int64_t));
     std::vector<uint32_t> uq;
-    if (int rc = unique_terms(terms, T, uq, "ak_index_lex_scores")) return rc;
+    if (int rc = lex_unique_terms(terms, T, uq, "ak_index_lex_scores")) return rc;
     std::shared_lock<std::shared_mutex> lk(ix.mu);
     const int64_t n = ix.n;
     if (n == 0) return 0;
@@ -647,30 +672,44 @@ int ak_index_hybrid_search(ak_index_t h, const float *query, const int32_t *term
         n_also < 0 || n_also > (1 << 24) || (n_also > 0 && !also_ids))
         AK_FAIL(-1, "ak_index_hybrid_search: bad arguments");
     *n_hit = 0; *n_scan = 0;
-    std::vector<uint32_t> uq;
-    if (int rc = unique_terms(terms, T, uq, "ak_index_hybrid_search")) return rc;
-    RoctxRange range("ak_index_hybrid_search");
-    std::shared_lock<std::shared_mutex> lk(ix.mu);
-    if (int frc = filter_is_current(ix, row_filter, filter_len, filter_epoch, "ak_index_hybrid_search")) return frc;
-    const int64_t n = ix.n;
-    if (n == 0) return 0;
-    // the suspects' slots: a const look at the id map (the shared lock allows no lazy build; generated rows go by the id array)
-    std::vector<int64_t> also;
     {
-        std::unordered_set<int64_t> seen;
-        for (int64_t i = 0; i < n_also; i++) {
-            int64_t s = -1;
-            if (ix.map_built) {
-                auto it = ix.id2slot.find(also_ids[i]);
-                if (it != ix.id2slot.end()) s = it->second;
-            } else {
-                for (int64_t r = 0; r < n; r++) if (ix.h_ids[r] == also_ids[i] && ix.h_alive[r]) { s = r; break; }
-            }
-            if (s >= 0 && ix.h_alive[s] && seen.insert(s).second) also.push_back(s);
-        }
+        std::vector<uint32_t> uq;          // a caller's bad terms are its own error, not its group's
+        if (int rc = lex_unique_terms(terms, T, uq, "ak_index_hybrid_search")) return rc;
     }
-    const int na = (int)also.size();
+    RoctxRange range("ak_index_hybrid_search");
+    HybridReq me{query, terms, T, k1, b, sign, w_s, w_b, also_ids, n_also, row_filter, filter_len, filter_epoch, k,
+                 out_hit_ids, out_hit_combined, n_hit, out_scan_ids, out_scan_dist, n_scan, out_info};
+    if (!switches().coalesce.load(std::memory_order_relaxed)) return lex_hybrid_single(ix, me);
+    // concurrent calls meet in the coalescer (coalesce.h): a caller on an idle index serves itself at once through the single-query
+    // path; calls that queued behind a running one are served per (k, k1, b, sign, w_s, w_b, filter) group by ONE batch call
+    const int rc = ix.hco.submit(me, [&](std::vector<HybridReq *> &g) { lex_hybrid_group(ix, g); });
+    if (rc) set_error(me.err);
+    return rc;
+}
+
+}  // extern "C"
+
+int ak::lex_hybrid_single(Index &ix, const HybridReq &r) {
+    std::vector<uint32_t> uq;
+    if (int rc = lex_unique_terms(r.terms, r.T, uq, "ak_index_hybrid_search")) return rc;
+    std::shared_lock<std::shared_mutex> lk(ix.mu);
+    if (int frc = filter_is_current(ix, r.filter, r.flen, r.fepoch, "ak_index_hybrid_search")) return frc;
+    if (ix.n == 0) return 0;
+    std::vector<int64_t> also;
+    lex_also_slots(ix, r.also, r.n_also, also);
     std::lock_guard<std::mutex> ql(ix.lex_mu);
+    return lex_hybrid_one(ix, r.q, uq, r.k1, r.b, r.sign, r.w_s, r.w_b, also, r.filter, r.k, r.out_hit_ids, r.out_hit_comb, r.n_hit,
+                          r.out_scan_ids, r.out_scan_dist, r.n_scan, r.out_info);
+}
+
+// ak_index_hybrid_search behind its argument checks: the caller holds ix.mu (shared) and ix.lex_mu, has checked the filter's epoch
+// and zeroed the outputs' counts and out_info; ix.n > 0
+int ak::lex_hybrid_one(Index &ix, const float *query, const std::vector<uint32_t> &uq, double k1, double b, double sign, double w_s,
+                       double w_b, const std::vector<int64_t> &also, const uint8_t *row_filter, int k, int64_t *out_hit_ids,
+                       double *out_hit_combined, int *n_hit, int64_t *out_scan_ids, double *out_scan_dist, int *n_scan,
+                       int64_t *out_info) {
+    const int64_t n = ix.n;
+    const int na = (int)also.size();
     hipStream_t st;
     if (thread_stream(&st)) return -10;
     const size_t need = lex_plan(nullptr, n, (int)uq.size(), na, k, ix.dim, row_filter != nullptr).bytes;
@@ -709,7 +748,7 @@ int ak_index_hybrid_search(ak_index_t h, const float *query, const int32_t *term
         const bool masked = row_filter || n_list > 0;
         if ((rc = search_dev_locked(ix, p.dq, 1, k, AK_SEARCH_AUTO, masked ? p.mask : nullptr, p.scan_ids, p.scan_dist, p.cert, st))) break;
         if (ev && hipEventRecord(ev[4], st) != hipSuccess) { rc = -10; break; }
-        if (pin_reserve(ix, 4 * ob)) { rc = -10; break; }
+        if (lex_pin_reserve(ix, 4 * ob)) { rc = -10; break; }
         char *pin = ix.lex_pin;
         if (n_list > 0 && (hipMemcpyAsync(pin, p.sids, ob, hipMemcpyDeviceToHost, st) != hipSuccess ||
                            hipMemcpyAsync(pin + ob, p.out_comb, ob, hipMemcpyDeviceToHost, st) != hipSuccess)) { rc = -10; break; }
@@ -744,5 +783,3 @@ int ak_index_hybrid_search(ak_index_t h, const float *query, const int32_t *term
     }
     return 0;
 }
-
-}  // extern "C"

@@ -215,6 +215,41 @@ class HipIndex:
                                                _ptr(si), _ptr(sd), ctypes.byref(ns), _ptr(info)), "ak_index_hybrid_search")
         return hi[: nh.value], hc[: nh.value], si[: ns.value], sd[: ns.value], info
 
+    HYBRID_BATCH_INFO = ("n", "sum_len", "union_rows", "hit_rows", "terms", "arena_entries", "stats_ns", "score_ns", "hit_ns", "scan_ns",
+                         "stats_passes", "score_passes", "scans", "sub_batches", "own_hit_rows", "pairs")
+
+    def hybrid_search_batch(self, queries, terms_per_query, k1: float, b: float, sign: float, w_s: float, w_b: float, also_ids, k: int,
+                            row_filter: Optional[np.ndarray] = None, filter_epoch: Optional[int] = None):
+        """The hybrid query's two legs for a batch of queries in one call (ak_index_hybrid_search_batch): one pass over the lists,
+        one score pass and one scan per sub-batch of 32 queries. queries [Q, dim]; terms_per_query: Q sequences of term ids.
+        -> (per query a tuple (hit ids, hit combined scores, scan ids, scan distances), info dict of HYBRID_BATCH_INFO). The merged
+        top k of each query equals hybrid_search's for that query alone; the two lists differ. StaleFilterError as search()."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim or q.shape[0] < 1:
+            raise ValueError(f"queries must be [Q >= 1, {self.dim}]")
+        nq = q.shape[0]
+        if len(terms_per_query) != nq:
+            raise ValueError("hybrid_search_batch: one term list per query")
+        lists = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in terms_per_query]
+        to = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum([t.size for t in lists], out=to[1:])
+        te = np.concatenate(lists) if int(to[-1]) else np.zeros(1, np.int32)
+        al = np.ascontiguousarray(also_ids, dtype=np.int64)
+        flt, flen, fep = None, 0, 0
+        if row_filter is not None:
+            flt = np.ascontiguousarray(row_filter, dtype=np.uint8)
+            flen = flt.shape[0]
+            fep = self.layout()[1] if filter_epoch is None else int(filter_epoch)
+        hi, hc = np.full((nq, k), -1, np.int64), np.full((nq, k), np.nan, np.float64)
+        si, sd = np.full((nq, k), -1, np.int64), np.full((nq, k), np.nan, np.float64)
+        nh, ns = np.zeros(nq, np.int32), np.zeros(nq, np.int32)
+        info = np.zeros(16, dtype=np.int64)
+        check(self._lib.ak_index_hybrid_search_batch(self._h, _ptr(q), nq, _ptr(to), _ptr(te), float(k1), float(b), float(sign), float(w_s),
+                                                     float(w_b), _ptr(al), al.size, _ptr(flt), flen, fep, k, _ptr(hi), _ptr(hc), _ptr(nh),
+                                                     _ptr(si), _ptr(sd), _ptr(ns), _ptr(info)), "ak_index_hybrid_search_batch")
+        out = [(hi[i, : nh[i]], hc[i, : nh[i]], si[i, : ns[i]], sd[i, : ns[i]]) for i in range(nq)]
+        return out, dict(zip(self.HYBRID_BATCH_INFO, (int(v) for v in info)))
+
     def fetch(self, slots: Sequence[int]) -> np.ndarray:
         """Stored rows (exact stored values widened to float32) by row slot."""
         s = np.ascontiguousarray(slots, dtype=np.int64)

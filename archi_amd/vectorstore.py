@@ -1203,6 +1203,74 @@ class ArchiHipHybridVectorStore(ArchiHipVectorStore):
         c_score = np.concatenate([hit_comb, (1.0 - scan_dist.astype(np.float64)) * semantic_weight + 0 * bm25_weight])
         return c_score, np.concatenate([hit_ids, scan_ids]).astype(np.int64)
 
+    def hybrid_search_batch(self, queries: List[str], k: int = 4, *, semantic_weight: float = 0.7, bm25_weight: float = 0.3,
+                            **kwargs: Any) -> List[List[Tuple[Any, float]]]:
+        """`hybrid_search` for a list of queries -> one result list per query, each equal to `hybrid_search(query, ...)`. With a
+        scorer whose index lives in HBM (lexical.DeviceBm25) the whole list is ONE library call (HipIndex.hybrid_search_batch):
+        one pass over the BM25 lists, one score pass and one scan per 32 queries instead of one of each per query. Known cost: every
+        query's exact distances are computed for the rows matching ANY query of the batch. Every query is embedded with
+        `embed_query` (not `embed_documents`: the two may take different kernels). The rare cases keep the single path: a degenerate
+        query vector, and a query whose selected rows were deleted before their text was read. With HostBm25 (or any scorer without
+        `device_query`) this is a loop over `hybrid_search`."""
+        queries = list(queries)
+        if self._bm25 is None:                                                      # :415-418
+            raise RuntimeError("Hybrid search requires pg_textsearch BM25 index on document_chunks; none found.")
+        if semantic_weight < 0:
+            raise ValueError("semantic_weight must be >= 0 (the two-leg evaluation relies on it)")
+
+        def single(query: str) -> List[Tuple[Any, float]]:
+            return self.hybrid_search(query, k, semantic_weight=semantic_weight, bm25_weight=bm25_weight, **kwargs)
+        col = self._collection()
+        if not queries or col is None or k <= 0 or not callable(getattr(self._bm25, "device_query", None)):
+            return [single(query) for query in queries]
+        self._bm25.use_index(col.index)                  # raises on an index without the lexical entry points: no fallback
+        metadata_filter = kwargs.get("filter", {}) or {}
+        include_deleted = kwargs.get("include_deleted", False)
+        qs = np.asarray([[float(x) for x in self._embedding_function.embed_query(query)] for query in queries], dtype=np.float32)
+        bad = np.asarray(_suspect_rows(qs), bool)
+        out: List[Any] = [None] * len(queries)
+        good = [i for i in range(len(queries)) if not bad[i]]
+        if good:
+            legs = self._hybrid_device_legs_batch(col, qs[good], [queries[i] for i in good], k, semantic_weight, bm25_weight,
+                                                  metadata_filter, include_deleted)
+            for i, (c_score, c_id) in zip(good, legs):
+                results, vanished = self._hybrid_results(col, c_score, c_id, k)
+                if not vanished:
+                    out[i] = results or self.similarity_search_with_score(queries[i], k=k, **kwargs)
+        return [single(queries[i]) if out[i] is None else out[i] for i in range(len(queries))]
+
+    def _hybrid_device_legs_batch(self, col: _Collection, qs: np.ndarray, queries: List[str], k: int, semantic_weight: float,
+                                  bm25_weight: float, metadata_filter: Dict[str, Any], include_deleted: bool) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """_hybrid_device_legs for a batch through HipIndex.hybrid_search_batch -> per query (combined scores, row ids) of its
+        <= 2 k candidates. The prepare-under-lock / call-without-lock / StaleFilterError discipline applies once per batch."""
+        t, bm = col.table, self._bm25
+
+        def prepare():
+            terms = [bm.device_query(query, t, col.index) for query in queries]
+            rf, _, epoch = self._where(col, metadata_filter, include_deleted)
+            return terms, rf, epoch, np.fromiter(t.suspects, np.int64, len(t.suspects))
+
+        def call(terms, rf, epoch, also):
+            return col.index.hybrid_search_batch(qs, terms, bm.k1, bm.b, bm.sign, semantic_weight, bm25_weight, also, k,
+                                                 row_filter=rf, filter_epoch=epoch)
+        out = None
+        for _ in range(self.STALE_RETRIES):
+            with t.lock:
+                args = prepare()
+            try:
+                out = call(*args)
+                break
+            except StaleFilterError:
+                continue
+        if out is None:
+            with t.lock:
+                out = call(*prepare())
+        legs = []
+        for hit_ids, hit_comb, scan_ids, scan_dist in out[0]:
+            c_score = np.concatenate([hit_comb, (1.0 - scan_dist.astype(np.float64)) * semantic_weight + 0 * bm25_weight])
+            legs.append((c_score, np.concatenate([hit_ids, scan_ids]).astype(np.int64)))
+        return legs
+
     def _hybrid_results(self, col: _Collection, c_score: np.ndarray, c_id: np.ndarray, k: int) -> Tuple[List[Tuple[Any, float]], int]:
         """ORDER BY combined_score DESC LIMIT k over the two legs' candidates, as hybrid_search orders them -> (results, number of
         selected rows that were deleted before their text could be read)."""

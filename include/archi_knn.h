@@ -178,11 +178,52 @@ int ak_index_lex_scores(ak_index_t h, const int32_t *terms, int T, double k1, do
  *   out_info   : NULL or int64[12] = {n, sum of lengths, matching rows that pass the filter, rows of the hit leg, terms with
  *                df > 0, arena entries streamed per pass, then -- when ak_index_profile is on -- nanoseconds of the statistics
  *                pass, the score pass (with the host's idf step), the hit leg and the scan leg, 0, 0}
- * Workspace comes from the index (grown on first use); calls on one index are serialised. */
+ * Workspace comes from the index (grown on first use); evaluations on one index are serialised, and concurrent calls are
+ * coalesced into batch evaluations (see ak_index_hybrid_search_batch). */
 int ak_index_hybrid_search(ak_index_t h, const float *query, const int32_t *terms, int T, double k1, double b, double sign,
                            double w_s, double w_b, const int64_t *also_ids, int64_t n_also, const uint8_t *row_filter,
                            int64_t filter_len, uint64_t filter_epoch, int k, int64_t *out_hit_ids, double *out_hit_combined,
                            int *n_hit, int64_t *out_scan_ids, double *out_scan_dist, int *n_scan, int64_t *out_info);
+/* ak_index_hybrid_search for a BATCH of queries: one pass over the lists for the statistics, one host step (idf), one score pass and
+ * ONE scan for up to 32 queries. The scan takes one mask for all its queries, so the batch is evaluated the way also_ids rows are:
+ *   U = the live rows that pass row_filter and hold a term of ANY query of the batch, plus the also rows;
+ *   HIT leg, per query q: the exact distance of EVERY row of U, bm_q = the query's BM25 exactly as ak_index_lex_scores computes it for
+ *   rows holding a term of q and +0.0 for the rest of U, combined = (1.0 - d) * w_s + bm_q * w_b, the best k by (NaN first, combined
+ *   descending, id ascending); SCAN leg: one ak_index_search (AUTO) of all queries over the rows that pass row_filter and are not in U.
+ * A row of U without a term of q scores (1.0 - d) * w_s + 0.0 * w_b, the expression the caller evaluates for a scan row, so the
+ * MERGED top k of query q -- ids and float64 score bits -- equals that of ak_index_hybrid_search for q alone; the two lists
+ * themselves differ (rows move from the scan list to the hit list). Known cost: the hit leg computes nq * |U| exact distances where
+ * nq single calls compute the sum of their own hit counts; with frequent words U approaches the whole collection.
+ *   queries      : [nq][dim] float32, host; 1 <= nq
+ *   term_offsets : [nq + 1], terms: query q's term ids are terms[term_offsets[q], term_offsets[q + 1]) (CSR). A query with no terms,
+ *                  with only unknown terms, with repeated terms, and identical queries are all fine.
+ *   k1 / b / sign / w_s / w_b / k, also_ids [n_also], row_filter with (filter_len, filter_epoch): ONE of each for the batch, as for
+ *                  the single call (AK_ERR_STALE_FILTER when the index has moved on, nothing read)
+ *   out_hit_ids / out_hit_combined [nq][k], n_hit [nq]; out_scan_ids / out_scan_dist [nq][k], n_scan [nq]
+ *   out_info     : NULL or int64[16] = {n, sum of lengths, |U| without the also rows, rows of the hit leg, union terms with df > 0,
+ *                  arena entries streamed per statistics pass, then -- when ak_index_profile is on -- nanoseconds of the statistics
+ *                  pass, the score pass (with the host's idf step), the hit leg and the scan leg; [10] statistics passes run,
+ *                  [11] score passes run, [12] scans run, [13] sub-batches, [14] the sum over queries of their own matching rows
+ *                  (what nq single calls would re-rank), [15] (query, row) pairs the hit leg evaluated}; [2]-[4] and [6]-[15] are
+ *                  summed over the sub-batches
+ * Limits: 32 queries (one bit each in a uint32 per row) and 2048 distinct terms (the kernels' LDS table) per sub-batch; more of
+ * either runs as consecutive sub-batches INSIDE the call, under one reader lock = one state of the index. A single query with more
+ * than 2048 distinct terms goes through the single-query passes. The [queries][rows of U] arrays of the hit leg (48 bytes per pair)
+ * are allocated after the host has read |U| and hold at most AK_LEX_BATCH_PAIRS pairs (ak_debug_set; default 2^24, about 0.8 GB):
+ * beyond it the hit leg runs in query groups, each with its own score pass over U's lists; the statistics pass over the whole arena
+ * and the scan stay shared. AK_LEX_BATCH_TERMS lowers the term limit (tests). One host synchronisation between the statistics and
+ * the score pass per sub-batch, as in the single call.
+ *
+ * Concurrent ak_index_hybrid_search calls on one index are coalesced (AK_COALESCE=0 turns it off): a call on an idle index runs at
+ * once; calls that arrive while one is running queue up and are then served together, per group of equal (k, k1, b, sign, w_s,
+ * w_b, row_filter pointer, filter_len, filter_epoch), by ONE batch evaluation with their also lists united. Each caller gets its own
+ * rows; its out_info [0..9] then describes the SHARED evaluation (|U| of the group, its times) and out_info[10] is the number of
+ * calls it served (0: the call ran alone). An error of the shared evaluation reaches every caller of the group with its message. */
+int ak_index_hybrid_search_batch(ak_index_t h, const float *queries, int nq, const int64_t *term_offsets, const int32_t *terms,
+                                 double k1, double b, double sign, double w_s, double w_b, const int64_t *also_ids, int64_t n_also,
+                                 const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch, int k, int64_t *out_hit_ids,
+                                 double *out_hit_combined, int *n_hit, int64_t *out_scan_ids, double *out_scan_dist, int *n_scan,
+                                 int64_t *out_info);
 
 /* SELECT ... embedding <op> %s::vector AS distance ... WHERE ... ORDER BY distance
  * ASC LIMIT k   (postgres_vectorstore.py:317-332).

@@ -11,6 +11,15 @@ Per query: HIP-event times of the statistics pass, the score pass (with the host
 distances over all rows); exit status 1 on a mismatch. Prints ONE JSON line.
 
     python scripts/bench_hybrid.py [--shape a|b|ab] [--queries 50] [--rows-b 1000000]
+
+--batch: the batch call and the coalescing of concurrent calls on shape A's collection (device scorer only), 32 distinct queries
+with distinct vectors. For Q = 1, 4, 16, 32: hybrid_search_batch of Q queries against the loop of Q hybrid_search calls, the two
+alternating in one job after a warm-up, medians; per-query p50 / p99 and queries per second; stage times, |U|, the sum of the
+queries' own hit counts and the hit leg's share from out_info; GB/s of the list passes. Then 32 Python request threads calling
+hybrid_search with the coalescer on and with AK_COALESCE=0, alternating. Every batch answer is checked against the single call's.
+The JSON line also goes to profiles/hybrid_batch_bench.json.
+
+    python scripts/bench_hybrid.py --batch [--queries 20] [--rows-a 300000]
 """
 import argparse
 import json
@@ -223,14 +232,157 @@ def shape_b(args):
     return res, ok
 
 
+def batch_mode(args):
+    import threading
+    import zlib
+    from archi_amd import _lib
+    from archi_amd import vectorstore as vs
+    from archi_amd.lexical import DeviceBm25
+    from archi_amd.vectorstore import ArchiHipHybridVectorStore
+    from oracle import knn_oracle as ko
+    n, dim, per, k = args.rows_a, 64, 50, 10
+    rng = np.random.default_rng(11)
+    vec = ko.gen_rows(515, 0, 0, n, dim, True, "f32")
+    vocab = np.array([f"w{i}" for i in range(2000)])
+    common = rng.random(n) < 0.33
+    words = rng.integers(0, 2000, size=(n, 6))
+    texts = [" ".join(vocab[words[i]]) + (" detector" if common[i] else "") + (" muon" if i % 977 == 0 else "") for i in range(n)]
+
+    class Emb:
+        def embed_query(self, text):
+            return [float(x) for x in ko.gen_rows(zlib.crc32(text.encode()) & 0x7fffffff, 1, 0, 1, dim, True, "f32")[0]]
+
+    vs.reset_collections()
+    s = ArchiHipHybridVectorStore({"hip": {"dtype": "f32", "capacity": 1 << 19}}, Emb(), collection_name="bench_batch", bm25=DeviceBm25())
+    for lo in range(0, n, 20000):
+        s.add_texts_batch([(texts[a: a + per], [{"source": "web" if (a // per) % 4 else "git"} for _ in range(per)], 1 + a // per, vec[a: a + per])
+                           for a in range(lo, min(lo + 20000, n), per)])
+    # half of the queries hold the frequent word (a third of the rows match), the rest only rare ones
+    queries = [f"w{7 * i} w{7 * i + 1000}" + (" detector" if i % 2 == 0 else "") + (" muon" if i % 8 == 0 else "") for i in range(32)]
+    col = s._collection()
+    ix, bm = col.index, s._bm25
+    for q in queries[:2]:
+        s.hybrid_search(q, k=k)
+    s.hybrid_search_batch(queries, k=k)
+    flat = lambda r: [(d.page_content, sc) for d, sc in r]      # noqa: E731
+    singles = [flat(s.hybrid_search(q, k=k)) for q in queries]
+    ok = [flat(r) for r in s.hybrid_search_batch(queries, k=k)] == singles
+    n_slots, arena = ix.slots, int(ix.lex_info()["arena_bytes"]) // 8
+    res = {"rows": n, "dim": dim, "dtype": "f32", "k": k, "reps": args.queries, "batches": []}
+    for Q in (1, 4, 16, 32):
+        qs = queries[:Q]
+        for _ in range(3):
+            s.hybrid_search_batch(qs, k=k)
+            [s.hybrid_search(q, k=k) for q in qs]
+        tb, tl = [], []
+        for _ in range(args.queries):                                # the two variants alternate
+            t0 = time.perf_counter()
+            s.hybrid_search_batch(qs, k=k)
+            tb.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            [s.hybrid_search(q, k=k) for q in qs]
+            tl.append((time.perf_counter() - t0) * 1e3)
+        with s.table.lock:
+            terms = [bm.device_query(q, col.table, ix) for q in qs]
+        qv = np.asarray([Emb().embed_query(q) for q in qs], np.float32)
+        ix.profile(True)
+        infos = [ix.hybrid_search_batch(qv, terms, bm.k1, bm.b, bm.sign, 0.7, 0.3, [], k)[1] for _ in range(10)]
+        ix.profile(False)
+        st = {key: float(np.median([i[key] for i in infos])) / 1e6 for key in ("stats_ns", "score_ns", "hit_ns", "scan_ns")}
+        info = infos[0]
+        b_stats = arena * 8 + n_slots * (SLOT_BYTES_STATS + 4)
+        total = sum(st.values())
+        e = {"Q": Q, "batch_ms": pct(tb), "loop_ms": pct(tl), "speedup_p50": round(float(np.median(tl) / np.median(tb)), 2),
+             "per_query_ms_batch": {key: round(v / Q, 4) for key, v in pct(tb).items()}, "per_query_ms_loop": {key: round(v / Q, 4) for key, v in pct(tl).items()},
+             "qps_batch": round(Q / (np.median(tb) / 1e3), 1), "qps_loop": round(Q / (np.median(tl) / 1e3), 1),
+             "stats_pass_ms": round(st["stats_ns"], 4), "score_pass_ms": round(st["score_ns"], 4), "hit_leg_ms": round(st["hit_ns"], 4),
+             "scan_leg_ms": round(st["scan_ns"], 4), "hit_leg_share": round(st["hit_ns"] / total, 3) if total else None,
+             "stats_pass_gbs": round(b_stats / st["stats_ns"] / 1e6, 1) if st["stats_ns"] else None,
+             "union_rows": info["union_rows"], "own_hit_rows": info["own_hit_rows"], "pairs": info["pairs"],
+             "union_over_own": round(info["union_rows"] / info["own_hit_rows"], 3) if info["own_hit_rows"] else None,
+             "pairs_over_own": round(info["pairs"] / info["own_hit_rows"], 3) if info["own_hit_rows"] else None,
+             "passes": [info["stats_passes"], info["score_passes"], info["scans"]]}
+        res["batches"].append(e)
+
+    # 32 request threads, each its own query, calling hybrid_search in a loop
+    def threads_run(coalesce, seconds=1.0):
+        _lib.debug_set("AK_COALESCE", coalesce)
+        lat = [[] for _ in range(32)]
+        stop = threading.Event()
+
+        def run(j):
+            while not stop.is_set():
+                t0 = time.perf_counter()
+                s.hybrid_search(queries[j], k=k)
+                lat[j].append((time.perf_counter() - t0) * 1e3)
+        ts = [threading.Thread(target=run, args=(j,)) for j in range(32)]
+        t0 = time.perf_counter()
+        for t in ts:
+            t.start()
+        time.sleep(seconds)
+        stop.set()
+        for t in ts:
+            t.join()
+        wall = time.perf_counter() - t0
+        allms = np.concatenate([np.asarray(x) for x in lat])
+        return len(allms) / wall, allms
+    threads_run("1", 0.3), threads_run("0", 0.3)
+    runs = {"1": [], "0": []}
+    lats = {"1": [], "0": []}
+    for _ in range(3):
+        for c in ("1", "0"):
+            qps, ms = threads_run(c)
+            runs[c].append(qps)
+            lats[c].append(ms)
+    # how many calls shared an evaluation: the index-level call returns the group's size in info[10]
+    _lib.debug_set("AK_COALESCE", "1")
+    sizes = []
+    with s.table.lock:
+        tq = [bm.device_query(q, col.table, ix) for q in queries]
+    qv = np.asarray([Emb().embed_query(q) for q in queries], np.float32)
+    stop = threading.Event()
+
+    def probe(j):
+        while not stop.is_set():
+            sizes.append(int(ix.hybrid_search(qv[j], tq[j], bm.k1, bm.b, bm.sign, 0.7, 0.3, [], k)[4][10]))
+    ts = [threading.Thread(target=probe, args=(j,)) for j in range(32)]
+    for t in ts:
+        t.start()
+    time.sleep(0.5)
+    stop.set()
+    for t in ts:
+        t.join()
+    _lib.debug_set("AK_COALESCE", None)
+    sz = np.asarray(sizes)
+    res["threads32"] = {"coalesced_qps": round(float(np.median(runs["1"])), 1), "uncoalesced_qps": round(float(np.median(runs["0"])), 1),
+                        "coalesced": pct(np.concatenate(lats["1"])), "uncoalesced": pct(np.concatenate(lats["0"])),
+                        "speedup": round(float(np.median(runs["1"]) / np.median(runs["0"])), 2),
+                        "share_of_calls_served_in_a_group": round(float((sz > 0).mean()), 3), "median_group": int(np.median(sz[sz > 0])) if (sz > 0).any() else 0}
+    ok = ok and [flat(s.hybrid_search(q, k=k)) for q in queries] == singles
+    res["check_ok"] = bool(ok)
+    vs.reset_collections()
+    return res, ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="ab")
+    ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--rows-a", type=int, default=300_000)
     ap.add_argument("--queries", type=int, default=50)
     ap.add_argument("--rows-b", type=int, default=1_000_000)
     args = ap.parse_args()
     from archi_amd import _lib
     _lib.init(0)
+    if args.batch:
+        res, ok = batch_mode(args)
+        res = dict({"bench": "hybrid_batch", "hbm_nominal_gbs": HBM_GBS, "entry_bytes": 8}, **res)
+        line = json.dumps(res)
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "hybrid_batch_bench.json"), "w") as f:
+            f.write(line + "\n")
+        print(line)
+        sys.exit(0 if ok else 1)
     res = {"bench": "hybrid", "hbm_nominal_gbs": HBM_GBS, "entry_bytes": 8}
     ok = True
     if "a" in args.shape:
