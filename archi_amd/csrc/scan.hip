@@ -203,14 +203,20 @@ __device__ inline int compact_wave(uint64_t *buf, int m, int k, int limit, float
 // MFMA_ (phased tiles only): 32 = v_mfma_f32_32x32x16, 16 = v_mfma_f32_16x16x32 on the same LDS image, phases and output tile per
 // wave -- other fragment reads, other accumulator mapping, other filter groups (k_scan, "16x16x32"). Shape32: the same tile on the
 // 32x32x16 shape, which the pre-seeding launch always runs (its group-maxima layout feeds k_seed_kth).
-template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false, int MFMA_ = 32>
+// FILT_ (16x16x32 tiles only): arrangement of the per-tile filter. 0 = site by site (every filter group computes its bound, reads its
+// threshold, waits and branches into its slow path), 1 = the exact maxima of the whole tile first, branch-free, from thresholds and
+// row terms read once, and one branch around the sites that hold a true hit (tile_epilogue). Both append the same keys; which one
+// a tile ships on is decided like its MFMA shape (SHIP_FILT_* below).
+template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false, int FILT_ = 0, int MFMA_ = 32>
 struct ScanCfg {
     static constexpr int WM = WM_, WN = WN_, MI = MI_, NI = NI_, NSTAGE = NSTAGE_, MINW = MINW_;
     static constexpr bool PHASED = PHASED_;
     static constexpr int MFMA = MFMA_;
+    static constexpr int FILT = FILT_;
     static constexpr bool I8 = false;             // int8 operands (one byte per element, K-step 128): CfgP8 below
-    using Shape32 = ScanCfg<WM_, WN_, MI_, NI_, NSTAGE_, MINW_, PHASED_, 32>;
+    using Shape32 = ScanCfg<WM_, WN_, MI_, NI_, NSTAGE_, MINW_, PHASED_, 0, 32>;
     static_assert(MFMA_ == 32 || (MFMA_ == 16 && PHASED_), "the 16x16x32 shape exists for the phased tiles");
+    static_assert(FILT_ == 0 || (FILT_ == 1 && MFMA_ == 16), "the whole-tile filter exists for the 16x16x32 tiles");
     static constexpr int AHEAD = NSTAGE_ - 1;     // ring stages issued ahead of the compute cursor
     static constexpr int BKB = 128;               // bytes per LDS row per K-step
     static constexpr int RPP = 1024 / BKB;        // rows per 1 KiB staging piece
@@ -450,6 +456,154 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
             int ln = lane;
             asm volatile("" : "+v"(ln));
             const int r16 = ln & 15, kq = ln >> 4;
+            // bound of one filter group (site): max(0, its 8 dot products) -> U = fma(dpos, gea, geb)
+            // int8: the group maximum is taken on the integers and only the maximum is converted (|dot| <= 127^2 D < 2^24
+            // up to D = 1040 and the conversion is monotone beyond: the bound holds either way); plain integer max, which
+            // the compiler sees -- no inline-asm read of accumulators on this path
+            auto imax = [](int x, int y) { return x > y ? x : y; };
+            auto site_dpos = [&](int mi, int ni, int c) -> float {
+                const f32x16 &a = acc[mi][ni];
+                const int lo = 4 * c, hi = 8 + 4 * c;     // slices (h = 0, c) and (h = 1, c)
+                if constexpr (I8) {
+                    const i32x16 ia = __builtin_bit_cast(i32x16, a);
+                    return (float)imax(imax(imax(imax(ia[lo], ia[lo + 1]), imax(ia[lo + 2], ia[lo + 3])),
+                                            imax(imax(ia[hi], ia[hi + 1]), imax(ia[hi + 2], ia[hi + 3]))), 0);
+                } else {
+#if AK_DBG_KERNELS
+                    return fmaxf(fmaxf(fmaxf(fmaxf(a[lo], a[lo + 1]), fmaxf(a[lo + 2], a[lo + 3])),
+                                       fmaxf(fmaxf(a[hi], a[hi + 1]), fmaxf(a[hi + 2], a[hi + 3]))), 0.f);
+#else
+                    return max3z(max3f(max3f(a[lo], a[lo + 1], a[lo + 2]), max3f(a[lo + 3], a[hi], a[hi + 1]), a[hi + 2]), a[hi + 3]);
+#endif
+                }
+            };
+            // per-row terms of the 2 x 4 rows a lane holds of 32-row block mi (the same for every query column), rows past n masked
+            auto row_terms = [&](int mi, float4 (&e4)[2], float4 (&b4)[2]) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int base = (wr * MI + mi) * 32 + 16 * h + 4 * kq;   // rows base .. base+3 of the tile
+                    e4[h] = *(const float4 *)&t_ea[base];
+                    b4[h] = *(const float4 *)&t_eb[base];
+                    if (tail) {
+                        float *pe = (float *)&e4[h], *pb = (float *)&b4[h];
+#pragma unroll
+                        for (int j = 0; j < 4; j++)
+                            if (base + j >= rows_left) { pe[j] = 0.f; pb[j] = -__builtin_inff(); }
+                    }
+                }
+            };
+            // exact scores of one site: score = fma(dot, ea[row], eb[row]) of the 8 rows a lane holds for one query column; returns their maximum
+            auto site_scores = [&](int mi, int ni, int c, const float4 (&e4s)[2], const float4 (&b4s)[2], float (&sc)[8]) -> float {
+                const f32x16 &a = acc[mi][ni];
+                const i32x16 ia = __builtin_bit_cast(i32x16, a);
+                float mx = -__builtin_inff();
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const float4 e4 = e4s[h], b4 = b4s[h];
+                    const int o = 8 * h + 4 * c;
+                    const float d0 = I8 ? (float)ia[o + 0] : a[o + 0], d1 = I8 ? (float)ia[o + 1] : a[o + 1],
+                                d2 = I8 ? (float)ia[o + 2] : a[o + 2], d3 = I8 ? (float)ia[o + 3] : a[o + 3];
+                    sc[4 * h + 0] = fmaf(d0, e4.x, b4.x); sc[4 * h + 1] = fmaf(d1, e4.y, b4.y);
+                    sc[4 * h + 2] = fmaf(d2, e4.z, b4.z); sc[4 * h + 3] = fmaf(d3, e4.w, b4.w);
+                    mx = fmaxf(fmaxf(mx, sc[4 * h + 0]), fmaxf(fmaxf(sc[4 * h + 1], sc[4 * h + 2]), sc[4 * h + 3]));
+                }
+                return mx;
+            };
+            // the lanes of a site that hold a hit: one LDS atomic per lane reserves room for its hits of the group, then the appends
+            auto site_append = [&](int mi, int ni, int c, float thr, const float (&sc)[8]) {
+                if (INSTR && (flags & 64)) return;      // (ablation bit 64: exact scores, no appends)
+                const int qcol = (wc * NI + ni) * 32 + 16 * c + r16;
+                int nh = 0;
+#pragma unroll
+                for (int e = 0; e < 8; e++) nh += sc[e] >= thr ? 1 : 0;
+                int pos = atomicAdd(&s_cnt[qcol], nh);
+                if (pos + nh > s_trig[qcol]) *s_need = 1;
+                uint64_t *dstq = my_cand + (size_t)qcol * CAP;
+                const uint32_t rbase = (uint32_t)(tile_row0 + (wr * MI + mi) * 32 + 4 * kq);
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    if (sc[e] >= thr) {
+                        dstq[pos] = ((uint64_t)score_key(sc[e]) << 32) | (uint64_t)(rbase + (e & 3) + 16 * (e >> 2));
+                        pos++;
+                    }
+                }
+            };
+            if constexpr (C::FILT == 1) {
+                // Exact maxima of the whole tile first. What the site-by-site arrangement costs is not its bound but what follows it: a
+                // lane-site passes the bound about once in a hundred in the main pass, so about half of the wave's sites have SOME lane
+                // in the slow path, and the wave pays for each -- four LDS reads of row terms and their wait, the eight exact scores,
+                // and where a lane holds a true hit the atomic and the appends (measured: 1.3 k cycles per tile for all sixteen bounds,
+                // 3.7 k for the slow paths behind them). Here the per-row terms are read ONCE per tile, with the 2 * NI thresholds
+                // (s_thr changes only inside serve_compaction, behind barriers; the terms belong to this tile) -- all in flight
+                // before one wait --, the exact maximum of every site is computed branch-free, which costs what the bound cost on 16
+                // bits and eight conversions more on int8, and only the sites where a lane holds a TRUE hit are entered, behind one
+                // branch around them all. The block bounds (t_gb) are not read. A row is appended iff its score reaches the
+                // threshold in either arrangement -- the bound only ever skipped sites without one -- and scores, keys and counts
+                // are the same expressions: the same keys are appended, in another order. The accumulators are read by plain
+                // expressions only (no inline asm), so the compiler's own hazard handling covers them and mfma_settle is not needed.
+                static_assert(2 * MI * NI <= 32, "one hit bit per site");
+                // TG row blocks' terms at a time: all of the tile's, except on the 128-accumulator 16-bit tile, where the 64 registers
+                // of four blocks' terms beside the accumulators made hipcc spill two -- two blocks at a time there, read again in
+                // the slow section for a pair of blocks with a hit
+                constexpr int TG = (!I8 && MI * NI >= 8) ? 2 : MI;
+                float4 e4[TG][2], b4[TG][2];
+                float thr_s[NI][2];
+#pragma unroll
+                for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++) thr_s[ni][c] = s_thr[(wc * NI + ni) * 32 + 16 * c + r16];
+                uint32_t hits = 0;
+#pragma unroll
+                for (int g = 0; g < MI / TG; g++) {
+#pragma unroll
+                    for (int j = 0; j < TG; j++) row_terms(g * TG + j, e4[j], b4[j]);
+#pragma unroll
+                    for (int j = 0; j < TG; j++)
+#pragma unroll
+                        for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                            for (int c = 0; c < 2; c++) {
+                                float sc[8];
+                                const int mi = g * TG + j;
+                                hits |= site_scores(mi, ni, c, e4[j], b4[j], sc) >= thr_s[ni][c] ? 1u << ((mi * NI + ni) * 2 + c) : 0u;
+                            }
+                    if (MI / TG > 1) __builtin_amdgcn_sched_barrier(0);   // one group at a time: hoisting all the term loads spills
+                }
+                if (INSTR && (flags & 16)) hits = 0;
+                if (hits) {
+#pragma unroll
+                    for (int g = 0; g < MI / TG; g++) {
+                        if (MI / TG > 1) {
+                            if (!(hits & (((1u << (2 * NI * TG)) - 1u) << (g * TG * NI * 2)))) continue;
+#pragma unroll
+                            for (int j = 0; j < TG; j++) row_terms(g * TG + j, e4[j], b4[j]);
+                        }
+#pragma unroll
+                        for (int j = 0; j < TG; j++)
+#pragma unroll
+                            for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                                for (int c = 0; c < 2; c++) {
+                                    const int mi = g * TG + j;
+                                    if (hits & (1u << ((mi * NI + ni) * 2 + c))) {
+                                        if constexpr (INSTR) n_slow++;
+                                        float sc[8];
+                                        site_scores(mi, ni, c, e4[j], b4[j], sc);
+                                        site_append(mi, ni, c, thr_s[ni][c], sc);
+                                    }
+                                }
+                    }
+                }
+                return;
+            }
+            // slow path of one site whose bound reached the threshold: per-row terms, exact scores, appends where a lane holds a hit
+            auto site_slow = [&](int mi, int ni, int c, float thr) {
+                if constexpr (INSTR) n_slow++;
+                float4 e4[2], b4[2];
+                row_terms(mi, e4, b4);
+                float sc[8];
+                if (site_scores(mi, ni, c, e4, b4, sc) >= thr) site_append(mi, ni, c, thr, sc);
+            };
 #if !AK_DBG_KERNELS
             mfma_settle(acc);
 #endif
@@ -458,68 +612,11 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                 const float gea = t_gb[(wr * MI + mi) * 4 + (kq & 1)], geb = t_gb[(wr * MI + mi) * 4 + 2 + (kq & 1)];
 #pragma unroll
                 for (int ni = 0; ni < NI; ni++) {
-                    const f32x16 &a = acc[mi][ni];
 #pragma unroll
                     for (int c = 0; c < 2; c++) {
-                        const int lo = 4 * c, hi = 8 + 4 * c;     // slices (h = 0, c) and (h = 1, c)
-                        // int8: the group maximum is taken on the integers and only the maximum is converted (|dot| <= 127^2 D < 2^24
-                        // up to D = 1040 and the conversion is monotone beyond: the bound holds either way); plain integer max, which
-                        // the compiler sees -- no inline-asm read of accumulators on this path
-                        const i32x16 ia = __builtin_bit_cast(i32x16, a);
-                        auto imax = [](int x, int y) { return x > y ? x : y; };
-                        float dpos;
-                        if constexpr (I8) {
-                            dpos = (float)imax(imax(imax(imax(ia[lo], ia[lo + 1]), imax(ia[lo + 2], ia[lo + 3])),
-                                                    imax(imax(ia[hi], ia[hi + 1]), imax(ia[hi + 2], ia[hi + 3]))), 0);
-                        } else {
-#if AK_DBG_KERNELS
-                            dpos = fmaxf(fmaxf(fmaxf(fmaxf(a[lo], a[lo + 1]), fmaxf(a[lo + 2], a[lo + 3])),
-                                               fmaxf(fmaxf(a[hi], a[hi + 1]), fmaxf(a[hi + 2], a[hi + 3]))), 0.f);
-#else
-                            dpos = max3z(max3f(max3f(a[lo], a[lo + 1], a[lo + 2]), max3f(a[lo + 3], a[hi], a[hi + 1]), a[hi + 2]), a[hi + 3]);
-#endif
-                        }
-                        const float U = fmaf(dpos, gea, geb);
+                        const float U = fmaf(site_dpos(mi, ni, c), gea, geb);
                         const float thr = s_thr[(wc * NI + ni) * 32 + 16 * c + r16];
-                        if (U >= thr && !(INSTR && (flags & 16))) {
-                            if constexpr (INSTR) n_slow++;
-                            float sc[8];
-                            float mx = -__builtin_inff();
-#pragma unroll
-                            for (int h = 0; h < 2; h++) {
-                                const int base = (wr * MI + mi) * 32 + 16 * h + 4 * kq;   // rows base .. base+3 of the tile
-                                float4 e4 = *(const float4 *)&t_ea[base], b4 = *(const float4 *)&t_eb[base];
-                                if (tail) {
-                                    float *pe = (float *)&e4, *pb = (float *)&b4;
-#pragma unroll
-                                    for (int j = 0; j < 4; j++)
-                                        if (base + j >= rows_left) { pe[j] = 0.f; pb[j] = -__builtin_inff(); }
-                                }
-                                const int o = 8 * h + 4 * c;
-                                const float d0 = I8 ? (float)ia[o + 0] : a[o + 0], d1 = I8 ? (float)ia[o + 1] : a[o + 1],
-                                            d2 = I8 ? (float)ia[o + 2] : a[o + 2], d3 = I8 ? (float)ia[o + 3] : a[o + 3];
-                                sc[4 * h + 0] = fmaf(d0, e4.x, b4.x); sc[4 * h + 1] = fmaf(d1, e4.y, b4.y);
-                                sc[4 * h + 2] = fmaf(d2, e4.z, b4.z); sc[4 * h + 3] = fmaf(d3, e4.w, b4.w);
-                                mx = fmaxf(fmaxf(mx, sc[4 * h + 0]), fmaxf(fmaxf(sc[4 * h + 1], sc[4 * h + 2]), sc[4 * h + 3]));
-                            }
-                            if (mx >= thr) {
-                                const int qcol = (wc * NI + ni) * 32 + 16 * c + r16;
-                                int nh = 0;
-#pragma unroll
-                                for (int e = 0; e < 8; e++) nh += sc[e] >= thr ? 1 : 0;
-                                int pos = atomicAdd(&s_cnt[qcol], nh);       // one LDS atomic per lane reserves room for its hits of the group
-                                if (pos + nh > s_trig[qcol]) *s_need = 1;
-                                uint64_t *dstq = my_cand + (size_t)qcol * CAP;
-                                const uint32_t rbase = (uint32_t)(tile_row0 + (wr * MI + mi) * 32 + 4 * kq);
-#pragma unroll
-                                for (int e = 0; e < 8; e++) {
-                                    if (sc[e] >= thr) {
-                                        dstq[pos] = ((uint64_t)score_key(sc[e]) << 32) | (uint64_t)(rbase + (e & 3) + 16 * (e >> 2));
-                                        pos++;
-                                    }
-                                }
-                            }
-                        }
+                        if (U >= thr && !(INSTR && (flags & 16))) site_slow(mi, ni, c, thr);
                     }
                 }
             }
@@ -625,6 +722,13 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
         //        issued since in flight; every wave passes a barrier after that wait and before ANY wave's LOAD(p+1).
         // The halves stay one barrier apart across tiles (the filter of one runs under the other's MFMAs); only a compaction
         // -- rare, workgroup-uniform -- re-aligns them.
+        // What that boundary costs (10M x 768, Q = 1024, int8 tile, instrumented build, per wave and tile): the K-loop 20.3 k cycles, the
+        // filter 5.9 k, of which 1.3 k are the sixteen bounds and the rest the slow paths behind them -- a lane-site passes its bound
+        // once in a hundred, so half of the wave's sites are entered by SOME lane. The next barrier after a tile's last MFMA phase
+        // comes when the younger half has filtered too, i.e. one phase + one filter later: the filter is exposed on both halves
+        // whatever runs under its first 512 cycles. The whole-tile arrangement of the filter (ScanCfg::FILT = 1, tile_epilogue)
+        // shortens it instead: 4.2 k cycles. It neither defers a part of the filter into a later LOAD section nor moves the
+        // s_need sample: the sampling argument in the tile loop below stands for both arrangements.
         // 16x16x32 (C::MFMA = 16; the MFMA shape as a lever of its own in a loop whose clock the chip holds down): the same buffers, phases, barriers and 16 fragment reads per phase X (8 in Y), but a fragment is 16 rows x K32
         // (lane: row l & 15, chunk 4s + (l >> 4) of K32 sub-step s) and a phase issues twice as many MFMAs of half the length -- the
         // same 512 pipe cycles. The accumulators stay f32x16 per 32 x 32 block, each MFMA works on a four-float slice of one (slice
@@ -1610,11 +1714,16 @@ __global__ __launch_bounds__(64) void k_finalize(const uint64_t *__restrict__ to
 // R +5.7 % at 384, Q +3.0 % at 256 queries/s). libarchi_hip_dbg.so instantiates both shapes of each and AK_SCAN_MFMA = 16 / 32
 // picks one there.
 constexpr int SHIP_P = 16, SHIP_Q = 16, SHIP_R = 16;
-template <int S> using CfgPs = ScanCfg<2, 4, 4, 2, 2, 2, true, S>;
-template <int S> using CfgQs = ScanCfg<2, 4, 4, 1, 2, 2, true, S>;
-template <int S> using CfgRs = ScanCfg<4, 2, 2, 3, 2, 2, true, S>;
-using CfgP = CfgPs<SHIP_P>;                     // 256 x 256, 8 waves (128x64 each), phased K-loop, SIMD partners one barrier apart : MFMA-bound batches
-using CfgQ = CfgQs<SHIP_Q>;                     // 256 x 128, 8 waves (128x32 each), phased K-loop (three half-tiles per K-step) : 128-query groups of MFMA-bound batches
+// Filter arrangement of the 16x16x32 tiles in the product library (ScanCfg::FILT), by the same rule (docs/EXPERIMENTS.md, "whole-tile
+// filter": the int8 tile -2.7 % of the step at Q = 1024, every run ahead; the 16-bit P and Q slightly slower, R ahead by no more
+// than the spread: they keep the site-by-site filter). libarchi_hip_dbg.so instantiates both arrangements of P, P8, Q and R and
+// AK_SCAN_FILTER = 1 (site by site) / 2 (whole tile) picks one there; the 32x32x16 shape has one filter.
+constexpr int SHIP_FILT_P = 0, SHIP_FILT_P8 = 1, SHIP_FILT_Q = 0, SHIP_FILT_R = 0;
+template <int S, int F = 0> using CfgPs = ScanCfg<2, 4, 4, 2, 2, 2, true, S == 16 ? F : 0, S>;
+template <int S, int F = 0> using CfgQs = ScanCfg<2, 4, 4, 1, 2, 2, true, S == 16 ? F : 0, S>;
+template <int S, int F = 0> using CfgRs = ScanCfg<4, 2, 2, 3, 2, 2, true, S == 16 ? F : 0, S>;
+using CfgP = CfgPs<SHIP_P, SHIP_FILT_P>;                     // 256 x 256, 8 waves (128x64 each), phased K-loop, SIMD partners one barrier apart : MFMA-bound batches
+using CfgQ = CfgQs<SHIP_Q, SHIP_FILT_Q>;                     // 256 x 128, 8 waves (128x32 each), phased K-loop (three half-tiles per K-step) : 128-query groups of MFMA-bound batches
 using CfgX = ScanCfg<2, 4, 4, 2, 2, 2>;   // the same tile with the in-step K-loop of rounds 1-2 (2-slot ring, one barrier per K-step): A/B reference
 // Measured and not kept (round 1-2; docs/EXPERIMENTS.md has the numbers): an L2 prefetch of the corpus lines three K-steps
 // ahead of the staging cursor (the prefetch instruction costs half of what a wave's staging instructions issue per K-step:
@@ -1627,8 +1736,9 @@ using CfgM = ScanCfg<4, 1, 2, 2, 3, 1>;   // 256 x 64 , 4 waves, 3-slot ring : H
 using CfgS = ScanCfg<4, 1, 2, 1, 3, 1>;   // 256 x 32 , 4 waves, 3-slot ring : HBM-bound, Q <= 32
 using CfgO = ScanCfg<2, 2, 2, 2, 2, 2>;   // 128 x 128, 4 waves, 2-slot ring, 2 blocks/CU (first version; A/B reference)
 // the 256 x 256 phased tile on int8 operands (v_mfma_i32_16x16x64_i8): a type of its own, so the names of the 16-bit kernels stand
-struct CfgP8 : CfgPs<16> { static constexpr bool I8 = true; };
-using CfgR = CfgRs<SHIP_R>;                     // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
+struct CfgP8 : CfgPs<16, SHIP_FILT_P8> { static constexpr bool I8 = true; };
+struct CfgP8f : CfgPs<16, 1 - SHIP_FILT_P8> { static constexpr bool I8 = true; };      // its other filter arrangement (dbg library only)
+using CfgR = CfgRs<SHIP_R, SHIP_FILT_R>;                     // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
 
 struct CfgInfo { int bm, bn, cap, threads, lds, blocks_per_cu; };
 template <class C> constexpr CfgInfo info_of(int bpc) { return CfgInfo{C::BM, C::BN, C::CAP, C::THREADS, C::LDS_BYTES, bpc}; }
@@ -1925,10 +2035,11 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
     // refuses it, and a value in its environment is ignored, like a forced X / O tile)
 #if AK_DBG_KERNELS
     const int mfma_forced = switches().scan_mfma.load(std::memory_order_relaxed);
-#define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)                         \
-    if (mfma_forced == 16) { SCAN(T<16>, R0, R1, NS, THR, SOFF, DBG, SP); }             \
-    else if (mfma_forced == 32) { SCAN(T<32>, R0, R1, NS, THR, SOFF, DBG, SP); }        \
-    else { SCAN(SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP); }
+    const int filt_forced = switches().scan_filter.load(std::memory_order_relaxed) - 1;      // -1 = the arrangement the tile ships on
+#define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)                                                                  \
+    if ((mfma_forced ? mfma_forced : SHIPPED::MFMA) == 32) { using C_ = T<32>; SCAN(C_, R0, R1, NS, THR, SOFF, DBG, SP); }          \
+    else if ((filt_forced < 0 ? SHIPPED::FILT : filt_forced) == 1) { using C_ = T<16, 1>; SCAN(C_, R0, R1, NS, THR, SOFF, DBG, SP); } \
+    else { using C_ = T<16, 0>; SCAN(C_, R0, R1, NS, THR, SOFF, DBG, SP); }
 #else
 #define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP) SCAN(SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)
 #endif
@@ -1944,9 +2055,16 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
         default: AK_FAIL(-1, "scan: tile configuration not in this library (X and O: libarchi_hip_dbg.so)"); \
     }
     // the int8 plan: one tile, one element type
-#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP)                                                                                     \
-    rc = launch_scan<true, CfgP8, false, SP>(ix, filter_dev, R0, R1, (const uint16_t *)qs8, nq, NS, nqg, k, kp, THR, mar8, SOFF, ns_tot, \
-                                             cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
+#define SCAN8_T(T, R0, R1, NS, THR, SOFF, DBG, SP)                                                                                \
+    rc = launch_scan<true, T, false, SP>(ix, filter_dev, R0, R1, (const uint16_t *)qs8, nq, NS, nqg, k, kp, THR, mar8, SOFF, ns_tot, \
+                                         cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
+#if AK_DBG_KERNELS
+#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP)                                                                  \
+    if (filt_forced >= 0 && filt_forced != CfgP8::FILT) { SCAN8_T(CfgP8f, R0, R1, NS, THR, SOFF, DBG, SP); }   \
+    else { SCAN8_T(CfgP8, R0, R1, NS, THR, SOFF, DBG, SP); }
+#else
+#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP) SCAN8_T(CfgP8, R0, R1, NS, THR, SOFF, DBG, SP)
+#endif
     long long *dbg0 = nullptr, *dbg1 = nullptr;
     if (want_dbg) {
         if (!ix.dbg_dev) { AK_HIP(hipMalloc((void **)&ix.dbg_dev, 2 * 65536 * 8)); }
@@ -2028,6 +2146,7 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
     if (i8) { SCAN8(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false); }
     else { SCAN_ANY(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false); }
 #undef SCAN8
+#undef SCAN8_T
 #undef SCAN_ANY
 #undef SCAN_SHAPED
 #undef SCAN

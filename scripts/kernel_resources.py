@@ -24,10 +24,11 @@ def makefile_flags():
     return re.search(r"^FLAGS\s*:=\s*(.*)$", mk, re.M).group(1).replace("$(ARCH)", arch).split()
 
 
-def kernel_resources(src, csrc=CSRC):
+def kernel_resources(src, csrc=CSRC, extra_flags=()):
     """src: a file name in `csrc` (or a path) -> {kernel: {field: value}}; every integer field of the compiler's remark, under the
-    compiler's names. Raises RuntimeError with the compiler's output when the file does not compile."""
-    r = subprocess.run([HIPCC] + makefile_flags() + ["--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
+    compiler's names. extra_flags: on top of the Makefile's, e.g. ["-DAK_DBG_KERNELS=1"] for the dbg library's instantiations.
+    Raises RuntimeError with the compiler's output when the file does not compile."""
+    r = subprocess.run([HIPCC] + makefile_flags() + list(extra_flags) + ["--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage",
                                                      os.path.join(csrc, src)], capture_output=True, text=True, cwd=csrc)
     if r.returncode:
         raise RuntimeError(f"{src}: hipcc failed\n{r.stderr[-4000:]}")
