@@ -49,6 +49,7 @@ const SwitchName g_switch_names[] = {
     {"AK_SCAN_CFG", &Switches::scan_cfg, 0, false, false, true},
     {"AK_SCAN_MFMA", &Switches::scan_mfma, 0, false, false, false},
     {"AK_SCAN_FILTER", &Switches::scan_filter, 0, false, false, false},
+    {"AK_SCAN_HITQ", &Switches::scan_hitq, 0, false, false, false},
     {"AK_SCAN_I8", &Switches::scan_i8, AK_SCAN_I8_DEFAULT, false, false, false},
     {"AK_SCAN_BLOCKS", &Switches::scan_blocks, 0, false, false, false},
     {"AK_SCAN_NO192", &Switches::scan_no192, 0, true, false, false},
@@ -112,6 +113,9 @@ int switches_set(const char *name, const char *value) {
             // ... and the filter arrangement a tile does not ship on (AK_SCAN_FILTER = 1 / 2)
             if (!DBG_KERNELS && n.field == &Switches::scan_filter && switch_value(n, value) != 0) return -1;
             if (n.field == &Switches::scan_filter && (switch_value(n, value) < 0 || switch_value(n, value) > 2)) return -1;
+            // ... and the passes of the int8 tile on the queued filter (AK_SCAN_HITQ = 1 .. 4)
+            if (!DBG_KERNELS && n.field == &Switches::scan_hitq && switch_value(n, value) != 0) return -1;
+            if (n.field == &Switches::scan_hitq && (switch_value(n, value) < 0 || switch_value(n, value) > 4)) return -1;
             (sw.*(n.field)).store(switch_value(n, value), std::memory_order_relaxed);
             return 0;
         }

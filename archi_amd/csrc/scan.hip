@@ -207,16 +207,19 @@ __device__ inline int compact_wave(uint64_t *buf, int m, int k, int limit, float
 // threshold, waits and branches into its slow path), 1 = the exact maxima of the whole tile first, branch-free, from thresholds and
 // row terms read once, and one branch around the sites that hold a true hit (tile_epilogue). Both append the same keys; which one
 // a tile ships on is decided like its MFMA shape (SHIP_FILT_* below).
+// 2 (the int8 tile only) = queued: the sixteen bounds first, branch-free; the lane-sites that pass are gathered, site by site behind a
+// ballot, into the wave's own LDS queue and scored once per tile, one lane per entry (tile_epilogue, "queued"). Same keys again.
 template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false, int FILT_ = 0, int MFMA_ = 32>
 struct ScanCfg {
     static constexpr int WM = WM_, WN = WN_, MI = MI_, NI = NI_, NSTAGE = NSTAGE_, MINW = MINW_;
     static constexpr bool PHASED = PHASED_;
     static constexpr int MFMA = MFMA_;
     static constexpr int FILT = FILT_;
+    static constexpr int FILT_SEED = FILT_;       // the seeding pass's arrangement: the tile's, unless a tile type says otherwise (CfgP8 below)
     static constexpr bool I8 = false;             // int8 operands (one byte per element, K-step 128): CfgP8 below
     using Shape32 = ScanCfg<WM_, WN_, MI_, NI_, NSTAGE_, MINW_, PHASED_, 0, 32>;
     static_assert(MFMA_ == 32 || (MFMA_ == 16 && PHASED_), "the 16x16x32 shape exists for the phased tiles");
-    static_assert(FILT_ == 0 || (FILT_ == 1 && MFMA_ == 16), "the whole-tile filter exists for the 16x16x32 tiles");
+    static_assert(FILT_ == 0 || ((FILT_ == 1 || FILT_ == 2) && MFMA_ == 16), "the whole-tile and queued filters exist for the 16x16x32 tiles");
     static constexpr int AHEAD = NSTAGE_ - 1;     // ring stages issued ahead of the compute cursor
     static constexpr int BKB = 128;               // bytes per LDS row per K-step
     static constexpr int RPP = 1024 / BKB;        // rows per 1 KiB staging piece
@@ -231,13 +234,18 @@ struct ScanCfg {
     static constexpr int B_PW = BN / RPP / NW;
     static constexpr int LOADS = A_PW + B_PW;     // glds per wave per stage
     static constexpr int CAP = BM >= 256 ? 1024 : 512;   // append-buffer entries per (block, query)
-    static constexpr int LDS_BYTES = NSTAGE * (A_BYTES + B_BYTES) + (4 * BM + 4 * BN + 4 + 128) * 4;
+    // the queued filter's per-wave queues, behind the common layout: [wave][9 words][64 slots] -- eight raw dot products and the
+    // entry's (site, lane); slot-minor, so the pushes of a site's passing lanes (consecutive slots) and the drain (lane i reads slot
+    // i) touch 64 distinct banks per word
+    static constexpr int HQ_WORDS = 9, HQ_SLOTS = 64;
+    static constexpr int HQ_BYTES = FILT_ == 2 ? WM_ * WN_ * HQ_WORDS * HQ_SLOTS * 4 : 0;
+    static constexpr int LDS_BYTES = NSTAGE * (A_BYTES + B_BYTES) + (4 * BM + 4 * BN + 4 + 128) * 4 + HQ_BYTES;
     // the pre-seeding (SEED) instantiation of the 128-accumulator phased tile keeps its running group maxima -- MI * NI floats per
     // lane, live across every tile -- in LDS behind the common layout instead of in registers: those eight registers on top of a
     // full 256 made hipcc spill 62 (round-5 review); one read-modify-write per (tile, group) of a launch that runs ~50 us
     static constexpr bool SEED_GM_LDS = PHASED_ && MI_ * NI_ >= 8;
-    static constexpr int SEED_LDS_BYTES = LDS_BYTES + (SEED_GM_LDS ? NW * MI_ * NI_ * 64 * 4 : 0);
-    static_assert(SEED_LDS_BYTES <= 160 * 1024, "LDS budget");
+    static constexpr int SEED_LDS_BYTES = LDS_BYTES - HQ_BYTES + (SEED_GM_LDS ? NW * MI_ * NI_ * 64 * 4 : 0);    // (no queue in that launch)
+    static_assert(SEED_LDS_BYTES <= 160 * 1024 && LDS_BYTES <= 160 * 1024, "LDS budget");
     static_assert((BM / RPP) % NW == 0 && (BN / RPP) % NW == 0, "pieces must divide over the waves");
     static_assert(NSTAGE >= 2 && NSTAGE <= 4, "ring depth");
     static_assert(BM / 64 <= NW, "ea/eb staging uses one wave per 64 rows");
@@ -272,6 +280,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
     constexpr bool I8 = C::I8;               // int8 shadow rows and int8 queries: K-step 128 elements, int32 accumulator bits
     constexpr int EB = I8 ? 1 : 2;           // bytes per element of rows / qs
     static_assert(!I8 || (C::MFMA == 16 && C::PHASED && !SEED), "the int8 scan is the phased tile on the 16x16 shape; its pre-seeding stays on 16 bits");
+    constexpr int FILT_K = SEEDPASS ? C::FILT_SEED : C::FILT;      // filter arrangement of this launch
     constexpr bool M16 = C::MFMA == 16;      // 16x16x32 MFMAs: a lane owns query columns 16c + (lane & 15) and rows 16h + 4 * (lane >> 4) + j
     static_assert(!(M16 && SEED), "the pre-seeding launch runs the 32x32x16 shape (C::Shape32)");
     const int flags = INSTR ? flags_arg : 0;
@@ -287,7 +296,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
     int *s_trig = (int *)(s_mar + BN);
     int *s_need = s_trig + BN;
     float *s_gb = (float *)(s_need + 4);      // [2][64]: [BM/32][4] per-32-row-block bounds of a tile
-    long long t_loop = 0, t_epi = 0, t_sync = 0, t_comp = 0, t_fin = 0, t_mark = 0, n_slow = 0, n_comp = 0;
+    long long t_loop = 0, t_epi = 0, t_sync = 0, t_comp = 0, t_fin = 0, t_mark = 0, n_slow = 0, n_comp = 0, n_drain = 0;
     auto TICK = [&]() -> long long {
         if constexpr (INSTR) return dbg ? (long long)__builtin_readcyclecounter() : 0;
         else return 0;
@@ -528,7 +537,132 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                     }
                 }
             };
-            if constexpr (C::FILT == 1) {
+            if constexpr (FILT_K == 2) {
+                // Queued. What the other two arrangements pay for is wave divergence: each of the sixteen sites is its own unrolled
+                // code over its own accumulator registers, and the wave runs a site's exact scores and appends in full when ONE of
+                // its 64 lanes needs them. Here the sixteen bounds come first, branch-free (16 of the whole-tile arrangement's 128
+                // conversions and fma). Then, site by site, the lanes that passed are balloted; an empty ballot skips the site on a
+                // scalar branch, otherwise each passing lane writes its eight raw dot products and its (site, lane) to slot
+                // `queue count + its rank in the ballot` of the wave's own LDS queue. The queue is drained once, after the last
+                // site -- lane i takes entry i, gathers the entry's row terms and threshold, and scores and appends as site_scores /
+                // site_append do -- or, where a site's entries would not fit in the 64 slots, before that site as well. Nothing
+                // stays queued when the tile ends: the terms' parity buffers and the two tiles of append room behind a buffer's
+                // trigger stand as they are. A row is appended iff its score reaches the threshold, every lane-site with such a row
+                // passes its bound, and s_thr only changes behind barriers: the same keys as the other arrangements, in another
+                // order. One copy of the drain's code, behind the straight-line sites in a loop that runs again only for
+                // the sites that did not fit.
+                static_assert(I8, "the queued filter exists for the int8 tile");
+                constexpr int NSITE = 2 * MI * NI, HQS = C::HQ_SLOTS;
+                int *const s_hq = (int *)(smem + C::LDS_BYTES - C::HQ_BYTES) + wave * (C::HQ_WORDS * HQS);      // [word][slot]
+                float thr_s[NI][2];
+#pragma unroll
+                for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++) thr_s[ni][c] = s_thr[(wc * NI + ni) * 32 + 16 * c + r16];
+                float gea[MI], geb[MI];
+#pragma unroll
+                for (int mi = 0; mi < MI; mi++) {
+                    gea[mi] = t_gb[(wr * MI + mi) * 4 + (kq & 1)];
+                    geb[mi] = t_gb[(wr * MI + mi) * 4 + 2 + (kq & 1)];
+                }
+                // the sixteen bounds, branch-free: a site's compare IS its ballot (an SGPR pair), and the lanes' own bits of it mask the push
+                bool pb[NSITE];
+                uint64_t bal[NSITE];
+#pragma unroll
+                for (int S = 0; S < NSITE; S++) {
+                    const int mi = S / (2 * NI), ni = (S >> 1) % NI, c = S & 1;
+                    pb[S] = fmaf(site_dpos(mi, ni, c), gea[mi], geb[mi]) >= thr_s[ni][c];
+                    bal[S] = __builtin_amdgcn_ballot_w64(pb[S]);
+                }
+                // sites still to queue, a scalar bit each. A round runs the sites of `todo` in order: the ballot's test
+                // and the push, until a site's entries do not fit; then the drain, and the sites left over
+                // make the next round. Straight-line code with forward scalar branches, one copy of the drain behind it.
+                uint32_t todo = (INSTR && (flags & 16)) ? 0u : (1u << NSITE) - 1u;
+                int qn = 0;                                  // entries queued: wave-uniform
+                auto site = [&](auto S_, uint32_t &open) {
+                    constexpr int S = decltype(S_)::value, mi = S / (2 * NI), ni = (S >> 1) % NI, c = S & 1;
+                    if (!(open & (1u << S))) return;
+                    const bool p = pb[S];
+                    const uint64_t b = bal[S];
+                    // (scalar copies: the compiler's uniformity analysis loses the ballot through the loop and would run the
+                    // sites on vector compares and exec masks)
+                    const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)b), bhi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+                    if ((blo | bhi) != 0) {
+                        const int cnt = __builtin_popcount(blo) + __builtin_popcount(bhi);
+                        if (qn + cnt > HQS) { open = 0; return; }       // this site and those behind it: after the drain
+                        if (p) {
+                            const int slot = qn + (int)__builtin_amdgcn_mbcnt_hi(bhi, __builtin_amdgcn_mbcnt_lo(blo, 0u));
+                            const i32x16 ia = __builtin_bit_cast(i32x16, acc[mi][ni]);
+#pragma unroll
+                            for (int e = 0; e < 8; e++) s_hq[e * HQS + slot] = ia[8 * (e >> 2) + 4 * c + (e & 3)];
+                            s_hq[8 * HQS + slot] = S * 64 + ln;
+                        }
+                        qn = __builtin_amdgcn_readfirstlane(qn + cnt);
+                        if constexpr (INSTR) n_slow += cnt;
+                    }
+                    todo &= ~(1u << S);
+                };
+                auto drain = [&]() {
+                    if constexpr (INSTR) n_drain++;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // the pushes of other lanes, this wave's
+                    __builtin_amdgcn_wave_barrier();
+                    if (ln < qn) {
+                        const int id = s_hq[8 * HQS + ln];
+                        const int site = id >> 6, el = id & 63;
+                        const int rb = (wr * MI + site / (2 * NI)) * 32 + 4 * (el >> 4);        // tile-relative row of element 0
+                        const int qcol = (wc * NI + (site >> 1) % NI) * 32 + 16 * (site & 1) + (el & 15);
+                        const float thr = s_thr[qcol];
+                        float sc[8];
+                        float mx = -__builtin_inff();
+#pragma unroll
+                        for (int h = 0; h < 2; h++) {
+                            const int base = rb + 16 * h;
+                            float4 e4 = *(const float4 *)&t_ea[base], b4 = *(const float4 *)&t_eb[base];
+                            if (tail) {
+                                float *pe = (float *)&e4, *pb = (float *)&b4;
+#pragma unroll
+                                for (int j = 0; j < 4; j++)
+                                    if (base + j >= rows_left) { pe[j] = 0.f; pb[j] = -__builtin_inff(); }
+                            }
+                            sc[4 * h + 0] = fmaf((float)s_hq[(4 * h + 0) * HQS + ln], e4.x, b4.x);
+                            sc[4 * h + 1] = fmaf((float)s_hq[(4 * h + 1) * HQS + ln], e4.y, b4.y);
+                            sc[4 * h + 2] = fmaf((float)s_hq[(4 * h + 2) * HQS + ln], e4.z, b4.z);
+                            sc[4 * h + 3] = fmaf((float)s_hq[(4 * h + 3) * HQS + ln], e4.w, b4.w);
+                            mx = fmaxf(fmaxf(mx, sc[4 * h + 0]), fmaxf(fmaxf(sc[4 * h + 1], sc[4 * h + 2]), sc[4 * h + 3]));
+                        }
+                        if (mx >= thr && !(INSTR && (flags & 64))) {       // (ablation bit 64: exact scores, no appends)
+                            int nh = 0;
+#pragma unroll
+                            for (int e = 0; e < 8; e++) nh += sc[e] >= thr ? 1 : 0;
+                            int pos = atomicAdd(&s_cnt[qcol], nh);
+                            if (pos + nh > s_trig[qcol]) *s_need = 1;
+                            uint64_t *dstq = my_cand + (size_t)qcol * CAP;
+                            const uint32_t rbase = (uint32_t)(tile_row0 + rb);
+#pragma unroll
+                            for (int e = 0; e < 8; e++) {
+                                if (sc[e] >= thr) {
+                                    dstq[pos] = ((uint64_t)score_key(sc[e]) << 32) | (uint64_t)(rbase + (e & 3) + 16 * (e >> 2));
+                                    pos++;
+                                }
+                            }
+                        }
+                    }
+                    __builtin_amdgcn_wave_barrier();          // the next pushes overwrite the slots read above
+                    qn = 0;
+                };
+                static_assert(NSITE == 16, "the sites below");
+                while (todo) {
+                    todo = __builtin_amdgcn_readfirstlane(todo);
+                    uint32_t open = todo;
+#define AK_HQ_SITE(S) site(std::integral_constant<int, S>{}, open);
+                    AK_HQ_SITE(0) AK_HQ_SITE(1) AK_HQ_SITE(2) AK_HQ_SITE(3) AK_HQ_SITE(4) AK_HQ_SITE(5) AK_HQ_SITE(6) AK_HQ_SITE(7)
+                    AK_HQ_SITE(8) AK_HQ_SITE(9) AK_HQ_SITE(10) AK_HQ_SITE(11) AK_HQ_SITE(12) AK_HQ_SITE(13) AK_HQ_SITE(14) AK_HQ_SITE(15)
+#undef AK_HQ_SITE
+                    if (qn) drain();
+                }
+                return;
+            }
+            if constexpr (FILT_K == 1) {
                 // Exact maxima of the whole tile first. What the site-by-site arrangement costs is not its bound but what follows it: a
                 // lane-site passes the bound about once in a hundred in the main pass, so about half of the wave's sites have SOME lane
                 // in the slow path, and the wave pays for each -- four LDS reads of row terms and their wait, the eight exact scores,
@@ -729,6 +863,12 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
         // whatever runs under its first 512 cycles. The whole-tile arrangement of the filter (ScanCfg::FILT = 1, tile_epilogue)
         // shortens it instead: 4.2 k cycles. It neither defers a part of the filter into a later LOAD section nor moves the
         // s_need sample: the sampling argument in the tile loop below stands for both arrangements.
+        // The queued arrangement (FILT = 2, int8 tile) shortens what divergence is left: lane-sites that pass their bound go to a per-wave
+        // LDS queue and are scored once per tile, one lane per entry. Beside the partner's MFMA stream a filter's cycles follow its
+        // INSTRUCTION COUNT (8 to 10 cycles each, vector or scalar), so it pays where the whole-tile filter enters most sites: the seeding
+        // pass, 14.5 k -> 9.8 k cycles and 892 -> 763 us per launch; in the main pass (ten entries per wave and tile) its ~450
+        // instructions buy nothing over the whole-tile filter's ~420 and it does not ship there (docs/EXPERIMENTS.md, "hit queue").
+        // It too ends inside tile_epilogue with an empty queue: nothing of a tile's filter crosses into the next tile.
         // 16x16x32 (C::MFMA = 16; the MFMA shape as a lever of its own in a loop whose clock the chip holds down): the same buffers, phases, barriers and 16 fragment reads per phase X (8 in Y), but a fragment is 16 rows x K32
         // (lane: row l & 15, chunk 4s + (l >> 4) of K32 sub-step s) and a phase issues twice as many MFMAs of half the length -- the
         // same 512 pipe cycles. The accumulators stay f32x16 per 32 x 32 block, each MFMA works on a four-float slice of one (slice
@@ -1203,7 +1343,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
             t_fin = TICK() - t_mark;
             if (lane == 0) {
                 long long *d = dbg + ((size_t)blockIdx.x * NW + wave) * 8;
-                d[0] = t_loop; d[1] = t_epi; d[2] = t_sync; d[3] = t_comp; d[4] = t_fin; d[5] = n_slow; d[6] = n_comp; d[7] = ntiles;
+                d[0] = t_loop; d[1] = t_epi; d[2] = t_sync; d[3] = t_comp; d[4] = t_fin; d[5] = n_slow | (n_drain << 32); d[6] = n_comp; d[7] = ntiles;
             }
         }
     }
@@ -1716,7 +1856,8 @@ __global__ __launch_bounds__(64) void k_finalize(const uint64_t *__restrict__ to
 constexpr int SHIP_P = 16, SHIP_Q = 16, SHIP_R = 16;
 // Filter arrangement of the 16x16x32 tiles in the product library (ScanCfg::FILT), by the same rule (docs/EXPERIMENTS.md, "whole-tile
 // filter": the int8 tile -2.7 % of the step at Q = 1024, every run ahead; the 16-bit P and Q slightly slower, R ahead by no more
-// than the spread: they keep the site-by-site filter). libarchi_hip_dbg.so instantiates both arrangements of P, P8, Q and R and
+// than the spread: they keep the site-by-site filter; "hit queue": the int8 tile's main pass on the queue: ahead by less than the
+// spread, stays on the whole tile). libarchi_hip_dbg.so instantiates both arrangements of P, P8, Q and R and
 // AK_SCAN_FILTER = 1 (site by site) / 2 (whole tile) picks one there; the 32x32x16 shape has one filter.
 constexpr int SHIP_FILT_P = 0, SHIP_FILT_P8 = 1, SHIP_FILT_Q = 0, SHIP_FILT_R = 0;
 template <int S, int F = 0> using CfgPs = ScanCfg<2, 4, 4, 2, 2, 2, true, S == 16 ? F : 0, S>;
@@ -1736,8 +1877,28 @@ using CfgM = ScanCfg<4, 1, 2, 2, 3, 1>;   // 256 x 64 , 4 waves, 3-slot ring : H
 using CfgS = ScanCfg<4, 1, 2, 1, 3, 1>;   // 256 x 32 , 4 waves, 3-slot ring : HBM-bound, Q <= 32
 using CfgO = ScanCfg<2, 2, 2, 2, 2, 2>;   // 128 x 128, 4 waves, 2-slot ring, 2 blocks/CU (first version; A/B reference)
 // the 256 x 256 phased tile on int8 operands (v_mfma_i32_16x16x64_i8): a type of its own, so the names of the 16-bit kernels stand
-struct CfgP8 : CfgPs<16, SHIP_FILT_P8> { static constexpr bool I8 = true; };
-struct CfgP8f : CfgPs<16, 1 - SHIP_FILT_P8> { static constexpr bool I8 = true; };      // its other filter arrangement (dbg library only)
+// The int8 tile has a third arrangement, the queued one (ScanCfg::FILT = 2), and its two passes choose on their own (FILT the main
+// pass, FILT_SEED the seeding pass: k_scan takes the one its SEEDPASS tag names). CfgP8 is what ships: the main pass on the whole tile,
+// the seeding pass on the queue (docs/EXPERIMENTS.md, "hit queue": the seeding pass -14.5 % per launch and -0.157 ms of the step at
+// Q = 1024 on the queue, every run ahead of every parent run; the main pass ahead by less than the spread). CfgP8f and CfgP8g hold the
+// other arrangements of either pass, in the dbg library -- AK_SCAN_FILTER as above, AK_SCAN_HITQ = 1 (seeding pass) / 2 (main pass) /
+// 3 (both) / 4 (neither) puts a pass on the queue or takes it off. A type with a queued pass carries the queues' LDS.
+constexpr int SHIP_FILT_P8_SEED = 2;
+template <int FM, int FS> struct CfgP8T : CfgPs<16, FM> {
+    using Base = CfgPs<16, FM>;
+    static constexpr bool I8 = true;
+    static constexpr int FILT_SEED = FS;
+    static constexpr int HQ_BYTES = (FM == 2 || FS == 2) ? Base::NW * Base::HQ_WORDS * Base::HQ_SLOTS * 4 : 0;
+    static constexpr int LDS_BYTES = Base::LDS_BYTES - Base::HQ_BYTES + HQ_BYTES;
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+};
+struct CfgP8 : CfgP8T<SHIP_FILT_P8, SHIP_FILT_P8_SEED> {};
+struct CfgP8f : CfgP8T<0, 0> {};      // site by site, both passes
+struct CfgP8g : CfgP8T<2, 1> {};      // main pass queued, seeding pass whole tile
+static_assert(SHIP_FILT_P8 == 1 && SHIP_FILT_P8_SEED == 2, "CfgP8f / CfgP8g hold the arrangements CfgP8 does not");
+// the type that runs arrangement F in the seeding (SEEDP) or the main pass
+template <bool SEEDP, int F> using CfgP8of =
+    std::conditional_t<(SEEDP ? CfgP8::FILT_SEED : CfgP8::FILT) == F, CfgP8, std::conditional_t<(SEEDP ? CfgP8f::FILT_SEED : CfgP8f::FILT) == F, CfgP8f, CfgP8g>>;
 using CfgR = CfgRs<SHIP_R, SHIP_FILT_R>;                     // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
 
 struct CfgInfo { int bm, bn, cap, threads, lds, blocks_per_cu; };
@@ -2059,9 +2220,21 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
     rc = launch_scan<true, T, false, SP>(ix, filter_dev, R0, R1, (const uint16_t *)qs8, nq, NS, nqg, k, kp, THR, mar8, SOFF, ns_tot, \
                                          cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
 #if AK_DBG_KERNELS
-#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP)                                                                  \
-    if (filt_forced >= 0 && filt_forced != CfgP8::FILT) { SCAN8_T(CfgP8f, R0, R1, NS, THR, SOFF, DBG, SP); }   \
-    else { SCAN8_T(CfgP8, R0, R1, NS, THR, SOFF, DBG, SP); }
+    // arrangement of a pass: AK_SCAN_HITQ says which passes run queued, the others -- and all of them without it -- what
+    // AK_SCAN_FILTER says or, unforced, what they ship on (whole tile where that is the queue and the queue is switched off)
+    const int hitq_forced = switches().scan_hitq.load(std::memory_order_relaxed);
+    auto p8_filt = [&](bool seedpass) -> int {
+        const int shipped = seedpass ? SHIP_FILT_P8_SEED : SHIP_FILT_P8;
+        if (hitq_forced && hitq_forced != 4 && (hitq_forced & (seedpass ? 1 : 2))) return 2;
+        if (filt_forced >= 0) return filt_forced;
+        return hitq_forced && shipped == 2 ? 1 : shipped;
+    };
+#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP)                                                         \
+    switch (p8_filt(SP)) {                                                                            \
+        case 0: { using C_ = CfgP8of<SP, 0>; SCAN8_T(C_, R0, R1, NS, THR, SOFF, DBG, SP); } break;    \
+        case 1: { using C_ = CfgP8of<SP, 1>; SCAN8_T(C_, R0, R1, NS, THR, SOFF, DBG, SP); } break;    \
+        default: { using C_ = CfgP8of<SP, 2>; SCAN8_T(C_, R0, R1, NS, THR, SOFF, DBG, SP); } break;   \
+    }
 #else
 #define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP) SCAN8_T(CfgP8, R0, R1, NS, THR, SOFF, DBG, SP)
 #endif

@@ -20,6 +20,8 @@ struct Switches {
                                          // ships for the tile. Both shapes exist in the dbg library only: the product library refuses 16 / 32
     std::atomic<int> scan_filter{0};     // AK_SCAN_FILTER: filter arrangement of the 16x16x32 tiles P / P8 / Q / R, 1 = site by site, 2 = whole-tile maxima
                                          // first; 0 = the one the tile ships on. Both exist in the dbg library only: the product library refuses 1 / 2
+    std::atomic<int> scan_hitq{0};       // AK_SCAN_HITQ: passes of the int8 tile P8 that run the queued filter, 1 = seeding pass, 2 = main pass, 3 = both,
+                                         // 4 = neither; 0 = as shipped. The dbg library only: the product library refuses 1 .. 4
     std::atomic<int> scan_i8{AK_SCAN_I8_DEFAULT};   // AK_SCAN_I8: the int8 scan plan. 0 = off, 1 = where the plan finds it eligible, 2 = wherever the shape allows (tests)
     std::atomic<int> scan_blocks{0};     // AK_SCAN_BLOCKS: workgroups per launch (0 = resident count)
     std::atomic<int> scan_r192_pm{850};  // AK_SCAN_R192: relative cost of a 192-query pass, per mille

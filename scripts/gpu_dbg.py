@@ -20,14 +20,23 @@ for li, lname in enumerate(("seed", "main")):
     a = dbg[li]; a = a[a[:, 7] > 0]
     if not len(a): continue
     print(f"{lname}: waves={len(a)} tiles/wave={a[:,7].mean():.1f}")
-    tot = a[:, :5].sum(1).mean()
+    # slot 5: slow-path entries of lane 0 (site-by-site and whole-tile filter); the queued filter of the int8 tile (AK_SCAN_HITQ, or
+    # the pass ships on it) puts the wave's queued entries there and its drains in the high half
+    drains = (a[:, 5] >> 32).astype(np.float64)
+    a[:, 5] &= 0xffffffff
     stage = (a[:, 2] & 0xffffffff).astype(np.float64); wait = (a[:, 2] >> 32).astype(np.float64)
-    a = a.astype(np.float64); a[:, 2] = 0
+    a = a.astype(np.float64); a[:, 2] = 0             # (slot 2 packs the two parts of the k-loop printed below: not a phase of its own)
+    tot = a[:, :5].sum(1).mean()
     for j in range(5):
         print(f"   {names[j]:8s} mean {a[:, j].mean()/1e3:9.1f} kcyc  ({100*a[:, j].mean()/tot:5.1f}%)  max {a[:, j].max()/1e3:9.1f}")
     print(f"   k-loop split: staging issue {stage.mean()/1e3:9.1f} kcyc, wait+barrier {wait.mean()/1e3:9.1f} kcyc, "
           f"fragments+MFMA {(a[:,0]-stage-wait).mean()/1e3:9.1f} kcyc; per k-step: "
           f"{stage.mean()/(a[:,7].mean()*int(sys.argv[2])//64):.0f} / {wait.mean()/(a[:,7].mean()*int(sys.argv[2])//64):.0f} / "
           f"{(a[:,0]-stage-wait).mean()/(a[:,7].mean()*int(sys.argv[2])//64):.0f} cycles")
-    print(f"   slow-path entries/wave {a[:,5].mean():.1f} (of {a[:,7].mean()*8:.0f} groups)  compactions/wave {a[:,6].mean():.1f}   total {tot/1e3:.0f} kcyc")
+    if drains.sum() > 0:
+        print(f"   queued filter: entries/wave {a[:,5].mean():.1f} = {a[:,5].mean()/a[:,7].mean():.1f} per tile (of 1024 lane-sites), "
+              f"drains/wave {drains.mean():.1f} = {drains.mean()/a[:,7].mean():.2f} per tile, max {(drains/a[:,7]).max():.2f}  "
+              f"compactions/wave {a[:,6].mean():.1f}   total {tot/1e3:.0f} kcyc")
+    else:
+        print(f"   slow-path entries/wave {a[:,5].mean():.1f} (of {a[:,7].mean()*8:.0f} groups)  compactions/wave {a[:,6].mean():.1f}   total {tot/1e3:.0f} kcyc")
 ix.close()
