@@ -378,7 +378,7 @@ def load() -> ctypes.CDLL:
             # measurement switches select the library that carries the instrumented kernel instantiations (`make dbg`)
             path = LIB_PATH
             if os.environ.get("ARCHI_HIP_DBG") or any(os.environ.get(v) for v in DBG_SWITCHES) or \
-                    os.environ.get("AK_SCAN_CFG", "")[:1] in ("X", "O") or os.environ.get("AK_ATTN_STREAM", "") in ("3", "4"):
+                    os.environ.get("AK_ATTN_STREAM", "") in ("3", "4"):
                 dbg = os.path.join(_HERE, "lib", "libarchi_hip_dbg.so")
                 if not os.path.exists(dbg):
                     raise HipBackendError(f"{dbg} not found: the instrumented kernels are built by `make -C archi_amd/csrc dbg`")

@@ -23,6 +23,7 @@
 #include "coalesce.h"      // request coalescing of ak_index_search: host-only, sanitizer-tested on its own
 #include "common.h"
 #include "index_book.h"    // id <-> slot map, tombstones, growth plan, layout epoch: host-only, sanitizer-tested on its own
+#include "scan_plan.h"     // QPrep, FastPlan and the scan's plan and workspace layout: host-only, sanitizer-tested on its own
 
 namespace ak {
 
@@ -170,9 +171,6 @@ int lex_hybrid_single(Index &ix, const HybridReq &r);
 void lex_hybrid_group(Index &ix, std::vector<HybridReq *> &g);
 
 // ---- fast path (scan.hip) ----------------------------------------------------
-// per-query certificate terms: s~_units = a * s~' + b where s~' is the scan's score; eps in score units
-struct QPrep { double eps, a, b; };
-
 // Fused tail of the fast path (exact.hip), one workgroup per query: the dense candidate list the scans appended to
 // (list [nq][lcap], cnt [nq]) -> drop candidates below the main-pass starting threshold thr0 -> best kp = 64 by approximate
 // score -> exact re-rank in the reference arithmetic (rows staged through LDS) -> top-k by (distance, id) + certificate.
@@ -180,22 +178,7 @@ struct QPrep { double eps, a, b; };
 int fused_tail(Index &ix, const float *queries_dev, const float *nb_dev, int nq, int k, const uint64_t *list, int64_t lcap,
                const int *cnt, const unsigned int *thr_max, const float *thr0, const QPrep *prep, int64_t *out_ids_dev,
                double *out_dist_dev, int *out_cnt_dev, int *cert_dev, int64_t *stats_dev, hipStream_t st);
-constexpr int TAIL_KP = 64, TAIL_MAX_DIM = 4096;
 
-struct FastPlan {
-    int cfg;        // tile configuration (scan.hip)
-    int kprime;     // candidates kept per (slice, query) and re-ranked per query
-    int qtile;      // queries per block
-    int nslices;    // corpus slices (blocks along the corpus) of the main pass
-    int ns_seed;    // slices of the seeding pass (0 = single pass)
-    int64_t seed_rows;  // rows [0, seed_rows) are scanned first to seed the thresholds
-    int64_t pre_tiles;  // pre-seeding sample: pre_tiles tiles, every pre_stride-th tile of the corpus (0 = none)
-    int pre_slices;     // workgroups along the sample
-    int pre_stride;
-    int nqg;        // query groups
-    int i8;         // 1 = the main and seeding pass scan the int8 shadow (tile P on v_mfma_i32_16x16x64_i8, k' = 512 dense tail)
-    size_t bytes;   // workspace bytes
-};
 // int8 shadow (index.hip): make it cover rows [0, ix.n) of the current layout; synchronises `st` when it had to build
 // AK_SHADOW8_NOMEM: the device has no room for it (nothing is left allocated; the caller runs the 16-bit plan)
 constexpr int AK_SHADOW8_NOMEM = -1008;

@@ -104,9 +104,9 @@ int switches_set(const char *name, const char *value) {
     for (const SwitchName &n : g_switch_names)
         if (!strcmp(name, n.name)) {
             if (n.wrong_results && !DBG_KERNELS) return -1;
-            // the A/B reference tiles X and O are compiled into the dbg library only: refuse them here rather than accept the
+            // the A/B reference tiles X and O are retired (no library carries them): refuse their letters rather than accept the
             // switch and run the plan's own tile under a probe that believes it forced another (round-5 advisor finding)
-            if (!DBG_KERNELS && n.is_char && value && (*value == 'X' || *value == 'O')) return -1;
+            if (n.is_char && value && (*value == 'X' || *value == 'O')) return -1;
             // ... and so is the MFMA shape a phased tile does not ship with (AK_SCAN_MFMA = 16 / 32); 0 and a reset pass
             if (!DBG_KERNELS && n.field == &Switches::scan_mfma && switch_value(n, value) != 0) return -1;
             if (n.field == &Switches::scan_mfma && switch_value(n, value) != 0 && switch_value(n, value) != 16 && switch_value(n, value) != 32) return -1;

@@ -27,8 +27,11 @@
 //   output = [nq][slots][k'] keys (score key << 32 | row slot) + each workgroup's final threshold
 // then: select top-k' per query -> re-rank k' candidates in reference arithmetic -> top-k + certificate (the k-th exact
 // score beats every non-candidate's upper bound), else the caller falls back to the exact path.
+// This file: the kernels, then the host side that launches them. Which tile runs, how a search is sliced and where its
+// buffers lie in the workspace is host-only arithmetic in scan_plan.h (tile types and table, pick_cfg, scan_plan, ScanWorkspace).
 #include <atomic>
 #include "index.h"
+#include "scan_plan.h"
 #include "switches.h"
 #include "mfma_tile.h"
 
@@ -36,8 +39,6 @@
 
 namespace ak {
 using namespace mt;
-
-constexpr int BK = 64;         // k per LDS stage (128 B per row)
 
 // Candidate entries are written by other waves of the same workgroup (plain stores, then
 // vmcnt(0) + barrier) and must not be served from a stale L1 line: non-temporal loads bypass the
@@ -195,64 +196,6 @@ __device__ inline int compact_wave(uint64_t *buf, int m, int k, int limit, float
     else if (CAP >= 512 && m <= 512) return compact_impl<8>(buf, m, k, limit, mar, lane, thr_io, cnt_out, trig_out, trig_max, final_out);
     else return compact_impl<CAP / 64>(buf, m, k, limit, mar, lane, thr_io, cnt_out, trig_out, trig_max, final_out);
 }
-
-// Tile configuration: WM x WN waves, each wave (MI*32) corpus rows x (NI*32) queries; K-step 64 (128 B per LDS row,
-// 8-row staging pieces, chunk ^= (row>>1)&7 spreads the 16 lanes of a ds_read_b128 group over all 16 bank quads).
-// PHASED_ (the 256 x 256 tile of the MFMA-bound batches): a K-step runs as two phases of 16 MFMAs and the two waves of
-// every SIMD run them one barrier apart -- see the phased K-loop in k_scan.
-// MFMA_ (phased tiles only): 32 = v_mfma_f32_32x32x16, 16 = v_mfma_f32_16x16x32 on the same LDS image, phases and output tile per
-// wave -- other fragment reads, other accumulator mapping, other filter groups (k_scan, "16x16x32"). Shape32: the same tile on the
-// 32x32x16 shape, which the pre-seeding launch always runs (its group-maxima layout feeds k_seed_kth).
-// FILT_ (16x16x32 tiles only): arrangement of the per-tile filter. 0 = site by site (every filter group computes its bound, reads its
-// threshold, waits and branches into its slow path), 1 = the exact maxima of the whole tile first, branch-free, from thresholds and
-// row terms read once, and one branch around the sites that hold a true hit (tile_epilogue). Both append the same keys; which one
-// a tile ships on is decided like its MFMA shape (SHIP_FILT_* below).
-// 2 (the int8 tile only) = queued: the sixteen bounds first, branch-free; the lane-sites that pass are gathered, site by site behind a
-// ballot, into the wave's own LDS queue and scored once per tile, one lane per entry (tile_epilogue, "queued"). Same keys again.
-template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false, int FILT_ = 0, int MFMA_ = 32>
-struct ScanCfg {
-    static constexpr int WM = WM_, WN = WN_, MI = MI_, NI = NI_, NSTAGE = NSTAGE_, MINW = MINW_;
-    static constexpr bool PHASED = PHASED_;
-    static constexpr int MFMA = MFMA_;
-    static constexpr int FILT = FILT_;
-    static constexpr int FILT_SEED = FILT_;       // the seeding pass's arrangement: the tile's, unless a tile type says otherwise (CfgP8 below)
-    static constexpr bool I8 = false;             // int8 operands (one byte per element, K-step 128): CfgP8 below
-    using Shape32 = ScanCfg<WM_, WN_, MI_, NI_, NSTAGE_, MINW_, PHASED_, 0, 32>;
-    static_assert(MFMA_ == 32 || (MFMA_ == 16 && PHASED_), "the 16x16x32 shape exists for the phased tiles");
-    static_assert(FILT_ == 0 || ((FILT_ == 1 || FILT_ == 2) && MFMA_ == 16), "the whole-tile and queued filters exist for the 16x16x32 tiles");
-    static constexpr int AHEAD = NSTAGE_ - 1;     // ring stages issued ahead of the compute cursor
-    static constexpr int BKB = 128;               // bytes per LDS row per K-step
-    static constexpr int RPP = 1024 / BKB;        // rows per 1 KiB staging piece
-    static constexpr int CPR = BKB / 16;          // 16-byte chunks per LDS row
-    static constexpr int NSUB = BKB / 32;         // k16 MFMA sub-steps per K-step
-    static constexpr int NW = WM * WN;
-    static constexpr int THREADS = NW * 64;
-    static constexpr int BM = WM * MI * 32;       // corpus rows per tile
-    static constexpr int BN = WN * NI * 32;       // queries per block
-    static constexpr int A_BYTES = BM * BKB, B_BYTES = BN * BKB;
-    static constexpr int A_PW = BM / RPP / NW;    // 1 KiB pieces per wave per stage
-    static constexpr int B_PW = BN / RPP / NW;
-    static constexpr int LOADS = A_PW + B_PW;     // glds per wave per stage
-    static constexpr int CAP = BM >= 256 ? 1024 : 512;   // append-buffer entries per (block, query)
-    // the queued filter's per-wave queues, behind the common layout: [wave][9 words][64 slots] -- eight raw dot products and the
-    // entry's (site, lane); slot-minor, so the pushes of a site's passing lanes (consecutive slots) and the drain (lane i reads slot
-    // i) touch 64 distinct banks per word
-    static constexpr int HQ_WORDS = 9, HQ_SLOTS = 64;
-    static constexpr int HQ_BYTES = FILT_ == 2 ? WM_ * WN_ * HQ_WORDS * HQ_SLOTS * 4 : 0;
-    static constexpr int LDS_BYTES = NSTAGE * (A_BYTES + B_BYTES) + (4 * BM + 4 * BN + 4 + 128) * 4 + HQ_BYTES;
-    // the pre-seeding (SEED) instantiation of the 128-accumulator phased tile keeps its running group maxima -- MI * NI floats per
-    // lane, live across every tile -- in LDS behind the common layout instead of in registers: those eight registers on top of a
-    // full 256 made hipcc spill 62 (round-5 review); one read-modify-write per (tile, group) of a launch that runs ~50 us
-    static constexpr bool SEED_GM_LDS = PHASED_ && MI_ * NI_ >= 8;
-    static constexpr int SEED_LDS_BYTES = LDS_BYTES - HQ_BYTES + (SEED_GM_LDS ? NW * MI_ * NI_ * 64 * 4 : 0);    // (no queue in that launch)
-    static_assert(SEED_LDS_BYTES <= 160 * 1024 && LDS_BYTES <= 160 * 1024, "LDS budget");
-    static_assert((BM / RPP) % NW == 0 && (BN / RPP) % NW == 0, "pieces must divide over the waves");
-    static_assert(NSTAGE >= 2 && NSTAGE <= 4, "ring depth");
-    static_assert(BM / 64 <= NW, "ea/eb staging uses one wave per 64 rows");
-    static_assert(!PHASED_ || (NSTAGE_ == 2 && ((WM_ == 2 && WN_ == 4 && MI_ == 4 && (NI_ == 2 || NI_ == 1)) ||
-                                                 (WM_ == 4 && WN_ == 2 && MI_ == 2 && NI_ == 3))),
-                  "phased K-loop: 256 x 256 / 256 x 128 tile (8 waves of 128 x 64 / 128 x 32) or 256 x 192 (8 waves of 64 x 96), two K-tile buffers");
-};
 
 // rows: [n][D] 16-bit (allocated in whole 256-row tiles: the phased loop reads the rows of a tail tile past n, the
 // epilogue masks them); qs: [nq_pad][D] 16-bit (queries rounded to the scan dtype)
@@ -1354,63 +1297,17 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
 // the per-query terms of the certificate.
 //   prep[q] = { eps (score units), scale a, offset b } with
 //   s~_units = a * s~' + b  where s~' is the scan's score.
+// eps: erel is the operand-rounding error relative to |a||q| -- the query's own rounding rho_q, measured here, and rho_c, for an f32
+// corpus scanned through its bf16 shadow the max of |a - shadow(a)| / |a| measured at ingest -- plus the float32 summation (gamma).
+// cosine: erel and the normalisation's 4 gamma. ip: erel |q| max|a|.
+// l2: -d^2 = 2 a.q - |a|^2 - |q|^2: the operand-rounding part of the error (erel, relative to |a||q|) enters through
+// the dot product only, twice; the float32 summation / fma parts scale with the magnitudes (|a| + |q|)^2.
+// (Was (2 erel + 6 gamma)(|a| + |q|)^2: four times the needed margin on unit vectors, and f32 corpora under l2
+// -- rho_c = 2^-8 -- sent 23-100% of their queries to the wide second scan.)
 // ---------------------------------------------------------------------------
-template <bool IS_BF16>
-__global__ void k_query_prep(const float *__restrict__ q, const float *__restrict__ nb, int nq, int nq_pad, int D,
-                             int metric, float max_na, float corpus_rho, uint16_t *__restrict__ qs,
-                             QPrep *__restrict__ prep, float *__restrict__ mar) {
-    int qi = blockIdx.x;
-    int lane = threadIdx.x;  // 64 threads
-    uint16_t *dst = qs + (int64_t)qi * D;
-    if (qi >= nq) {
-        for (int i = lane; i < D; i += 64) dst[i] = 0;
-        return;
-    }
-    const float *v = q + (int64_t)qi * D;
-    double err2 = 0.0;
-    for (int i = lane; i < D; i += 64) {
-        float x = v[i];
-        uint16_t h = IS_BF16 ? f32_to_bf16(x) : f32_to_f16(x);
-        float y = IS_BF16 ? bf16_to_f32(h) : f16_to_f32(h);
-        dst[i] = h;
-        double d = (double)x - (double)y;
-        err2 += d * d;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) err2 += __shfl_xor(err2, off);
-    if (lane == 0) {
-        double nq2 = (double)nb[qi];
-        double qn = sqrt(nq2);
-        double gamma = (double)D * 5.9604644775390625e-08;           // D * 2^-24
-        double rho_q = qn > 0 ? sqrt(err2) / qn : 0.0;
-        double rho_c = (double)corpus_rho;   // f32 corpus scanned through its bf16 shadow: max |a - shadow(a)| / |a|, measured at ingest
-        double erel = 4.0 * gamma + rho_q + rho_c + rho_q * rho_c + 1e-6;
-        double maxn = sqrt((double)max_na) * (1.0 + gamma);
-        QPrep p;
-        if (metric == AK_METRIC_COSINE) {
-            p.eps = erel + 4.0 * gamma;
-            p.a = qn > 0 ? 1.0 / qn : 0.0;
-            p.b = 0.0;
-        } else if (metric == AK_METRIC_IP) {
-            p.eps = erel * qn * maxn;
-            p.a = 1.0; p.b = 0.0;
-        } else {
-            // -d^2 = 2 a.q - |a|^2 - |q|^2: the operand-rounding part of the error (erel, relative to |a||q|) enters through
-            // the dot product only, twice; the float32 summation / fma parts scale with the magnitudes (|a| + |q|)^2.
-            // (Was (2 erel + 6 gamma)(|a| + |q|)^2: four times the needed margin on unit vectors, and f32 corpora under l2
-            // -- rho_c = 2^-8 -- sent 23-100% of their queries to the wide second scan.)
-            double s = qn + maxn;
-            p.eps = 2.0 * erel * qn * maxn + 6.0 * gamma * s * s;
-            p.a = 2.0; p.b = -nq2;
-        }
-        prep[qi] = p;
-        mar[qi] = p.a > 0.0 ? (float)(3.0 * p.eps / p.a * 1.0001) : 3.0e38f;   // 3 eps in scan-score units
-    }
-}
-
-// One launch in front of the scans instead of three (memset of the statistics, k_query_norms, k_query_prep: ~5 us each on a
-// search whose whole fixed cost is ~80 us): nb in the reference's arithmetic (sequential float32 chain over the row staged in
-// LDS, every lane walks it with broadcast reads -- k_query_norms' method), then k_query_prep's work; block 0 also zeroes the
+// One launch in front of the scans instead of three (memset of the statistics, a norms kernel, a preparation kernel: ~5 us each on
+// a search whose whole fixed cost is ~80 us): nb in the reference's arithmetic (sequential float32 chain over the row staged in
+// LDS, every lane walks it with broadcast reads -- k_query_norms' method), then the terms above; block 0 also zeroes the
 // statistics and every block its query's dense-list counter / threshold.
 template <bool IS_BF16>
 __global__ __launch_bounds__(64) void k_query_setup(const float *__restrict__ q, float *__restrict__ nb, int compute_nb, int nq,
@@ -1476,7 +1373,7 @@ __global__ __launch_bounds__(64) void k_query_setup(const float *__restrict__ q,
             p.eps = erel * qn * maxn;
             p.a = 1.0; p.b = 0.0;
         } else {
-            double ss = qn + maxn;                                   // see k_query_prep for the derivation
+            double ss = qn + maxn;                                   // (the l2 derivation above the kernel)
             p.eps = 2.0 * erel * qn * maxn + 6.0 * gamma * ss * ss;
             p.a = 2.0; p.b = -nq2;
         }
@@ -1846,241 +1743,49 @@ __global__ __launch_bounds__(64) void k_finalize(const uint64_t *__restrict__ to
 }
 
 // ---------------------------------------------------------------------------
-// host side: configuration table, plan, launch
+// host side: plan entry points, launch, the stages of a search (scan_plan.h: the tile table, the plan, the workspace layout)
 // ---------------------------------------------------------------------------
-//                      WM WN MI NI ring minw
-// MFMA shape of the phased tiles in the product library: the winner by wall time on the benchmark's own workload, parent and variant
-// alternating in one job, every run of the winner above every run of the other (docs/EXPERIMENTS.md "16x16x32": P +6.0 % at Q = 1024,
-// R +5.7 % at 384, Q +3.0 % at 256 queries/s). libarchi_hip_dbg.so instantiates both shapes of each and AK_SCAN_MFMA = 16 / 32
-// picks one there.
-constexpr int SHIP_P = 16, SHIP_Q = 16, SHIP_R = 16;
-// Filter arrangement of the 16x16x32 tiles in the product library (ScanCfg::FILT), by the same rule (docs/EXPERIMENTS.md, "whole-tile
-// filter": the int8 tile -2.7 % of the step at Q = 1024, every run ahead; the 16-bit P and Q slightly slower, R ahead by no more
-// than the spread: they keep the site-by-site filter; "hit queue": the int8 tile's main pass on the queue: ahead by less than the
-// spread, stays on the whole tile). libarchi_hip_dbg.so instantiates both arrangements of P, P8, Q and R and
-// AK_SCAN_FILTER = 1 (site by site) / 2 (whole tile) picks one there; the 32x32x16 shape has one filter.
-constexpr int SHIP_FILT_P = 0, SHIP_FILT_P8 = 1, SHIP_FILT_Q = 0, SHIP_FILT_R = 0;
-template <int S, int F = 0> using CfgPs = ScanCfg<2, 4, 4, 2, 2, 2, true, S == 16 ? F : 0, S>;
-template <int S, int F = 0> using CfgQs = ScanCfg<2, 4, 4, 1, 2, 2, true, S == 16 ? F : 0, S>;
-template <int S, int F = 0> using CfgRs = ScanCfg<4, 2, 2, 3, 2, 2, true, S == 16 ? F : 0, S>;
-using CfgP = CfgPs<SHIP_P, SHIP_FILT_P>;                     // 256 x 256, 8 waves (128x64 each), phased K-loop, SIMD partners one barrier apart : MFMA-bound batches
-using CfgQ = CfgQs<SHIP_Q, SHIP_FILT_Q>;                     // 256 x 128, 8 waves (128x32 each), phased K-loop (three half-tiles per K-step) : 128-query groups of MFMA-bound batches
-using CfgX = ScanCfg<2, 4, 4, 2, 2, 2>;   // the same tile with the in-step K-loop of rounds 1-2 (2-slot ring, one barrier per K-step): A/B reference
-// Measured and not kept (round 1-2; docs/EXPERIMENTS.md has the numbers): an L2 prefetch of the corpus lines three K-steps
-// ahead of the staging cursor (the prefetch instruction costs half of what a wave's staging instructions issue per K-step:
-// 15.9 vs 14.7 ms); the same 256 x 256 tile on FOUR waves of 128 x 128 (one wave per SIMD: nothing runs under the staging
-// issue, the vmcnt wait, the barrier or the first fragment reads of a K-step: 27.3 vs 14.4 ms); K-step 32 with a 4-slot ring
-// (twice the barriers: +4 %), and that ring with the SIMD partners one barrier apart (+2 % over itself in step, still behind
-// the K-step-64 loop) -- the forerunner of CfgP, which keeps K-step 64 and staggers at quadrant granularity instead.
-using CfgL = ScanCfg<4, 2, 2, 2, 3, 2>;   // 256 x 128, 8 waves (64x64 each), 3-slot ring
-using CfgM = ScanCfg<4, 1, 2, 2, 3, 1>;   // 256 x 64 , 4 waves, 3-slot ring : HBM-bound, Q <= 64
-using CfgS = ScanCfg<4, 1, 2, 1, 3, 1>;   // 256 x 32 , 4 waves, 3-slot ring : HBM-bound, Q <= 32
-using CfgO = ScanCfg<2, 2, 2, 2, 2, 2>;   // 128 x 128, 4 waves, 2-slot ring, 2 blocks/CU (first version; A/B reference)
-// the 256 x 256 phased tile on int8 operands (v_mfma_i32_16x16x64_i8): a type of its own, so the names of the 16-bit kernels stand
-// The int8 tile has a third arrangement, the queued one (ScanCfg::FILT = 2), and its two passes choose on their own (FILT the main
-// pass, FILT_SEED the seeding pass: k_scan takes the one its SEEDPASS tag names). CfgP8 is what ships: the main pass on the whole tile,
-// the seeding pass on the queue (docs/EXPERIMENTS.md, "hit queue": the seeding pass -14.5 % per launch and -0.157 ms of the step at
-// Q = 1024 on the queue, every run ahead of every parent run; the main pass ahead by less than the spread). CfgP8f and CfgP8g hold the
-// other arrangements of either pass, in the dbg library -- AK_SCAN_FILTER as above, AK_SCAN_HITQ = 1 (seeding pass) / 2 (main pass) /
-// 3 (both) / 4 (neither) puts a pass on the queue or takes it off. A type with a queued pass carries the queues' LDS.
-constexpr int SHIP_FILT_P8_SEED = 2;
-template <int FM, int FS> struct CfgP8T : CfgPs<16, FM> {
-    using Base = CfgPs<16, FM>;
-    static constexpr bool I8 = true;
-    static constexpr int FILT_SEED = FS;
-    static constexpr int HQ_BYTES = (FM == 2 || FS == 2) ? Base::NW * Base::HQ_WORDS * Base::HQ_SLOTS * 4 : 0;
-    static constexpr int LDS_BYTES = Base::LDS_BYTES - Base::HQ_BYTES + HQ_BYTES;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-};
-struct CfgP8 : CfgP8T<SHIP_FILT_P8, SHIP_FILT_P8_SEED> {};
-struct CfgP8f : CfgP8T<0, 0> {};      // site by site, both passes
-struct CfgP8g : CfgP8T<2, 1> {};      // main pass queued, seeding pass whole tile
-static_assert(SHIP_FILT_P8 == 1 && SHIP_FILT_P8_SEED == 2, "CfgP8f / CfgP8g hold the arrangements CfgP8 does not");
-// the type that runs arrangement F in the seeding (SEEDP) or the main pass
-template <bool SEEDP, int F> using CfgP8of =
-    std::conditional_t<(SEEDP ? CfgP8::FILT_SEED : CfgP8::FILT) == F, CfgP8, std::conditional_t<(SEEDP ? CfgP8f::FILT_SEED : CfgP8f::FILT) == F, CfgP8f, CfgP8g>>;
-using CfgR = CfgRs<SHIP_R, SHIP_FILT_R>;                     // 256 x 192, 8 waves of 64 x 96, phased: batches between the regimes (Q mod 256 in (128, 192], ...)
-
-struct CfgInfo { int bm, bn, cap, threads, lds, blocks_per_cu; };
-template <class C> constexpr CfgInfo info_of(int bpc) { return CfgInfo{C::BM, C::BN, C::CAP, C::THREADS, C::LDS_BYTES, bpc}; }
-static const CfgInfo g_cfgs[8] = {info_of<CfgL>(1), info_of<CfgM>(1), info_of<CfgS>(1), info_of<CfgO>(2), info_of<CfgX>(1), info_of<CfgP>(1), info_of<CfgQ>(1),
-                                  info_of<CfgR>(1)};
-enum { CFG_L = 0, CFG_M = 1, CFG_S = 2, CFG_O = 3, CFG_X = 4, CFG_P = 5, CFG_Q = 6, CFG_R = 7 };
-// The A/B reference tiles X (the 256 x 256 tile with the in-step K-loop of rounds 1-2) and O (the first 128 x 128 version) are
-// instantiated in libarchi_hip_dbg.so only (12 k_scan kernels less in the product library); the product plan never picks them.
-#if AK_DBG_KERNELS
-#define AK_SCAN_XO_CASES(SCAN, R0, R1, NS, THR, SOFF, DBG, SP)            \
-        case CFG_X: SCAN(CfgX, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_O: SCAN(CfgO, R0, R1, NS, THR, SOFF, DBG, SP); break;
-#else
-#define AK_SCAN_XO_CASES(SCAN, R0, R1, NS, THR, SOFF, DBG, SP)
-#endif
-
-// Tile choice by (Q, N, D), from sweeps on the MI355X (scripts/gpu_ridge_sweep.sh, scripts/gpu_probe3.py; search time in ms,
-// 10M x 768 bf16, round 3 -- P = 256-query groups on the phased 256 x 256 tile, Q = 128-query groups on the phased 256 x 128
-// tile, L = 128-query groups on the in-step 256 x 128 tile of rounds 1-2):
-//   queries   128    256    384    512    640   1024
-//   P          -    3.93   6.43   6.82   9.74  12.75
-//   Q        3.10   4.46   6.34   7.78   9.97  14.62
-//   L        3.15   4.75   6.95    -      -      -
-// and R = 192-query groups on the phased 256 x 192 tile (8 waves of 64 x 96: 24 MFMAs per K-tile and wave where P has 32),
-// on another box, R / P / Q:  Q = 192: 3.72 / 3.84 / 4.59   320: 5.51 / 6.32 / -   384: 5.70 / 6.55 / 6.45   576: 8.32 / 9.70 / -
-//   768: 10.44 / 10.22 / -   1024: 15.29 / 13.02 / -   -- a 192-query pass costs 0.77 (four groups) to 0.87 (two) of a 256-query one.
-// A query group is a full pass over the slice's tiles whatever it holds, so what counts is the PADDED batch: a 128-query
-// group costs ~0.62 of a 256-query group. Between the regimes -- Q in (256, 384], (768, 896] ... -- the narrower tile
-// wastes less. Small shards (1M x 384 f32, Q = 256: L 0.455, Q 0.455, P 0.509 ms; 1.25M x 768 bf16: L 0.864, Q 0.872,
-// P 0.759; Q = 1024: Q 2.15, P 1.91): the wide tile needs long rows and enough tiles per workgroup to pay.
-// long rows and many tiles: where the wide tiles pay and the scan is bound by the matrix pipe (pick_cfg, the int8 plan's eligibility)
-static bool big_shard(const Index &ix) { return ix.dim >= 768 && (ix.n + 255) / 256 >= 4096; }
-
-static int pick_cfg(int nq, const Index &ix) {
-    if (const int forced = switches().scan_cfg.load(std::memory_order_relaxed)) {
-        switch (forced) { case 'L': return CFG_L; case 'M': return CFG_M; case 'S': return CFG_S;
-                        case 'O': if (DBG_KERNELS) return CFG_O; break;
-                        case 'X': if (DBG_KERNELS) return CFG_X; break;
-                        case 'P': return ix.dim < 128 ? CFG_L : CFG_P; case 'Q': return ix.dim < 128 ? CFG_L : CFG_Q;
-                        case 'R': return ix.dim < 128 ? CFG_L : CFG_R; }
-    }
-    if (nq <= 32) return CFG_S;
-    if (nq <= 64) return CFG_M;
-    if (nq <= 128) return CFG_L;          // HBM-bound: the in-step loop with its three-slot ring
-    if (ix.dim < 128) return CFG_L;       // one K-step per tile: the phased loop wants two (its compaction-request sampling)
-    const int g128 = (nq + 127) / 128, g192 = (nq + 191) / 192, g256 = (nq + 255) / 256;
-    const bool big = big_shard(ix);
-    // A query group is a full pass over the slice's tiles whatever it holds; relative cost of a pass: 256-query group 1,
-    // 192-query group 0.85, 128-query group 0.62. Long rows and many tiles: the cheapest padded batch. Small or short-row shards:
-    // the wide tile pays later (two 128-groups at Q <= 256, the measured 1.62 rule above), the 192 tile when it beats that choice
-    // (1M x 384 f32 Q = 384: R 0.551 / Q 0.569 / P 0.607 ms; 12.5M x 384 f16 Q = 384: 3.89 / 4.45 / 4.53; 1.25M x 768 Q = 576:
-    // R 1.229 / P 1.426)
-    const double r192 = switches().scan_r192_pm.load(std::memory_order_relaxed) * 1e-3;
-    const bool no192 = switches().scan_no192.load(std::memory_order_relaxed) != 0;
-    const double cp = g256, cr = no192 ? 1e9 : g192 * r192, cq = g128 * 0.62;
-    if (big) {
-        if (cr < cp && cr < cq) return CFG_R;
-        return cp <= cq ? CFG_P : CFG_Q;
-    }
-    const int base = nq <= 256 ? CFG_Q : (g256 * 1.62 < g128 ? CFG_P : CFG_Q);
-    return cr < (base == CFG_P ? cp : cq) ? CFG_R : base;
+static ScanShape shape_of(const Index &ix) { return ScanShape{ix.n, ix.dim, ix.dtype, ix.metric}; }
+static int sw_get(const std::atomic<int> &s) { return s.load(std::memory_order_relaxed); }
+static PlanSwitches plan_switches() {
+    const Switches &s = switches();
+    return PlanSwitches{sw_get(s.scan_cfg), sw_get(s.scan_i8), sw_get(s.scan_blocks), sw_get(s.scan_r192_pm), sw_get(s.scan_no192),
+                        sw_get(s.seed_ratio), sw_get(s.seed_div), sw_get(s.pre_div), sw_get(s.scan_noseed), sw_get(s.scan_nopre)};
 }
 
-constexpr int I8_KP = 512;      // candidates the int8 plan re-ranks per query (k_finalize<8>; the append buffers' limit)
+bool fast_supported(const Index &ix, int nq, int k) { return fast_supported(shape_of(ix), nq, k); }
 
-bool fast_supported(const Index &ix, int nq, int k) {
-    if (ix.dim % BK != 0) return false;
-    if (ix.n < 4096) return false;                          // tiny index: exact path is cheaper
-    if (k > 128) return false;
-    return nq > 0;
+// the plan's workspace; the selection scratch behind its lists is sized by its owners (exact.hip, select.hip)
+static ScanWorkspace workspace_of(const Index &ix, const FastPlan &p, int nq, int k) {
+    const int64_t lists = (int64_t)(p.nslices + p.ns_seed) * p.kprime;
+    return scan_workspace(p, shape_of(ix), nq, k, select_scratch_bytes(nq, lists, p.kprime) + select_keys_scratch_bytes(nq, lists, p.kprime));
 }
-
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 FastPlan fast_plan(const Index &ix, int nq, int k, bool widest, bool allow_i8) {
-    FastPlan p;
-    p.cfg = pick_cfg(nq, ix);
-    const CfgInfo &c = g_cfgs[p.cfg];
-    p.kprime = k <= 16 ? 64 : (k <= 48 ? 128 : 256);
-    // the int8 plan: tile P, cosine / inner product (no additive row term), a 16-bit corpus, rows of >= two 128-element K-steps,
-    // the common k' (k <= 16); by its own choice (AK_SCAN_I8 = 1) only where the scan is bound by the matrix pipe -- a big shard
-    // and at least two 256-query groups. AK_SCAN_I8 = 2 takes every shape the kernel allows (tests, A/B runs).
-    p.i8 = 0;
-    if (const int i8m = switches().scan_i8.load(std::memory_order_relaxed)) {
-        const bool shape_ok = allow_i8 && !widest && p.cfg == CFG_P && ix.metric != AK_METRIC_L2 && ix.dtype != AK_DTYPE_F32 && ix.dim % 128 == 0 &&
-                              ix.dim >= 256 && ix.dim <= TAIL_MAX_DIM && k <= 16;
-        const bool big = big_shard(ix);
-        if (shape_ok && (i8m >= 2 || (big && nq > 256))) p.i8 = 1;
-    }
-    if (p.i8) p.kprime = I8_KP;
-    // second-chance plan (AUTO mode, queries the first pass could not certify): the widest candidate lists the
-    // append buffers and k_finalize<8> allow, so a pile-up of up to 512 equal scores still certifies
-    if (widest) p.kprime = 512;
-    if (p.kprime > c.cap - c.bm) p.kprime = (c.cap - c.bm) / 64 * 64;
-    p.qtile = c.bn;
-    p.nqg = (nq + c.bn - 1) / c.bn;
-    int64_t ntiles = (ix.n + c.bm - 1) / c.bm;
-    int target = 256 * c.blocks_per_cu;                    // resident workgroups on 256 CUs
-    const Switches &sw = switches();
-    if (const int forced = sw.scan_blocks.load(std::memory_order_relaxed)) target = forced;
-    int ns = target / p.nqg;
-    if (ns < 8) ns = 8;
-    ns = (ns / 8) * 8;
-    while (ns > 8 && ntiles / ns < 2) ns -= 8;             // keep >= 2 tiles per slice
-    if (ns > ntiles) ns = (int)ntiles;
-    p.nslices = ns < 1 ? 1 : ns;
-    // seeding pass: 3-12% of the rows first (seed_div below), so the main pass starts with thresholds close to the
-    // final k-th best instead of discovering them slice by slice
-    p.ns_seed = 0; p.seed_rows = 0; p.pre_tiles = 0; p.pre_slices = 0; p.pre_stride = 1;
-    const int64_t seed_ratio = sw.seed_ratio.load(std::memory_order_relaxed);   // tiles per slice below which the seeding pass does not pay
-    const bool noseed = sw.scan_noseed.load(std::memory_order_relaxed) != 0;
-    if (!noseed && ntiles >= seed_ratio * (int64_t)p.nslices && ntiles >= 256) {
-        // share of the tiles the seeding pass scans: 1/32 on large shards, 1/8 below ~5M rows (round-3 sweep with the phased
-        // tiles, search ms at Q = 1024 for 1/32, 1/16, 1/8: 10M x 768 12.97 / 12.94 / 12.97 and 12.5M x 384 f16 9.18 / 9.09 /
-        // 9.13 -- flat; 1.25M x 768 1.96 / 1.91 / 1.88; 1M x 384 f32 1.19 / 1.10 / 1.04 -- on a small shard tighter thresholds
-        // spare the main pass's filter more than the extra seed rows cost)
-        int seed_div = sw.seed_div.load(std::memory_order_relaxed);
-        // (round 5, after the filter got cheaper: 10M x 768 Q = 1024 search ms for 1/64 .. 1/8: 13.05 / 12.98 (1/48) / 12.87 (1/32) / 12.79
-        // (1/24) / 12.77 (1/16) / 12.73 (1/12) / 12.74 -- and from 1/96 on queries lose their certificate: 1/12 up to 100k tiles)
-        if (seed_div <= 0) seed_div = ntiles >= 100000 ? 32 : (ntiles >= 20000 ? 12 : 8);
-        int64_t seed_tiles = ntiles / seed_div;
-        int nss = p.nslices;
-        while (nss > 8 && seed_tiles / nss < 2) nss -= 8;
-        if (seed_tiles >= nss && nss >= 1) {
-            p.ns_seed = nss;
-            p.seed_rows = seed_tiles * c.bm;
-        }
-    }
-    // pre-seeding (group maxima over a strided sample): spares the seeding pass -- or, on shards too small to
-    // have one, the main pass -- its all-pass start. 16 (8 for the 128-row tile) groups per workgroup; want >= 4k
-    // groups so the k-th largest is not starved. With a seeding pass behind it 0.2% of the rows is enough; on its
-    // own it is the only source of the starting thresholds, so it samples 3% like the seeding pass would.
-    if (!noseed && !sw.scan_nopre.load(std::memory_order_relaxed) && ntiles >= 64) {
-        int pre_div = sw.pre_div.load(std::memory_order_relaxed);
-        if (pre_div <= 0) pre_div = p.ns_seed > 0 ? 512 : 32;
-        int64_t pt = ntiles / pre_div;
-        int64_t need_tiles = ((int64_t)4 * k + c.bm / 16 - 1) / (c.bm / 16);
-        if (pt < 16) pt = 16;
-        if (pt < need_tiles) pt = need_tiles;
-        if (pt > ntiles) pt = ntiles;
-        int ps = 1024 / (c.bm / 16);                   // k_seed_kth holds <= 1024 maxima per query
-        if (ps > pt) ps = (int)pt;
-        p.pre_tiles = pt;
-        p.pre_slices = ps;
-        p.pre_stride = (int)(ntiles / pt);
-    }
-    int nq_pad = p.nqg * c.bn;
-    int ns_tot = p.nslices + p.ns_seed;
-    size_t bytes = 0;
-    bytes += al((size_t)nq_pad * ix.dim * 2);                               // qs
-    bytes += al((size_t)nq * sizeof(QPrep));                                // prep
-    bytes += al((size_t)nq * 4) * 2;                                        // thr0, margins
-    bytes += al((size_t)nq * 4) * 2;                                        // dense-list counters, max-reduced thresholds
-    bytes += al((size_t)nq * ns_tot * 4);                                   // final thresholds per slot
-    bytes += al((size_t)nq * 1024 * 4);                                     // pre-seeding group maxima
-    bytes += al((size_t)p.nslices * p.nqg * c.bn * c.cap * 8);              // cand
-    bytes += al((size_t)nq * ns_tot * p.kprime * 8);                        // out_c
-    bytes += al((size_t)nq * p.kprime * 8) * 2;                             // top_kp keys + ids
-    bytes += al((size_t)nq * p.kprime * 8) * 2;                             // rerank keys + ids
-    bytes += al((size_t)nq * k * 8) * 2;                                    // final keys + ids
-    bytes += al(select_scratch_bytes(nq, (int64_t)ns_tot * p.kprime, p.kprime) +
-                select_keys_scratch_bytes(nq, (int64_t)ns_tot * p.kprime, p.kprime));
-    if (p.i8) {
-        bytes += al((size_t)nq_pad * ix.dim);                                // int8 queries
-        bytes += al((size_t)nq * sizeof(QPrep));                             // their prep
-        bytes += al((size_t)nq * 4) * 4;                                     // margins, final cut, seed re-rank counts + flags
-    }
-    bytes += 4096;
-    p.bytes = bytes;
+    FastPlan p = scan_plan(shape_of(ix), plan_switches(), nq, k, widest, allow_i8);
+    p.bytes = workspace_of(ix, p, nq, k).bytes;
     return p;
 }
 
 // AK_SCAN_DBG / AK_SCAN_ABLATE (measurement only) select the instrumented instantiation of the main-pass kernels
-static int scan_ablate_flags() { return switches().scan_ablate.load(std::memory_order_relaxed); }
-static bool scan_instrumented() { return switches().scan_dbg.load(std::memory_order_relaxed) != 0 || scan_ablate_flags() != 0; }
+static int scan_ablate_flags() { return sw_get(switches().scan_ablate); }
+static bool scan_instrumented() { return sw_get(switches().scan_dbg) != 0 || scan_ablate_flags() != 0; }
 
-template <bool BF, class C, bool SEED = false, bool SEEDPASS = false>
-static int launch_scan(const Index &ix, const uint8_t *filter_dev, int64_t row_begin, int64_t row_end,
-                       const uint16_t *qs, int nq, int ns, int nqg, int k, int kp, const float *thr0, const float *mar,
-                       int slice_off, int ns_total, uint64_t *cand, uint64_t *out_c, float *thr_slots, long long *dbg, hipStream_t st,
-                       int64_t sample_tiles = 0, int tstride = 1, int *dense_cnt = nullptr, unsigned int *dense_thr = nullptr) {
+// One k_scan launch. The first line is the search's own; the three passes (pre-seeding, seeding, main) differ in the rest.
+struct ScanArgs {
+    const Index &ix; const uint8_t *filter_dev; hipStream_t st; const uint16_t *qs; const float *mar; int nq, nqg, k, kp;
+    int64_t row_begin = 0, row_end = 0;
+    int ns = 0, slice_off = 0, ns_total = 0;
+    const float *thr0 = nullptr;
+    uint64_t *cand = nullptr, *out_c = nullptr;
+    float *thr_slots = nullptr;                              // (the pre-seeding launch: its group maxima)
+    long long *dbg = nullptr;
+    int64_t sample_tiles = 0; int tstride = 1;               // pre-seeding only
+    int *dense_cnt = nullptr; unsigned int *dense_thr = nullptr;
+};
+
+template <bool BF, class C, bool SEED, bool SEEDPASS>
+static int launch_scan(const ScanArgs &a) {
     static std::atomic<bool> attr_set{false};
     constexpr int LDSB = SEED ? C::SEED_LDS_BYTES : C::LDS_BYTES;
     if (!attr_set) {
@@ -2089,6 +1794,7 @@ static int launch_scan(const Index &ix, const uint8_t *filter_dev, int64_t row_b
             AK_HIP(hipFuncSetAttribute((const void *)k_scan<BF, C, SEED, true, SEEDPASS>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
         attr_set = true;
     }
+    const Index &ix = a.ix;
     const uint16_t *rows16 = (const uint16_t *)(C::I8 ? (const void *)ix.rows8 : (ix.dtype == AK_DTYPE_F32 ? ix.shadow : ix.rows));
     const float *ea = C::I8 ? ix.ea8 : ix.ea, *gb = C::I8 ? ix.gb8 : ix.gb;      // int8: the scale-folded terms; eb (0 / -inf) is the index's own
     const int64_t gbb = (ix.n + 31) / 32;
@@ -2097,24 +1803,212 @@ static int launch_scan(const Index &ix, const uint8_t *filter_dev, int64_t row_b
     if (instr) {
         if constexpr (!DBG_KERNELS) AK_FAIL(-1, "AK_SCAN_DBG and the scan ablation switch need libarchi_hip_dbg.so (make -C archi_amd/csrc dbg): the product library carries no instrumented scan kernels");
         if constexpr (!SEED && DBG_KERNELS)
-            k_scan<BF, C, SEED, true, SEEDPASS><<<(unsigned)(ns * nqg), C::THREADS, C::LDS_BYTES, st>>>(
-                rows16, ea, ix.eb, gb, gbb, filter_dev, row_begin, row_end, ix.dim, qs, nq, ns, nqg, k, kp, thr0, mar, slice_off,
-                ns_total, cand, out_c, thr_slots, scan_ablate_flags(), dbg, sample_tiles, tstride, dense_cnt, dense_thr);
+            k_scan<BF, C, SEED, true, SEEDPASS><<<(unsigned)(a.ns * a.nqg), C::THREADS, C::LDS_BYTES, a.st>>>(
+                rows16, ea, ix.eb, gb, gbb, a.filter_dev, a.row_begin, a.row_end, ix.dim, a.qs, a.nq, a.ns, a.nqg, a.k, a.kp, a.thr0, a.mar, a.slice_off,
+                a.ns_total, a.cand, a.out_c, a.thr_slots, scan_ablate_flags(), a.dbg, a.sample_tiles, a.tstride, a.dense_cnt, a.dense_thr);
     } else {
-        k_scan<BF, C, SEED, false, SEEDPASS><<<(unsigned)(ns * nqg), C::THREADS, LDSB, st>>>(
-            rows16, ea, ix.eb, gb, gbb, filter_dev, row_begin, row_end, ix.dim, qs, nq, ns, nqg, k, kp, thr0, mar, slice_off,
-            ns_total, cand, out_c, thr_slots, 0, nullptr, sample_tiles, tstride, dense_cnt, dense_thr);
+        k_scan<BF, C, SEED, false, SEEDPASS><<<(unsigned)(a.ns * a.nqg), C::THREADS, LDSB, a.st>>>(
+            rows16, ea, ix.eb, gb, gbb, a.filter_dev, a.row_begin, a.row_end, ix.dim, a.qs, a.nq, a.ns, a.nqg, a.k, a.kp, a.thr0, a.mar, a.slice_off,
+            a.ns_total, a.cand, a.out_c, a.thr_slots, 0, nullptr, a.sample_tiles, a.tstride, a.dense_cnt, a.dense_thr);
     }
     AK_HIP(hipGetLastError());
     return 0;
 }
+
+// Tile dispatch: tile number -> f(tag), f's int. A tag names the type the tile ships on and, for the phased tiles, the family of
+// its MFMA shapes and filter arrangements (Shaped<shape, arrangement>).
+template <class C> struct TileTag { using Shipped = C; static constexpr bool PHASED = false; };
+template <template <int, int> class T, class C> struct PhasedTag { using Shipped = C; static constexpr bool PHASED = true; template <int S, int F> using Shaped = T<S, F>; };
+template <class F> static int visit_tile(int cfg, F &&f) {
+    switch (cfg) {
+        case CFG_L: return f(TileTag<CfgL>{});
+        case CFG_M: return f(TileTag<CfgM>{});
+        case CFG_S: return f(TileTag<CfgS>{});
+        case CFG_P: return f(PhasedTag<CfgPs, CfgP>{});
+        case CFG_Q: return f(PhasedTag<CfgQs, CfgQ>{});
+        case CFG_R: return f(PhasedTag<CfgRs, CfgR>{});
+    }
+    AK_FAIL(-1, "scan: no such tile configuration");
+}
+// The type a seeding or main pass of a tile runs: the shipped one. The dbg library carries both shapes and both arrangements of the
+// phased tiles and honours AK_SCAN_MFMA / AK_SCAN_FILTER (the product library's ak_debug_set refuses them, and a value in its
+// environment is ignored).
+template <class Tag, class F> static int with_forced_shape(Tag, F &&f) {
+    using C = typename Tag::Shipped;
+    if constexpr (DBG_KERNELS && Tag::PHASED) {
+        const int mfma = sw_get(switches().scan_mfma), filt = sw_get(switches().scan_filter) - 1;      // 0 / -1: as the tile ships
+        if ((mfma ? mfma : C::MFMA) == 32) return f(TileTag<typename Tag::template Shaped<32, 0>>{});
+        if ((filt < 0 ? C::FILT : filt) == 1) return f(TileTag<typename Tag::template Shaped<16, 1>>{});
+        return f(TileTag<typename Tag::template Shaped<16, 0>>{});
+    } else {
+        return f(TileTag<C>{});
+    }
+}
+// Arrangement of a pass of the int8 tile, dbg library: AK_SCAN_HITQ says which passes run queued, the others -- and all of them
+// without it -- what AK_SCAN_FILTER says or, unforced, what they ship on (whole tile where that is the queue and the queue is
+// switched off)
+static int p8_filt(bool seedpass) {
+    const int hitq = sw_get(switches().scan_hitq), filt = sw_get(switches().scan_filter) - 1;
+    const int shipped = seedpass ? SHIP_FILT_P8_SEED : SHIP_FILT_P8;
+    if (hitq && hitq != 4 && (hitq & (seedpass ? 1 : 2))) return 2;
+    if (filt >= 0) return filt;
+    return hitq && shipped == 2 ? 1 : shipped;
+}
+// the int8 plan: one tile, one element type; its two passes take their arrangements on their own
+template <bool SEEDPASS, class F> static int with_tile8(F &&f) {
+    if constexpr (DBG_KERNELS) {
+        switch (p8_filt(SEEDPASS)) {
+            case 0: return f(TileTag<CfgP8of<SEEDPASS, 0>>{});
+            case 1: return f(TileTag<CfgP8of<SEEDPASS, 1>>{});
+            default: return f(TileTag<CfgP8of<SEEDPASS, 2>>{});
+        }
+    } else {
+        return f(TileTag<CfgP8>{});
+    }
+}
+
+// One fast_search call: what its stages share, and the stages in the order they run
+struct Search {
+    Index &ix; const FastPlan &plan; const float *queries_dev; float *nb_dev; int nq, k; const uint8_t *filter_dev;
+    int64_t *out_ids_dev; double *out_dist_dev; int *out_cnt_dev, *cert_dev; int64_t *stats_dev; void *ws; hipStream_t st;
+    ScanWorkspace w;
+    bool i8, dense, bf;
+    int kp, ns_tot;
+    int *dcnt; unsigned int *dthr;                                   // the dense lists' counters and thresholds; NULL on the slot layout
+    long long *dbg0 = nullptr, *dbg1 = nullptr;
+    const float *thr_seed = nullptr, *thr_main = nullptr;            // starting thresholds of the seeding / the main pass
+    template <class T> T *at(const WsRegion<T> &r) const { return r.at(ws); }
+
+    int query_setup(bool nb_ready) const {
+        const int nq_pad = plan.nqg * g_cfgs[plan.cfg].bn, compute_nb = nb_ready ? 0 : 1;
+        // f32 corpora are scanned through their bf16 shadow (candidates only; the re-rank reads the f32 rows)
+        const float rho = ix.dtype == AK_DTYPE_F32 ? ix.max_rho : 0.f;
+        if (bf) k_query_setup<true><<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, compute_nb, nq, nq_pad, ix.dim, ix.metric, ix.max_na, rho, at(w.qs), at(w.prep),
+                                                          at(w.mar), stats_dev, dcnt, dthr);
+        else k_query_setup<false><<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, compute_nb, nq, nq_pad, ix.dim, ix.metric, ix.max_na, 0.f, at(w.qs), at(w.prep),
+                                                        at(w.mar), stats_dev, dcnt, dthr);
+        if (i8) k_query_setup8<<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, nq, ix.dim, ix.metric, ix.max_na, ix.max_rho8, at(w.qs8), at(w.prep8), at(w.mar8));
+        AK_HIP(hipGetLastError());
+        return 0;
+    }
+
+    // pre-seeding: group maxima over a strided sample -> first thresholds
+    int pre_seed() {
+        ScanArgs a{ix, filter_dev, st, at(w.qs), at(w.mar), nq, plan.nqg, k, kp};      // the 16-bit queries on every plan
+        a.row_end = ix.n; a.ns = plan.pre_slices; a.thr_slots = at(w.gmax); a.sample_tiles = plan.pre_tiles; a.tstride = plan.pre_stride;
+        // the pre-seeding launch stays on 32x32x16 whatever the tile ships
+        const int rc = visit_tile(plan.cfg, [&](auto tag) {
+            using C = typename decltype(tag)::Shipped::Shape32;
+            return bf ? launch_scan<true, C, true, false>(a) : launch_scan<false, C, true, false>(a);
+        });
+        if (rc) return rc;
+        k_seed_kth<<<nq, 64, 0, st>>>(at(w.gmax), plan.pre_slices * (g_cfgs[plan.cfg].bm / 16), at(w.prep), k, at(w.thr0));
+        if (i8) k_thr_to_i8<<<(nq + 63) / 64, 64, 0, st>>>(at(w.prep), at(w.prep8), nq, at(w.thr0));      // the 16-bit sample's threshold in int8 units
+        AK_HIP(hipGetLastError());
+        thr_seed = thr_main = at(w.thr0);
+        return 0;
+    }
+
+    // seeding (SEEDPASS) or main pass: rows [r0, r1) in ns slices, into slots [soff, soff + ns)
+    template <bool SEEDPASS> int scan_pass(int64_t r0, int64_t r1, int ns, const float *thr, int soff, long long *dbg) const {
+        ScanArgs a{ix, filter_dev, st, at(w.qs), at(w.mar), nq, plan.nqg, k, kp};
+        a.row_begin = r0; a.row_end = r1; a.ns = ns; a.slice_off = soff; a.ns_total = ns_tot; a.thr0 = thr; a.dbg = dbg;
+        a.cand = at(w.cand); a.out_c = at(w.out_c); a.thr_slots = at(w.thr_slots); a.dense_cnt = dcnt; a.dense_thr = dthr;
+        if (i8) {
+            a.qs = (const uint16_t *)at(w.qs8); a.mar = at(w.mar8);
+            return with_tile8<SEEDPASS>([&](auto t) { return launch_scan<true, typename decltype(t)::Shipped, false, SEEDPASS>(a); });
+        }
+        return visit_tile(plan.cfg, [&](auto tag) {
+            return with_forced_shape(tag, [&](auto t) {
+                using C = typename decltype(t)::Shipped;
+                return bf ? launch_scan<true, C, false, SEEDPASS>(a) : launch_scan<false, C, false, SEEDPASS>(a);
+            });
+        });
+    }
+
+    // seeding pass over rows [0, seed_rows) and its threshold: per-query thresholds for the main pass
+    int seed_pass() {
+        const int nss = plan.ns_seed;
+        uint64_t *out_c = at(w.out_c);
+        float *thr0 = at(w.thr0);
+        int rc = scan_pass<true>(0, plan.seed_rows, nss, thr_seed, 0, dbg0);
+        if (rc) return rc;
+        if (i8) {
+            // the int8 seeding pass is followed by the exact seed threshold: the fused tail re-ranks the best 64 seed candidates of every
+            // query in the reference arithmetic (its usual work, on the lists as they stand before the main pass) and k_seed_exact_thr
+            // turns their exact k-th best into theta. "k-th best approximate score - 3 eps" with the int8 eps lets 10-20 k rows
+            // per query through the main pass (docs/EXPERIMENTS.md, "int8 shadow"); this one about as many as the bf16 plan.
+            rc = fused_tail(ix, queries_dev, nb_dev, nq, k, out_c, (int64_t)ns_tot * kp, at(w.d_cnt), at(w.d_thr), thr_seed, at(w.prep8), at(w.fin_i),
+                            at(w.fin_d), at(w.sd_cnt), at(w.sd_cert), nullptr, st);
+            if (rc) return rc;
+            k_seed_exact_thr<<<(nq + 63) / 64, 64, 0, st>>>(at(w.fin_d), at(w.sd_cnt), at(w.prep8), nq, k, ix.metric, thr_seed != nullptr, thr0);
+        } else {
+            // top-k of the seed candidates (slots [0,nss) of out_c -- or, dense, the lists as they stand; the main pass has not
+            // written yet). Only the k-th best is needed here: k selection rounds, not kp
+            const int64_t seed_in = (int64_t)nss * kp, seed_stride = (int64_t)ns_tot * kp;
+#define KTH(EPT)                                                                                                                \
+    do {                                                                                                                        \
+        if (thr_seed) k_seed_kth_lists<EPT, true><<<nq, 256, 0, st>>>(out_c, seed_in, seed_stride, at(w.prep), k, thr0, dcnt);    \
+        else k_seed_kth_lists<EPT, false><<<nq, 256, 0, st>>>(out_c, seed_in, seed_stride, at(w.prep), k, thr0, dcnt);            \
+    } while (0)
+            if (seed_in <= 16 * 256) KTH(16);
+            else if (seed_in <= 32 * 256) KTH(32);
+            else if (seed_in <= 64 * 256) KTH(64);
+            else {
+                if (dense) AK_FAIL(-1, "fast_search: dense lists with more than 16384 seed candidates");   // kp = 64, nss <= 256
+                rc = select_topk_strided(out_c, nq, seed_in, seed_stride, k, at(w.top_k), at(w.top_i), at(w.scratch), st);
+                if (rc) return rc;
+                if (thr_seed) k_seed_thr<true><<<(nq + 63) / 64, 64, 0, st>>>(at(w.top_k), at(w.prep), nq, k, k, thr0);
+                else k_seed_thr<false><<<(nq + 63) / 64, 64, 0, st>>>(at(w.top_k), at(w.prep), nq, k, k, thr0);
+            }
+#undef KTH
+        }
+        AK_HIP(hipGetLastError());
+        thr_main = thr0;
+        return 0;
+    }
+
+    int tail() const {
+        const int64_t lists = (int64_t)ns_tot * kp;
+        uint64_t *out_c = at(w.out_c), *top_k = at(w.top_k), *rr_k = at(w.rr_k);
+        int64_t *rr_i = at(w.rr_i);
+        int rc = 0;
+        if (i8) {
+            // the int8 tail: best 512 of the dense list -> exact re-rank against the stored 16-bit rows -> top-k + certificate with
+            // the int8 eps (one cut for the whole query where the slot layout had one threshold per slice)
+            ix.s8_searches.fetch_add(1, std::memory_order_relaxed);
+            k_select_dense<<<nq, SD_THREADS, 0, st>>>(out_c, lists, at(w.d_cnt), at(w.d_thr), thr_main, kp, top_k, at(w.thr_fin));
+            AK_HIP(hipGetLastError());
+            rc = rerank(ix, queries_dev, nb_dev, nq, kp, top_k, rr_k, rr_i, st);
+            if (rc) return rc;
+            k_finalize<8><<<nq, 64, 0, st>>>(top_k, rr_k, rr_i, at(w.prep8), nb_dev, at(w.thr_fin), 1, k, kp, ix.metric, out_ids_dev, out_dist_dev,
+                                             out_cnt_dev, cert_dev, stats_dev);
+            AK_HIP(hipGetLastError());
+            return 0;
+        }
+        if (dense)
+            return fused_tail(ix, queries_dev, nb_dev, nq, k, out_c, lists, at(w.d_cnt), at(w.d_thr), thr_main, at(w.prep), out_ids_dev, out_dist_dev,
+                              out_cnt_dev, cert_dev, stats_dev, st);
+        rc = select_keys_topk(out_c, nq, lists, lists, kp, top_k, at(w.scratch), st);
+        if (rc) return rc;
+        rc = rerank(ix, queries_dev, nb_dev, nq, kp, top_k, rr_k, rr_i, st);
+        if (rc) return rc;
+#define FIN(NS) k_finalize<NS><<<nq, 64, 0, st>>>(top_k, rr_k, rr_i, at(w.prep), nb_dev, at(w.thr_slots), ns_tot, k, kp, ix.metric, out_ids_dev, \
+                                                  out_dist_dev, out_cnt_dev, cert_dev, stats_dev)
+        if (kp <= 64) FIN(1); else if (kp <= 128) FIN(2); else if (kp <= 256) FIN(4); else FIN(8);
+#undef FIN
+        AK_HIP(hipGetLastError());
+        return 0;
+    }
+};
 
 int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_ready, int nq, int k, const uint8_t *filter_dev,
                 int64_t *out_ids_dev, double *out_dist_dev, int *out_cnt_dev, int *cert_dev, int64_t *stats_dev,
                 void *ws, const FastPlan &plan, hipStream_t st) {
     if (plan.i8) {
         // the shadow is +50 % of the corpus: on a device too full for it the search runs the 16-bit plan it ran before the int8
-        // plan existed (same tile and slices, k' = 64: every part of its workspace is no larger than this plan's)
+        // plan existed (same tile and slices, k' = 64) in the workspace it was handed: that plan's layout has to end inside it
+        // (tests/native/scan_plan_main.cpp holds that over the plan's whole range)
         const int src = ensure_shadow8(ix, st);
         if (src == AK_SHADOW8_NOMEM) {
             const FastPlan alt = fast_plan(ix, nq, k, false, false);
@@ -2123,59 +2017,25 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
                                stats_dev, ws, alt, st);
         }
         if (src) return src;
+        if (plan.cfg != CFG_P || plan.kprime != I8_KP) AK_FAIL(-1, "fast_search: the int8 plan is tile P with k' = 512");
     }
-    const CfgInfo &c = g_cfgs[plan.cfg];
-    const int kp = plan.kprime, ns = plan.nslices, nss = plan.ns_seed, ns_tot = ns + nss, nqg = plan.nqg,
-              nq_pad = nqg * c.bn;
-    char *p = (char *)ws;
-    uint16_t *qs = (uint16_t *)p; p += al((size_t)nq_pad * ix.dim * 2);
-    QPrep *prep = (QPrep *)p; p += al((size_t)nq * sizeof(QPrep));
-    float *thr0 = (float *)p; p += al((size_t)nq * 4);
-    float *mar = (float *)p; p += al((size_t)nq * 4);
-    int *d_cnt = (int *)p; p += al((size_t)nq * 4);
-    unsigned int *d_thr = (unsigned int *)p; p += al((size_t)nq * 4);
-    float *thr_slots = (float *)p; p += al((size_t)nq * ns_tot * 4);
-    float *gmax = (float *)p; p += al((size_t)nq * 1024 * 4);
-    uint64_t *cand = (uint64_t *)p; p += al((size_t)ns * nqg * c.bn * c.cap * 8);
-    uint64_t *out_c = (uint64_t *)p; p += al((size_t)nq * ns_tot * kp * 8);
-    uint64_t *top_k = (uint64_t *)p; p += al((size_t)nq * kp * 8);
-    int64_t *top_i = (int64_t *)p; p += al((size_t)nq * kp * 8);
-    uint64_t *rr_k = (uint64_t *)p; p += al((size_t)nq * kp * 8);
-    int64_t *rr_i = (int64_t *)p; p += al((size_t)nq * kp * 8);
-    int64_t *fin_i = (int64_t *)p; p += al((size_t)nq * k * 8);        // (the int8 plan parks its seed re-rank here)
-    double *fin_d = (double *)p; p += al((size_t)nq * k * 8);
-    const bool i8 = plan.i8 != 0;
-    int8_t *qs8 = nullptr; QPrep *prep8 = nullptr; float *mar8 = nullptr, *thr_fin = nullptr; int *sd_cnt = nullptr, *sd_cert = nullptr;
-    if (i8) {
-        qs8 = (int8_t *)p; p += al((size_t)nq_pad * ix.dim);
-        prep8 = (QPrep *)p; p += al((size_t)nq * sizeof(QPrep));
-        mar8 = (float *)p; p += al((size_t)nq * 4);
-        thr_fin = (float *)p; p += al((size_t)nq * 4);
-        sd_cnt = (int *)p; p += al((size_t)nq * 4);
-        sd_cert = (int *)p; p += al((size_t)nq * 4);
-        if (plan.cfg != CFG_P || kp != I8_KP) AK_FAIL(-1, "fast_search: the int8 plan is tile P with k' = 512");
-    }
-    void *scratch = p;
-
+    Search s{ix, plan, queries_dev, nb_dev, nq, k, filter_dev, out_ids_dev, out_dist_dev, out_cnt_dev, cert_dev, stats_dev, ws, st,
+             workspace_of(ix, plan, nq, k)};
+    s.i8 = plan.i8 != 0;
+    s.kp = plan.kprime;
+    s.ns_tot = plan.nslices + plan.ns_seed;
     // The common plan (k' = 64, i.e. k <= 16) runs with dense candidate lists and the fused tail kernel; the wide plans
     // (k' = 128 / 256 / 512: large k, second-chance scans) keep the slot layout and the three-kernel tail.
-    const bool dense = i8 || (kp == TAIL_KP && ix.dim <= TAIL_MAX_DIM && !switches().tail_old.load(std::memory_order_relaxed));
-    int *dcnt = dense ? d_cnt : nullptr;
-    unsigned int *dthr = dense ? d_thr : nullptr;
-
-    // f32 corpora are scanned through their bf16 shadow (candidates only; the re-rank reads the f32 rows)
-    const bool bf = ix.dtype != AK_DTYPE_F16;
-    const int shadowed = ix.dtype == AK_DTYPE_F32;
-    if (bf) k_query_setup<true><<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, nb_ready ? 0 : 1, nq, nq_pad, ix.dim, ix.metric, ix.max_na,
-                                                       shadowed ? ix.max_rho : 0.f, qs, prep, mar, stats_dev, dcnt, dthr);
-    else k_query_setup<false><<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, nb_ready ? 0 : 1, nq, nq_pad, ix.dim, ix.metric, ix.max_na, 0.f,
-                                                     qs, prep, mar, stats_dev, dcnt, dthr);
-    if (i8) k_query_setup8<<<nq_pad, 64, 0, st>>>(queries_dev, nb_dev, nq, ix.dim, ix.metric, ix.max_na, ix.max_rho8, qs8, prep8, mar8);
-    AK_HIP(hipGetLastError());
+    s.dense = s.i8 || (s.kp == TAIL_KP && ix.dim <= TAIL_MAX_DIM && !sw_get(switches().tail_old));
+    s.dcnt = s.dense ? s.at(s.w.d_cnt) : nullptr;
+    s.dthr = s.dense ? s.at(s.w.d_thr) : nullptr;
+    s.bf = ix.dtype != AK_DTYPE_F16;
+    int rc = s.query_setup(nb_ready);
+    if (rc) return rc;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::unique_lock<std::mutex> prof_lk(ix.prof_mu, std::defer_lock);   // concurrent host searches share the index under a shared lock
-    const bool want_dbg = switches().scan_dbg.load(std::memory_order_relaxed) != 0;
+    const bool want_dbg = sw_get(switches().scan_dbg) != 0;
     if (ix.profile || want_dbg) prof_lk.lock();
     if (ix.profile) {
         if (ix.prof_used == ix.prof_events.size()) {
@@ -2188,170 +2048,18 @@ int fast_search(Index &ix, const float *queries_dev, float *nb_dev, bool nb_read
         ev1 = ix.prof_events[ix.prof_used].second;
         ix.prof_used++;
     }
-    int rc = 0;
-#define SCAN(CFG, R0, R1, NS, THR, SOFF, DBG, SP)                                                                    \
-    rc = bf ? launch_scan<true, CFG, false, SP>(ix, filter_dev, R0, R1, qs, nq, NS, nqg, k, kp, THR, mar, SOFF, ns_tot, cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr) \
-            : launch_scan<false, CFG, false, SP>(ix, filter_dev, R0, R1, qs, nq, NS, nqg, k, kp, THR, mar, SOFF, ns_tot, cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
-    // phased tiles: the shipped shape; the dbg library carries both and honours AK_SCAN_MFMA (the product library's ak_debug_set
-    // refuses it, and a value in its environment is ignored, like a forced X / O tile)
-#if AK_DBG_KERNELS
-    const int mfma_forced = switches().scan_mfma.load(std::memory_order_relaxed);
-    const int filt_forced = switches().scan_filter.load(std::memory_order_relaxed) - 1;      // -1 = the arrangement the tile ships on
-#define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)                                                                  \
-    if ((mfma_forced ? mfma_forced : SHIPPED::MFMA) == 32) { using C_ = T<32>; SCAN(C_, R0, R1, NS, THR, SOFF, DBG, SP); }          \
-    else if ((filt_forced < 0 ? SHIPPED::FILT : filt_forced) == 1) { using C_ = T<16, 1>; SCAN(C_, R0, R1, NS, THR, SOFF, DBG, SP); } \
-    else { using C_ = T<16, 0>; SCAN(C_, R0, R1, NS, THR, SOFF, DBG, SP); }
-#else
-#define SCAN_SHAPED(T, SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP) SCAN(SHIPPED, R0, R1, NS, THR, SOFF, DBG, SP)
-#endif
-#define SCAN_ANY(R0, R1, NS, THR, SOFF, DBG, SP)                         \
-    switch (plan.cfg) {                                          \
-        case CFG_L: SCAN(CfgL, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_M: SCAN(CfgM, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_S: SCAN(CfgS, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        AK_SCAN_XO_CASES(SCAN, R0, R1, NS, THR, SOFF, DBG, SP)            \
-        case CFG_P: SCAN_SHAPED(CfgPs, CfgP, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_Q: SCAN_SHAPED(CfgQs, CfgQ, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        case CFG_R: SCAN_SHAPED(CfgRs, CfgR, R0, R1, NS, THR, SOFF, DBG, SP); break;    \
-        default: AK_FAIL(-1, "scan: tile configuration not in this library (X and O: libarchi_hip_dbg.so)"); \
-    }
-    // the int8 plan: one tile, one element type
-#define SCAN8_T(T, R0, R1, NS, THR, SOFF, DBG, SP)                                                                                \
-    rc = launch_scan<true, T, false, SP>(ix, filter_dev, R0, R1, (const uint16_t *)qs8, nq, NS, nqg, k, kp, THR, mar8, SOFF, ns_tot, \
-                                         cand, out_c, thr_slots, DBG, st, 0, 1, dcnt, dthr)
-#if AK_DBG_KERNELS
-    // arrangement of a pass: AK_SCAN_HITQ says which passes run queued, the others -- and all of them without it -- what
-    // AK_SCAN_FILTER says or, unforced, what they ship on (whole tile where that is the queue and the queue is switched off)
-    const int hitq_forced = switches().scan_hitq.load(std::memory_order_relaxed);
-    auto p8_filt = [&](bool seedpass) -> int {
-        const int shipped = seedpass ? SHIP_FILT_P8_SEED : SHIP_FILT_P8;
-        if (hitq_forced && hitq_forced != 4 && (hitq_forced & (seedpass ? 1 : 2))) return 2;
-        if (filt_forced >= 0) return filt_forced;
-        return hitq_forced && shipped == 2 ? 1 : shipped;
-    };
-#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP)                                                         \
-    switch (p8_filt(SP)) {                                                                            \
-        case 0: { using C_ = CfgP8of<SP, 0>; SCAN8_T(C_, R0, R1, NS, THR, SOFF, DBG, SP); } break;    \
-        case 1: { using C_ = CfgP8of<SP, 1>; SCAN8_T(C_, R0, R1, NS, THR, SOFF, DBG, SP); } break;    \
-        default: { using C_ = CfgP8of<SP, 2>; SCAN8_T(C_, R0, R1, NS, THR, SOFF, DBG, SP); } break;   \
-    }
-#else
-#define SCAN8(R0, R1, NS, THR, SOFF, DBG, SP) SCAN8_T(CfgP8, R0, R1, NS, THR, SOFF, DBG, SP)
-#endif
-    long long *dbg0 = nullptr, *dbg1 = nullptr;
     if (want_dbg) {
         if (!ix.dbg_dev) { AK_HIP(hipMalloc((void **)&ix.dbg_dev, 2 * 65536 * 8)); }
         AK_HIP(hipMemsetAsync(ix.dbg_dev, 0, 2 * 65536 * 8, st));
-        dbg0 = ix.dbg_dev; dbg1 = ix.dbg_dev + 65536;
+        s.dbg0 = ix.dbg_dev; s.dbg1 = ix.dbg_dev + 65536;
     }
-    const float *thr_main = nullptr;
-    const float *thr_seed = nullptr;
-    {
-        if (plan.pre_tiles > 0) {
-            // pre-seeding: group maxima over a strided sample -> first thresholds
-#define PRE(CFG)                                                                                                          \
-    rc = bf ? launch_scan<true, CFG, true>(ix, filter_dev, 0, ix.n, qs, nq, plan.pre_slices, nqg, k, kp, nullptr, mar, 0, 0, \
-                                           nullptr, nullptr, gmax, nullptr, st, plan.pre_tiles, plan.pre_stride)         \
-            : launch_scan<false, CFG, true>(ix, filter_dev, 0, ix.n, qs, nq, plan.pre_slices, nqg, k, kp, nullptr, mar, 0, 0, \
-                                            nullptr, nullptr, gmax, nullptr, st, plan.pre_tiles, plan.pre_stride)
-            switch (plan.cfg) {
-                case CFG_L: PRE(CfgL); break;
-                case CFG_M: PRE(CfgM); break;
-                case CFG_S: PRE(CfgS); break;
-#if AK_DBG_KERNELS
-                case CFG_X: PRE(CfgX); break;
-                case CFG_O: PRE(CfgO); break;
-#endif
-                case CFG_P: PRE(CfgP::Shape32); break;      // the pre-seeding launch stays on 32x32x16 whatever the tile ships
-                case CFG_Q: PRE(CfgQ::Shape32); break;
-                case CFG_R: PRE(CfgR::Shape32); break;
-                default: AK_FAIL(-1, "scan: tile configuration not in this library (X and O: libarchi_hip_dbg.so)");
-            }
-#undef PRE
-            if (rc) return rc;
-            k_seed_kth<<<nq, 64, 0, st>>>(gmax, plan.pre_slices * (c.bm / 16), prep, k, thr0);
-            if (i8) k_thr_to_i8<<<(nq + 63) / 64, 64, 0, st>>>(prep, prep8, nq, thr0);      // the 16-bit sample's threshold in int8 units
-            AK_HIP(hipGetLastError());
-            thr_seed = thr0;
-            thr_main = thr0;
-        }
-    }
-    if (nss > 0 && i8) {
-        // int8 seeding pass, then the exact seed threshold: the fused tail re-ranks the best 64 seed candidates of every query
-        // in the reference arithmetic (its usual work, on the lists as they stand before the main pass) and k_seed_exact_thr
-        // turns their exact k-th best into theta. "k-th best approximate score - 3 eps" with the int8 eps lets 10-20 k rows
-        // per query through the main pass (docs/EXPERIMENTS.md, "int8 shadow"); this one about as many as the bf16 plan.
-        SCAN8(0, plan.seed_rows, nss, thr_seed, 0, dbg0, true);
-        if (rc) return rc;
-        rc = fused_tail(ix, queries_dev, nb_dev, nq, k, out_c, (int64_t)ns_tot * kp, d_cnt, d_thr, thr_seed, prep8, fin_i, fin_d, sd_cnt,
-                        sd_cert, nullptr, st);
-        if (rc) return rc;
-        k_seed_exact_thr<<<(nq + 63) / 64, 64, 0, st>>>(fin_d, sd_cnt, prep8, nq, k, ix.metric, thr_seed != nullptr, thr0);
-        AK_HIP(hipGetLastError());
-        thr_main = thr0;
-    } else if (nss > 0) {
-        // seeding pass over rows [0, seed_rows) -> per-query thresholds for the main pass
-        SCAN_ANY(0, plan.seed_rows, nss, thr_seed, 0, dbg0, true);
-        if (rc) return rc;
-        // top-k of the seed candidates (slots [0,nss) of out_c -- or, dense, the lists as they stand; the main pass has not
-        // written yet). Only the k-th best is needed here: k selection rounds, not kp
-        const int64_t seed_in = (int64_t)nss * kp, seed_stride = (int64_t)ns_tot * kp;
-#define KTH(EPT)                                                                                                         \
-    do {                                                                                                                 \
-        if (thr_seed) k_seed_kth_lists<EPT, true><<<nq, 256, 0, st>>>(out_c, seed_in, seed_stride, prep, k, thr0, dcnt);   \
-        else k_seed_kth_lists<EPT, false><<<nq, 256, 0, st>>>(out_c, seed_in, seed_stride, prep, k, thr0, dcnt);           \
-    } while (0)
-        if (seed_in <= 16 * 256) KTH(16);
-        else if (seed_in <= 32 * 256) KTH(32);
-        else if (seed_in <= 64 * 256) KTH(64);
-        else {
-            if (dense) AK_FAIL(-1, "fast_search: dense lists with more than 16384 seed candidates");   // kp = 64, nss <= 256
-            rc = select_topk_strided(out_c, nq, seed_in, seed_stride, k, top_k, top_i, scratch, st);
-            if (rc) return rc;
-            if (thr_seed) k_seed_thr<true><<<(nq + 63) / 64, 64, 0, st>>>(top_k, prep, nq, k, k, thr0);
-            else k_seed_thr<false><<<(nq + 63) / 64, 64, 0, st>>>(top_k, prep, nq, k, k, thr0);
-        }
-#undef KTH
-        AK_HIP(hipGetLastError());
-        thr_main = thr0;
-    }
+    if (plan.pre_tiles > 0 && (rc = s.pre_seed())) return rc;
+    if (plan.ns_seed > 0 && (rc = s.seed_pass())) return rc;
     if (ev0) AK_HIP(hipEventRecord(ev0, st));   // the timed "dominant kernel" is the main-pass launch
-    if (i8) { SCAN8(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false); }
-    else { SCAN_ANY(plan.seed_rows, ix.n, ns, thr_main, nss, dbg1, false); }
-#undef SCAN8
-#undef SCAN8_T
-#undef SCAN_ANY
-#undef SCAN_SHAPED
-#undef SCAN
+    rc = s.scan_pass<false>(plan.seed_rows, ix.n, plan.nslices, s.thr_main, plan.ns_seed, s.dbg1);
     if (rc) return rc;
     if (ev1) AK_HIP(hipEventRecord(ev1, st));
-
-    if (i8) {
-        // the int8 tail: best 512 of the dense list -> exact re-rank against the stored 16-bit rows -> top-k + certificate with
-        // the int8 eps (one cut for the whole query where the slot layout had one threshold per slice)
-        ix.s8_searches.fetch_add(1, std::memory_order_relaxed);
-        k_select_dense<<<nq, SD_THREADS, 0, st>>>(out_c, (int64_t)ns_tot * kp, d_cnt, d_thr, thr_main, kp, top_k, thr_fin);
-        AK_HIP(hipGetLastError());
-        rc = rerank(ix, queries_dev, nb_dev, nq, kp, top_k, rr_k, rr_i, st);
-        if (rc) return rc;
-        k_finalize<8><<<nq, 64, 0, st>>>(top_k, rr_k, rr_i, prep8, nb_dev, thr_fin, 1, k, kp, ix.metric, out_ids_dev, out_dist_dev,
-                                         out_cnt_dev, cert_dev, stats_dev);
-        AK_HIP(hipGetLastError());
-        return 0;
-    }
-    if (dense)
-        return fused_tail(ix, queries_dev, nb_dev, nq, k, out_c, (int64_t)ns_tot * kp, d_cnt, d_thr, thr_main, prep, out_ids_dev,
-                          out_dist_dev, out_cnt_dev, cert_dev, stats_dev, st);
-    rc = select_keys_topk(out_c, nq, (int64_t)ns_tot * kp, (int64_t)ns_tot * kp, kp, top_k, scratch, st);
-    if (rc) return rc;
-    rc = rerank(ix, queries_dev, nb_dev, nq, kp, top_k, rr_k, rr_i, st);
-    if (rc) return rc;
-#define FIN(NS) k_finalize<NS><<<nq, 64, 0, st>>>(top_k, rr_k, rr_i, prep, nb_dev, thr_slots, ns_tot, k, kp, ix.metric, out_ids_dev, \
-                                              out_dist_dev, out_cnt_dev, cert_dev, stats_dev)
-    if (kp <= 64) FIN(1); else if (kp <= 128) FIN(2); else if (kp <= 256) FIN(4); else FIN(8);
-#undef FIN
-    AK_HIP(hipGetLastError());
-    return 0;
+    return s.tail();
 }
 
 }  // namespace ak

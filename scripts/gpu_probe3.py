@@ -3,9 +3,9 @@ import sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 runs = [a.split(":") for a in sys.argv[4:]]   # nq:cfg[:blocks[:ablate]]
-# the product library unless a run needs what only libarchi_hip_dbg.so has (tiles X / O, the ablation switch); ARCHI_HIP_DBG=1 in
+# the product library unless a run needs what only libarchi_hip_dbg.so has (the ablation switch); ARCHI_HIP_DBG=1 in
 # the environment selects the dbg library for everything (its main-pass kernel keeps the round-4 filter: the A/B reference)
-if any((len(r) > 1 and r[1][:1] in ("X", "O")) or len(r) > 3 for r in runs):
+if any(len(r) > 3 for r in runs):
     os.environ.setdefault("ARCHI_HIP_DBG", "1")
 from archi_amd import _lib
 from archi_amd.index import HipIndex

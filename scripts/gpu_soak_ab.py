@@ -1,11 +1,11 @@
 """Soak of the phased scan kernels (round 3): EVERY query of large batches through the default plan (phased 256x256 /
-256x192 / 256x128 tiles), through the 256x192 tile forced (AK_SCAN_CFG=R) and through the in-step kernels of rounds 1-2 (AK_SCAN_CFG=X / L) -- two independent K-loop structures that
+256x192 / 256x128 tiles), through the 256x192 tile forced (AK_SCAN_CFG=R) and through the in-step 256 x 128 kernel of rounds 1-2 (AK_SCAN_CFG=L) -- two independent K-loop structures that
 must return identical ids and float8 distance bits -- repeated with fresh query sets (a staging race would be timing
 dependent).  python3 scripts/gpu_soak_ab.py [seconds]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-os.environ.setdefault("ARCHI_HIP_DBG", "1")     # the in-step reference tile X lives in libarchi_hip_dbg.so (make -C archi_amd/csrc dbg)
+os.environ.setdefault("ARCHI_HIP_DBG", "1")     # libarchi_hip_dbg.so (make -C archi_amd/csrc dbg); ARCHI_HIP_DBG= (empty) soaks the product library
 from archi_amd import _lib
 from archi_amd.index import HipIndex
 
@@ -28,9 +28,9 @@ for n, d, dtype in shapes:
         _lib.debug_set("AK_SCAN_CFG", None)
         plan = ix.scan_plan(nq, k)["cfg_name"]
         a = ix.search(q, k, return_stats=True)
-        # in-step reference: tile X exists only in the dbg library; with ARCHI_HIP_DBG= (empty) the PRODUCT library is soaked against its
-        # own in-step 256 x 128 tile (round 5: the product's phased kernels carry the v_max3 filter and the carried lane constants)
-        _lib.debug_set("AK_SCAN_CFG", "X" if (nq > 256 and _lib.is_dbg_library()) else "L")
+        # in-step reference: either library is soaked against its own in-step 256 x 128 tile (round 5: the product's phased kernels
+        # carry the v_max3 filter and the carried lane constants)
+        _lib.debug_set("AK_SCAN_CFG", "L")
         b = ix.search(q, k, return_stats=True)
         _lib.debug_set("AK_SCAN_CFG", "R")                   # the 256 x 192 phased tile, whatever the plan would pick
         c = ix.search(q, k, return_stats=True)

@@ -116,6 +116,22 @@ def test_index_bookkeeping_under_sanitizers(target, binary):
     assert p.returncode == 0 and out.rstrip().endswith("index_book: ok") and "Sanitizer" not in out, out[-3000:]
 
 
+def test_scan_plan_and_workspace_layout_under_sanitizers():
+    """The host side of the kNN scan that is pure arithmetic -- tile choice, slices, seeding and pre-seeding shares, the int8 plan's
+    eligibility, and the one layout of the workspace (csrc/scan_plan.h) -- driven alone by tests/native/scan_plan_main.cpp: every
+    plan recorded in tests/golden/scan_plans.txt (taken from the code before the plan moved into the header) is reproduced field
+    by field, `bytes` included; and the invariants the launches rely on (regions aligned, ascending and inside `bytes`; k' within
+    the append buffers; the seeding and pre-seeding limits; the 16-bit fallback of every int8 plan fits that plan's workspace) hold
+    on those cases and on a seeded random sweep. -fsanitize=address,undefined; any report or failed check exits non-zero."""
+    import subprocess
+    csrc = os.path.join(ROOT, "archi_amd", "csrc")
+    subprocess.check_call(["make", "-s", "-C", csrc, "asan-plan"])
+    p = subprocess.run([os.path.join(csrc, "build", "scan_plan_asan"), os.path.join(ROOT, "tests", "golden", "scan_plans.txt")],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = p.stdout.decode("utf-8", "replace")
+    assert p.returncode == 0 and out.rstrip().splitlines()[-1] == "scan_plan: ok" and "Sanitizer" not in out, out[-3000:]
+
+
 def test_scan_filter_reads_mfma_results_only_behind_the_settle_fence(tmp_path):
     """Round-5 advisor finding: the main-pass filter reads raw MFMA accumulators through inline-asm v_max3_f32, which LLVM's
     hazard recogniser does not cover. The fix is structural (mfma_settle in scan.hip: every accumulator tied through one asm

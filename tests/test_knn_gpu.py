@@ -251,8 +251,7 @@ def scan_cfg():
 
 @pytest.mark.parametrize("cfg", ["P", "Q", "R", "L", "M", "S"])
 def test_every_scan_tile_config_matches_oracle(hip, cfg, scan_cfg):
-    """The tile configuration is a speed choice only: results are identical. (The A/B reference tiles X and O live in
-    libarchi_hip_dbg.so: test_reference_tiles_of_the_dbg_library_match_oracle.)"""
+    """The tile configuration is a speed choice only: results are identical."""
     scan_cfg(cfg)
     ix, stored = _gen_index("bf16", "cosine", 70001, 192)      # ragged: n % 256 != 0, several slices
     q = ko.gen_rows(4321, 1, 0, 70, 192, True, "f32")
@@ -261,37 +260,6 @@ def test_every_scan_tile_config_matches_oracle(hip, cfg, scan_cfg):
     assert st["certified"] == 70, st
     assert np.array_equal(gi, oi) and np.array_equal(gd, od)
     ix.close()
-
-
-def test_reference_tiles_of_the_dbg_library_match_oracle():
-    """The A/B reference tiles X (256 x 256, in-step K-loop of rounds 1-2) and O (the first 128 x 128 version) are instantiated in
-    libarchi_hip_dbg.so only; a child process loads that library (one library per process) and holds both to the oracle."""
-    import subprocess, sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    if not os.path.exists(os.path.join(os.path.dirname(here), "archi_amd", "lib", "libarchi_hip_dbg.so")):
-        pytest.skip("libarchi_hip_dbg.so not built (make -C archi_amd/csrc dbg)")
-    code = (
-        "import sys, numpy as np\n"
-        f"sys.path.insert(0, {os.path.dirname(here)!r})\n"
-        "from archi_amd import _lib\n"
-        "from archi_amd.index import HipIndex\n"
-        "from oracle import knn_oracle as ko\n"
-        "assert _lib.is_dbg_library()\n"
-        "ix = HipIndex(192, 70001, dtype='bf16', metric='cosine', device=0)\n"
-        "ix.generate(seed=1234, n=70001, normalise=True)\n"
-        "stored = ko.gen_rows(1234, 0, 0, 70001, 192, True, 'bf16')\n"
-        "q = ko.gen_rows(4321, 1, 0, 70, 192, True, 'f32')\n"
-        "oi, od, oc = ko.search(stored, q, 10, 'cosine')\n"
-        "for cfg in ('X', 'O'):\n"
-        "    _lib.debug_set('AK_SCAN_CFG', cfg)\n"
-        "    gi, gd, gc, st = ix.search(q, 10, mode='fast_only', return_stats=True)\n"
-        "    assert st['certified'] == 70, (cfg, st)\n"
-        "    assert np.array_equal(gi, oi) and np.array_equal(gd, od), cfg\n"
-        "print('ok')\n")
-    env = {k: v for k, v in os.environ.items() if not k.startswith("AK_")}
-    env["ARCHI_HIP_DBG"] = "1"
-    p = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0 and b"ok" in p.stdout, p.stderr.decode("utf-8", "replace")[-3000:]
 
 
 @pytest.mark.parametrize("metric", METRICS)

@@ -15,12 +15,12 @@ import pytest
 from scripts.kernel_resources import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCAN_HIP = os.path.join(ROOT, "archi_amd", "csrc", "scan.hip")
+SCAN_PLAN_H = os.path.join(ROOT, "archi_amd", "csrc", "scan_plan.h")      # the tile types: constants and static_asserts only
 P8 = re.compile(r"void ak::k_scan<true, ak::(CfgP8[fg]?), false, (true|false), (true|false)>")
 
 
 def _const(name):
-    m = re.search(rf"\b{name} = (\d+)\b", open(SCAN_HIP).read())
+    m = re.search(rf"\b{name} = (\d+)\b", open(SCAN_PLAN_H).read())
     assert m, name
     return int(m.group(1))
 
@@ -60,7 +60,7 @@ def test_the_queued_tile_fits_the_lds():
     thresholds, counts, margins and triggers, the request word and the block bounds -- 139 792 bytes -- plus [8 waves][HQ_WORDS][HQ_SLOTS]
     words. The compiler holds ScanCfg to the same figure (static_assert `LDS budget`); the kernels' LDS is dynamic, so the resource
     remark does not show it."""
-    src = open(SCAN_HIP).read()
+    src = open(SCAN_PLAN_H).read()
     words, slots = _const("HQ_WORDS"), _const("HQ_SLOTS")
     assert words == 9 and slots == 64                                   # eight dot products + (site, lane); one slot per lane of the drain
     common = 2 * (256 * 128 + 256 * 128) + (4 * 256 + 4 * 256 + 4 + 128) * 4
