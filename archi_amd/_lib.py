@@ -365,6 +365,26 @@ KTS_SYMBOLS = [
     ("ak_kts_rr_choice", _I, [_P]),
 ]
 
+# the float32 and split-bf16 parity modes' launchers, one launch each (tests/test_parity_kernels_gpu.py): libarchi_hip_dbg.so only, a
+# fourth set of its own (ak_ktp_*)
+KTP_SYMBOLS = [
+    ("ak_ktp_gemm_f32", _I, [_I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
+    ("ak_ktp_gemm_x3", _I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
+    ("ak_ktp_gemm_f32_scalar", _I, [_I, _P, _P, _P, _I, _I, _I, _P, _P]),      # k32_gemm, the cross-check k32m_gemm's comment names
+    ("ak_ktp_attn_f32", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    ("ak_ktp_attn_x3", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    ("ak_ktp_attn_x3_split", _I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    ("ak_ktp_split_hilo", _I, [_P, _I64, _P, _P, _P]),
+    ("ak_ktp_split_rows", _I, [_P, _I64, _I, _P, _P]),
+    ("ak_ktp_embed_split", _I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P]),
+    ("ak_ktp_add_ln_split", _I, [_P, _I, _P, _I64, _I, _P, _P, _F, _P, _P, _P]),
+    ("ak_ktp_embed_f32", _I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    ("ak_ktp_add_ln_f32", _I, [_P, _P, _I64, _I, _P, _P, _F, _P, _P]),
+    ("ak_ktp_pool_f32", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("ak_ktp_gemm_x3w", _I, [_I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    ("ak_ktp_gemm_ln_x3", _I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+]
+
 
 def load() -> ctypes.CDLL:
     """dlopen the library and bind every declared symbol (no GPU needed)."""
@@ -393,7 +413,7 @@ def load() -> ctypes.CDLL:
                 fn.restype = res
                 fn.argtypes = args
             if path != LIB_PATH:
-                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS + KTS_SYMBOLS:
+                for name, res, args in KT_SYMBOLS + KTG_SYMBOLS + KTS_SYMBOLS + KTP_SYMBOLS:
                     fn = getattr(lib, name)
                     fn.restype = res
                     fn.argtypes = args

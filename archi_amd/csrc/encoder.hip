@@ -509,6 +509,36 @@ __global__ __launch_bounds__(256) void k32_attn(const float *__restrict__ qkv, c
     }
 }
 
+// The launches of the parity modes' row kernels: forward_f32 below and the single-launch wrappers of kernel_test.hip (ak_ktp_*) both
+// call these, so the kernel-level tests run the grid, block and arguments the forward pass runs. H <= 1024 (16 values per lane).
+int launch_embed_f32(const int *ids, int64_t T, int S, int H, int vocab, const float *word, const float *pos, const float *type, const float *g,
+                     const float *b, float eps, float *x, const int *posid, hipStream_t st) {
+    k32_embed<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(ids, (int)T, S, H, vocab, word, pos, type, g, b, eps, x, posid);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_add_ln_f32(const float *x, const float *r, int64_t T, int H, const float *g, const float *b, float eps, float *y, hipStream_t st) {
+    k32_add_ln<<<(unsigned)((T + 3) / 4), 256, 0, st>>>(x, r, (int)T, H, g, b, eps, y);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+// float32 rows [B][S][H] -> out [B][H] (k_pool<false>: S <= 512, H % 8 == 0, H <= 1024)
+int launch_pool_f32(const float *x, const int *mask, int B, int S, int H, int pooling, int normalise, float *out, hipStream_t st) {
+    k_pool<false><<<B, 256, 0, st>>>(x, nullptr, mask, S, H, pooling, normalise, out);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+#if AK_DBG_KERNELS
+// the scalar GEMM as forward_f32's AK_F32_SCALAR path launches it: Y [T][N], N % 64 == 0, K % 16 == 0
+int launch_gemm_f32_scalar(int gelu, const float *X, const float *W, const float *bias, int T, int N, int K, float *Y, hipStream_t st) {
+    const dim3 grid((unsigned)(N / 64), (unsigned)((T + 63) / 64));
+    if (gelu) k32_gemm<true><<<grid, 256, 0, st>>>(X, W, bias, T, N, K, Y);
+    else k32_gemm<false><<<grid, 256, 0, st>>>(X, W, bias, T, N, K, Y);
+    AK_HIP(hipGetLastError());
+    return 0;
+}
+#endif
+
 // the whole forward pass in float32; ws (grown here) holds x | y | qkv | ctx | f
 static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16_t *const *x3, const int *ids, const int *mask, int B, int S,
                        int pooling, int normalise, float *out, float **ws, size_t *ws_bytes, hipStream_t st);
@@ -629,14 +659,13 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
         *ws_bytes = need;
     }
     float *x = *ws, *y = x + Ta * H, *ctx = y + Ta * H, *qkv = ctx + Ta * H, *sep = qkv + Ta * 3 * H, *f = sep + Ta * 3 * H;
-    const unsigned rows4 = (unsigned)((T + 3) / 4);
     if (!x3_tiles) {
-        k32_embed<<<rows4, 256, 0, st>>>(ids, (int)T, S, H, c.vocab_size, (const float *)w[0], (const float *)w[1], (const float *)w[2],
-                                         (const float *)w[3], (const float *)w[4], c.ln_eps, x, posid);
-        AK_HIP(hipGetLastError());
+        if (int rc = launch_embed_f32(ids, T, S, H, c.vocab_size, (const float *)w[0], (const float *)w[1], (const float *)w[2], (const float *)w[3],
+                                      (const float *)w[4], c.ln_eps, x, posid, st)) return rc;
     }
     // the matrix-core kernels (encoder_f32.hip); the scalar kernels above stay as their cross-check in libarchi_hip_dbg.so
-    // (AK_F32_SCALAR=1 there; the GEMM is bit-identical, the attention agrees to float32 rounding)
+    // (AK_F32_SCALAR=1 there; the GEMM is bit-identical -- held launch by launch by tests/test_parity_kernels_gpu.py --, the attention
+    // agrees to float32 rounding)
     static const bool scalar = dbg_env_int("AK_F32_SCALAR", 0) != 0;
     if (x3_tiles) {
         // Activations between the launches as bf16 [hi | lo] rows beside the float32 residual stream: xs (LayerNorm output), cs
@@ -680,9 +709,7 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
                 if (launch_add_ln_split(y2, Dn, x, T, H, (const float *)p[14], (const float *)p[15], c.ln_eps, x, xs, st)) return -10;
             }
         }
-        k_pool<false><<<B, 256, 0, st>>>(x, nullptr, mask, S, H, pooling, normalise, out);
-        AK_HIP(hipGetLastError());
-        return 0;
+        return launch_pool_f32(x, mask, B, S, H, pooling, normalise, out, st);
     }
     if ((x3 || !scalar) && f32_mfma_supported(H, I, c.heads)) {
         for (int l = 0; l < L; l++) {
@@ -704,40 +731,33 @@ static int forward_f32(const AkBertConfig &c, const void *const *w, const uint16
             if (s3 && !x3_attn_f32) { if (launch_attn_x3(qkv, mask, B, S, H, c.heads, ctx, st, rel2)) return -10; }
             else if (launch_attn_f32(qkv, mask, B, S, H, c.heads, ctx, st, rel)) return -10;
             if (gemm(2, ctx, 3, 6, (const float *)p[7], x, H, H, y, H, 0)) return -10;      // + residual
-            k32_add_ln<<<rows4, 256, 0, st>>>(y, nullptr, (int)T, H, (const float *)p[8], (const float *)p[9], c.ln_eps, x);
-            AK_HIP(hipGetLastError());
+            if (int rc = launch_add_ln_f32(y, nullptr, T, H, (const float *)p[8], (const float *)p[9], c.ln_eps, x, st)) return rc;
             if (gemm(1, x, 4, 10, (const float *)p[11], nullptr, I, H, f, I, 0)) return -10;  // erf GELU
             if (gemm(2, f, 5, 12, (const float *)p[13], x, H, I, y, H, 0)) return -10;
-            k32_add_ln<<<rows4, 256, 0, st>>>(y, nullptr, (int)T, H, (const float *)p[14], (const float *)p[15], c.ln_eps, x);
-            AK_HIP(hipGetLastError());
+            if (int rc = launch_add_ln_f32(y, nullptr, T, H, (const float *)p[14], (const float *)p[15], c.ln_eps, x, st)) return rc;
         }
-        k_pool<false><<<B, 256, 0, st>>>(x, nullptr, mask, S, H, pooling, normalise, out);
-        AK_HIP(hipGetLastError());
-        return 0;
+        return launch_pool_f32(x, mask, B, S, H, pooling, normalise, out, st);
     }
 #if AK_DBG_KERNELS
     if (rel) AK_FAIL(-1, "ak_encoder_forward (precision f32): the scalar attention kernel has no relative-position bias");
-    const dim3 gt((unsigned)((T + 63) / 64));
     for (int l = 0; l < L; l++) {
         const void *const *p = w + 5 + 16 * l;
         // q, k, v: three GEMMs (the caller's three weight matrices as they lie), then interleaved to qkv[t] = q[t] | k[t] | v[t]
         for (int j = 0; j < 3; j++)
-            k32_gemm<false><<<dim3(H / 64, gt.x), 256, 0, st>>>((const float *)x, (const float *)p[2 * j], (const float *)p[2 * j + 1], (int)T, H, H, sep + (int64_t)j * T * H);
+            if (int rc = launch_gemm_f32_scalar(0, x, (const float *)p[2 * j], (const float *)p[2 * j + 1], (int)T, H, H, sep + (int64_t)j * T * H, st)) return rc;
         AK_HIP(hipGetLastError());
         for (int j = 0; j < 3; j++)
             AK_HIP(hipMemcpy2DAsync(qkv + (int64_t)j * H, (size_t)3 * H * 4, sep + (int64_t)j * T * H, (size_t)H * 4, (size_t)H * 4, (size_t)T,
                                     hipMemcpyDeviceToDevice, st));
         k32_attn<<<(unsigned)(((int64_t)B * c.heads * S + 3) / 4), 256, 0, st>>>(qkv, mask, B, S, H, c.heads, ctx);
-        k32_gemm<false><<<dim3(H / 64, gt.x), 256, 0, st>>>(ctx, (const float *)p[6], (const float *)p[7], (int)T, H, H, y);
-        k32_add_ln<<<rows4, 256, 0, st>>>(y, x, (int)T, H, (const float *)p[8], (const float *)p[9], c.ln_eps, x);
-        k32_gemm<true><<<dim3(I / 64, gt.x), 256, 0, st>>>(x, (const float *)p[10], (const float *)p[11], (int)T, I, H, f);
-        k32_gemm<false><<<dim3(H / 64, gt.x), 256, 0, st>>>(f, (const float *)p[12], (const float *)p[13], (int)T, H, I, y);
-        k32_add_ln<<<rows4, 256, 0, st>>>(y, x, (int)T, H, (const float *)p[14], (const float *)p[15], c.ln_eps, x);
+        if (int rc = launch_gemm_f32_scalar(0, ctx, (const float *)p[6], (const float *)p[7], (int)T, H, H, y, st)) return rc;
+        if (int rc = launch_add_ln_f32(y, x, T, H, (const float *)p[8], (const float *)p[9], c.ln_eps, x, st)) return rc;
+        if (int rc = launch_gemm_f32_scalar(1, x, (const float *)p[10], (const float *)p[11], (int)T, I, H, f, st)) return rc;
+        if (int rc = launch_gemm_f32_scalar(0, f, (const float *)p[12], (const float *)p[13], (int)T, H, I, y, st)) return rc;
+        if (int rc = launch_add_ln_f32(y, x, T, H, (const float *)p[14], (const float *)p[15], c.ln_eps, x, st)) return rc;
         AK_HIP(hipGetLastError());
     }
-    k_pool<false><<<B, 256, 0, st>>>(x, nullptr, mask, S, H, pooling, normalise, out);
-    AK_HIP(hipGetLastError());
-    return 0;
+    return launch_pool_f32(x, mask, B, S, H, pooling, normalise, out, st);
 #else
     AK_FAIL(-1, "ak_encoder_forward (precision f32): hidden / intermediate sizes must be multiples of 128, head size 32 or 64");
 #endif

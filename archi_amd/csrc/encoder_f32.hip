@@ -13,7 +13,8 @@
 //               global loads are issued before the current step's 64 MFMAs); rows padded to 33 floats: the per-lane
 //               ds_read_b32 of an operand (32 rows x one k) touches 32 banks. Every output is ONE fmaf chain over k
 //               ascending, started from zero, bias added last: bit-identical to the scalar kernel it replaces (k32_gemm, kept
-//               in libarchi_hip_dbg.so as the cross-check).
+//               in libarchi_hip_dbg.so as the cross-check: tests/test_parity_kernels_gpu.py runs both on one case list and holds
+//               epilogue 0 and the erf GELU of epilogue 1 to each other bit for bit).
 //   k32m_attn   softmax(q k^T / sqrt(hd) + mask) v per (sequence, head, 128 queries): keys on M like the bf16 kernels (a lane
 //               owns a query column of the 32 x 32 score tile, 16 keys per register set), online softmax in float32 with expf,
 //               P feeds P.V straight from the score registers: lane halves hold the two k-slots of a 32x32x2 B operand, so
@@ -310,7 +311,9 @@ __global__ __launch_bounds__(256, 2) void k32m_attn(const float *__restrict__ qk
 // one. Here every GEMM operand is split  x = hi + lo  (hi = bf16(x), lo = bf16(x - hi): 16 mantissa bits between them) and the
 // product is  hi.hi + lo.hi + hi.lo  on v_mfma_f32_32x32x16_bf16 into ONE float32 accumulator -- three bf16 MFMAs (3 x 32
 // cycles per 32 x 32 x 16) where the float32 path issues eight 32x32x2 MFMAs (8 x 64 cycles). What is dropped: lo.lo and the
-// 2^-18 |x| each split leaves behind, ~4e-6 relative per product with random sign; measured on the CPU emulation of this
+// 2^-18 |x| each split leaves behind, ~4e-6 relative per product with random sign (typical values; as bounds, with u = 2^-8: the
+// remainder of a split is at most u^2 |x| = 2^-16 |x| and a product loses at most (3 u^2 + 3 u^3) |x| |w| = 4.6e-5 |x| |w|, which is
+// what tests/parity_kernel_refs.py derives and the kernel-level tests hold every output to); measured on the CPU emulation of this
 // arithmetic (random-init MiniLM / bge-base, against float64): max |delta| 1-1.7e-6 per embedding component, |delta score|
 // <= 1.2e-6 -- the float32 path itself sits at 1e-7. Everything between the GEMMs (LayerNorm, softmax, erf GELU, residuals,
 // pooling) stays float32, and attention is the float32 kernel above.
@@ -830,6 +833,13 @@ int launch_add_ln_split(const float *y, int ldy, const float *r, int64_t T, int 
 
 // grid of the float32-grade attention kernels: (sequence, head) groups dealt over the 8 XCDs, a group's query blocks 8 apart
 static unsigned attn_grid(int B, int heads, int nqb) { return (unsigned)(((int64_t)B * heads + 7) / 8 * 8 * nqb); }
+// THE BIAS BAND AND S. Both attention kernels copy band[i], i < S + 128, into sBias[512 + 128]: with a table, S must not exceed 512.
+// Every caller guarantees it: the only ones are forward_f32's three call sites (encoder.hip), reached from ak_encoder_forward and
+// ak_encoder_forward_lens, which refuse S > max(512, pos_max_seq); pos_max_seq > 512 is accepted by ak_encoder_set_positions_from_ids at
+// precision bf16 only (forward_f32 is the path of precisions f32 and bf16x3), and that call and ak_encoder_set_rel_bias refuse each
+// other. So S <= 512 holds on this path with or without a table. The launchers say it once more for any caller to come (and for
+// the single-launch test wrappers): a table with S > 512 is an error code, never a launch.
+static bool attn_rel_fits(const float *rel, int S) { return !rel || S <= 512; }
 
 bool f32_mfma_supported(int H, int I, int heads) {
     const int hd = heads > 0 ? H / heads : 0;
@@ -855,6 +865,7 @@ int launch_gemm_f32(int epi, const float *X, const float *W, const float *bias, 
 }
 
 int launch_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel) {
+    if (!attn_rel_fits(rel, S)) AK_FAIL(-1, "launch_attn_x3: a relative-position table needs S <= 512");
     const int hd = H / heads;
     const int nqb = (S + 127) / 128;
     const unsigned grid = attn_grid(B, heads, nqb);
@@ -866,6 +877,7 @@ int launch_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int h
 }
 int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, hipStream_t st,
                          const float *rel) {
+    if (!attn_rel_fits(rel, S)) AK_FAIL(-1, "launch_attn_x3_split: a relative-position table needs S <= 512");
     const int hd = H / heads;
     const int nqb = (S + 127) / 128;
     const unsigned grid = attn_grid(B, heads, nqb);
@@ -877,6 +889,7 @@ int launch_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int 
 }
 
 int launch_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel) {
+    if (!attn_rel_fits(rel, S)) AK_FAIL(-1, "launch_attn_f32: a relative-position table needs S <= 512");
     const int hd = H / heads;
     const int nqb = (S + 127) / 128;
     const unsigned grid = attn_grid(B, heads, nqb);

@@ -132,7 +132,17 @@ int launch_gemm_ln_x3(const GemmLnArgs &a, hipStream_t st);   // split-bf16 oper
 bool f32_mfma_supported(int H, int I, int heads);
 int launch_gemm_f32(int epi, const float *X, const float *W, const float *bias, const float *R, int T, int N, int K, float *Y, int ldc,
                     int col0, hipStream_t st);
-// rel (launch_attn_f32: natural domain; launch_attn_x3 / _split: base 2): the per-distance bias table (AttnArgs::rel), or NULL
+// the row kernels of the parity modes' forward pass (encoder.hip: k32_embed, k32_add_ln, k_pool<false>), launched as forward_f32 launches them
+int launch_embed_f32(const int *ids, int64_t T, int S, int H, int vocab, const float *word, const float *pos, const float *type, const float *g,
+                     const float *b, float eps, float *x, const int *posid, hipStream_t st);
+int launch_add_ln_f32(const float *x, const float *r, int64_t T, int H, const float *g, const float *b, float eps, float *y, hipStream_t st);
+int launch_pool_f32(const float *x, const int *mask, int B, int S, int H, int pooling, int normalise, float *out, hipStream_t st);
+#if AK_DBG_KERNELS
+// the scalar float32 GEMM (k32_gemm<gelu != 0>), the cross-check of launch_gemm_f32: Y [T][N], N % 64 == 0, K % 16 == 0
+int launch_gemm_f32_scalar(int gelu, const float *X, const float *W, const float *bias, int T, int N, int K, float *Y, hipStream_t st);
+#endif
+// rel (launch_attn_f32: natural domain; launch_attn_x3 / _split: base 2): the per-distance bias table (AttnArgs::rel), or NULL.
+// With a table, S <= 512: the kernels keep a head's bias band of S + 128 floats in 640 floats of LDS (see attn_rel_fits, encoder_f32.hip).
 int launch_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, hipStream_t st, const float *rel = nullptr);
 // split-bf16 parity mode (precision 2): W as bf16 hi + lo (split_hilo, once), X float32 split on its way into LDS; three bf16
 // MFMAs per product into one float32 accumulator (encoder_f32.hip k3_gemm); epilogues as launch_gemm_f32

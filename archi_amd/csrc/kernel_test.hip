@@ -437,4 +437,120 @@ extern "C" int ak_kts_rr_choice(void *index) {
     return rerank_takes_panel(*(Index *)index) ? 1 : 0;
 }
 
+// ---- the float32 and split-bf16 parity modes (tests/test_parity_kernels_gpu.py). Named ak_ktp_*: a set of their own, like ak_ktg_* and
+// ak_kts_*. Each wrapper hands its arguments to the launcher forward_f32 calls; it refuses only what forward_f32 and the handle's
+// create guarantee (positive sizes, S <= 512, rows of whole float4, a residual where the epilogue reads one), so that a mistaken test shape
+// cannot leave a buffer. Shapes the launchers themselves refuse (N % 128, K % 32, head size 48, ...) reach them and come back as their code ----
+static bool ktp_gemm(int epi, const void *X, const void *W, const void *bias, const void *R, int T, int N, int K, const void *Y, int ldc, int col0) {
+    return X && W && bias && Y && epi >= 0 && epi <= 2 && (epi != 2 || R) && T > 0 && N > 0 && K > 0 && col0 >= 0 && col0 % 4 == 0 && ldc % 4 == 0 &&
+           (int64_t)col0 + N <= ldc;
+}
+extern "C" int ak_ktp_gemm_f32(int epi, const float *X, const float *W, const float *bias, const float *R, int T, int N, int K, float *Y, int ldc,
+                               int col0, void *stream) {
+    AK_BIND();
+    if (!ktp_gemm(epi, X, W, bias, R, T, N, K, Y, ldc, col0)) AK_FAIL(-1, "ak_ktp_gemm_f32: bad arguments");
+    return launch_gemm_f32(epi, X, W, bias, R, T, N, K, Y, ldc, col0, (hipStream_t)stream);
+}
+extern "C" int ak_ktp_gemm_x3(int epi, const float *X, const uint16_t *Whi, const uint16_t *Wlo, const float *bias, const float *R, int T, int N,
+                              int K, float *Y, int ldc, int col0, void *stream) {
+    AK_BIND();
+    if (!ktp_gemm(epi, X, Whi, bias, R, T, N, K, Y, ldc, col0) || !Wlo) AK_FAIL(-1, "ak_ktp_gemm_x3: bad arguments");
+    return launch_gemm_x3(epi, X, Whi, Wlo, bias, R, T, N, K, Y, ldc, col0, (hipStream_t)stream);
+}
+// the scalar kernel the comment of k32m_gemm names as its cross-check: k32_gemm<gelu != 0>, Y [T][N]
+extern "C" int ak_ktp_gemm_f32_scalar(int gelu, const float *X, const float *W, const float *bias, int T, int N, int K, float *Y, void *stream) {
+    AK_BIND();
+    if (!X || !W || !bias || !Y || T <= 0 || N <= 0 || K <= 0 || N % 64 || K % 16) AK_FAIL(-1, "ak_ktp_gemm_f32_scalar: N % 64 == 0, K % 16 == 0");
+    return launch_gemm_f32_scalar(gelu, X, W, bias, T, N, K, Y, (hipStream_t)stream);
+}
+
+static bool ktp_attn(const void *qkv, const void *mask, const void *out, int B, int S, int H, int heads, int ldq) {
+    return qkv && mask && out && B > 0 && S > 0 && S <= 512 && heads > 0 && H > 0 && H % heads == 0 && (H / heads) % 4 == 0 && ldq >= 3 * H && ldq % 4 == 0 &&
+           (int64_t)B * S <= 0x7fffffff;
+}
+// qkv [B * S][3 H] float32 (q | k | v), mask [B][S], ctx [B * S][H]; rel: [heads][REL_ROW] floats (natural domain) or NULL
+extern "C" int ak_ktp_attn_f32(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, const float *rel, void *stream) {
+    AK_BIND();
+    if (!ktp_attn(qkv, mask, ctx, B, S, H, heads, 3 * H)) AK_FAIL(-1, "ak_ktp_attn_f32: bad arguments");
+    return launch_attn_f32(qkv, mask, B, S, H, heads, ctx, (hipStream_t)stream, rel);
+}
+// rel: the table times log2(e) (the base-2 kernel)
+extern "C" int ak_ktp_attn_x3(const float *qkv, const int *mask, int B, int S, int H, int heads, float *ctx, const float *rel, void *stream) {
+    AK_BIND();
+    if (!ktp_attn(qkv, mask, ctx, B, S, H, heads, 3 * H)) AK_FAIL(-1, "ak_ktp_attn_x3: bad arguments");
+    return launch_attn_x3(qkv, mask, B, S, H, heads, ctx, (hipStream_t)stream, rel);
+}
+// qkv rows of ldq >= 3 H floats, ctx2 [B * S][2 H] bf16 = [hi | lo]
+extern "C" int ak_ktp_attn_x3_split(const float *qkv, int ldq, const int *mask, int B, int S, int H, int heads, uint16_t *ctx2, const float *rel,
+                                    void *stream) {
+    AK_BIND();
+    if (!ktp_attn(qkv, mask, ctx2, B, S, H, heads, ldq)) AK_FAIL(-1, "ak_ktp_attn_x3_split: bad arguments");
+    return launch_attn_x3_split(qkv, ldq, mask, B, S, H, heads, ctx2, (hipStream_t)stream, rel);
+}
+
+extern "C" int ak_ktp_split_hilo(const float *w, long long n, uint16_t *hi, uint16_t *lo, void *stream) {
+    AK_BIND();
+    if (!w || !hi || !lo || n <= 0) AK_FAIL(-1, "ak_ktp_split_hilo: bad arguments");
+    return split_hilo(w, n, hi, lo, (hipStream_t)stream);
+}
+extern "C" int ak_ktp_split_rows(const float *x, long long rows, int K, uint16_t *out, void *stream) {
+    AK_BIND();
+    if (!x || !out || rows <= 0 || K <= 0) AK_FAIL(-1, "ak_ktp_split_rows: bad arguments");
+    return split_rows(x, rows, K, out, (hipStream_t)stream);
+}
+
+static bool ktp_rows(long long T, int H) { return T > 0 && T <= 0x7fffffff && H > 0; }
+// word [vocab][H], pos [>= S rows, or every row posid names][H], type [H]; out [T][H] float32, out2 [T][2 H] bf16
+extern "C" int ak_ktp_embed_split(const int *ids, long long T, int S, int H, int vocab, const float *word, const float *pos, const float *type,
+                                  const float *g, const float *b, float eps, float *out, uint16_t *out2, const int *posid, void *stream) {
+    AK_BIND();
+    if (!ids || !word || !pos || !type || !g || !b || !out || !out2 || !ktp_rows(T, H) || S <= 0 || vocab <= 0) AK_FAIL(-1, "ak_ktp_embed_split: bad arguments");
+    return launch_embed_split(ids, T, S, H, vocab, word, pos, type, g, b, eps, out, out2, (hipStream_t)stream, posid);
+}
+extern "C" int ak_ktp_add_ln_split(const float *y, int ldy, const float *r, long long T, int H, const float *g, const float *b, float eps, float *out,
+                                   uint16_t *out2, void *stream) {
+    AK_BIND();
+    if (!y || !g || !b || !out || !out2 || !ktp_rows(T, H) || ldy < H || ldy % 4) AK_FAIL(-1, "ak_ktp_add_ln_split: bad arguments");
+    return launch_add_ln_split(y, ldy, r, T, H, g, b, eps, out, out2, (hipStream_t)stream);
+}
+// the launches forward_f32 makes itself (encoder.hip launch_embed_f32 / launch_add_ln_f32 / launch_pool_f32)
+extern "C" int ak_ktp_embed_f32(const int *ids, long long T, int S, int H, int vocab, const float *word, const float *pos, const float *type,
+                                const float *g, const float *b, float eps, float *x, const int *posid, void *stream) {
+    AK_BIND();
+    if (!ids || !word || !pos || !type || !g || !b || !x || !ktp_rows(T, H) || H > 1024 || S <= 0 || vocab <= 0) AK_FAIL(-1, "ak_ktp_embed_f32: bad arguments");
+    return launch_embed_f32(ids, T, S, H, vocab, word, pos, type, g, b, eps, x, posid, (hipStream_t)stream);
+}
+extern "C" int ak_ktp_add_ln_f32(const float *x, const float *r, long long T, int H, const float *g, const float *b, float eps, float *y, void *stream) {
+    AK_BIND();
+    if (!x || !g || !b || !y || !ktp_rows(T, H) || H > 1024) AK_FAIL(-1, "ak_ktp_add_ln_f32: bad arguments");
+    return launch_add_ln_f32(x, r, T, H, g, b, eps, y, (hipStream_t)stream);
+}
+extern "C" int ak_ktp_pool_f32(const float *x, const int *mask, int B, int S, int H, int pooling, int normalise, float *out, void *stream) {
+    AK_BIND();
+    if (!x || !mask || !out || B <= 0 || B > 65535 || S <= 0 || S > 512 || H <= 0 || H % 8 || H > 1024 || (pooling != AK_POOL_MEAN && pooling != AK_POOL_CLS))
+        AK_FAIL(-1, "ak_ktp_pool_f32: bad arguments");
+    return launch_pool_f32(x, mask, B, S, H, pooling, normalise, out, (hipStream_t)stream);
+}
+
+// launch_gemm_x3w: X [T][2 K1], W [N][2 K1] bf16 rows [hi | lo], bias [N]; mode 5 -> out_f32 [T][N] (columns >= nvalid unwritten),
+// mode 6 -> out_bf16 [T][2 N] = [hi | lo] of gelu(.)
+extern "C" int ak_ktp_gemm_x3w(int mode, const uint16_t *X, const uint16_t *W, const float *bias, int T, int N, int K1, float *out_f32,
+                               uint16_t *out_bf16, int nvalid, void *stream) {
+    AK_BIND();
+    if (!X || !W || !bias || T <= 0 || N <= 0 || K1 <= 0 || K1 > 0x7fffffff / 3 || (mode == 5 && !out_f32) || (mode == 6 && !out_bf16))
+        AK_FAIL(-1, "ak_ktp_gemm_x3w: bad arguments");
+    GemmArgs g{};
+    g.X = X; g.W = W; g.bias = bias; g.T = T; g.N = N; g.K = 3 * K1; g.out_f32 = out_f32; g.out_bf16 = out_bf16; g.ldo = 2 * N; g.nvalid = nvalid;
+    return launch_gemm_x3w(mode, g, (hipStream_t)stream);
+}
+// launch_gemm_ln_x3 (hidden 384): X [T][2 K1], W [384][2 K1], x32 [T][384] in place, x16 [T][768] = [hi | lo]
+extern "C" int ak_ktp_gemm_ln_x3(const uint16_t *X, const uint16_t *W, const float *bias, const float *gamma, const float *beta, float *x32,
+                                 uint16_t *x16, int T, int K1, float eps, void *stream) {
+    AK_BIND();
+    if (!X || !W || !bias || !gamma || !beta || T <= 0 || K1 <= 0 || K1 > 0x7fffffff / 3 || !gemm_ln_supported(384, T, K1))
+        AK_FAIL(-1, "ak_ktp_gemm_ln_x3: gemm_ln_supported refuses this shape");
+    GemmLnArgs a{X, W, bias, gamma, beta, x32, x16, T, 3 * K1, eps, nullptr};
+    return launch_gemm_ln_x3(a, (hipStream_t)stream);
+}
+
 #endif  // AK_DBG_KERNELS

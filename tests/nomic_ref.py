@@ -121,14 +121,42 @@ def sensitivities(shape_name, seed, std, ids, lens, pooling, expected, max_len=N
 
 # ---- text end to end: a checkpoint directory as sentence-transformers lays it out -------------------------------------------
 def make_wordpiece(path: str, corpus, vocab_size: int = 1000, lowercase: bool = True):
-    """A small BERT WordPiece vocabulary trained offline from `corpus`: <path>/vocab.txt and the matching <path>/tokenizer.json
-    ([PAD] [UNK] [CLS] [SEP] [MASK] first; [CLS] $A [SEP]) and tokenizer_config.json. Returns the number of tokens."""
+    """A small BERT WordPiece vocabulary built from `corpus`: <path>/vocab.txt and the matching <path>/tokenizer.json
+    ([PAD] [UNK] [CLS] [SEP] [MASK] first; [CLS] $A [SEP]) and tokenizer_config.json. Returns the number of tokens.
+    The vocabulary is a FUNCTION of the corpus: the words the BERT normaliser and pre-tokeniser cut it into, counted; every character
+    and its ## form, then whole words, word beginnings and ## word endings of 2 to 4 characters in turn, each list by (count descending,
+    text). (It used to be trained with tokenizers' WordPiece trainer, whose ties fall by the iteration order of a hash map seeded per
+    process: every run gave another vocabulary, hence other token ids and other embeddings of the same texts, and what a test saw of
+    its own assertions -- how many ranks of a top-k are separated, say -- changed from run to run.)"""
+    from collections import Counter
     from tokenizers import BertWordPieceTokenizer
     tok = BertWordPieceTokenizer(lowercase=lowercase)
-    tok.train_from_iterator(list(corpus) * 4, vocab_size=vocab_size, min_frequency=1, show_progress=False,
-                            special_tokens=["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"])
+    words = Counter()
+    for text in corpus:
+        for wd, _ in tok._tokenizer.pre_tokenizer.pre_tokenize_str(tok._tokenizer.normalizer.normalize_str(text)):
+            words[wd] += 1
+    heads, tails = Counter(), Counter()
+    for wd, n in words.items():
+        for m in (2, 3, 4):
+            if len(wd) > m:
+                heads[wd[:m]] += n
+                tails["##" + wd[-m:]] += n
+    by_count = lambda c: [t for t, _ in sorted(c.items(), key=lambda kv: (-kv[1], kv[0]))]
+    chars = sorted({ch for wd in words for ch in wd})
+    vocab = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + chars + ["##" + ch for ch in chars]
+    seen = set(vocab)
+    lists = [by_count(words), by_count(heads), by_count(tails)]
+    i = 0
+    while len(vocab) < vocab_size and any(lists):
+        if lists[i % 3]:
+            t = lists[i % 3].pop(0)
+            if t not in seen:
+                seen.add(t)
+                vocab.append(t)
+        i += 1
     os.makedirs(path, exist_ok=True)
-    tok.save_model(path)                                      # vocab.txt
+    with open(os.path.join(path, "vocab.txt"), "w", encoding="utf-8") as f:
+        f.write("\n".join(vocab[:vocab_size]) + "\n")
     full = BertWordPieceTokenizer(os.path.join(path, "vocab.txt"), lowercase=lowercase)
     full.save(os.path.join(path, "tokenizer.json"))
     json.dump({"do_lower_case": lowercase, "tokenizer_class": "BertTokenizer"}, open(os.path.join(path, "tokenizer_config.json"), "w"))

@@ -85,6 +85,26 @@ def test_kernel_test_entry_points_exist_in_the_dbg_library_only(built):
     assert [dbg.ak_kt_vt_pos(s) for s in range(8192)] == kr.vt_pos(np.arange(8192)).tolist()
 
 
+def test_parity_kernel_entry_points_exist_in_the_dbg_library_only(built):
+    """The ak_ktp_* set (the float32 and split-bf16 parity modes' launchers, tests/test_parity_kernels_gpu.py): none in the product
+    library, every one KTP_SYMBOLS binds in the dbg library, the scalar cross-check of k32m_gemm among them; the ak_kt_* set above
+    is not touched by it."""
+    import subprocess
+
+    def exported(name):
+        out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "archi_amd", "lib", name)], stdout=subprocess.PIPE,
+                             check=True).stdout.decode()
+        return set(re.findall(r"\b(ak_ktp_[a-z0-9_]+)\b", out))
+
+    names = {name for name, _, _ in built.KTP_SYMBOLS}
+    assert exported("libarchi_hip.so") == set()
+    assert exported("libarchi_hip_dbg.so") == names and len(names) == len(built.KTP_SYMBOLS) == 15
+    assert names >= {"ak_ktp_gemm_f32", "ak_ktp_gemm_x3", "ak_ktp_gemm_f32_scalar", "ak_ktp_attn_f32", "ak_ktp_attn_x3", "ak_ktp_attn_x3_split",
+                     "ak_ktp_split_hilo", "ak_ktp_split_rows", "ak_ktp_embed_split", "ak_ktp_add_ln_split", "ak_ktp_gemm_x3w", "ak_ktp_gemm_ln_x3",
+                     "ak_ktp_embed_f32", "ak_ktp_add_ln_f32", "ak_ktp_pool_f32"}
+    assert not names & {name for name, _, _ in built.KT_SYMBOLS + built.KTG_SYMBOLS + built.KTS_SYMBOLS}
+
+
 @pytest.mark.parametrize("target,binary", [("tsan", "index_host_tsan"), ("asan-index", "index_host_asan")])
 def test_index_host_side_under_sanitizers(target, binary):
     """the host-side C++ under sanitizers in a CPU-only target (GPU sanitizers are not available on the
