@@ -9,6 +9,7 @@
 // float32 accumulators, strictly sequential i = 0..dim-1, one rounding per
 // multiply and per add (NO fma contraction), float8 result. See
 // oracle/knn_oracle.c for the CPU statement of the same thing.
+#include "exact_arith.h"
 #include "index.h"
 #include "switches.h"
 
@@ -16,35 +17,7 @@ namespace ak {
 
 #pragma clang fp contract(off)
 
-// Stored row elements in chunks of 8 (16 B for 16-bit dtypes, 2 x 16 B for f32): the reference
-// arithmetic is a strictly sequential chain, so the only thing to vectorise is the LOAD.
-template <int DT>
-__device__ inline void load8(const typename Store<DT>::T *row, int i, float (&v)[8]) {
-    if constexpr (DT == AK_DTYPE_F32) {
-        float4 a = *(const float4 *)(row + i), b = *(const float4 *)(row + i + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-        uint4 u = *(const uint4 *)(row + i);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint16_t lo = (uint16_t)(w[j] & 0xffffu), hi = (uint16_t)(w[j] >> 16);
-            v[2 * j] = DT == AK_DTYPE_BF16 ? bf16_to_f32(lo) : f16_to_f32(lo);
-            v[2 * j + 1] = DT == AK_DTYPE_BF16 ? bf16_to_f32(hi) : f16_to_f32(hi);
-        }
-    }
-}
-
-// The finish of one (query,row) distance: the float32 accumulator of the sequential chain -> float8 distance. One function for
-// exact_distance and the panel re-rank, so that the two kernels cannot drift apart.
-__device__ inline double exact_finish(float acc, int metric, float na, float nb) {
-    if (metric == AK_METRIC_L2) return sqrt((double)acc);
-    if (metric == AK_METRIC_IP) return (double)(-acc);
-    double sim = (double)acc / sqrt((double)na * (double)nb);
-    if (sim > 1.0) sim = 1.0;
-    else if (sim < -1.0) sim = -1.0;
-    return 1.0 - sim;
-}
+// load8 (the 8-element row load) and exact_finish (accumulator -> float8 distance) live in exact_arith.h: mmr.hip shares them.
 
 // One (query,row) distance in the oracle's arithmetic. `na` is the row's
 // precomputed pgvector-order sum of squares, `nb` the query's.

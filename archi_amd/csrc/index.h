@@ -170,6 +170,25 @@ int lex_hybrid_single(Index &ix, const HybridReq &r);
 // lexical_batch.hip: one group of same-keyed concurrent calls as one batch call; fills every request's outputs, rc and err
 void lex_hybrid_group(Index &ix, std::vector<HybridReq *> &g);
 
+// ---- max-marginal-relevance selection (mmr.hip) ------------------------------------------------------------------------------
+// The second half of ak_index_mmr_search: the candidate search has run (index.hip), the host has resolved the candidates' row
+// slots. k_mmr_gram writes the float32 accumulator of every candidate pair i < j of a query -- exact_distance's chain over the two
+// stored rows -- into a packed upper triangle; k_mmr_select, one wave per query, finishes pairs to float64 on the fly and runs the
+// greedy pick. Cosine indexes only (the caller has checked).
+constexpr int MMR_MAX_FETCH = 128;
+struct MmrWs {                  // one block of the calling thread's scratch
+    int *slots = nullptr;       // [nq][fetch_k] row slot of candidate rank r; ranks >= the query's count are never read
+    float *acc = nullptr;       // [nq][fetch_k (fetch_k - 1) / 2] pair (i < j) at i * fetch_k - i (i + 1) / 2 + (j - i - 1)
+    int64_t *ids = nullptr;     // [nq][k] results, pick order
+    double *dist = nullptr;     // [nq][k]
+    int *rank = nullptr;        // [nq][k]
+    size_t bytes = 0;
+};
+MmrWs mmr_layout(void *base, int nq, int k, int fetch_k);      // base == NULL: only .bytes means anything
+// dq_dev [nq][fetch_k] float64 distances and cnt_dev [nq] counts of the candidate search, rank order; everything on `st`
+int mmr_run(Index &ix, int nq, int k, int fetch_k, double lambda_mult, const double *dq_dev, const int *cnt_dev, const MmrWs &w,
+            hipStream_t st);
+
 // ---- fast path (scan.hip) ----------------------------------------------------
 // Fused tail of the fast path (exact.hip), one workgroup per query: the dense candidate list the scans appended to
 // (list [nq][lcap], cnt [nq]) -> drop candidates below the main-pass starting threshold thr0 -> best kp = 64 by approximate

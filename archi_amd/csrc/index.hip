@@ -1215,10 +1215,16 @@ int filter_is_current(const Index &ix, const void *row_filter, int64_t filter_le
 
 extern "C" {
 
-static int search_host(Index &ix, const float *queries, int nq, int k, int mode, const uint8_t *row_filter, int64_t filter_len,
-                       uint64_t filter_epoch, int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats) {
-    std::shared_lock<std::shared_mutex> lk(ix.mu);
-    if (int frc = filter_is_current(ix, row_filter, filter_len, filter_epoch, "ak_index_search")) return frc;
+// Where search_host_locked left the results on the device (the calling thread's scratch block): valid until that thread's next
+// call that reserves the block. ak_index_mmr_search reads the candidates' distances and counts from there.
+struct HostSearchDev { const double *dist = nullptr; const int *counts = nullptr; };
+
+// ak_index_search behind its lock: the caller holds ix.mu (shared) and trims the thread scratch when it is done. `who` names the
+// entry point in the filter's error message.
+static int search_host_locked(Index &ix, const float *queries, int nq, int k, int mode, const uint8_t *row_filter, int64_t filter_len,
+                              uint64_t filter_epoch, int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats,
+                              const char *who, HostSearchDev *left) {
+    if (int frc = filter_is_current(ix, row_filter, filter_len, filter_epoch, who)) return frc;
     hipStream_t st;
     if (thread_stream(&st)) return -10;
     const size_t qb = (size_t)nq * ix.dim * 4, ob = (size_t)nq * k * 8;
@@ -1280,6 +1286,15 @@ static int search_host(Index &ix, const float *queries, int nq, int k, int mode,
         if (hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error(std::string("ak_index_search: ") + hipGetErrorString(hipGetLastError())); }
     } while (0);
     if (rc) hipStreamSynchronize(st);      // nothing of a failed call may still be running on the cached buffers
+    if (left) { left->dist = dod; left->counts = dct; }
+    return rc;
+}
+
+static int search_host(Index &ix, const float *queries, int nq, int k, int mode, const uint8_t *row_filter, int64_t filter_len,
+                       uint64_t filter_epoch, int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats) {
+    std::shared_lock<std::shared_mutex> lk(ix.mu);
+    const int rc = search_host_locked(ix, queries, nq, k, mode, row_filter, filter_len, filter_epoch, out_ids, out_dist, out_counts,
+                                      out_stats, "ak_index_search", nullptr);
     t_ctx.trim();
     return rc;
 }
@@ -1344,6 +1359,92 @@ int ak_index_search(ak_index_t h, const float *queries, int nq, int k, int mode,
     const int rc = ix.co.submit(me, [&](std::vector<SearchReq *> &g) { run_group(ix, g); }, window_us);
     if (rc) set_error(me.err);
     return rc;
+}
+
+// Max-marginal-relevance search (no counterpart in the reference's store; LangChain's VectorStore contract [upstream, not in tree]):
+// the candidate search (search_host_locked, k = fetch_k), the candidates' row slots resolved on the host from the id map -- the
+// search emits ids only --, then the two kernels of mmr.hip, all under ONE hold of the shared lock: a remove or a compaction cannot
+// move a slot between the scan and the row reads. The lazy id map of generated rows needs the unique lock to be built
+// (IndexBook::slot_of), so it is built BEFORE that hold; an ak_index_generate that slips in between un-builds it again and the call
+// goes round once more. The results' distances and counts never leave the device between the two halves.
+int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int fetch_k, double lambda_mult, int mode,
+                        const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch, int64_t *out_ids, double *out_dist,
+                        int *out_rank, int *out_counts, int64_t *out_stats) {
+    AK_BIND();
+    if (!h) AK_FAIL(-1, "ak_index_mmr_search: NULL index");
+    Index &ix = *(Index *)h;
+    if (nq < 0 || (nq > 0 && (!queries || !out_ids || !out_dist))) AK_FAIL(-1, "ak_index_mmr_search: bad arguments");
+    if (k < 1) AK_FAIL(-1, "ak_index_mmr_search: k must be >= 1");
+    if (fetch_k < k) AK_FAIL(-1, "ak_index_mmr_search: fetch_k must be >= k");
+    if (fetch_k > MMR_MAX_FETCH) AK_FAIL(-1, "ak_index_mmr_search: fetch_k > 128 not supported");
+    if (!(lambda_mult >= 0.0 && lambda_mult <= 1.0)) AK_FAIL(-1, "ak_index_mmr_search: lambda_mult must be in [0, 1]");
+    if (mode < AK_SEARCH_AUTO || mode > AK_SEARCH_FAST_ONLY) AK_FAIL(-1, "ak_index_mmr_search: bad mode");
+    if (ix.metric != AK_METRIC_COSINE)      // immutable after ak_index_create: no lock needed
+        AK_FAIL(-1, std::string("ak_index_mmr_search: cosine indexes only, this index is ") + (ix.metric == AK_METRIC_L2 ? "l2" : "inner_product"));
+    if (nq > (1 << 20)) AK_FAIL(-1, "ak_index_mmr_search: more than 2^20 queries");
+    if (nq == 0) { if (out_stats) memset(out_stats, 0, 4 * sizeof(int64_t)); return 0; }
+    RoctxRange range("ak_index_mmr_search");
+    static thread_local std::vector<int64_t> cid;
+    static thread_local std::vector<double> cd;
+    static thread_local std::vector<int> cc, cs;
+    const size_t nc = (size_t)nq * fetch_k;
+    cid.resize(nc); cd.resize(nc); cc.resize(nq); cs.resize(nc);
+    int64_t stats[4] = {0, 0, 0, 0};
+    for (;;) {
+        std::shared_lock<std::shared_mutex> lk(ix.mu);
+        if (!ix.map_built) {                                 // generated rows not in the map yet (or a generate ran in between)
+            lk.unlock();
+            std::unique_lock<std::shared_mutex> wl(ix.mu);
+            if (!ix.map_built) (void)ix.slot_of(-1);        // a miss builds the lazy map
+            continue;
+        }
+        const IndexBook &book = ix;                          // readers: const members only
+        HostSearchDev left;
+        int rc = search_host_locked(ix, queries, nq, fetch_k, mode, row_filter, filter_len, filter_epoch, cid.data(), cd.data(), cc.data(),
+                                    stats, "ak_index_mmr_search", &left);
+        if (rc) { t_ctx.trim(); return rc; }
+        for (int q = 0; q < nq; q++) {
+            if (cc[q] < 0 || cc[q] > fetch_k) { t_ctx.trim(); AK_FAIL(-1, "ak_index_mmr_search: candidate count out of range"); }
+            for (int r = 0; r < fetch_k; r++) {
+                int64_t slot = -1;
+                if (r < cc[q]) {
+                    const auto it = book.id2slot.find(cid[(size_t)q * fetch_k + r]);
+                    if (it == book.id2slot.end() || it->second < 0 || it->second >= book.n) {
+                        t_ctx.trim();
+                        AK_FAIL(-1, "ak_index_mmr_search: a candidate id has no row slot");
+                    }
+                    slot = it->second;
+                }
+                cs[(size_t)q * fetch_k + r] = (int)(uint32_t)slot;
+            }
+        }
+        hipStream_t st;
+        if (thread_stream(&st)) return -10;
+        // the candidate search's workspace is free again (its results sit in the thread's device block): the selection takes it
+        const MmrWs need = mmr_layout(nullptr, nq, k, fetch_k);
+        if (scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, need.bytes, false)) { t_ctx.trim(); return -10; }
+        const MmrWs w = mmr_layout(t_ctx.ws, nq, k, fetch_k);
+        rc = 0;
+        do {
+            if (hipMemcpyAsync(w.slots, cs.data(), nc * 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -10; set_error("ak_index_mmr_search: H2D failed"); break; }
+            if ((rc = mmr_run(ix, nq, k, fetch_k, lambda_mult, left.dist, left.counts, w, st))) break;
+            // results land in the thread-local host vectors first (k <= fetch_k: they fit): a failed call leaves the caller's outputs untouched
+            if (hipMemcpyAsync(cid.data(), w.ids, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(cd.data(), w.dist, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(cs.data(), w.rank, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = -10; set_error("ak_index_mmr_search: D2H failed"); break; }
+            if (hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error(std::string("ak_index_mmr_search: ") + hipGetErrorString(hipGetLastError())); }
+        } while (0);
+        if (rc) hipStreamSynchronize(st);
+        t_ctx.trim();
+        if (rc) return rc;
+        break;
+    }
+    memcpy(out_ids, cid.data(), (size_t)nq * k * 8);
+    memcpy(out_dist, cd.data(), (size_t)nq * k * 8);
+    if (out_rank) memcpy(out_rank, cs.data(), (size_t)nq * k * 4);
+    if (out_counts) for (int q = 0; q < nq; q++) out_counts[q] = cc[q] < k ? cc[q] : k;
+    if (out_stats) memcpy(out_stats, stats, sizeof(stats));
+    return 0;
 }
 
 int ak_index_search_dev(ak_index_t h, const float *queries_dev, int nq, int k, int mode, const uint8_t *row_filter_dev,

@@ -292,6 +292,48 @@ class HipIndex:
                                          "reranked": int(stats[2]), "second_chance": int(stats[3])}
         return out_ids, out_d, cnt
 
+    MMR_MAX_FETCH_K = 128
+
+    def mmr_search(self, queries, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, mode: str = "auto",
+                   row_filter: Optional[np.ndarray] = None, filter_epoch: Optional[int] = None, return_rank: bool = False,
+                   return_stats: bool = False):
+        """Max-marginal-relevance search (ak_index_mmr_search; LangChain's VectorStore contract, no counterpart in the reference's
+        store): greedy pick of k among the first fetch_k rows of search(), trading distance to the query against the largest
+        similarity to a row already picked. Returns (ids [Q,k], distances to the query [Q,k] f64, counts [Q][, ranks [Q,k]]) in pick
+        order; rank = the pick's position in search()'s list; return_stats appends search()'s stats dict, of the candidate search. Cosine indexes, 1 <= k <= fetch_k <= 128, 0 <= lambda_mult <= 1.
+        row_filter / filter_epoch and the errors (StaleFilterError, HipBackendError) as search()."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq,{self.dim}] float32")
+        nq, k, fetch_k = q.shape[0], int(k), int(fetch_k)
+        kk = max(k, 0)
+        out_ids = np.full((nq, kk), -1, dtype=np.int64)
+        out_d = np.full((nq, kk), np.nan, dtype=np.float64)
+        out_r = np.full((nq, kk), -1, dtype=np.int32)
+        cnt = np.zeros((nq,), dtype=np.int32)
+        stats = np.zeros(4, dtype=np.int64)
+        flt, flen, fep = None, 0, 0
+        if row_filter is not None:
+            flt = np.ascontiguousarray(row_filter, dtype=np.uint8)
+            if flt.ndim != 1:
+                raise ValueError("row_filter must be one byte per row slot")
+            flen = flt.shape[0]
+            if filter_epoch is None:
+                slots, fep = self.layout()
+                if flen != slots:
+                    raise ValueError(f"row_filter must have {slots} entries (one per row slot)")
+            else:
+                fep = int(filter_epoch)
+        check(self._lib.ak_index_mmr_search(self._h, _ptr(q), nq, k, fetch_k, float(lambda_mult), SEARCH_MODES[mode], _ptr(flt), flen,
+                                            fep, _ptr(out_ids), _ptr(out_d), _ptr(out_r), _ptr(cnt), _ptr(stats)), "ak_index_mmr_search")
+        out = (out_ids, out_d, cnt) + ((out_r,) if return_rank else ())
+        if return_stats:
+            out += ({"certified": int(stats[0]), "exact_reruns": int(stats[1]), "reranked": int(stats[2]),
+                     "second_chance": int(stats[3])},)
+        return out
+
     def search_device(self, queries_ptr: int, nq: int, k: int, out_ids_ptr: int, out_dist_ptr: int,
                       out_cert_ptr: int, stream: int = 0, mode: str = "fast_only", row_filter_ptr: int = 0,
                       filter_len: int = 0, filter_epoch: Optional[int] = None) -> None:

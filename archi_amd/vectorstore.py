@@ -533,6 +533,13 @@ class ArchiHipVectorStore(_VectorStoreBase):
         self, embedding: List[float], k: int = 4, **kwargs: Any
     ) -> List[Tuple[Any, float]]:
         """Reference :272-364: filter -> distance -> ORDER BY distance ASC LIMIT k -> score."""
+        return self._read_by_vector(embedding, k, kwargs, None)
+
+    def _read_by_vector(self, embedding: List[float], k: int, kwargs: Dict[str, Any], search: Optional[Callable[..., Any]]
+                        ) -> List[Tuple[Any, float]]:
+        """One filtered read -> (Document, score) in the index's result order. `search`: None for the collection index's search(),
+        or a callable with its signature (queries, k, row_filter=, filter_epoch=) -> (ids, dist, counts): how the MMR read runs
+        through the same WHERE clause, snapshot retry and `vanished` retry."""
         metadata_filter = kwargs.get("filter", {}) or {}
         include_deleted = kwargs.get("include_deleted", False)
         col = self._collection()
@@ -544,7 +551,8 @@ class ArchiHipVectorStore(_VectorStoreBase):
         # the WHERE clause is resolved under the table lock, the scan runs WITHOUT it: request threads search concurrently (the
         # library coalesces concurrent single-query calls into one launch) and a writer is never kept waiting behind a GPU call
         for attempt in range(self.STALE_RETRIES + 1):
-            ids, dist, cnt = self._search_snapshot(col, q, k, lambda: self._where(col, metadata_filter, include_deleted)[::2])
+            ids, dist, cnt = self._search_snapshot(col, q, k, lambda: self._where(col, metadata_filter, include_deleted)[::2],
+                                                   search(col) if search else None)
             results: List[Tuple[Any, float]] = []
             vanished = 0
             with t.lock:
@@ -565,28 +573,71 @@ class ArchiHipVectorStore(_VectorStoreBase):
 
     STALE_RETRIES = 2
 
-    def _search_snapshot(self, col: _Collection, q: np.ndarray, k: int, build_mask: Callable[[], Tuple[Any, int]]):
+    def _search_snapshot(self, col: _Collection, q: np.ndarray, k: int, build_mask: Callable[[], Tuple[Any, int]],
+                         search: Optional[Callable[..., Any]] = None):
         """One filtered top-k with the snapshot semantics of the reference's single SQL statement (WHERE, distance, ORDER BY and
         LIMIT see one state of the table: postgres_vectorstore.py:296-332). build_mask() -> (per-slot byte mask or None, layout
         epoch) runs under the table lock; the scan runs outside it and hands the epoch back to the library, which refuses the
         mask (StaleFilterError, nothing read) if a writer has added rows or reclaimed tombstones in between -- a stale mask
         would address other rows: soft-deleted or filtered-out chunks could come back. Then the mask is rebuilt; after
-        STALE_RETRIES collisions the scan runs under the table lock, which every writer of the index takes."""
+        STALE_RETRIES collisions the scan runs under the table lock, which every writer of the index takes. `search`: what runs
+        instead of col.index.search (same signature: the MMR read)."""
         t = col.table
+        search = search or col.index.search
         for _ in range(self.STALE_RETRIES):
             with t.lock:
                 mask, epoch = build_mask()
             if mask is None:
-                return col.index.search(q[None, :], k)
+                return search(q[None, :], k)
             try:
-                return col.index.search(q[None, :], k, row_filter=mask, filter_epoch=epoch)
+                return search(q[None, :], k, row_filter=mask, filter_epoch=epoch)
             except StaleFilterError:
                 continue
         with t.lock:
             mask, epoch = build_mask()
             if mask is None:
-                return col.index.search(q[None, :], k)
-            return col.index.search(q[None, :], k, row_filter=mask, filter_epoch=epoch)
+                return search(q[None, :], k)
+            return search(q[None, :], k, row_filter=mask, filter_epoch=epoch)
+
+    # -- max-marginal-relevance reads -------------------------------------------------------------
+    # NO COUNTERPART in the reference's PostgresVectorStore: these follow LangChain's VectorStore contract
+    # (max_marginal_relevance_search / _by_vector, what as_retriever(search_type="mmr") calls) [upstream, not in tree]. The
+    # candidates are the first fetch_k rows of the plain search, the pick is the library's (ak_index_mmr_search: exact pair
+    # distances in the search's arithmetic, float64 greedy rule). Cosine stores only, as LangChain's helper.
+    MMR_MAX_FETCH_K = 128
+
+    def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
+                                      **kwargs: Any) -> List[Any]:
+        query_embedding = self._embedding_function.embed_query(query)
+        return self.max_marginal_relevance_search_by_vector(query_embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, **kwargs)
+
+    def max_marginal_relevance_search_by_vector(self, embedding: List[float], k: int = 4, fetch_k: int = 20,
+                                                lambda_mult: float = 0.5, **kwargs: Any) -> List[Any]:
+        return [doc for doc, _ in self.max_marginal_relevance_search_by_vector_with_score(
+            embedding, k=k, fetch_k=fetch_k, lambda_mult=lambda_mult, **kwargs)]
+
+    def max_marginal_relevance_search_by_vector_with_score(self, embedding: List[float], k: int = 4, fetch_k: int = 20,
+                                                           lambda_mult: float = 0.5, **kwargs: Any) -> List[Tuple[Any, float]]:
+        """(Document, score) in pick order; the score is similarity_search_by_vector_with_score's (1 - cosine distance to the query).
+        filter / include_deleted as there. fetch_k below k is raised to k."""
+        k, fetch_k, lambda_mult = int(k), int(fetch_k), float(lambda_mult)
+        if self._distance_metric != "cosine":
+            raise NotImplementedError(f"max_marginal_relevance_search supports cosine stores only, this store's distance_metric is "
+                                      f"{self._distance_metric!r}")
+        fetch_k = max(fetch_k, k)
+        if fetch_k > self.MMR_MAX_FETCH_K:
+            raise ValueError(f"max_marginal_relevance_search: fetch_k = {fetch_k} exceeds the limit of {self.MMR_MAX_FETCH_K}")
+        if not 0.0 <= lambda_mult <= 1.0:
+            raise ValueError(f"max_marginal_relevance_search: lambda_mult must be in [0, 1], got {lambda_mult}")
+
+        def search(col: _Collection):
+            mmr = getattr(col.index, "mmr_search", None)
+            if mmr is None:
+                raise NotImplementedError(f"max_marginal_relevance_search: {type(col.index).__name__} has no mmr_search "
+                                          "(sharded MMR is not supported)")
+            return lambda qs, kk, **kw: mmr(qs, kk, fetch_k=fetch_k, lambda_mult=lambda_mult, **kw)
+
+        return self._read_by_vector(embedding, k, kwargs, search)
 
     def _where(self, col: _Collection, metadata_filter: Dict[str, Any], include_deleted: bool):
         """The WHERE clause (:296-310) as a per-slot byte mask for the scan, or None when every row passes; the passing row ids

@@ -252,6 +252,31 @@ int ak_index_search(ak_index_t h, const float *queries, int nq, int k, int mode,
                     const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch,
                     int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats);
 
+/* Max-marginal-relevance search. NO COUNTERPART in the reference's store (PostgresVectorStore has no MMR read): the method follows
+ * LangChain's VectorStore contract, max_marginal_relevance_search(query, k, fetch_k, lambda_mult) [upstream, not in tree], which
+ * as_retriever(search_type="mmr") calls. Cosine indexes only (LangChain's helper is cosine-only too); an l2 / ip index is refused
+ * by name before any GPU work. Requires 1 <= k <= fetch_k <= 128 and 0 <= lambda_mult <= 1.
+ *   1. Candidates: the first fetch_k rows of ak_index_search for this query, mask and mode, in its order (distance ascending, ties
+ *      by id, NaN last); m <= fetch_k of them. Rank r = position in that list, dq[r] its float64 distance, sq[r] = 1.0 - dq[r].
+ *   2. Pair distances, ranks i < j: d(i,j) = the cosine distance of the two STORED rows in the search's exact arithmetic (float32
+ *      chain in element order, one rounding per multiply and per add, the index's stored row norms, float64 finish);
+ *      s(i,j) = s(j,i) = 1.0 - d(i,j).
+ *   3. Greedy pick, float64, no contraction: the first pick is rank 0. red[r] starts at -inf; after a pick p every unpicked r gets
+ *      red[r] = s(r,p) if s(r,p) > red[r] (a NaN never updates). The next pick is the unpicked r with the largest
+ *      score[r] = lambda_mult * sq[r] - (1.0 - lambda_mult) * red[r], (1.0 - lambda_mult) computed once; strict > scanning ranks
+ *      upward (the lowest rank wins a tie); a NaN score never wins, and when every remaining score is NaN the lowest remaining
+ *      rank is picked. min(k, m) picks.
+ *   out_ids / out_dist [nq][k]: the picks in pick order with dq of each pick; out_rank [nq][k] (NULL allowed): each pick's rank;
+ *   out_counts [nq] (NULL allowed) = min(k, m). Unused tail: id -1, distance NaN, rank -1.
+ *   out_stats: NULL or int64[4], that of the candidate search. row_filter / filter_len / filter_epoch: as ak_index_search,
+ *   AK_ERR_STALE_FILTER included.
+ * With lambda_mult = 1 the result is the first k rows of ak_index_search. The candidate search and the selection run under ONE hold
+ * of the index's reader lock. Re-entrant like ak_index_search; not coalesced. A refused call launches nothing and leaves the
+ * outputs untouched. */
+int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int fetch_k, double lambda_mult, int mode,
+                        const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch,
+                        int64_t *out_ids, double *out_dist, int *out_rank, int *out_counts, int64_t *out_stats);
+
 /* Same query, everything resident in HBM (bench path and the row-sharded multi-GPU path: inputs already on the device
  * when the timed region starts; `stream` orders the work).
  *   mode AK_SEARCH_FAST_ONLY: asynchronous, nothing synchronises with the host. out_cert_dev [nq] int32 receives 1 for
