@@ -332,7 +332,7 @@ KTG_SYMBOLS = [
     ("ak_ktg_gemm_geglu_tanh", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 ]
 
-# the small kernels of the stacks (decoder.hip, mbert.hip, nomic.hip, gemma.hip, llama.hip) and k_gemm MODE 3, one launch each
+# the small kernels of the stacks (decoder128.hip, mbert.hip, nomic.hip, gemma.hip) and k_gemm MODE 3, one launch each
 # (tests/test_stack_kernels_gpu.py, tests/test_llama_kernels_gpu.py): libarchi_hip_dbg.so only, a third set of its own (ak_kts_*)
 _F = ctypes.c_float
 _EMBED = [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P]

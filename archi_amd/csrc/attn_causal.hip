@@ -1,8 +1,8 @@
-// attn_causal.hip -- causal grouped-query flash attention at head dim 128 (the decoder's attention, decoder.hip):
+// attn_causal.hip -- causal grouped-query flash attention at head dim 128 (the decoder's attention, decoder128.hip):
 //   ctx[t][h * 128 + d] = sum_{s' <= s} softmax_s'(q_h[s] . k_g[s']) v_g[s'][d],   g = h / (nq / nkv)
-// q arrives pre-scaled by log2(e) / sqrt(128) (decoder.hip k_dec_qk_rope). The per-key-block algorithm is flash_tile.h's; this file's own:
+// q arrives pre-scaled by log2(e) / sqrt(128) (decoder128.hip k_dec_qk_rope). The per-key-block algorithm is flash_tile.h's; this file's own:
 //
-// Layouts (decoder.hip writes them): q [B][nq][S][128], k and v [B][nkv][S][128] bf16; ctx [T][nq * 128] bf16 (the out-projection's
+// Layouts (decoder128.hip writes them): q [B][nq][S][128], k and v [B][nkv][S][128] bf16; ctx [T][nq * 128] bf16 (the out-projection's
 // A operand). Rows are right-padded; lens[b] is the row's length, clamped to [0, S] by the embedding kernel.
 //
 // Workgroup = (query block, kv head, sequence) and holds every query head of the group: wave w computes query head g = w % G of the
@@ -14,7 +14,7 @@
 // block keys past the query are masked. The first block always holds a visible key (key 0), so the softmax step runs without its -inf
 // guard. Query blocks wholly past the row's length are not computed: their context rows are zero (finite, and nothing valid reads
 // them: a valid query never sees a pad key under the causal mask).
-// BAND (k_attn_causal_band: Mistral's sliding window, llama.hip; CausalAttnArgs::window = w): key <= query and query - key <= w - 1, flash_tile.h's band of
+// BAND (k_attn_causal_band: Mistral's sliding window, decoder128.hip; CausalAttnArgs::window = w): key <= query and query - key <= w - 1, flash_tile.h's band of
 // half-width w - 1 under the diagonal. The workgroup stages from the block of its first wave's lowest visible key (at S = 8192,
 // w = 4096 three quarters of the plain walk's blocks); a wave skips the blocks its band does not reach (BAND_OUT). The first block a
 // wave computes may hold no visible key for its later queries, so this kernel runs the guarded softmax step; every query sees

@@ -185,21 +185,21 @@ struct QfArgs {
 };
 bool query_forward_supported(int H, int I, int heads, int64_t T, int S);
 int launch_query_forward(const QfArgs &a, hipStream_t st);
-// causal grouped-query attention at head dim 128 (attn_causal.hip; the decoder, decoder.hip): q [B][nq][S][128] pre-scaled by
+// causal grouped-query attention at head dim 128 (attn_causal.hip; the decoder, decoder128.hip): q [B][nq][S][128] pre-scaled by
 // log2(e) / sqrt(128), k / v [B][nkv][S][128], ctx [B * S][nq * 128]; lens [B] already clamped to [0, S]
 struct CausalAttnArgs {
     const uint16_t *q, *k, *v;
     const int *lens;
     uint16_t *ctx;
     int B, S, nq, nkv;
-    // sliding window (llama.hip; Mistral's sliding_window): key k visible to query q iff k <= q and q - k <= window - 1. 0: no band
+    // sliding window (decoder128.hip; Mistral's sliding_window): key k visible to query q iff k <= q and q - k <= window - 1. 0: no band
     // (Qwen3: the kernel it ran before the band existed)
     int window = 0;
-    int bidirectional = 0;       // != 0 (llama.hip): every key below the row's length, for every query below it; the window is ignored
+    int bidirectional = 0;       // != 0 (decoder128.hip): every key below the row's length, for every query below it; the window is ignored
 };
 bool attn_causal_supported(int nq, int nkv, int head_dim, int S);
 int launch_attn_causal(const CausalAttnArgs &a, hipStream_t st);
-// the same attention at 5 to 8 query heads per kv head (qwen2.hip), a kv group split over two workgroups: causal or bidirectional,
+// the same attention at 5 to 8 query heads per kv head (Qwen2), a kv group split over two workgroups: causal or bidirectional,
 // window must be 0; S % 32 == 0, S <= 8192
 bool attn_causal_split_supported(int nq, int nkv, int head_dim, int S);
 int launch_attn_causal_split(const CausalAttnArgs &a, hipStream_t st);
@@ -221,7 +221,7 @@ int launch_attn_gqa(const GqaAttnArgs &a, int half_window, hipStream_t st);
 // q scaled; q / k head-major, v transposed -- the layouts of GqaAttnArgs. rc / rs: [n_pos][128]
 int launch_gm_qk_norm_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
                            const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *vt, hipStream_t st);
-// the small kernels between the large launches of the stacks (decoder.hip, mbert.hip, gemma.hip, nomic.hip), each behind the one function
+// the small kernels between the large launches of the stacks (decoder128.hip, mbert.hip, gemma.hip, nomic.hip), each behind the one function
 // that spells its grid: the forward passes call these, and so do the single-launch tests (kernel_test.hip). Shapes are the callers'
 // business (the handles check them at create): H % 128 == 0; H <= 1024 where a row is held in registers (every mb / gm / nb row kernel and
 // both pools' stage 1); S as check_forward_lens takes it.
@@ -231,8 +231,9 @@ int launch_dec_add_rmsnorm(float *x32, const float *y32, int64_t T, int H, const
 int launch_dec_qk_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *qn, const float *kn, float eps, const float *rc,
                        const float *rs, float qscale, uint16_t *q, uint16_t *k, uint16_t *v, hipStream_t st);
 int launch_dec_pool(const float *x32, const int *lens, int B, int S, int H, const float *w, float eps, int normalise, float *out, hipStream_t st);
-// llama.hip (Mistral / Llama: its embed, residual norms and last-token pool are the launch_dec_* above): q | k | v rows
-// [B * S][(nq + 2 nkv) 128] -> rotate_half RoPE of the q and k heads (no per-head norm), q scaled; the layouts of CausalAttnArgs
+// launch_dec_qk_rope without the per-head norm (Mistral / Llama, Qwen2: the same kernel body in decoder128.hip; their embed, residual
+// norms and last-token pool are the launch_dec_* above): q | k | v rows [B * S][(nq + 2 nkv) 128] -> rotate_half RoPE of the q and k
+// heads, q scaled; the layouts of CausalAttnArgs. Both refuse B, S, nq, nkv <= 0 and B * S >= 2^31.
 int launch_ll_rope(const uint16_t *qkv, int B, int S, int nq, int nkv, const float *rc, const float *rs, float qscale, uint16_t *q, uint16_t *k,
                    uint16_t *v, hipStream_t st);
 // mean over t < len of RMSNorm(x_t) (the norm per token, before the mean), times the final norm's weight, then the optional L2: any

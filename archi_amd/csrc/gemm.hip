@@ -15,7 +15,7 @@
 //           the other -- and normalises the rows it has just stored, from L2, instead of a LayerNorm launch: bge-base 128 x 512
 //           17.1 ms against 15.6 with one row per wave at a time, 20.2 with eight rows in flight -- the tail's registers spill
 //           into a kernel that has none to spare, and its loads run with two waves per SIMD to hide them.) (what the LayerNorm of the hidden != 384 path reads: one array instead of two)
-//   MODE 7  SwiGLU (the decoder's gate / up projection, decoder.hip): W holds the gate and up rows INTERLEAVED (row 2 j = gate j,
+//   MODE 7  SwiGLU (the decoder's gate / up projection, decoder128.hip): W holds the gate and up rows INTERLEAVED (row 2 j = gate j,
 //           row 2 j + 1 = up j), so each lane's four consecutive features are (g_j, u_j, g_j+1, u_j+1); it stores silu(g) u as bf16,
 //           N / 2 columns wide (a.ldo = N / 2) -- the 2I-wide product never reaches memory
 //   MODE 8  GeGLU (ModernBERT's Wi, mbert.hip): the same interleaved layout (row 2 j = row j of Wi's first half, the GELU input a_j;

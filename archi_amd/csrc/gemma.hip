@@ -16,7 +16,7 @@
 // tokens in chunks of 64 (k_gm_pool_part, k_gm_pool_fin: which tokens meet in which sum depends on the row's length alone), the Dense
 // head of the sentence-transformers checkpoint in float32 (0 - 2 matrices without bias, k_gm_dense) and the L2 normalisation (k_gm_l2).
 // The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in mbert.hip.
-// Here: the config checks, the layer struct, the layer loop and the family's own kernels and formulas. The plumbing shared with decoder.hip
+// Here: the config checks, the layer struct, the layer loop and the family's own kernels and formulas. The plumbing shared with decoder128.hip
 // and mbert.hip is stack.h / stack.hip: the token-slot prologue and the row load of k_gm_embed, the body of k_gm_pool_part, the L2 tail of
 // k_gm_l2, the NJ dispatch, the workspace, the weight preparation at create (concatenation, interleave, the pad-to-256 rule), the rotary
 // tables (also behind ak_gemma_set_rope_inv_freq), the GemmArgs of the launches.

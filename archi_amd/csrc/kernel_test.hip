@@ -263,7 +263,7 @@ extern "C" int ak_kts_dec_pool(const float *x32, const int *lens, int B, int S, 
     return launch_dec_pool(x32, lens, B, S, H, w, eps, normalise, out, (hipStream_t)stream);
 }
 
-// launch_attn_causal through the new arguments (llama.hip): window 0 = the plain causal kernel, w > 0 the sliding window; bidirectional != 0: every key below the length
+// launch_attn_causal through the new arguments (decoder128.hip): window 0 = the plain causal kernel, w > 0 the sliding window; bidirectional != 0: every key below the length
 extern "C" int ak_kts_ll_attn(const uint16_t *q, const uint16_t *k, const uint16_t *v, const int *lens, uint16_t *ctx, int B, int S, int nq,
                               int nkv, int window, int bidirectional, void *stream) {
     AK_BIND();
@@ -273,7 +273,7 @@ extern "C" int ak_kts_ll_attn(const uint16_t *q, const uint16_t *k, const uint16
     return launch_attn_causal(a, (hipStream_t)stream);
 }
 
-// launch_attn_causal_split (qwen2.hip: 5 to 8 query heads per kv head), the arguments of ak_kts_ll_attn without the window.
+// launch_attn_causal_split (Qwen2: 5 to 8 query heads per kv head), the arguments of ak_kts_ll_attn without the window.
 // Named ak_kts_q2_*: the ak_kts_ll_* set stays the three it is
 extern "C" int ak_kts_q2_attn(const uint16_t *q, const uint16_t *k, const uint16_t *v, const int *lens, uint16_t *ctx, int B, int S, int nq,
                               int nkv, int bidirectional, void *stream) {

@@ -12,7 +12,7 @@
 //                                                      padded_intermediate, stack.h)
 //   x += f Wo^T; h = LayerNorm(x; next attn_norm)      k_gemm MODE 2 + k_mb_add_ln
 // then final_norm per token, mean / cls pooling over the valid tokens and L2 normalisation in float32 (k_mb_pool_part, k_mb_pool_fin).
-// The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in decoder.hip.
+// The residual stream x is float32 throughout; GEMM operands are bf16. Token counts are padded to the GEMM tile (256) as in decoder128.hip.
 // Here: the config struct's own checks, the layer struct, the order of a layer (block, join, block, join) and the family's kernels: the
 // embedding, the join k_mb_add_ln (x32 keeps the SUM), k_mb_rope, the per-token transform of the pool. stack.h holds the token-slot
 // prologue, the LayerNorm of a row in registers, both pooling bodies and the NJ dispatch; enc64.h (shared with nomic.hip) the handle's

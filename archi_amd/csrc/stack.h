@@ -1,4 +1,4 @@
-// stack.h -- what the stacks (decoder.hip: Qwen3, mbert.hip: ModernBERT, gemma.hip: EmbeddingGemma, nomic.hip: NomicBERT) share: a
+// stack.h -- what the stacks (decoder128.hip: Qwen3 / Llama / Qwen2, mbert.hip: ModernBERT, gemma.hip: EmbeddingGemma, nomic.hip: NomicBERT) share: a
 // float32 residual stream feeding bf16 GEMM rows, one wave per token in the row kernels, pooling in chunks of 64 tokens. Plumbing
 // only: each family keeps its own kernels, and where a formula is stated here (the LayerNorm statistics of a row in registers, the
 // pooling stages) the order of its sums is part of the statement.

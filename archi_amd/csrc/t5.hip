@@ -10,7 +10,7 @@
 //                                                      saturates at relative_attention_max_distance D, so the bias is a function of
 //                                                      clamp(key - query, -D, D): ONE table [heads][2 D + 1] for all layers (block 0's
 //                                                      weight), built and scaled by log2(e) by the binding (archi_amd/t5.py)
-//   x += a Wo^T; h = bf16(RMSNorm(x; ln1))             k_gemm MODE 2 (float32 out) + k_dec_add_rmsnorm (decoder.hip)
+//   x += a Wo^T; h = bf16(RMSNorm(x; ln1))             k_gemm MODE 2 (float32 out) + k_dec_add_rmsnorm (decoder128.hip)
 //   f = relu(h Wi^T)                                   k_gemm MODE 10 (T5 v1.0: feed_forward_proj relu), or
 //   f = gelu_new(h Wi0^T) (h Wi1^T)                    k_gemm MODE 9 (T5 v1.1: gated-gelu; Wi0 / Wi1 rows interleaved at create)
 //   x += f Wo_ff^T; h = bf16(RMSNorm(x; next ln0))     k_gemm MODE 2 + k_dec_add_rmsnorm (after the last layer: the add alone)

@@ -2,9 +2,10 @@
 name as instruction-aware embedders (src/data_manager/vectorstore/retrievers/utils.py:7-11).
 
 PyTorch-ROCm only HOLDS the weights in HBM (bf16 matrices, fp32 vectors) and hands raw device pointers to the C ABI; every
-arithmetic step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/decoder.hip, attn_causal.hip, gemm.hip).
-Also here: the checkpoint loader (load_qwen3_weights), seeded random weights of the named shapes, the sentence-transformers
-configuration of a decoder checkpoint and the byte-level BPE tokenizer wrapper.
+arithmetic step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/decoder128.hip, the head-128 decoder stack
+behind decoder.hip's ABI; attn_causal.hip, gemm.hip). Also here: the checkpoint loader (load_qwen3_weights), seeded random weights
+of the named shapes, the sentence-transformers configuration of a decoder checkpoint (all three on _decoder128.py, which the
+Mistral / Llama and Qwen2 handles share) and the byte-level BPE tokenizer wrapper.
 """
 from __future__ import annotations
 
@@ -18,10 +19,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import AkDecoderConfig, check
-from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
-
-MAX_SEQ = 8192          # longest sequence the decoder kernels take (attn_causal.hip)
-HEAD_DIM = 128
+from . import _decoder128 as _d128
+from ._decoder128 import HEAD_DIM, MATRIX_KEYS, MAX_SEQ, hf_layer_names, layer_keys  # noqa: F401 (re-exported)
+from ._stack import HipStack, read_safetensors_dir
 
 # name -> config.json numbers (vocab, hidden, layers, q_heads, kv_heads, intermediate, max_position, rope_theta, rms_eps)
 QWEN3_SHAPES = {
@@ -34,49 +34,23 @@ QWEN3_SHAPES = {
     "qwen3-tiny-g4": (1000, 256, 4, 8, 2, 512, 8192, 1e4, 1e-6),
 }
 
-LAYER_KEYS = ("wq", "wk", "wv", "q_norm", "k_norm", "wo", "ln_in", "ln_post", "w_gate", "w_up", "w_down")
-MATRIX_KEYS = {"wq", "wk", "wv", "wo", "w_gate", "w_up", "w_down"}
-# our name -> HF Qwen3Model state-dict name (layer keys under "layers.{l}.")
-HF_LAYER_NAMES = {"wq": "self_attn.q_proj.weight", "wk": "self_attn.k_proj.weight", "wv": "self_attn.v_proj.weight",
-                  "q_norm": "self_attn.q_norm.weight", "k_norm": "self_attn.k_norm.weight", "wo": "self_attn.o_proj.weight",
-                  "ln_in": "input_layernorm.weight", "ln_post": "post_attention_layernorm.weight",
-                  "w_gate": "mlp.gate_proj.weight", "w_up": "mlp.up_proj.weight", "w_down": "mlp.down_proj.weight"}
+LAYER_KEYS = layer_keys(qk_norm=True)      # wq wk wv q_norm k_norm wo ln_in ln_post w_gate w_up w_down
+HF_LAYER_NAMES = hf_layer_names(LAYER_KEYS)      # our name -> HF Qwen3Model state-dict name (layer keys under "layers.{l}.")
 
 
 def weight_order(layers: int) -> List[str]:
-    """The header's weight order: embed_tokens, final norm, then per layer wq wk wv q_norm k_norm wo ln_in ln_post w_gate w_up w_down."""
-    names = ["embed_tokens", "norm"]
-    for l in range(layers):
-        names += [f"l{l}.{k}" for k in LAYER_KEYS]
-    return names
+    """The header's weight order: embed_tokens, final norm, then per layer LAYER_KEYS (2 + 11 * layers names)."""
+    return _d128.weight_order(LAYER_KEYS, layers)
 
 
 def hf_state_dict(weights: Dict[str, "np.ndarray"], layers: int) -> Dict[str, "np.ndarray"]:
     """Our weight names -> HF Qwen3Model's (no "model." prefix)."""
-    sd = {"embed_tokens.weight": weights["embed_tokens"], "norm.weight": weights["norm"]}
-    for l in range(layers):
-        for k, hf in HF_LAYER_NAMES.items():
-            sd[f"layers.{l}.{hf}"] = weights[f"l{l}.{k}"]
-    return sd
+    return _d128.hf_state_dict(HF_LAYER_NAMES, weights, layers)
 
 
 def random_qwen3_weights(shape, seed: int = 0) -> Dict[str, "np.ndarray"]:
-    """Seeded random weights of a Qwen3 shape (a QWEN3_SHAPES tuple or name). Matrices are drawn with std 0.02 and ROUNDED TO
-    bf16 (kept as float32 values): the released checkpoints are bf16, and a float32 reference on the same values measures the
-    kernels' activation rounding alone. Norm weights are drawn around 1, not set to it."""
-    if isinstance(shape, str):
-        shape = QWEN3_SHAPES[shape]
-    vocab, H, L, nq, nkv, I = shape[:6]
-    mat, vec = seeded_mat_vec(seed)
-    w = {"embed_tokens": mat(vocab, H), "norm": vec(H)}
-    for l in range(L):
-        p = f"l{l}."
-        w[p + "wq"], w[p + "wk"], w[p + "wv"] = mat(nq * HEAD_DIM, H), mat(nkv * HEAD_DIM, H), mat(nkv * HEAD_DIM, H)
-        w[p + "q_norm"], w[p + "k_norm"] = vec(HEAD_DIM), vec(HEAD_DIM)
-        w[p + "wo"] = mat(H, nq * HEAD_DIM)
-        w[p + "ln_in"], w[p + "ln_post"] = vec(H), vec(H)
-        w[p + "w_gate"], w[p + "w_up"], w[p + "w_down"] = mat(I, H), mat(I, H), mat(H, I)
-    return w
+    """Seeded random weights of a Qwen3 shape (a QWEN3_SHAPES tuple or name), as _decoder128.random_weights draws them."""
+    return _d128.random_weights(LAYER_KEYS, QWEN3_SHAPES[shape] if isinstance(shape, str) else shape, seed)
 
 
 def _rope_theta(cfg: dict) -> float:
@@ -119,39 +93,14 @@ def load_qwen3_weights(model_dir: str):
     the header's names). A "model." prefix on the tensor names is stripped. No network."""
     cfg = json.load(open(os.path.join(model_dir, "config.json")))
     shape = qwen3_config_shape(cfg, os.path.join(model_dir, "config.json"))
-    sd = read_safetensors_dir(model_dir)
-    L = shape[2]
-    w = {"embed_tokens": sd["embed_tokens.weight"], "norm": sd["norm.weight"]}
-    for l in range(L):
-        for k, hf in HF_LAYER_NAMES.items():
-            w[f"l{l}.{k}"] = sd[f"layers.{l}.{hf}"]
-    return shape, w
+    return shape, _d128.from_hf_state_dict(HF_LAYER_NAMES, read_safetensors_dir(model_dir), shape[2])
 
 
 def read_decoder_st_config(model_dir: str):
     """sentence-transformers files of a decoder checkpoint: `modules.json` (Normalize module?), the Pooling module's config (must be
     lasttoken) and `sentence_bert_config.json` (max_seq_length). Returns (max_seq_length | None, always_normalise)."""
-    max_len, norm, pool_dir = None, False, "1_Pooling"
-    mj = os.path.join(model_dir, "modules.json")
-    if os.path.exists(mj):
-        for m in json.load(open(mj)):
-            kind = m.get("type", "")
-            if kind.endswith("Normalize"):
-                norm = True
-            elif kind.endswith("Pooling"):
-                pool_dir = m.get("path", pool_dir)
-    pj = os.path.join(model_dir, pool_dir, "config.json")
-    if not os.path.exists(pj):
-        raise ValueError(f"{model_dir}: no {pool_dir}/config.json (a decoder embedder needs lasttoken pooling)")
-    pc = json.load(open(pj))
-    modes = [k for k in ("cls_token", "mean_tokens", "max_tokens", "mean_sqrt_len_tokens", "weightedmean_tokens", "lasttoken")
-             if pc.get("pooling_mode_" + k)]
-    if modes != ["lasttoken"]:
-        raise ValueError(f"{model_dir}: pooling modes {modes} (the HIP decoder implements lasttoken)")
-    sj = os.path.join(model_dir, "sentence_bert_config.json")
-    if os.path.exists(sj):
-        max_len = json.load(open(sj)).get("max_seq_length")
-    return max_len, norm
+    return _d128.read_st_config(model_dir, {"lasttoken": "last"}, False, "a decoder embedder needs lasttoken pooling",
+                                "the HIP decoder implements lasttoken")[1:]
 
 
 class BpeTokenizer:

@@ -3,10 +3,11 @@ Mistral-7B / Llama-3.1-8B decoders (intfloat/e5-mistral-7b-instruct, Salesforce/
 the other group the reference's retrievers single out beside Qwen3-Embedding (src/data_manager/vectorstore/retrievers/utils.py:7-19).
 
 PyTorch-ROCm only HOLDS the weights in HBM (bf16 matrices, fp32 vectors) and hands raw device pointers to the C ABI; every arithmetic
-step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/llama.hip, attn_causal.hip, decoder.hip, gemm.hip). Against
-the Qwen3 decoder (decoder.py): no per-head q / k norm, Mistral's sliding window inside the causal mask, Llama-3's frequency-dependent
-RoPE scaling. Also here: the config check (llama_config_shape), the checkpoint loader, seeded random weights of the named shapes and the
-sentence-transformers configuration of such a checkpoint.
+step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/decoder128.hip, the head-128 decoder stack behind llama.hip's
+ABI; attn_causal.hip, gemm.hip). Against the Qwen3 decoder (decoder.py): no per-head q / k norm, Mistral's sliding window inside the
+causal mask, Llama-3's frequency-dependent RoPE scaling. Also here: the config check (llama_config_shape), the checkpoint loader, seeded
+random weights of the named shapes and the sentence-transformers configuration of such a checkpoint (the last three on _decoder128.py,
+which the three families share). HipQwen2 (qwen2.py) is this handle with its own shape, keys and config struct.
 
 Attention is causal with the config's window unless the caller states model_kwargs={"attention": "bidirectional"} (an embedder trained
 without the causal mask: every key below the row's length, mean pooling by default); pooling is last-token or mean (the mean of the
@@ -22,11 +23,10 @@ from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
+from . import _decoder128 as _d128
+from ._decoder128 import HEAD_DIM, MATRIX_KEYS, MAX_SEQ, hf_layer_names, layer_keys  # noqa: F401 (re-exported)
 from ._lib import AkLlamaConfig, check
-from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
-
-MAX_SEQ = 8192          # longest row the kernels take (attn_causal.hip)
-HEAD_DIM = 128
+from ._stack import HipStack, read_safetensors_dir
 
 
 class Llama3Scaling(NamedTuple):
@@ -73,47 +73,23 @@ LLAMA_SHAPES = {
     "mistral-7b-2l": LlamaShape(2000, 4096, 2, 32, 8, 14336, 32768, 1e4, 1e-5, 4096),
 }
 
-LAYER_KEYS = ("wq", "wk", "wv", "wo", "ln_in", "ln_post", "w_gate", "w_up", "w_down")
-MATRIX_KEYS = {"wq", "wk", "wv", "wo", "w_gate", "w_up", "w_down"}
-# our name -> HF MistralModel / LlamaModel state-dict name (layer keys under "layers.{l}.")
-HF_LAYER_NAMES = {"wq": "self_attn.q_proj.weight", "wk": "self_attn.k_proj.weight", "wv": "self_attn.v_proj.weight",
-                  "wo": "self_attn.o_proj.weight", "ln_in": "input_layernorm.weight", "ln_post": "post_attention_layernorm.weight",
-                  "w_gate": "mlp.gate_proj.weight", "w_up": "mlp.up_proj.weight", "w_down": "mlp.down_proj.weight"}
+LAYER_KEYS = layer_keys()                  # wq wk wv wo ln_in ln_post w_gate w_up w_down
+HF_LAYER_NAMES = hf_layer_names(LAYER_KEYS)      # our name -> HF MistralModel / LlamaModel state-dict name (layer keys under "layers.{l}.")
 
 
 def weight_order(layers: int) -> List[str]:
-    """The header's weight order: embed_tokens, final norm, then per layer wq wk wv wo ln_in ln_post w_gate w_up w_down."""
-    names = ["embed_tokens", "norm"]
-    for l in range(layers):
-        names += [f"l{l}.{k}" for k in LAYER_KEYS]
-    return names
+    """The header's weight order: embed_tokens, final norm, then per layer LAYER_KEYS (2 + 9 * layers names)."""
+    return _d128.weight_order(LAYER_KEYS, layers)
 
 
 def hf_state_dict(weights: Dict[str, "np.ndarray"], layers: int) -> Dict[str, "np.ndarray"]:
     """Our weight names -> HF MistralModel / LlamaModel's (no "model." prefix)."""
-    sd = {"embed_tokens.weight": weights["embed_tokens"], "norm.weight": weights["norm"]}
-    for l in range(layers):
-        for k, hf in HF_LAYER_NAMES.items():
-            sd[f"layers.{l}.{hf}"] = weights[f"l{l}.{k}"]
-    return sd
+    return _d128.hf_state_dict(HF_LAYER_NAMES, weights, layers)
 
 
 def random_llama_weights(shape, seed: int = 0, std: float = 0.02) -> Dict[str, "np.ndarray"]:
-    """Seeded random weights of a shape (a LlamaShape or a LLAMA_SHAPES name). Matrices are drawn with std `std` and ROUNDED TO bf16
-    (kept as float32 values): the released checkpoints are bf16, and a float32 reference on the same values measures the kernels'
-    activation rounding alone. Norm weights are drawn around 1, not set to it."""
-    if isinstance(shape, str):
-        shape = LLAMA_SHAPES[shape]
-    vocab, H, L, nq, nkv, I = shape[:6]
-    mat, vec = seeded_mat_vec(seed, std=std)
-    w = {"embed_tokens": mat(vocab, H), "norm": vec(H)}
-    for l in range(L):
-        p = f"l{l}."
-        w[p + "wq"], w[p + "wk"], w[p + "wv"] = mat(nq * HEAD_DIM, H), mat(nkv * HEAD_DIM, H), mat(nkv * HEAD_DIM, H)
-        w[p + "wo"] = mat(H, nq * HEAD_DIM)
-        w[p + "ln_in"], w[p + "ln_post"] = vec(H), vec(H)
-        w[p + "w_gate"], w[p + "w_up"], w[p + "w_down"] = mat(I, H), mat(I, H), mat(H, I)
-    return w
+    """Seeded random weights of a shape (a LlamaShape or a LLAMA_SHAPES name), as _decoder128.random_weights draws them."""
+    return _d128.random_weights(LAYER_KEYS, LLAMA_SHAPES[shape] if isinstance(shape, str) else shape, seed, std)
 
 
 def _rope(cfg: dict):
@@ -209,42 +185,16 @@ def load_llama_weights(model_dir: str):
     in the header's names). A "model." prefix on the tensor names is stripped; lm_head is ignored. No network."""
     cj = os.path.join(model_dir, "config.json")
     shape = llama_config_shape(json.load(open(cj)), cj)
-    sd = read_safetensors_dir(model_dir)
-    w = {"embed_tokens": sd["embed_tokens.weight"], "norm": sd["norm.weight"]}
-    for l in range(shape.layers):
-        for k, hf in HF_LAYER_NAMES.items():
-            w[f"l{l}.{k}"] = sd[f"layers.{l}.{hf}"]
-    return shape, w
+    return shape, _d128.from_hf_state_dict(HF_LAYER_NAMES, read_safetensors_dir(model_dir), shape.layers)
 
 
 def read_llama_st_config(model_dir: str):
     """sentence-transformers files of a Mistral / Llama checkpoint: `modules.json` (Normalize module?), the Pooling module's config and
     `sentence_bert_config.json` (max_seq_length). Returns (pooling, max_seq_length | None, always_normalise); pooling is "last"
     (lasttoken) or "mean" (mean_tokens) -- what the checkpoint says; what the kernels implement is HipLlama's to decide --, anything
-    else is refused."""
-    max_len, norm, pool_dir = None, False, "1_Pooling"
-    mj = os.path.join(model_dir, "modules.json")
-    if os.path.exists(mj):
-        for m in json.load(open(mj)):
-            kind = m.get("type", "")
-            if kind.endswith("Normalize"):
-                norm = True
-            elif kind.endswith("Pooling"):
-                pool_dir = m.get("path", pool_dir)
-            elif not kind.endswith("Transformer"):
-                raise ValueError(f"{model_dir}: modules.json module {kind!r} is not supported (Transformer, Pooling, Normalize)")
-    pj = os.path.join(model_dir, pool_dir, "config.json")
-    if not os.path.exists(pj):
-        raise ValueError(f"{model_dir}: no {pool_dir}/config.json (a decoder embedder states its pooling there)")
-    pc = json.load(open(pj))
-    modes = [k for k in ("cls_token", "mean_tokens", "max_tokens", "mean_sqrt_len_tokens", "weightedmean_tokens", "lasttoken")
-             if pc.get("pooling_mode_" + k)]
-    if modes not in (["lasttoken"], ["mean_tokens"]):
-        raise ValueError(f"{model_dir}: pooling modes {modes} (a Mistral / Llama embedder pools lasttoken or mean_tokens)")
-    sj = os.path.join(model_dir, "sentence_bert_config.json")
-    if os.path.exists(sj):
-        max_len = json.load(open(sj)).get("max_seq_length")
-    return "last" if modes == ["lasttoken"] else "mean", max_len, norm
+    else is refused, a module other than Transformer / Pooling / Normalize too."""
+    return _d128.read_st_config(model_dir, {"lasttoken": "last", "mean_tokens": "mean"}, True, "a decoder embedder states its pooling there",
+                                "a Mistral / Llama embedder pools lasttoken or mean_tokens")
 
 
 def resolve_mode(model_name: str, shape: Optional[LlamaShape], model_kwargs: dict, st_pool: Optional[str]) -> str:
@@ -271,26 +221,32 @@ def apply_mode(shape: LlamaShape, model_kwargs: dict) -> LlamaShape:
 class HipLlama(HipStack):
     family, prefix, embed_key, matrix_keys = "llama", "llama", "embed_tokens", MATRIX_KEYS
     poolings, pooling_noun = ("last", "mean"), "Mistral / Llama embedders"
+    shape_type, layer_keys = LlamaShape, LAYER_KEYS      # HipQwen2 restates these, the four names above and _config
 
     def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
         """shape: a LlamaShape (or a plain tuple in its order); weights: the header's names (weight_order), numpy arrays or torch
         tensors. Under llama3 scaling the rotary table is rebuilt from rope_inv_freq(shape), HF's own float32 frequencies."""
-        shape = LlamaShape(*shape)
+        shape = self.shape_type(*shape)
         self.shape = shape
         self.hidden, self.layers, self.vocab, self.out_dim = shape.hidden, shape.layers, shape.vocab, shape.hidden
         self.max_seq = min(int(shape.max_position), MAX_SEQ)
         if shape.attention not in ("causal", "bidirectional"):
             raise ValueError(f"attention {shape.attention!r} (\"causal\" or \"bidirectional\")")
         self.bidirectional = shape.attention == "bidirectional"
-        self.window = 0 if self.bidirectional else int(shape.window)
         self.pooling = shape.pooling            # what forward() pools with when it is not told
-        self._upload(weights, weight_order(shape.layers), device)
-        self._create(AkLlamaConfig(shape.vocab, shape.hidden, shape.layers, shape.q_heads, shape.kv_heads, HEAD_DIM, shape.intermediate,
-                                   shape.max_position, shape.rms_eps, shape.rope_theta, self.window, int(self.bidirectional)),
-                     weight_order(shape.layers))
-        if shape.scaling is not None:           # default RoPE: the table ak_llama_create built from theta
+        names = _d128.weight_order(self.layer_keys, shape.layers)
+        self._upload(weights, names, device)
+        self._create(self._config(shape), names)
+        if shape.scaling is not None:           # default RoPE: the table ak_<prefix>_create built from theta
             inv = np.ascontiguousarray(rope_inv_freq(shape), np.float32)
-            check(self._lib.ak_llama_set_rope_inv_freq(self._h, ctypes.c_void_p(inv.ctypes.data)), "ak_llama_set_rope_inv_freq")
+            fn = f"ak_{self.prefix}_set_rope_inv_freq"
+            check(getattr(self._lib, fn)(self._h, ctypes.c_void_p(inv.ctypes.data)), fn)
+
+    def _config(self, shape):
+        """The library's config struct of a checked shape."""
+        self.window = 0 if self.bidirectional else int(shape.window)
+        return AkLlamaConfig(shape.vocab, shape.hidden, shape.layers, shape.q_heads, shape.kv_heads, HEAD_DIM, shape.intermediate,
+                             shape.max_position, shape.rms_eps, shape.rope_theta, self.window, int(self.bidirectional))
 
     def forward(self, ids, lens, pooling: Optional[str] = None, normalise: bool = True, S: Optional[int] = None):
         """ids [B, W] (row i holds lens[i] ids), lens [B] -> [B, hidden] float32 CUDA tensor (one tile, S = W rounded up to 32)."""

@@ -3,27 +3,28 @@
 reference's retrievers single out (src/data_manager/vectorstore/retrievers/utils.py:7-19) and loads by name through HuggingFaceEmbeddings.
 
 PyTorch-ROCm only HOLDS the weights in HBM (bf16 matrices, fp32 vectors and biases) and hands raw device pointers to the C ABI; every
-arithmetic step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/qwen2.hip on llama.hip's layer loop, attn_causal.hip,
-decoder.hip, gemm.hip). Against the Mistral / Llama path (llama.py): a bias on the q, k and v projections, up to 8 query heads per kv
-head (attn_causal.hip's split mapping from 5 on), no sliding window. Also here: the config check (qwen2_config_shape), the checkpoint
-loader and seeded random weights of the named shapes. The sentence-transformers files, the attention / pooling modes and the rotary
-frequencies are llama.py's.
+arithmetic step of the forward pass runs in hand-written HIP kernels (archi_amd/csrc/decoder128.hip, the head-128 decoder stack behind
+qwen2.hip's ABI; attn_causal.hip, gemm.hip). Against the Mistral / Llama path (llama.py): a bias on the q, k and v projections, up to
+8 query heads per kv head (attn_causal.hip's split mapping from 5 on), no sliding window. Also here: the config check
+(qwen2_config_shape), the checkpoint loader and seeded random weights of the named shapes. The handle's body, the sentence-transformers
+files, the attention / pooling modes and the rotary frequencies are llama.py's.
 
 Attention is causal unless the checkpoint's config.json says `is_causal: false` or the caller states
 model_kwargs={"attention": "bidirectional"} (which always wins); pooling is last-token or mean, resolved as llama.resolve_mode does.
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import os
 from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
-from ._lib import AkQwen2Config, check
-from ._stack import HipStack, read_safetensors_dir, seeded_mat_vec
-from .llama import HEAD_DIM, MAX_SEQ, Llama3Scaling, _rope, read_llama_st_config, resolve_mode, rope_inv_freq  # noqa: F401 (re-exported)
+from . import _decoder128 as _d128
+from ._decoder128 import HEAD_DIM, MATRIX_KEYS, MAX_SEQ, hf_layer_names, layer_keys  # noqa: F401 (re-exported)
+from ._lib import AkQwen2Config
+from ._stack import read_safetensors_dir
+from .llama import HipLlama, Llama3Scaling, _rope, read_llama_st_config, resolve_mode, rope_inv_freq  # noqa: F401 (re-exported)
 
 MAX_GROUP = 8           # most query heads per kv head (attn_causal.hip: one workgroup up to 4, two workgroups for 5 .. 8)
 
@@ -59,50 +60,25 @@ QWEN2_SHAPES = {
     "gte-qwen2-1.5b-2l": Qwen2Shape(2000, 1536, 2, 12, 2, 8960, 131072, 1e6, 1e-6),
 }
 
-LAYER_KEYS = ("wq", "wk", "wv", "bq", "bk", "bv", "wo", "ln_in", "ln_post", "w_gate", "w_up", "w_down")
-MATRIX_KEYS = {"wq", "wk", "wv", "wo", "w_gate", "w_up", "w_down"}
-# our name -> HF Qwen2Model state-dict name (layer keys under "layers.{l}.")
-HF_LAYER_NAMES = {"wq": "self_attn.q_proj.weight", "wk": "self_attn.k_proj.weight", "wv": "self_attn.v_proj.weight",
-                  "bq": "self_attn.q_proj.bias", "bk": "self_attn.k_proj.bias", "bv": "self_attn.v_proj.bias",
-                  "wo": "self_attn.o_proj.weight", "ln_in": "input_layernorm.weight", "ln_post": "post_attention_layernorm.weight",
-                  "w_gate": "mlp.gate_proj.weight", "w_up": "mlp.up_proj.weight", "w_down": "mlp.down_proj.weight"}
+LAYER_KEYS = layer_keys(qkv_bias=True)     # wq wk wv bq bk bv wo ln_in ln_post w_gate w_up w_down
+HF_LAYER_NAMES = hf_layer_names(LAYER_KEYS)      # our name -> HF Qwen2Model state-dict name (layer keys under "layers.{l}.")
 
 
 def weight_order(layers: int) -> List[str]:
-    """The header's weight order: embed_tokens, final norm, then per layer wq wk wv bq bk bv wo ln_in ln_post w_gate w_up w_down
-    (2 + 12 * layers names)."""
-    names = ["embed_tokens", "norm"]
-    for l in range(layers):
-        names += [f"l{l}.{k}" for k in LAYER_KEYS]
-    return names
+    """The header's weight order: embed_tokens, final norm, then per layer LAYER_KEYS (2 + 12 * layers names)."""
+    return _d128.weight_order(LAYER_KEYS, layers)
 
 
 def hf_state_dict(weights: Dict[str, "np.ndarray"], layers: int) -> Dict[str, "np.ndarray"]:
     """Our weight names -> HF Qwen2Model's (no "model." prefix)."""
-    sd = {"embed_tokens.weight": weights["embed_tokens"], "norm.weight": weights["norm"]}
-    for l in range(layers):
-        for k, hf in HF_LAYER_NAMES.items():
-            sd[f"layers.{l}.{hf}"] = weights[f"l{l}.{k}"]
-    return sd
+    return _d128.hf_state_dict(HF_LAYER_NAMES, weights, layers)
 
 
 def random_qwen2_weights(shape, seed: int = 0, std: float = 0.02, bias_std: float = 2.0) -> Dict[str, "np.ndarray"]:
-    """Seeded random weights of a shape (a Qwen2Shape or a QWEN2_SHAPES name), as llama.random_llama_weights draws them; the q / k / v
+    """Seeded random weights of a shape (a Qwen2Shape or a QWEN2_SHAPES name), as _decoder128.random_weights draws them; the q / k / v
     biases are drawn at their own `bias_std` (released Qwen2 biases are large, the k biases above all) and ROUNDED TO bf16 like the
     matrices (kept as float32 values): the released checkpoints are bf16."""
-    if isinstance(shape, str):
-        shape = QWEN2_SHAPES[shape]
-    vocab, H, L, nq, nkv, I = shape[:6]
-    mat, vec = seeded_mat_vec(seed, std=std)
-    w = {"embed_tokens": mat(vocab, H), "norm": vec(H)}
-    for l in range(L):
-        p = f"l{l}."
-        w[p + "wq"], w[p + "wk"], w[p + "wv"] = mat(nq * HEAD_DIM, H), mat(nkv * HEAD_DIM, H), mat(nkv * HEAD_DIM, H)
-        w[p + "bq"], w[p + "bk"], w[p + "bv"] = (mat(1, n * HEAD_DIM, bias_std)[0] for n in (nq, nkv, nkv))
-        w[p + "wo"] = mat(H, nq * HEAD_DIM)
-        w[p + "ln_in"], w[p + "ln_post"] = vec(H), vec(H)
-        w[p + "w_gate"], w[p + "w_up"], w[p + "w_down"] = mat(I, H), mat(I, H), mat(H, I)
-    return w
+    return _d128.random_weights(LAYER_KEYS, QWEN2_SHAPES[shape] if isinstance(shape, str) else shape, seed, std, bias_std)
 
 
 def qwen2_config_shape(cfg: dict, where: str = "config.json") -> Qwen2Shape:
@@ -146,12 +122,7 @@ def load_qwen2_weights(model_dir: str):
     header's names). A "model." prefix on the tensor names is stripped; lm_head is ignored. No network."""
     cj = os.path.join(model_dir, "config.json")
     shape = qwen2_config_shape(json.load(open(cj)), cj)
-    sd = read_safetensors_dir(model_dir)
-    w = {"embed_tokens": sd["embed_tokens.weight"], "norm": sd["norm.weight"]}
-    for l in range(shape.layers):
-        for k, hf in HF_LAYER_NAMES.items():
-            w[f"l{l}.{k}"] = sd[f"layers.{l}.{hf}"]
-    return shape, w
+    return shape, _d128.from_hf_state_dict(HF_LAYER_NAMES, read_safetensors_dir(model_dir), shape.layers)
 
 
 def apply_mode(shape: Qwen2Shape, model_kwargs: dict) -> Qwen2Shape:
@@ -159,29 +130,11 @@ def apply_mode(shape: Qwen2Shape, model_kwargs: dict) -> Qwen2Shape:
     return Qwen2Shape(*shape)._replace(attention=model_kwargs.get("attention", Qwen2Shape(*shape).attention))
 
 
-class HipQwen2(HipStack):
-    family, prefix, embed_key, matrix_keys = "qwen2", "qwen2", "embed_tokens", MATRIX_KEYS
-    poolings, pooling_noun = ("last", "mean"), "Qwen2 embedders"
+class HipQwen2(HipLlama):
+    """HipLlama (its __init__: shape: a Qwen2Shape or a plain tuple in its order) behind ak_qwen2_*, on Qwen2's shape and weight names."""
+    family, prefix, pooling_noun = "qwen2", "qwen2", "Qwen2 embedders"
+    shape_type, layer_keys = Qwen2Shape, LAYER_KEYS
 
-    def __init__(self, shape, weights: Dict[str, "np.ndarray"], device: Optional[int] = None):
-        """shape: a Qwen2Shape (or a plain tuple in its order); weights: the header's names (weight_order), numpy arrays or torch
-        tensors. Under llama3 scaling the rotary table is rebuilt from llama.rope_inv_freq(shape), HF's own float32 frequencies."""
-        shape = Qwen2Shape(*shape)
-        self.shape = shape
-        self.hidden, self.layers, self.vocab, self.out_dim = shape.hidden, shape.layers, shape.vocab, shape.hidden
-        self.max_seq = min(int(shape.max_position), MAX_SEQ)
-        if shape.attention not in ("causal", "bidirectional"):
-            raise ValueError(f"attention {shape.attention!r} (\"causal\" or \"bidirectional\")")
-        self.bidirectional = shape.attention == "bidirectional"
-        self.pooling = shape.pooling            # what forward() pools with when it is not told
-        self._upload(weights, weight_order(shape.layers), device)
-        self._create(AkQwen2Config(shape.vocab, shape.hidden, shape.layers, shape.q_heads, shape.kv_heads, HEAD_DIM, shape.intermediate,
-                                   shape.max_position, shape.rms_eps, shape.rope_theta, int(self.bidirectional)),
-                     weight_order(shape.layers))
-        if shape.scaling is not None:           # default RoPE: the table ak_qwen2_create built from theta
-            inv = np.ascontiguousarray(rope_inv_freq(shape), np.float32)
-            check(self._lib.ak_qwen2_set_rope_inv_freq(self._h, ctypes.c_void_p(inv.ctypes.data)), "ak_qwen2_set_rope_inv_freq")
-
-    def forward(self, ids, lens, pooling: Optional[str] = None, normalise: bool = True, S: Optional[int] = None):
-        """ids [B, W] (row i holds lens[i] ids), lens [B] -> [B, hidden] float32 CUDA tensor (one tile, S = W rounded up to 32)."""
-        return super().forward(ids, lens, pooling=pooling, normalise=normalise, S=S)
+    def _config(self, shape):
+        return AkQwen2Config(shape.vocab, shape.hidden, shape.layers, shape.q_heads, shape.kv_heads, HEAD_DIM, shape.intermediate,
+                             shape.max_position, shape.rms_eps, shape.rope_theta, int(self.bidirectional))

@@ -482,7 +482,9 @@ int ak_encoder_gelu_table(uint16_t *out8192);
 /* ---- decoder: Qwen3-Embedding (0.6B / 4B / 8B), the instruction-aware embedders of the reference's retrievers -------- */
 /* retrievers/utils.py:7-11, semantic_retriever.py:31-38. The forward pass of HF Qwen3Model (RMSNorm, per-head q / k RMSNorm, rotate_half
  * RoPE, grouped-query causal attention at head dim 128, SwiGLU MLP), then the final norm of each row's LAST valid token and L2
- * normalisation (sentence-transformers' lasttoken Pooling + Normalize). bf16 MFMA GEMMs, float32 residual stream. */
+ * normalisation (sentence-transformers' lasttoken Pooling + Normalize). bf16 MFMA GEMMs, float32 residual stream.
+ * One of three ABIs over one implementation, the head-128 decoder stack (csrc/decoder128.hip; ak_llama_* and ak_qwen2_* below are the
+ * others): Qwen3 is the Mistral / Llama layer plus the per-head q / k norm, causal without a window, last-token pooling only. */
 typedef void *ak_decoder_t;
 typedef struct AkDecoderConfig {
     int vocab_size;     /* 151669 */
@@ -503,7 +505,10 @@ typedef struct AkDecoderConfig {
  *     +5 wo [H][q_heads 128] +6 ln_in [H] (input_layernorm) +7 ln_post [H] (post_attention_layernorm)
  *     +8 w_gate [I][H] +9 w_up [I][H] +10 w_down [H][I]
  * The library copies wq | wk | wv into one matrix and interleaves the gate and up rows at create; the other pointers must stay valid
- * until ak_decoder_destroy. */
+ * until ak_decoder_destroy. Refused (non-zero, message naming the field in the last-error string) by the stack's one config check,
+ * as ak_llama_create refuses it: head_dim != 128, q_heads % kv_heads, more than 4 query heads per kv head, hidden % 128,
+ * intermediate % 64, a non-positive size (hidden and intermediate among them), rms_eps or rope_theta, a weight count other than
+ * 2 + 11 * layers, a NULL pointer. */
 int ak_decoder_create(const AkDecoderConfig *cfg, const void *const *weights_dev, int n_weights, ak_decoder_t *out);
 int ak_decoder_destroy(ak_decoder_t h);
 /* The tile layout of ak_encoder_forward_lens: B right-padded rows of S token ids `ld_ids` int32 apart, lengths `lens_stride` apart
@@ -707,7 +712,8 @@ int ak_t5_forward_lens(ak_t5_t h, const int32_t *ids_dev, int ld_ids, const int3
  * q / k norm, grouped-query causal attention -- with sliding_window = w > 0 key k is visible to query q iff k <= q and q - k <= w - 1
  * (HF's sliding_window_overlay), or bidirectional attention for the embedders trained without the causal mask --, SwiGLU MLP; then the
  * final norm of each row's LAST valid token, or the mean of the final norm over the valid tokens, and L2 normalisation
- * (sentence-transformers' lasttoken / mean Pooling + Normalize). No bias anywhere. bf16 MFMA GEMMs, float32 residual stream / norms / softmax. */
+ * (sentence-transformers' lasttoken / mean Pooling + Normalize). No bias anywhere. bf16 MFMA GEMMs, float32 residual stream / norms / softmax.
+ * The plain layer of the head-128 decoder stack (csrc/decoder128.hip): ak_decoder_* adds the per-head norm to it, ak_qwen2_* the biases. */
 typedef void *ak_llama_t;
 typedef struct AkLlamaConfig {
     int vocab_size;     /* 32000 (Mistral) / 128256 (Llama 3.1) */
@@ -731,7 +737,7 @@ typedef struct AkLlamaConfig {
  * The library copies wq | wk | wv into one matrix and interleaves the gate and up rows at create; the other pointers must stay valid
  * until ak_llama_destroy. Refused (non-zero, message naming the field in the last-error string): head_dim != 128, q_heads % kv_heads,
  * more than 4 query heads per kv head, hidden % 128, intermediate % 64, sliding_window < 0, bidirectional other than 0 / 1, a non-positive size,
- * rms_eps or rope_theta, a weight count other than 2 + 9 * layers. */
+ * rms_eps or rope_theta, a weight count other than 2 + 9 * layers, a NULL pointer. */
 int ak_llama_create(const AkLlamaConfig *cfg, const void *const *weights_dev, int n_weights, ak_llama_t *out);
 int ak_llama_destroy(ak_llama_t h);
 /* Replace the rotary table ak_llama_create built from rope_theta by the table of GIVEN inverse frequencies (ak_decoder_rope_table_inv):
@@ -753,7 +759,8 @@ int ak_llama_forward_lens(ak_llama_t h, const int32_t *ids_dev, int ld_ids, cons
  * before its bf16 store -- and with up to 8 query heads per kv head (Qwen2-1.5B: 6, Qwen2-7B: 7, Qwen2.5-3B: 8, Qwen2.5-14B: 5). Causal
  * attention without a window, or bidirectional attention for the embedders trained without the causal mask; then the final norm of
  * each row's LAST valid token, or the mean of the final norm over the valid tokens, and L2 normalisation (sentence-transformers'
- * lasttoken / mean Pooling + Normalize). bf16 MFMA GEMMs, float32 residual stream / norms / softmax / biases. */
+ * lasttoken / mean Pooling + Normalize). bf16 MFMA GEMMs, float32 residual stream / norms / softmax / biases. The same handle, create
+ * and layer loop as ak_llama_* (csrc/decoder128.hip); with all-zero biases the two give the same bits. */
 typedef void *ak_qwen2_t;
 typedef struct AkQwen2Config {
     int vocab_size;     /* 151646 (gte-Qwen2) */

@@ -1,4 +1,4 @@
-"""Float64 statement of what k_ll_rope (llama.hip) computes, the bound a float32 / bf16 kernel must meet against it, a float32 emulation in
+"""Float64 statement of what k_ll_rope (decoder128.hip) computes, the bound a float32 / bf16 kernel must meet against it, a float32 emulation in
 the kernel's own order and the mutants the bound must see; in the manner of tests/stack_kernel_refs.py, whose RoPE bound this is without
 the RMSNorm in front. Plain numpy, written from the mathematics.
 

@@ -1,5 +1,5 @@
 """Cases and inputs of tests/test_stack_kernels_gpu.py, shared by the parent (float64 references), the child (launches) and the CPU
-suite (tests/test_stack_kernels_cpu.py): the small kernels of the pre-norm stacks -- decoder.hip (Qwen3, `dec`), mbert.hip (ModernBERT,
+suite (tests/test_stack_kernels_cpu.py): the small kernels of the pre-norm stacks -- decoder128.hip (Qwen3, `dec`), mbert.hip (ModernBERT,
 `mb`), gemma.hip (EmbeddingGemma, `gm`) -- and k_gemm MODE 3, one launch each, in the manner of tests/gemma_kernel_cases.py. Everything
 comes from a seed (the case's name); the shapes are the smallest at which each kernel can still go wrong."""
 import math

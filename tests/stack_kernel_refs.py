@@ -1,4 +1,4 @@
-"""Float64 statements of what the small kernels of the pre-norm stacks compute (decoder.hip, mbert.hip, gemma.hip), the bounds a
+"""Float64 statements of what the small kernels of the pre-norm stacks compute (decoder128.hip, mbert.hip, gemma.hip), the bounds a
 float32 / bf16 kernel must meet against them, float32 emulations in the kernels' summation order, and the mutants the bounds must see.
 Plain numpy, written from the mathematics; nothing here goes through the library or the HF-based *_ref.py files.
 

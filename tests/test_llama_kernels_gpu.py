@@ -1,4 +1,4 @@
-"""Kernel-level GPU tests of the Mistral / Llama family (llama.hip, the window argument of attn_causal.hip), ONE launch at a time through
+"""Kernel-level GPU tests of the Mistral / Llama family (decoder128.hip, the window argument of attn_causal.hip), ONE launch at a time through
 the ak_kts_ll_* wrappers, in child processes on their own timeouts (tests/llama_kernel_worker.py), in the manner of
 tests/test_stack_kernels_gpu.py. A child that ends badly stops every later start from this file.
 

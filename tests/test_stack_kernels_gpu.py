@@ -1,5 +1,5 @@
 """GPU suite of the small kernels of the stacks, launch by launch, in the manner of tests/test_gemma_kernels_gpu.py: the embedding,
-add + norm, RoPE, pooling, dense and L2 kernels of decoder.hip (Qwen3, `dec`), mbert.hip (ModernBERT, `mb`), gemma.hip (EmbeddingGemma,
+add + norm, RoPE, pooling, dense and L2 kernels of decoder128.hip (Qwen3, `dec`), mbert.hip (ModernBERT, `mb`), gemma.hip (EmbeddingGemma,
 `gm`) and nomic.hip (NomicBERT, `nb`), and k_gemm MODE 3, ONE launch at a time through the ak_kts_* wrappers, in child processes on
 libarchi_hip_dbg.so (tests/stack_kernel_worker.py; each case once, nothing is run again after a failure). The wrappers call the
 launch_* functions the forward passes call.
