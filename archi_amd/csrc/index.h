@@ -61,15 +61,19 @@ struct Index : IndexBook {
     hipEvent_t lex_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // ak_index_profile: stage boundaries of the hybrid query
     float max_na = 0.f;  // max over rows of na (for the ip / l2 error bound)
     float max_rho = 0.f; // f32 corpora: max over rows of |a - shadow(a)| / |a| (measured at ingest; certificate term rho_c)
-    // ---- int8 shadow of a 16-bit corpus (the i8 scan plan, scan.hip): rows8 [cap in whole tiles][dim] int8 with one scale per
-    // row, ea8 = scale * ea (the scan-side term), gb8 the filter's per-32-row-block maxima of ea8 / eb. Built lazily by the first
-    // search whose plan asks for it (ensure_shadow8), extended for appended rows, dropped when rows moved (a reclaim of tombstones renumbers the slots) or the
-    // buffers grew. Removed rows need nothing: the scan takes eb (-inf for a tombstone) from the index itself.
+    // ---- int8 shadow of a 16-bit corpus (the i8 scan plan, scan.hip): rows8 [cap in whole tiles][dim] int8, ea8 = scale * ea (the
+    // scan-side term), gb8 the filter's per-32-row-block maxima of ea8 / eb. The rows of a filter class (the 16 rows of a 32-row
+    // block with one value of row bit 2: gb8's sets) share ONE ea8 wherever they can adopt it, so that the scan's bound
+    // max(dot) * gb8 is a site's exact maximum; a row that cannot (zeros, a non-finite value, removed before the build, beyond the
+    // cap) keeps scale = max|a| / 127 (shadow8_scale.h has the rule). Built lazily by the first search whose plan asks for it
+    // (ensure_shadow8), extended for appended rows -- a row a published shadow holds is never rewritten, so the block an append
+    // lands in may be mixed --, dropped when rows moved (a reclaim of tombstones renumbers the slots) or the buffers grew.
+    // Removed rows need nothing: the scan takes eb (-inf for a tombstone) from the index itself.
     int8_t *rows8 = nullptr;
     float *ea8 = nullptr, *gb8 = nullptr;
     int64_t s8_n = 0, s8_cap = 0;          // rows covered / rows allocated
     uint64_t s8_epoch = 0;                 // the layout it was built for: IndexBook::reclaims, the epoch changes that renumbered slots
-    float max_rho8 = 0.f;                  // max over rows of |a - scale * a8| / |a|, rounded up
+    float max_rho8 = 0.f;                  // max over rows of |a - scale * a8| / |a| with the scale the scan applies (ea8 / ea), rounded up
     int64_t s8_builds = 0;                 // full builds so far (ak_index_i8_info)
     std::atomic<int64_t> s8_searches{0};   // searches that ran the i8 plan
     std::mutex s8_mu;

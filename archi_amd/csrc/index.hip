@@ -5,6 +5,7 @@
 // query (:317-332) of the reference.
 #include "index.h"
 #include "switches.h"
+#include "shadow8_scale.h"
 
 #include <algorithm>
 #include <atomic>
@@ -475,57 +476,84 @@ static int finish_rows(Index &ix, int64_t slot0, int64_t n, hipStream_t st) {
 }
 
 // ---- int8 shadow of a 16-bit corpus (the i8 scan plan) -----------------------
-// One wave per row: scale = max|a| / 127, a8 = round(a / scale) (four values per lane and step, one 32-bit store), the scan-side
-// term ea8 = scale * ea, and rho = |a - scale * a8| / |a| in double, maximum over the rows as the float bits of a non-negative
-// value (k_shadow_rho's method, rounded up the same way). A row of zeros has scale 0 and an all-zero shadow; a row with a
-// non-finite value gets one too and its rho is skipped -- such a row has no finite score in any plan.
+// One workgroup per 32-row block, one wave per 8 of its rows, a row at a time. First every row's own scale max|a| / 127 and what
+// it contributes to its filter class's shared term E (shadow8_scale.h: the class is the 16 rows of the block with the row's bit 2,
+// the set k_group_bounds maximises over) go to LDS; a row that a published shadow already holds (row < pub_n, an append into a
+// partly filled block) contributes its ea8 as it stands and is not touched again. Then each new row takes its scale from the rule
+// there -- the class's, so that ea8 = E for the whole class and the scan's bound max(dot) * E is the site's exact maximum, or its
+// own where it cannot adopt --, a8 = round(a / scale) (four values per lane and step, one 32-bit store), and rho =
+// |a - applied scale * a8| / |a| in double against the scale the scan applies (ea8 / ea for an adopting row), maximum over the
+// rows as the float bits of a non-negative value (k_shadow_rho's method, rounded up the same way). A row of zeros has scale 0 and
+// an all-zero shadow; a row with a non-finite value gets one too and its rho is skipped -- such a row has no finite score in any
+// plan.
 template <int DT>
-__global__ __launch_bounds__(256) void k_shadow8(const typename Store<DT>::T *__restrict__ rows, const float *__restrict__ ea, int64_t slot0,
-                                                 int64_t n, int dim, int8_t *__restrict__ rows8, float *__restrict__ ea8,
+__global__ __launch_bounds__(256) void k_shadow8(const typename Store<DT>::T *__restrict__ rows, const float *__restrict__ ea, int64_t pub_n,
+                                                 int64_t n_rows, int64_t blk0, int dim, int8_t *__restrict__ rows8, float *ea8,
                                                  unsigned int *__restrict__ out_bits) {
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r >= n) return;
-    const typename Store<DT>::T *a = rows + (slot0 + r) * (int64_t)dim;
-    float mx = 0.f;
-    bool bad = false;
-    for (int i = lane * 4; i < dim; i += 256)
+    __shared__ float s_own[S8_BLOCK], s_p[S8_BLOCK];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row0 = (blk0 + blockIdx.x) * S8_BLOCK;
+    for (int t = 0; t < 8; t++) {
+        const int i = wave * 8 + t;
+        const int64_t r = row0 + i;
+        float own = 0.f, p = 0.f;
+        if (r < pub_n) p = s8_published(ea8[r]);
+        else if (r < n_rows) {
+            const typename Store<DT>::T *a = rows + r * (int64_t)dim;
+            float mx = 0.f;
+            bool bad = false;
+            for (int c = lane * 4; c < dim; c += 256)
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float ax = fabsf(Store<DT>::load(a, i + j));
-            if (!(ax < INFINITY)) bad = true;
-            else if (ax > mx) mx = ax;
+                for (int j = 0; j < 4; j++) {
+                    const float ax = fabsf(Store<DT>::load(a, c + j));
+                    if (!(ax < INFINITY)) bad = true;
+                    else if (ax > mx) mx = ax;
+                }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+            bad = __any(bad);
+            own = s8_own_scale(mx, bad);
+            p = s8_product(own, ea[r]);
         }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    bad = __any(bad);
-    const float s = bad ? 0.f : mx / 127.f;
-    const float inv = s > 0.f ? 1.f / s : 0.f;
-    double e2 = 0.0, a2 = 0.0;
-    uint32_t *dst = (uint32_t *)(rows8 + (slot0 + r) * (int64_t)dim);
-    for (int i = lane * 4; i < dim; i += 256) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float x = Store<DT>::load(a, i + j);
-            float v = rintf(x * inv);
-            v = v > 127.f ? 127.f : (v < -127.f ? -127.f : v);
-            if (!(v == v)) v = 0.f;
-            const double d = (double)x - (double)s * (double)v;
-            e2 += d * d; a2 += (double)x * (double)x;
-            w |= ((uint32_t)(int)v & 0xffu) << (8 * j);
-        }
-        dst[i >> 2] = w;
+        if (lane == 0) { s_own[i] = own; s_p[i] = p; }
     }
+    __syncthreads();
+    float rho_max = 0.f;
+    for (int t = 0; t < 8; t++) {
+        const int i = wave * 8 + t;
+        const int64_t r = row0 + i;
+        if (r < pub_n || r >= n_rows) continue;       // (wave-uniform)
+        const float ear = ea[r];
+        const S8Scale sc = s8_block_row_scale(s_own, s_p, i, ear);     // the class's E from the block's contributions, then the rule
+        const float s = sc.scale;
+        const bool bad = !(s == s) || s == 0.f;         // zero row or non-finite value: all-zero shadow, rho skipped
+        const float inv = s > 0.f ? 1.f / s : 0.f;
+        const double sd = s8_applied_scale(sc, ear);
+        const typename Store<DT>::T *a = rows + r * (int64_t)dim;
+        double e2 = 0.0, a2 = 0.0;
+        uint32_t *dst = (uint32_t *)(rows8 + r * (int64_t)dim);
+        for (int c = lane * 4; c < dim; c += 256) {
+            uint32_t w = 0;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { e2 += __shfl_xor(e2, off); a2 += __shfl_xor(a2, off); }
-    if (lane == 0) {
-        ea8[slot0 + r] = s * ea[slot0 + r];
-        if (!bad && a2 > 0.0 && e2 == e2 && a2 < 1e300) {
-            const float rho = (float)(sqrt(e2 / a2) * 1.0001) + 1e-9f;
-            atomicMax(out_bits, __float_as_uint(rho));
+            for (int j = 0; j < 4; j++) {
+                const float x = Store<DT>::load(a, c + j);
+                float v = rintf(x * inv);
+                v = v > 127.f ? 127.f : (v < -127.f ? -127.f : v);
+                if (!(v == v)) v = 0.f;
+                const double d = (double)x - sd * (double)v;
+                e2 += d * d; a2 += (double)x * (double)x;
+                w |= ((uint32_t)(int)v & 0xffu) << (8 * j);
+            }
+            dst[c >> 2] = w;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { e2 += __shfl_xor(e2, off); a2 += __shfl_xor(a2, off); }
+        if (lane == 0) {
+            ea8[r] = sc.ea8;
+            if (!bad && a2 > 0.0 && e2 == e2 && a2 < 1e300) rho_max = fmaxf(rho_max, (float)(sqrt(e2 / a2) * 1.0001) + 1e-9f);
         }
     }
+    if (lane == 0 && rho_max > 0.f) atomicMax(out_bits, __float_as_uint(rho_max));
 }
 
 void release_shadow8(Index &ix) {
@@ -564,13 +592,15 @@ int ensure_shadow8(Index &ix, hipStream_t st) {
         unsigned int *bits = nullptr;
         AK_HIP(hipMalloc((void **)&bits, 4));
         hipError_t e = hipMemsetAsync(bits, 0, 4, st);
-        const unsigned grid = (unsigned)((n + 3) / 4);
+        // whole 32-row blocks from the one the first new row falls into: its published rows are read (their ea8 enters the
+        // class's shared term), never written
+        const int64_t blk0 = slot0 / 32, nblk = (ix.n + 31) / 32 - blk0;
+        const unsigned grid = (unsigned)nblk;
         if (e == hipSuccess) {
             if (ix.dtype == AK_DTYPE_BF16)
-                k_shadow8<AK_DTYPE_BF16><<<grid, 256, 0, st>>>((const Store<AK_DTYPE_BF16>::T *)ix.rows, ix.ea, slot0, n, ix.dim, ix.rows8, ix.ea8, bits);
+                k_shadow8<AK_DTYPE_BF16><<<grid, 256, 0, st>>>((const Store<AK_DTYPE_BF16>::T *)ix.rows, ix.ea, slot0, ix.n, blk0, ix.dim, ix.rows8, ix.ea8, bits);
             else
-                k_shadow8<AK_DTYPE_F16><<<grid, 256, 0, st>>>((const Store<AK_DTYPE_F16>::T *)ix.rows, ix.ea, slot0, n, ix.dim, ix.rows8, ix.ea8, bits);
-            const int64_t blk0 = slot0 / 32, nblk = (ix.n + 31) / 32 - blk0;
+                k_shadow8<AK_DTYPE_F16><<<grid, 256, 0, st>>>((const Store<AK_DTYPE_F16>::T *)ix.rows, ix.ea, slot0, ix.n, blk0, ix.dim, ix.rows8, ix.ea8, bits);
             k_group_bounds<<<(unsigned)((nblk * 2 + 255) / 256), 256, 0, st>>>(ix.ea8, ix.eb, ix.n, blk0, nblk, ix.gb8);
             e = hipGetLastError();
         }

@@ -605,7 +605,65 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
                 }
                 return;
             }
+            if constexpr (FILT_K == 1 && I8) {
+                // The int8 tile's whole-tile arrangement works on the BOUNDS. The int8 shadow gives the rows of a filter class one
+                // shared ea8 wherever they can adopt it (shadow8_scale.h), and eb is 0 for every live row of the metrics this plan
+                // takes: fma(site_dpos, gea, geb) is then bit for bit the site's maximum score -- the one positive factor is monotone
+                // and rounds identically -- so the sixteen bounds ARE the exact maxima the 16-bit body below computes from 128
+                // conversions and 128 fma per lane, and no row term is held across the tile. The 2 * NI thresholds and the tile's
+                // block terms are read once, the bounds go branch-free into a hit mask, one branch goes around everything else, and
+                // behind it only the sites where some lane passed are entered: the row terms of that block are read there, then
+                // site_scores and site_append as they stand. Nothing here depends on a class being uniform: for a mixed class (a
+                // row the cap excluded, a removed or filtered row, the block an append extended) the bound is still an upper
+                // bound and the site is merely entered without a hit. The same holds in a tail tile: a 32-row block past the corpus
+                // takes the LAST block's terms (stage_terms clamps the block number to gb_blocks - 1, so no unwritten gb8 is read)
+                // against whatever the allocated rows past n hold, and it is row_terms' masking of those rows (ea = 0, eb = -inf)
+                // that keeps them out -- the exact-maxima body relied on that masking alone. A row is appended iff its score reaches
+                // the threshold, and the bound never skips a site that holds such a row: the same keys as the other arrangements,
+                // in another order.
+                static_assert(2 * MI * NI <= 32, "one hit bit per site");
+                float thr_s[NI][2];
+#pragma unroll
+                for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++) thr_s[ni][c] = s_thr[(wc * NI + ni) * 32 + 16 * c + r16];
+                float gea[MI], geb[MI];
+#pragma unroll
+                for (int mi = 0; mi < MI; mi++) {
+                    gea[mi] = t_gb[(wr * MI + mi) * 4 + (kq & 1)];
+                    geb[mi] = t_gb[(wr * MI + mi) * 4 + 2 + (kq & 1)];
+                }
+                uint32_t hits = 0;
+#pragma unroll
+                for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+                    for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                        for (int c = 0; c < 2; c++)
+                            hits |= fmaf(site_dpos(mi, ni, c), gea[mi], geb[mi]) >= thr_s[ni][c] ? 1u << ((mi * NI + ni) * 2 + c) : 0u;
+                if (INSTR && (flags & 16)) hits = 0;
+                if (hits) {
+#pragma unroll
+                    for (int mi = 0; mi < MI; mi++) {
+                        if (!(hits & (((1u << (2 * NI)) - 1u) << (mi * NI * 2)))) continue;
+                        float4 e4[2], b4[2];
+                        row_terms(mi, e4, b4);
+#pragma unroll
+                        for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+                            for (int c = 0; c < 2; c++)
+                                if (hits & (1u << ((mi * NI + ni) * 2 + c))) {
+                                    if constexpr (INSTR) n_slow++;
+                                    float sc[8];
+                                    if (site_scores(mi, ni, c, e4, b4, sc) >= thr_s[ni][c]) site_append(mi, ni, c, thr_s[ni][c], sc);
+                                    else if constexpr (INSTR) n_drain++;     // entered without a hit (every lane counts its own: summed at the end)
+                                }
+                    }
+                }
+                return;
+            }
             if constexpr (FILT_K == 1) {
+                // (the 16-bit tiles; the int8 tile's body of this arrangement is the one above)
                 // Exact maxima of the whole tile first. What the site-by-site arrangement costs is not its bound but what follows it: a
                 // lane-site passes the bound about once in a hundred in the main pass, so about half of the wave's sites have SOME lane
                 // in the slow path, and the wave pays for each -- four LDS reads of row terms and their wait, the eight exact scores,
@@ -812,6 +870,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
         // pass, 14.5 k -> 9.8 k cycles and 892 -> 763 us per launch; in the main pass (ten entries per wave and tile) its ~450
         // instructions buy nothing over the whole-tile filter's ~420 and it does not ship there (docs/EXPERIMENTS.md, "hit queue").
         // It too ends inside tile_epilogue with an empty queue: nothing of a tile's filter crosses into the next tile.
+        // Class scales (shadow8_scale.h) take the work away at its source: with one ea8 per filter class a site's bound IS its exact
+        // maximum, the int8 tile's whole-tile filter keeps the sixteen bounds and drops the 128 conversions and fma per lane, and a
+        // lane-site passes about once in a thousand, the true hit rate: main-pass filter 4.25 k -> 3.1 k cycles per wave and tile, the
+        // seeding pass's queue gets a third of the pushes (docs/EXPERIMENTS.md, "class scales").
         // 16x16x32 (C::MFMA = 16; the MFMA shape as a lever of its own in a loop whose clock the chip holds down): the same buffers, phases, barriers and 16 fragment reads per phase X (8 in Y), but a fragment is 16 rows x K32
         // (lane: row l & 15, chunk 4s + (l >> 4) of K32 sub-step s) and a phase issues twice as many MFMAs of half the length -- the
         // same 512 pipe cycles. The accumulators stay f32x16 per 32 x 32 block, each MFMA works on a four-float slice of one (slice
@@ -1284,6 +1346,14 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void k_scan(
     if constexpr (INSTR) {
         if (dbg) {
             t_fin = TICK() - t_mark;
+            if constexpr (I8 && FILT_K == 1) {
+                // the whole-tile int8 filter has no drains: the high half of slot 5 holds the WAVE's lane-sites that were entered and
+                // appended nothing -- 0 where every class of the corpus is uniform and no row is masked
+                int e = (int)n_drain;
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
+                n_drain = e;
+            }
             if (lane == 0) {
                 long long *d = dbg + ((size_t)blockIdx.x * NW + wave) * 8;
                 d[0] = t_loop; d[1] = t_epi; d[2] = t_sync; d[3] = t_comp; d[4] = t_fin; d[5] = n_slow | (n_drain << 32); d[6] = n_comp; d[7] = ntiles;
@@ -1383,8 +1453,9 @@ __global__ __launch_bounds__(64) void k_query_setup(const float *__restrict__ q,
 }
 
 // ---------------------------------------------------------------------------
-// The int8 plan (AK_SCAN_I8): seeding and main pass read an int8 shadow of the 16-bit corpus and int8 queries, each with one
-// scale per row / per query. The kernel's score is s' = dot_i32 * ea8[row] (ea8 = row scale * ea); with the query's scale folded
+// The int8 plan (AK_SCAN_I8): seeding and main pass read an int8 shadow of the 16-bit corpus and int8 queries, with one scale per
+// query and, for the rows, one scan-side term per filter class wherever the class's rows can share it (shadow8_scale.h; a row's
+// own scale otherwise). The kernel's score is s' = dot_i32 * ea8[row] (ea8 = row scale * ea); with the query's scale folded
 // into QPrep::a the true-unit score is a * s' + b as for every other plan, so thresholds, keys and margins of ONE query live in
 // that query's own units and QPrep is the only place that converts (lists are per query: nothing compares across queries).
 //   eps: |a.q - (s_r a8).(s_q q8)| <= (rho_q + rho_c + rho_q rho_c) |a| |q| with rho_c the measured maximum over the rows

@@ -31,7 +31,10 @@ constexpr int TAIL_KP = 64, TAIL_MAX_DIM = 4096;      // the fused tail (exact.h
 // FILT_ (16x16x32 tiles only): arrangement of the per-tile filter. 0 = site by site (every filter group computes its bound, reads its
 // threshold, waits and branches into its slow path), 1 = the exact maxima of the whole tile first, branch-free, from thresholds and
 // row terms read once, and one branch around the sites that hold a true hit (tile_epilogue). Both append the same keys; which one
-// a tile ships on is decided like its MFMA shape (SHIP_FILT_* below).
+// a tile ships on is decided like its MFMA shape (SHIP_FILT_* below). On the int8 tile arrangement 1 takes the maxima from the
+// sixteen BOUNDS: the int8 shadow gives the rows of a filter class one scale (shadow8_scale.h), which makes a site's bound its
+// exact maximum -- 16 conversions and fma per lane instead of 128, no row terms held, the sites some lane passed entered behind
+// the one branch (docs/EXPERIMENTS.md, "class scales").
 // 2 (the int8 tile only) = queued: the sixteen bounds first, branch-free; the lane-sites that pass are gathered, site by site behind a
 // ballot, into the wave's own LDS queue and scored once per tile, one lane per entry (tile_epilogue, "queued"). Same keys again.
 template <int WM_, int WN_, int MI_, int NI_, int NSTAGE_, int MINW_, bool PHASED_ = false, int FILT_ = 0, int MFMA_ = 32>

@@ -33,7 +33,14 @@ for li, lname in enumerate(("seed", "main")):
           f"fragments+MFMA {(a[:,0]-stage-wait).mean()/1e3:9.1f} kcyc; per k-step: "
           f"{stage.mean()/(a[:,7].mean()*int(sys.argv[2])//64):.0f} / {wait.mean()/(a[:,7].mean()*int(sys.argv[2])//64):.0f} / "
           f"{(a[:,0]-stage-wait).mean()/(a[:,7].mean()*int(sys.argv[2])//64):.0f} cycles")
-    if drains.sum() > 0:
+    # the int8 tile's whole-tile filter (the main pass unless AK_SCAN_HITQ / AK_SCAN_FILTER say otherwise) has no drains: the high half
+    # holds the WAVE's lane-sites that were entered and appended nothing -- 0 on a corpus whose filter classes all share one scale
+    whole_tile_i8 = lname == "main" and dtype != "f32" and os.environ.get("AK_SCAN_HITQ", "") not in ("2", "3") \
+        and os.environ.get("AK_SCAN_FILTER", "") in ("", "2") and ix.scan_plan(nq, k).get("kprime") == 512
+    if whole_tile_i8:
+        print(f"   slow-path entries/wave {a[:,5].mean():.1f} (lane 0, of {a[:,7].mean()*16:.0f} sites)  entered without a hit/wave "
+              f"{drains.mean():.2f} (all lanes)  compactions/wave {a[:,6].mean():.1f}   total {tot/1e3:.0f} kcyc")
+    elif drains.sum() > 0:
         print(f"   queued filter: entries/wave {a[:,5].mean():.1f} = {a[:,5].mean()/a[:,7].mean():.1f} per tile (of 1024 lane-sites), "
               f"drains/wave {drains.mean():.1f} = {drains.mean()/a[:,7].mean():.2f} per tile, max {(drains/a[:,7]).max():.2f}  "
               f"compactions/wave {a[:,6].mean():.1f}   total {tot/1e3:.0f} kcyc")
