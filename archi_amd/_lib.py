@@ -206,6 +206,7 @@ SYMBOLS = [
     ("ak_index_distances", _I, [_P, _P, _P, _I64, _P, _P]),
     ("ak_index_search", _I, [_P, _P, _I, _I, _I, _P, _I64, _U64, _P, _P, _P, _P]),
     ("ak_index_mmr_search", _I, [_P, _P, _I, _I, _I, _D, _I, _P, _I64, _U64, _P, _P, _P, _P, _P]),
+    ("ak_index_group_search", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _I64, _U64, _P, _P, _P, _P, _P, _P]),
     ("ak_index_lex_attach", _I, [_P, _P, _I64, _P, _P, _P, _P, _U64]),
     ("ak_index_lex_clear", _I, [_P, _U64]),
     ("ak_index_lex_info", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),

@@ -17,45 +17,8 @@ namespace ak {
 
 #pragma clang fp contract(off)
 
-// load8 (the 8-element row load) and exact_finish (accumulator -> float8 distance) live in exact_arith.h: mmr.hip shares them.
-
-// One (query,row) distance in the oracle's arithmetic. `na` is the row's
-// precomputed pgvector-order sum of squares, `nb` the query's.
-template <int DT>
-__device__ inline double exact_distance(const typename Store<DT>::T *row, const float *q, int dim,
-                                        int metric, float na, float nb) {
-    using S = Store<DT>;
-    const bool vec = (dim % 8 == 0) && (((uintptr_t)row & 15) == 0);
-    float acc = 0.0f;
-    if (metric == AK_METRIC_L2) {
-        int i = 0;
-        if (vec)
-            for (; i < dim; i += 8) {
-                float v[8];
-                load8<DT>(row, i, v);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    float diff = __fsub_rn(v[j], q[i + j]);
-                    acc = __fadd_rn(acc, __fmul_rn(diff, diff));
-                }
-            }
-        for (; i < dim; i++) {
-            float diff = __fsub_rn(S::load(row, i), q[i]);
-            acc = __fadd_rn(acc, __fmul_rn(diff, diff));
-        }
-        return exact_finish(acc, metric, na, nb);
-    }
-    int i = 0;
-    if (vec)
-        for (; i < dim; i += 8) {
-            float v[8];
-            load8<DT>(row, i, v);
-#pragma unroll
-            for (int j = 0; j < 8; j++) acc = __fadd_rn(acc, __fmul_rn(v[j], q[i + j]));
-        }
-    for (; i < dim; i++) acc = __fadd_rn(acc, __fmul_rn(S::load(row, i), q[i]));
-    return exact_finish(acc, metric, na, nb);
-}
+// load8 (the 8-element row load), exact_finish (accumulator -> float8 distance) and exact_distance (one (query,row) distance) live
+// in exact_arith.h: mmr.hip and group.hip share them.
 
 // Thread per row, QB queries per pass (row element loaded once, reused QB times).
 template <int DT, int QB>

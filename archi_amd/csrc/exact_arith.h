@@ -1,6 +1,7 @@
-// exact_arith.h -- the two device functions every kernel that restates the reference arithmetic shares: the 8-element row load and
-// the finish of a float32 chain. exact.hip (exact_distance, the re-rank kernels) and mmr.hip (the candidate Gram) include it, so
-// that a pair distance and a query distance cannot drift apart.
+// exact_arith.h -- the device functions every kernel that restates the reference arithmetic shares: the 8-element row load, the
+// finish of a float32 chain and the (query,row) distance built from the two. exact.hip (the exact path, the re-rank kernels),
+// mmr.hip (the candidate Gram) and group.hip (the members of a group) include it, so that a pair distance, a member's distance
+// and a query distance cannot drift apart.
 #pragma once
 #include "common.h"
 
@@ -34,6 +35,45 @@ __device__ inline double exact_finish(float acc, int metric, float na, float nb)
     if (sim > 1.0) sim = 1.0;
     else if (sim < -1.0) sim = -1.0;
     return 1.0 - sim;
+}
+
+// One (query,row) distance in the oracle's arithmetic. `na` is the row's
+// precomputed pgvector-order sum of squares, `nb` the query's. exact.hip (the exact path, the thread-per-candidate re-rank) and
+// group.hip (the members of a group) call it.
+template <int DT>
+__device__ inline double exact_distance(const typename Store<DT>::T *row, const float *q, int dim,
+                                        int metric, float na, float nb) {
+    using S = Store<DT>;
+    const bool vec = (dim % 8 == 0) && (((uintptr_t)row & 15) == 0);
+    float acc = 0.0f;
+    if (metric == AK_METRIC_L2) {
+        int i = 0;
+        if (vec)
+            for (; i < dim; i += 8) {
+                float v[8];
+                load8<DT>(row, i, v);
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    float diff = __fsub_rn(v[j], q[i + j]);
+                    acc = __fadd_rn(acc, __fmul_rn(diff, diff));
+                }
+            }
+        for (; i < dim; i++) {
+            float diff = __fsub_rn(S::load(row, i), q[i]);
+            acc = __fadd_rn(acc, __fmul_rn(diff, diff));
+        }
+        return exact_finish(acc, metric, na, nb);
+    }
+    int i = 0;
+    if (vec)
+        for (; i < dim; i += 8) {
+            float v[8];
+            load8<DT>(row, i, v);
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc = __fadd_rn(acc, __fmul_rn(v[j], q[i + j]));
+        }
+    for (; i < dim; i++) acc = __fadd_rn(acc, __fmul_rn(S::load(row, i), q[i]));
+    return exact_finish(acc, metric, na, nb);
 }
 
 }  // namespace ak

@@ -15,6 +15,7 @@
 #pragma once
 #include <atomic>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <shared_mutex>
 #include <unordered_map>
@@ -151,8 +152,9 @@ void thread_scratch_trim();
 int writer_fence(Index &ix);                          // wait for the last asynchronous device search (caller holds the unique lock)
 int filter_is_current(const Index &ix, const void *row_filter, int64_t filter_len, uint64_t filter_epoch, const char *who);
 // ak_index_search_dev behind its argument checks; the caller holds ix.mu (shared) and has checked the filter's epoch
+// stats4 (nullable, host int64[4]): ak_index_search's out_stats of this call, AUTO mode on the MFMA scan (zeros are left otherwise)
 int search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, int mode, const uint8_t *row_filter_dev, int64_t *out_ids_dev,
-                      double *out_dist_dev, int *out_cert_dev, hipStream_t st);
+                      double *out_dist_dev, int *out_cert_dev, hipStream_t st, int64_t *stats4 = nullptr);
 // lexical.hip: what rebuild() / ak_index_remove / ak_index_destroy do to the lexical store
 struct LexMove { int64_t *off = nullptr; int32_t *cnt = nullptr, *len = nullptr; };   // the new per-slot arrays (zeroed, new capacity)
 int lex_rebuild(Index &ix, const LexMove &to, const std::vector<int64_t> *src, hipStream_t st, uint2 **new_arena, int64_t *new_cap,
@@ -192,6 +194,37 @@ MmrWs mmr_layout(void *base, int nq, int k, int fetch_k);      // base == NULL: 
 // dq_dev [nq][fetch_k] float64 distances and cnt_dev [nq] counts of the candidate search, rank order; everything on `st`
 int mmr_run(Index &ix, int nq, int k, int fetch_k, double lambda_mult, const double *dq_dev, const int *cnt_dev, const MmrWs &w,
             hipStream_t st);
+
+// ---- grouped search (group.hip) ----------------------------------------------------------------------------------------------
+// The device side of ak_index_group_search. The searches run through search_dev_locked (index.hip), the host resolves the returned
+// ids to row slots between a search and its collapse.
+constexpr int GROUP_MAX_K = 32, GROUP_MAX_SIZE = 8, GROUP_MAX_FETCH = 128;
+struct GroupWs {                          // one block of the calling thread's scratch
+    float *q = nullptr, *nb = nullptr;    // [nq][dim] queries, [nq] their norms (stage B)
+    int64_t *sids = nullptr;              // [nq][fetch] a round's search results: query q's row, whichever round wrote it last
+    double *sdist = nullptr;              // [nq][fetch]
+    int *scert = nullptr;                 // [nq]
+    int *slots = nullptr;                 // [nq][fetch] row slot of each returned id, -1 behind the list's end
+    int32_t *keys = nullptr;              // [slots, rounded up to 16] the caller's row_group
+    uint8_t *filter = nullptr;            // [same] the caller's row_filter, or NULL
+    uint8_t *mask = nullptr;              // [same] a later round's mask
+    int32_t *wkey = nullptr, *wslot = nullptr;   // [nq][GROUP_MAX_K] winners in rank order: group key, representative slot
+    int *wcnt = nullptr;                  // [nq] winners so far
+    unsigned long long *mcnt = nullptr, *cursor = nullptr;   // [nq] rows the members pass matched / the fill pass's write position
+    int64_t *off = nullptr;               // [nq] start of the query's list in its batch
+    int *overflow = nullptr;
+    int64_t *rid = nullptr;               // [nq][k][g] results
+    double *rdist = nullptr;              // [nq][k][g]
+    int32_t *rgroup = nullptr;            // [nq][k]
+    int *rsizes = nullptr;                // [nq][k]
+    size_t bytes = 0;
+};
+GroupWs group_layout(void *base, int nq, int k, int g, int fetch, int64_t n, int dim, bool has_filter);   // base == NULL: only .bytes
+int group_init(const GroupWs &w, int nq, int k, int g, hipStream_t st);                                   // padding, zero counts
+int group_collapse(Index &ix, const GroupWs &w, int q0, int nqr, int fetch, int k, int g, hipStream_t st);  // queries q0 .. q0 + nqr
+int group_exclude(Index &ix, const GroupWs &w, int q, int64_t n, hipStream_t st);                         // w.mask for query q
+int group_members(Index &ix, const GroupWs &w, int nq, int k, int g, int64_t n, const std::function<void *(size_t)> &reserve,
+                  hipStream_t st, int64_t *matched);
 
 // ---- fast path (scan.hip) ----------------------------------------------------
 // Fused tail of the fast path (exact.hip), one workgroup per query: the dense candidate list the scans appended to

@@ -66,6 +66,7 @@ const SwitchName g_switch_names[] = {
     {"AK_COALESCE", &Switches::coalesce, 1, false, false, false},
     {"AK_LEX_BATCH_PAIRS", &Switches::lex_batch_pairs, 1 << 24, false, false, false},
     {"AK_LEX_BATCH_TERMS", &Switches::lex_batch_terms, 0, false, false, false},
+    {"AK_GROUP_FETCH", &Switches::group_fetch, 0, false, false, false},
     {"AK_SHARD_INJECT", &Switches::shard_inject, 0, false, false, false},
     {"AK_QUERY_FUSED", &Switches::query_fused, 0, false, false, false},
 #if AK_DBG_KERNELS      // WRONG RESULTS: the product library does not even know the names
@@ -117,6 +118,8 @@ int switches_set(const char *name, const char *value) {
             // ... and the passes of the int8 tile on the queued filter (AK_SCAN_HITQ = 1 .. 4)
             if (!DBG_KERNELS && n.field == &Switches::scan_hitq && switch_value(n, value) != 0) return -1;
             if (n.field == &Switches::scan_hitq && (switch_value(n, value) < 0 || switch_value(n, value) > 4)) return -1;
+            // ... and a grouped search's fetch width beyond what a round's collapse holds (AK_GROUP_FETCH = 1 .. 128; 0 and a reset pass)
+            if (n.field == &Switches::group_fetch && (switch_value(n, value) < 0 || switch_value(n, value) > GROUP_MAX_FETCH)) return -1;
             (sw.*(n.field)).store(switch_value(n, value), std::memory_order_relaxed);
             return 0;
         }
@@ -1477,6 +1480,141 @@ int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int f
     return 0;
 }
 
+// Grouped search (no counterpart in the reference's store, whose callers collapse the retriever's chunks by document on the host;
+// the contract is in include/archi_knn.h, the kernels in group.hip). Every round -- search, the host's id -> slot step (as
+// ak_index_mmr_search), collapse -- and the members stage run under ONE hold of the shared lock. Round 1 is one search for all
+// queries; a query that still misses groups, and whose round came back full, goes on alone, because the scan takes one mask for
+// all its queries. Results are gathered on the device and land in thread-local host vectors before they reach the caller's arrays.
+int ak_index_group_search(ak_index_t h, const float *queries, int nq, int k, int group_size, int mode, const int32_t *row_group,
+                          const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch, int64_t *out_ids, double *out_dist,
+                          int32_t *out_group, int *out_sizes, int *out_counts, int64_t *out_stats) {
+    // the limits first: they are refused by name before the device is bound or the handle looked at
+    if (k < 1 || k > GROUP_MAX_K) AK_FAIL(-1, "ak_index_group_search: k must be in 1 .. 32");
+    if (group_size < 1 || group_size > GROUP_MAX_SIZE) AK_FAIL(-1, "ak_index_group_search: group_size must be in 1 .. 8");
+    if (mode == AK_SEARCH_FAST_ONLY) AK_FAIL(-1, "ak_index_group_search: mode FAST_ONLY is not supported (AUTO or EXACT)");
+    if (mode != AK_SEARCH_AUTO && mode != AK_SEARCH_EXACT) AK_FAIL(-1, "ak_index_group_search: bad mode");
+    AK_BIND();
+    if (!h) AK_FAIL(-1, "ak_index_group_search: NULL index");
+    Index &ix = *(Index *)h;
+    if (!row_group) AK_FAIL(-1, "ak_index_group_search: row_group is required");
+    if (nq < 0 || (nq > 0 && (!queries || !out_ids || !out_dist || !out_group || !out_sizes))) AK_FAIL(-1, "ak_index_group_search: bad arguments");
+    if (nq > (1 << 20)) AK_FAIL(-1, "ak_index_group_search: more than 2^20 queries");
+    RoctxRange range("ak_index_group_search");
+    const int g = group_size;
+    const int forced = switches().group_fetch.load(std::memory_order_relaxed);
+    const int fetch = forced > 0 ? forced : std::min(std::max(4 * k, 16), GROUP_MAX_FETCH);
+    static thread_local std::vector<int64_t> hid, rid;
+    static thread_local std::vector<double> rd;
+    static thread_local std::vector<int> hslot, hm, hw, rs;
+    static thread_local std::vector<int32_t> rg;
+    const size_t nf = (size_t)nq * fetch, nr = (size_t)nq * k * g, ng = (size_t)nq * k;
+    hid.resize(nf); hslot.resize(nf); hm.resize(nq); hw.resize(nq);
+    rid.assign(nr, -1); rd.assign(nr, __builtin_nan("")); rg.assign(ng, -1); rs.assign(ng, 0);
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (;;) {
+        std::shared_lock<std::shared_mutex> lk(ix.mu);
+        if (!ix.map_built) {                                 // generated rows not in the map yet (or a generate ran in between)
+            lk.unlock();
+            std::unique_lock<std::shared_mutex> wl(ix.mu);
+            if (!ix.map_built) (void)ix.slot_of(-1);        // a miss builds the lazy map
+            continue;
+        }
+        const IndexBook &book = ix;                          // readers: const members only
+        // row_group is a statement about one layout, as the mask is: checked even when there is no mask
+        if (int frc = filter_is_current(ix, row_group, filter_len, filter_epoch, "ak_index_group_search")) return frc;
+        const int64_t n = ix.n;
+        if (nq == 0 || n == 0 || ix.n_alive == 0) { std::fill(hw.begin(), hw.end(), 0); break; }      // nothing to search: padding only
+        hipStream_t st;
+        if (thread_stream(&st)) return -10;
+        const GroupWs need = group_layout(nullptr, nq, k, g, fetch, n, ix.dim, row_filter != nullptr);
+        if (scratch_reserve(&t_ctx.dev, &t_ctx.dev_cap, need.bytes, false)) { t_ctx.trim(); return -10; }
+        const GroupWs w = group_layout(t_ctx.dev, nq, k, g, fetch, n, ix.dim, row_filter != nullptr);
+        // id -> slot of queries [q0, q0 + c): their rows of w.sids come to the host, their rows of w.slots go back
+        auto resolve = [&](int q0, int c) -> int {
+            AK_HIP(hipMemcpyAsync(hid.data() + (size_t)q0 * fetch, w.sids + (size_t)q0 * fetch, (size_t)c * fetch * 8, hipMemcpyDeviceToHost, st));
+            AK_HIP(hipStreamSynchronize(st));
+            for (int q = q0; q < q0 + c; q++) {
+                int m = 0;
+                for (int r = 0; r < fetch; r++) {
+                    const int64_t id = hid[(size_t)q * fetch + r];
+                    int slot = -1;
+                    if (id >= 0 && m == r) {
+                        const auto it = book.id2slot.find(id);
+                        if (it == book.id2slot.end() || it->second < 0 || it->second >= n)
+                            AK_FAIL(-1, "ak_index_group_search: a returned id has no row slot");
+                        slot = (int)(uint32_t)it->second;
+                        m++;
+                    }
+                    hslot[(size_t)q * fetch + r] = slot;
+                }
+                hm[q] = m;
+            }
+            AK_HIP(hipMemcpyAsync(w.slots + (size_t)q0 * fetch, hslot.data() + (size_t)q0 * fetch, (size_t)c * fetch * 4, hipMemcpyHostToDevice, st));
+            return 0;
+        };
+        int rc = 0;
+        do {
+            if (hipMemcpyAsync(w.q, queries, (size_t)nq * ix.dim * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+                hipMemcpyAsync(w.keys, row_group, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+                (row_filter && hipMemcpyAsync(w.filter, row_filter, (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)) {
+                rc = -10; set_error("ak_index_group_search: H2D failed"); break;
+            }
+            if ((rc = group_init(w, nq, k, g, st))) break;
+            // round 1: every query
+            if ((rc = search_dev_locked(ix, w.q, nq, fetch, mode, w.filter, w.sids, w.sdist, w.scert, st, stats))) break;
+            stats[7]++;
+            if ((rc = resolve(0, nq))) break;
+            if ((rc = group_collapse(ix, w, 0, nq, fetch, k, g, st))) break;
+            if (hipMemcpyAsync(hw.data(), w.wcnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error("ak_index_group_search: D2H failed"); break; }
+            stats[4] = nq;
+            // later rounds: a query is done when it has k groups or its last round came back short (the filtered set is exhausted)
+            for (int q = 0; q < nq && !rc; q++) {
+                int rounds = 1;
+                while (hw[q] < k && hm[q] == fetch) {
+                    if (rounds > k) { rc = -1; set_error("ak_index_group_search: more rounds than groups"); break; }
+                    const int before = hw[q];
+                    if ((rc = group_exclude(ix, w, q, n, st))) break;
+                    if ((rc = search_dev_locked(ix, w.q + (size_t)q * ix.dim, 1, fetch, mode, w.mask, w.sids + (size_t)q * fetch,
+                                                w.sdist + (size_t)q * fetch, w.scert + q, st))) break;
+                    stats[7]++;
+                    if ((rc = resolve(q, 1))) break;
+                    if ((rc = group_collapse(ix, w, q, 1, fetch, k, g, st))) break;
+                    if (hipMemcpyAsync(hw.data() + q, w.wcnt + q, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error("ak_index_group_search: D2H failed"); break; }
+                    rounds++;
+                    stats[4]++;
+                    if (hw[q] == before && hm[q] > 0) { rc = -1; set_error("ak_index_group_search: a round found no new group"); break; }
+                }
+                if (rounds > 1) stats[5]++;
+            }
+            if (rc) break;
+            if (g > 1) {
+                auto reserve = [&](size_t bytes) -> void * { return scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, bytes, false) ? nullptr : t_ctx.ws; };
+                if ((rc = group_members(ix, w, nq, k, g, n, reserve, st, &stats[6]))) break;
+            }
+            if (hipMemcpyAsync(rid.data(), w.rid, nr * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(rd.data(), w.rdist, nr * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(rg.data(), w.rgroup, ng * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(rs.data(), w.rsizes, ng * 4, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = -10; set_error("ak_index_group_search: D2H failed"); break; }
+            if (hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error(std::string("ak_index_group_search: ") + hipGetErrorString(hipGetLastError())); }
+        } while (0);
+        if (rc) hipStreamSynchronize(st);      // nothing of a failed call may still be running on the cached buffers
+        t_ctx.trim();
+        if (rc) return rc;
+        break;
+    }
+    if (nq > 0) {
+        memcpy(out_ids, rid.data(), nr * 8);
+        memcpy(out_dist, rd.data(), nr * 8);
+        memcpy(out_group, rg.data(), ng * 4);
+        memcpy(out_sizes, rs.data(), ng * 4);
+        if (out_counts) memcpy(out_counts, hw.data(), (size_t)nq * 4);
+    }
+    if (out_stats) memcpy(out_stats, stats, sizeof(stats));
+    return 0;
+}
+
 int ak_index_search_dev(ak_index_t h, const float *queries_dev, int nq, int k, int mode, const uint8_t *row_filter_dev,
                         int64_t filter_len, uint64_t filter_epoch, int64_t *out_ids_dev, double *out_dist_dev, int *out_cert_dev,
                         void *stream) {
@@ -1496,7 +1634,7 @@ int ak_index_search_dev(ak_index_t h, const float *queries_dev, int nq, int k, i
 }  // extern "C"
 
 int ak::search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, int mode, const uint8_t *row_filter_dev,
-                          int64_t *out_ids_dev, double *out_dist_dev, int *out_cert_dev, hipStream_t st) {
+                          int64_t *out_ids_dev, double *out_dist_dev, int *out_cert_dev, hipStream_t st, int64_t *stats4) {
     std::lock_guard<std::mutex> wl(ix.ws_mu);
     // the previous call's kernels may still be running out of ws_dev on another stream
     if (ix.ws_pending && ix.ws_stream != st) AK_HIP(hipStreamWaitEvent(st, ix.ws_event, 0));
@@ -1537,13 +1675,17 @@ int ak::search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, in
     // AUTO: read the certificate flags, re-run what is open
     std::vector<int> cert(nq, 0), todo;
     AK_HIP(hipMemcpyAsync(cert.data(), dce, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    if (stats4) AK_HIP(hipMemcpyAsync(stats4, dst, 32, hipMemcpyDeviceToHost, st));
     AK_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < nq; i++) if (!cert[i]) todo.push_back(i);
+    if (stats4) { stats4[0] = nq - (int64_t)todo.size(); stats4[1] = (int64_t)todo.size(); }
     if (!todo.empty()) {
+        RerunStats rs;
         auto reserve = [&](size_t bytes) -> void * { return ix.ws_fb.reserve(bytes) ? nullptr : ix.ws_fb.buf; };
         if ((rc = rerun_uncertified(ix, queries_dev, dnb, nq, k, row_filter_dev, out_ids_dev, out_dist_dev, dct, dce, todo, true,
-                                    plan.i8 ? TAIL_KP : plan.kprime, reserve, st, nullptr))) return rc;
+                                    plan.i8 ? TAIL_KP : plan.kprime, reserve, st, stats4 ? &rs : nullptr))) return rc;
         AK_HIP(hipStreamSynchronize(st));
+        if (stats4) { stats4[0] += rs.second_certified; stats4[1] = rs.exact; stats4[3] = rs.second_certified; }
     }
     guard.armed = false;      // the stream was synchronised after the last kernel: nothing of this call is in flight
     ix.ws_pending = false;

@@ -40,6 +40,7 @@ struct Switches {
     std::atomic<int> coalesce{1};        // AK_COALESCE: 0 = concurrent single-query calls are not served together
     std::atomic<int> lex_batch_pairs{1 << 24};   // AK_LEX_BATCH_PAIRS: (query, row of U) pairs the batch hybrid call's hit leg holds at once
     std::atomic<int> lex_batch_terms{0}; // AK_LEX_BATCH_TERMS: distinct terms per sub-batch below the table's capacity (0 = LEX_BT_CAP; tests)
+    std::atomic<int> group_fetch{0};     // AK_GROUP_FETCH: rows a round of ak_index_group_search fetches, 1 .. 128 (0 = clamp(4 k, 16, 128))
     std::atomic<int> shard_inject{0};    // AK_SHARD_INJECT: error injection of ak_index_search_sharded_dev (shardcomm.hip; errors only)
     // WRONG RESULTS, dbg library only (always 0 in the product library)
     std::atomic<int> scan_ablate{0};     // AK_SCAN_ABLATE

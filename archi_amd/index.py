@@ -334,6 +334,57 @@ class HipIndex:
                      "second_chance": int(stats[3])},)
         return out
 
+    GROUP_MAX_K = 32
+    GROUP_MAX_SIZE = 8
+    GROUP_STATS = ("certified", "exact_reruns", "reranked", "second_chance", "rounds", "multi_round_queries", "member_rows",
+                   "searches")
+
+    def group_search(self, queries, k: int, group_size: int = 1, *, row_group: np.ndarray, row_filter: Optional[np.ndarray] = None,
+                     filter_epoch: Optional[int] = None, mode: str = "auto", return_stats: bool = False):
+        """Grouped search (ak_index_group_search; no counterpart in the reference's store): the k nearest groups of rows and the
+        best group_size rows of each. row_group: int32 per row slot, a key >= 0 names the row's group, a negative key makes the row
+        a group by itself; it and row_filter belong to the layout `filter_epoch` (layout()). Returns (ids [Q,k,g], distances
+        [Q,k,g] f64, group keys [Q,k] i32, sizes [Q,k], counts [Q]); groups in the order of their best row in search()'s list,
+        members in that list's order; padding id -1, NaN, key -1, size 0. return_stats appends a dict of GROUP_STATS.
+        1 <= k <= 32, 1 <= group_size <= 8, mode "auto" or "exact". Errors as search()."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq,{self.dim}] float32")
+        nq, k, g = q.shape[0], int(k), int(group_size)
+        grp = np.ascontiguousarray(row_group, dtype=np.int32)
+        if grp.ndim != 1:
+            raise ValueError("row_group must be one int32 per row slot")
+        flen = grp.shape[0]
+        flt = None
+        if row_filter is not None:
+            flt = np.ascontiguousarray(row_filter, dtype=np.uint8)
+            if flt.ndim != 1 or flt.shape[0] != flen:
+                raise ValueError("row_filter must be one byte per row slot, as long as row_group")
+        if filter_epoch is None:
+            slots, fep = self.layout()
+            if flen != slots:
+                raise ValueError(f"row_group must have {slots} entries (one per row slot)")
+        else:
+            fep = int(filter_epoch)
+        kk, gg = max(k, 0), max(g, 0)
+        out_ids = np.full((nq, kk, gg), -1, dtype=np.int64)
+        out_d = np.full((nq, kk, gg), np.nan, dtype=np.float64)
+        out_g = np.full((nq, kk), -1, dtype=np.int32)
+        out_s = np.zeros((nq, kk), dtype=np.int32)
+        cnt = np.zeros((nq,), dtype=np.int32)
+        stats = np.zeros(8, dtype=np.int64)
+        if flen == 0:
+            grp = np.zeros(1, dtype=np.int32)          # a pointer the library can check for NULL; nothing of it is read
+        check(self._lib.ak_index_group_search(self._h, _ptr(q), nq, k, g, SEARCH_MODES[mode], _ptr(grp), _ptr(flt), flen, fep,
+                                              _ptr(out_ids), _ptr(out_d), _ptr(out_g), _ptr(out_s), _ptr(cnt), _ptr(stats)),
+              "ak_index_group_search")
+        out = (out_ids, out_d, out_g, out_s, cnt)
+        if return_stats:
+            out += (dict(zip(self.GROUP_STATS, (int(v) for v in stats))),)
+        return out
+
     def search_device(self, queries_ptr: int, nq: int, k: int, out_ids_ptr: int, out_dist_ptr: int,
                       out_cert_ptr: int, stream: int = 0, mode: str = "fast_only", row_filter_ptr: int = 0,
                       filter_len: int = 0, filter_epoch: Optional[int] = None) -> None:

@@ -587,9 +587,9 @@ class ArchiHipVectorStore(_VectorStoreBase):
         for _ in range(self.STALE_RETRIES):
             with t.lock:
                 mask, epoch = build_mask()
-            if mask is None:
-                return search(q[None, :], k)
-            try:
+            try:                                     # an unmasked read can be stale too when it carries per-slot group keys
+                if mask is None:
+                    return search(q[None, :], k)
                 return search(q[None, :], k, row_filter=mask, filter_epoch=epoch)
             except StaleFilterError:
                 continue
@@ -638,6 +638,123 @@ class ArchiHipVectorStore(_VectorStoreBase):
             return lambda qs, kk, **kw: mmr(qs, kk, fetch_k=fetch_k, lambda_mult=lambda_mult, **kw)
 
         return self._read_by_vector(embedding, k, kwargs, search)
+
+    # -- grouped reads: the k nearest documents, the best chunks of each ---------------------------
+    # NO COUNTERPART in the reference's PostgresVectorStore: its callers collapse the retriever's k chunks by document on the host
+    # (ChatWrapper.get_top_sources, src/interfaces/chat_app/app.py:442-484 there), so one long page can supply all k chunks and the
+    # user sees one source. The read is the library's (ak_index_group_search): groups ranked by their best chunk, chunks in the
+    # plain search's order, every distance the plain search's.
+    GROUP_MAX_K = 32
+    GROUP_MAX_SIZE = 8
+
+    def search_groups(self, query: str, k: int = 4, group_size: int = 1, group_by: str = "document_id",
+                      **kwargs: Any) -> List[Tuple[Any, List[Tuple[Any, float]]]]:
+        query_embedding = self._embedding_function.embed_query(query)
+        return self.search_groups_by_vector(query_embedding, k=k, group_size=group_size, group_by=group_by, **kwargs)
+
+    def search_groups_by_vector(self, embedding: List[float], k: int = 4, group_size: int = 1, group_by: str = "document_id",
+                                **kwargs: Any) -> List[Tuple[Any, List[Tuple[Any, float]]]]:
+        """[(group value, [(Document, score), ...])]: the k nearest groups in the order of their best chunk, each with its best
+        group_size chunks in the plain search's order; the score is similarity_search_by_vector_with_score's. group_by:
+        "document_id" (the table's document number) or a metadata key (through the table's inverted maps; `resource_hash` is always
+        there). A chunk without a document / without the key is a group by itself, and its group value is None.
+        filter / include_deleted as similarity_search_by_vector_with_score."""
+        k, g = int(k), int(group_size)
+        if not 1 <= k <= self.GROUP_MAX_K:
+            raise ValueError(f"search_groups: k = {k} is outside 1 .. {self.GROUP_MAX_K}")
+        if not 1 <= g <= self.GROUP_MAX_SIZE:
+            raise ValueError(f"search_groups: group_size = {g} is outside 1 .. {self.GROUP_MAX_SIZE}")
+        if not isinstance(group_by, str) or not group_by:
+            raise ValueError("search_groups: group_by must be 'document_id' or a metadata key")
+        metadata_filter = kwargs.get("filter", {}) or {}
+        include_deleted = kwargs.get("include_deleted", False)
+        col = self._collection()
+        if col is None:
+            return []
+        group_search = getattr(col.index, "group_search", None)
+        if group_search is None:
+            raise NotImplementedError(f"search_groups: {type(col.index).__name__} has no group_search "
+                                      "(sharded grouped search is not supported)")
+        t = col.table
+        q = np.asarray([float(x) for x in embedding], dtype=np.float32)
+        held: Dict[str, Any] = {}
+
+        def build():            # under the table lock: the WHERE mask and the key array are one state and one epoch
+            mask, _, epoch = self._where(col, metadata_filter, include_deleted)
+            held["keys"], held["values"] = self._group_keys(col, group_by, epoch)
+            held["epoch"] = epoch
+            return mask, epoch
+
+        def search(qs, kk, row_filter=None, filter_epoch=None):
+            return group_search(qs, kk, g, row_group=held["keys"], row_filter=row_filter, filter_epoch=held["epoch"])
+
+        out: List[Tuple[Any, List[Tuple[Any, float]]]] = []
+        for attempt in range(self.STALE_RETRIES + 1):
+            ids, dist, keys, sizes, cnt = self._search_snapshot(col, q, k, build, search)
+            out, vanished = [], 0
+            with t.lock:
+                for w in range(int(cnt[0])):
+                    key = int(keys[0, w])
+                    members: List[Tuple[Any, float]] = []
+                    for j in range(int(sizes[0, w])):
+                        p = t.pos(int(ids[0, w, j]))
+                        if p < 0:                    # deleted between the scan and here
+                            vanished += 1
+                            continue
+                        distance = float(dist[0, w, j])
+                        score = 1.0 - distance if self._distance_metric == "cosine" else distance
+                        members.append((self._document(t, p), score))
+                    if members:
+                        out.append((held["values"][key] if key >= 0 else None, members))
+            if not vanished:
+                break                                # otherwise: search again against the later state, as _read_by_vector does
+        return out
+
+    def similarity_search_by_document_with_score(self, query: str, k: int = 4, chunks_per_document: int = 1,
+                                                 **kwargs: Any) -> List[Tuple[Any, float]]:
+        """The chunks of the k nearest documents, chunks_per_document of each at most, as one flat list ordered by document rank,
+        then chunk rank: what a retriever swaps in for similarity_search_with_score."""
+        groups = self.search_groups(query, k=k, group_size=chunks_per_document, group_by="document_id", **kwargs)
+        return [pair for _, members in groups for pair in members]
+
+    def similarity_search_by_document(self, query: str, k: int = 4, chunks_per_document: int = 1, **kwargs: Any) -> List[Any]:
+        return [doc for doc, _ in self.similarity_search_by_document_with_score(query, k=k, chunks_per_document=chunks_per_document,
+                                                                              **kwargs)]
+
+    def _group_keys(self, col: _Collection, group_by: str, epoch: int):
+        """Per-slot int32 group keys for ak_index_group_search and the list that turns a key back into the group value. Caller
+        holds the table lock (as _where: slots, lookups and epoch are one state). -1: the row is a group by itself (no document /
+        no such metadata key) or the slot holds no live row of the table. Cached like the WHERE masks."""
+        t = col.table
+        key = (t.version, t.doc_version, epoch, "group_by", group_by)
+        if key in t.where_cache:
+            return t.where_cache[key]
+        n_slots = col.index.layout()[0]
+        keys = np.full(n_slots, -1, dtype=np.int32)
+        if group_by == "document_id":
+            pos = np.flatnonzero(t._alive[: t._n])
+            values: List[Any] = t._dockeys          # append-only: a key stays valid for as long as this entry is cached
+            if len(pos):
+                slots = col.index.lookup(t.rids_at(pos))
+                ok = slots >= 0
+                keys[slots[ok]] = t._doc[pos[ok]]
+        else:
+            values = []
+            for value, plist in t._index_key(group_by).items():
+                pos = np.asarray(plist, dtype=np.int64)
+                pos = pos[t._alive[pos]] if len(pos) else pos
+                if not len(pos):
+                    continue
+                slots = col.index.lookup(t.rids_at(pos))
+                keys[slots[slots >= 0]] = len(values)
+                values.append(value)
+        result = (keys, values)
+        for old in [k for k in t.where_cache if k[:3] != key[:3]]:
+            del t.where_cache[old]
+        if len(t.where_cache) >= 16:
+            t.where_cache.pop(next(iter(t.where_cache)))
+        t.where_cache[key] = result
+        return result
 
     def _where(self, col: _Collection, metadata_filter: Dict[str, Any], include_deleted: bool):
         """The WHERE clause (:296-310) as a per-slot byte mask for the scan, or None when every row passes; the passing row ids

@@ -277,6 +277,40 @@ int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int f
                         const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch,
                         int64_t *out_ids, double *out_dist, int *out_rank, int *out_counts, int64_t *out_stats);
 
+/* Grouped search: the k nearest GROUPS of rows (documents) and the best group_size rows (chunks) of each. NO COUNTERPART in the
+ * reference's store: its callers collapse the retriever's k chunks by document on the host (ChatWrapper.get_top_sources,
+ * src/interfaces/chat_app/app.py:442-484 there); this is the "group by" / "collapse" read of other vector stores.
+ *   row_group [filter_len] int32 on the host, REQUIRED, indexed by row slot: a key >= 0 names the row's group, a negative key means
+ *   "this row is a group by itself". It is valid for exactly the (filter_len, filter_epoch) pair ak_index_slots returned;
+ *   row_filter (NULL allowed) is under the same contract and has the same length. A stale pair returns AK_ERR_STALE_FILTER with
+ *   nothing read and the outputs untouched. Every metric. mode: AK_SEARCH_AUTO or AK_SEARCH_EXACT (FAST_ONLY is refused by name).
+ *   1 <= k <= 32 and 1 <= group_size <= 8, refused by name outside them before any GPU work; any nq >= 0.
+ * Definition:
+ *   1. Let L(q) be the complete result list of ak_index_search for query q with this mask and k = every live row that passes the
+ *      mask: distance ascending, ties by id ascending, NaN distances last; distances are the float8 values of the exact arithmetic.
+ *   2. Walk L(q) from the front.
+ *   3. A group is ranked by the position of its first row.
+ *   4. A group's members are its rows in list order.
+ * Result: the first min(k, number of groups) groups. For each: its first min(group_size, members) rows in out_ids / out_dist
+ * [nq][k][group_size], its key as given (so negative for a single-row group) in out_group [nq][k], the number of members returned
+ * in out_sizes [nq][k]; out_counts [nq] (NULL allowed) = groups returned. Padding: id -1, distance NaN, out_group -1, out_sizes 0.
+ * It follows that (a) every key negative and group_size = 1 gives the first k rows of ak_index_search, and (b) every row in one
+ * group gives one group whose members are the first group_size rows of ak_index_search, both bit for bit.
+ *   out_stats: NULL or int64[8] = {certified, exact re-runs, re-ranked, certified by the second scan (these four: the FIRST
+ *   round's search, as ak_index_search reports them), search rounds run summed over queries, queries that needed more than one
+ *   round, rows matched by the member pass, searches launched}.
+ * How: a certified search returns exactly the first k' rows of L(q), so the distinct groups among them, in order of first
+ * appearance, are the first groups of the ranking. Round 1 fetches k' = clamp(4 k, 16, 128) rows for all queries (AK_GROUP_FETCH,
+ * ak_debug_set, 1 .. 128, overrides k'); a query that then holds fewer than k groups although its round came back full runs
+ * further rounds alone, each with the groups found so far masked out, until it has k groups or a round comes back short. With
+ * group_size > 1 one pass over the row slots per query lists the members of the winning groups, whose distances are computed in
+ * the search's exact arithmetic; nothing is truncated, whatever a group's size. All rounds of one call run under ONE hold of the
+ * index's reader lock. Re-entrant; not coalesced. A refused or failed call leaves the outputs untouched. */
+int ak_index_group_search(ak_index_t h, const float *queries, int nq, int k, int group_size, int mode,
+                          const int32_t *row_group, const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch,
+                          int64_t *out_ids, double *out_dist, int32_t *out_group, int *out_sizes, int *out_counts,
+                          int64_t *out_stats);
+
 /* Same query, everything resident in HBM (bench path and the row-sharded multi-GPU path: inputs already on the device
  * when the timed region starts; `stream` orders the work).
  *   mode AK_SEARCH_FAST_ONLY: asynchronous, nothing synchronises with the host. out_cert_dev [nq] int32 receives 1 for
