@@ -231,6 +231,7 @@ int thread_stream(hipStream_t *out) {
 }
 static int scratch_reserve(char **p, size_t *cap, size_t need, bool pinned);
 char *thread_scratch(size_t bytes) { return scratch_reserve(&t_ctx.dev, &t_ctx.dev_cap, bytes, false) ? nullptr : t_ctx.dev; }
+static void *thread_ws(size_t bytes) { return scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, bytes, false) ? nullptr : t_ctx.ws; }
 void thread_scratch_trim() { t_ctx.trim(); }
 static int scratch_reserve(char **p, size_t *cap, size_t need, bool pinned) {
     if (need <= *cap) return 0;
@@ -1161,16 +1162,21 @@ int ak_index_distances(ak_index_t h, const float *query, const int64_t *ids, int
 namespace ak {
 
 struct RerunStats { int64_t second_certified = 0, exact = 0; };
+struct SearchBufs {      // the device buffers of one search: ak_index_search_dev's (ix.ws_dev, the caller's arrays) or ak_index_search's
+    const float *q = nullptr; float *nb = nullptr; const uint8_t *filter = nullptr;   // [nq][dim] queries, [nq] their sums of squares, [n] or NULL
+    int64_t *ids = nullptr; double *dist = nullptr; int *counts = nullptr;            // [nq][k], [nq][k], [nq]
+    int *cert = nullptr, *final_cert = nullptr;     // [nq] the scan's flags; where a re-run sets them: cert, or NULL (nobody reads them there)
+    int64_t *stats = nullptr; void *ws = nullptr;   // int64[4] the scan's counters; its workspace
+};
 
 // Queries the first MFMA scan could not certify (or, fast_ran == false, all of them): a second scan with the widest
 // candidate lists certifies what a wider list can fix -- more equal scores around the k-th place than k' holds, i.e.
 // duplicated chunks -- for the price of one more scan; what is still open goes through the exact path (reference
-// arithmetic over every row). Results are scattered into the caller's [nq][k] arrays by query index; cert (nullable)
+// arithmetic over every row). Results are scattered into d's [nq][k] arrays by query index; d.final_cert (nullable)
 // gets 1 for every re-run query. Everything is enqueued on st; the only host synchronisation is the read of the second
 // scan's certificate flags. reserve(bytes) returns a device buffer that stays valid until its next call.
 template <class Reserve>
-static int rerun_uncertified(Index &ix, const float *dq, const float *dnb, int nq, int k, const uint8_t *dfl, int64_t *doi,
-                             double *dod, int *dct, int *dce, std::vector<int> todo, bool fast_ran, int first_kprime,
+static int rerun_uncertified(Index &ix, const SearchBufs &d, int nq, int k, std::vector<int> todo, bool fast_ran, int first_kprime,
                              Reserve reserve, hipStream_t st, RerunStats *rs) {
     if (todo.empty()) return 0;
     int m = (int)todo.size();
@@ -1185,13 +1191,12 @@ static int rerun_uncertified(Index &ix, const float *dq, const float *dnb, int n
     if (!second && m == nq) {      // everything goes through the exact path: no gather
         void *ws = reserve(sub);
         if (!ws) return -10;
-        if (int rc = exact_search(ix, dq, dnb, nq, k, dfl, doi, dod, dct, ws, st)) return rc;
-        if (dce) k_fill_int<<<(nq + 255) / 256, 256, 0, st>>>(dce, nq, 1);
+        if (int rc = exact_search(ix, d.q, d.nb, nq, k, d.filter, d.ids, d.dist, d.counts, ws, st)) return rc;
+        if (d.final_cert) k_fill_int<<<(nq + 255) / 256, 256, 0, st>>>(d.final_cert, nq, 1);
         AK_HIP(hipGetLastError());
         if (rs) rs->exact += nq;
         return 0;
     }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_idx = 0, o_q = o_idx + al((size_t)m * 4), o_nb = o_q + al((size_t)m * ix.dim * 4), o_i = o_nb + al((size_t)m * 4),
                  o_d = o_i + al((size_t)m * k * 8), o_c = o_d + al((size_t)m * k * 8), o_ce = o_c + al((size_t)m * 4),
                  o_sub = o_ce + al((size_t)m * 4);
@@ -1199,17 +1204,16 @@ static int rerun_uncertified(Index &ix, const float *dq, const float *dnb, int n
     if (!base) return -10;
     int *didx = (int *)(base + o_idx);
     float *gq = (float *)(base + o_q), *gnb = (float *)(base + o_nb);
-    int64_t *gi = (int64_t *)(base + o_i);
-    double *gd = (double *)(base + o_d);
+    int64_t *gi = (int64_t *)(base + o_i); double *gd = (double *)(base + o_d);
     int *gc = (int *)(base + o_c), *gce = (int *)(base + o_ce);
     void *subws = base + o_sub;
     AK_HIP(hipMemcpyAsync(didx, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    k_gather_queries<<<m, 128, 0, st>>>(dq, dnb, didx, m, ix.dim, gq, gnb);
+    k_gather_queries<<<m, 128, 0, st>>>(d.q, d.nb, didx, m, ix.dim, gq, gnb);
     AK_HIP(hipGetLastError());
     if (second) {
-        if (int rc = fast_search(ix, gq, gnb, true, m, k, dfl, gi, gd, gc, gce, nullptr, subws, p2, st)) return rc;
+        if (int rc = fast_search(ix, gq, gnb, true, m, k, d.filter, gi, gd, gc, gce, nullptr, subws, p2, st)) return rc;
         std::vector<int> c2(m, 0);
-        k_scatter_results<<<m, 64, 0, st>>>(didx, gce, m, k, gi, gd, gc, doi, dod, dct, dce);
+        k_scatter_results<<<m, 64, 0, st>>>(didx, gce, m, k, gi, gd, gc, d.ids, d.dist, d.counts, d.final_cert);
         AK_HIP(hipGetLastError());
         AK_HIP(hipMemcpyAsync(c2.data(), gce, (size_t)m * 4, hipMemcpyDeviceToHost, st));
         AK_HIP(hipStreamSynchronize(st));
@@ -1221,16 +1225,69 @@ static int rerun_uncertified(Index &ix, const float *dq, const float *dnb, int n
         m = (int)todo.size();
         // the gather buffers were sized for the longer list: fine
         AK_HIP(hipMemcpyAsync(didx, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-        k_gather_queries<<<m, 128, 0, st>>>(dq, dnb, didx, m, ix.dim, gq, gnb);
+        k_gather_queries<<<m, 128, 0, st>>>(d.q, d.nb, didx, m, ix.dim, gq, gnb);
         AK_HIP(hipGetLastError());
     }
-    if (int rc = exact_search(ix, gq, gnb, m, k, dfl, gi, gd, gc, subws, st)) return rc;
-    k_scatter_results<<<m, 64, 0, st>>>(didx, nullptr, m, k, gi, gd, gc, doi, dod, dct, dce);
+    if (int rc = exact_search(ix, gq, gnb, m, k, d.filter, gi, gd, gc, subws, st)) return rc;
+    k_scatter_results<<<m, 64, 0, st>>>(didx, nullptr, m, k, gi, gd, gc, d.ids, d.dist, d.counts, d.final_cert);
     AK_HIP(hipGetLastError());
     // `todo` (pageable) was the source of an asynchronous copy: it must outlive it
     AK_HIP(hipStreamSynchronize(st));
     if (rs) rs->exact += m;
     return 0;
+}
+
+// What makes a kNN answer exact, for ak_index_search and ak_index_search_dev alike: the MFMA scan where fast_supported allows it, the
+// certificate flags, rerun_uncertified for the open queries -- for all of them in EXACT mode and on shapes the scan does not take.
+// The callers say where the buffers are -- bufs(bytes of the first scan's workspace, 0 without a scan), rerun_ws (rerun_uncertified's
+// reserve) -- and how the flags reach the host: read_flags(&flags), called once, in AUTO mode behind the scan, brings them home, the
+// scan's counters into stats4 (nullable, host int64[4]: ak_index_search's out_stats; left alone without a scan), and synchronises.
+// FAST_ONLY only enqueues the scan. Nothing synchronises behind a re-run's last kernel: *reran tells the caller that one ran.
+template <class Bufs, class RerunWs, class ReadFlags>
+static int search_auto(Index &ix, int nq, int k, int mode, hipStream_t st, Bufs bufs, RerunWs rerun_ws, ReadFlags read_flags,
+                       int64_t *stats4, bool *reran) {
+    const bool fast = mode != AK_SEARCH_EXACT && fast_supported(ix, nq, k);
+    const FastPlan plan = fast ? fast_plan(ix, nq, k) : FastPlan{};
+    const SearchBufs *d = bufs(plan.bytes);
+    if (!d) return -10;
+    std::vector<int> todo;
+    if (fast) {
+        if (int rc = fast_search(ix, d->q, d->nb, false, nq, k, d->filter, d->ids, d->dist, d->counts, d->cert, d->stats, d->ws, plan, st)) return rc;
+        if (mode == AK_SEARCH_FAST_ONLY) return 0;
+        const int *flags = nullptr;
+        if (int rc = read_flags(&flags)) return rc;
+        for (int i = 0; i < nq; i++) if (!flags[i]) todo.push_back(i);
+        if (stats4) { stats4[0] = nq - (int64_t)todo.size(); stats4[1] = (int64_t)todo.size(); }
+        if (todo.empty()) return 0;
+    } else {
+        if (int rc = query_norms(d->q, nq, ix.dim, d->nb, st)) return rc;      // the scan computes them in its set-up launch
+        for (int i = 0; i < nq; i++) todo.push_back(i);
+    }
+    *reran = true;
+    RerunStats rs;
+    // the second chance of an int8 plan is the widest 16-bit scan: it counts as TAIL_KP, although it re-ranks 512
+    if (int rc = rerun_uncertified(ix, *d, nq, k, std::move(todo), fast, plan.i8 ? TAIL_KP : plan.kprime, rerun_ws, st, &rs)) return rc;
+    if (stats4 && fast) { stats4[0] += rs.second_certified; stats4[1] = rs.exact; stats4[3] = rs.second_certified; }
+    return 0;
+}
+
+// ak_index_search's block of the calling thread's device scratch: queries | nb | ids | dist | counts | cert | stats | filter.
+// [ids .. stats] is one span, out_bytes long: the results come home in ONE device-to-host copy of it into pinned memory.
+struct HostSearchWs : SearchBufs { size_t out_bytes = 0, bytes = 0; };
+static HostSearchWs host_search_layout(void *base, int nq, int k, int64_t n, int dim, bool has_filter) {      // base == NULL: only .bytes
+    HostSearchWs w;
+    char *p = (char *)base; size_t o = 0;
+    w.q = (float *)(p + o); o += al((size_t)nq * dim * 4);
+    w.nb = (float *)(p + o); o += al((size_t)nq * 4);
+    w.ids = (int64_t *)(p + o); o += al((size_t)nq * k * 8);
+    w.dist = (double *)(p + o); o += al((size_t)nq * k * 8);
+    w.counts = (int *)(p + o); o += al((size_t)nq * 4);
+    w.cert = (int *)(p + o); o += al((size_t)nq * 4);
+    w.stats = (int64_t *)(p + o); o += 256;
+    w.out_bytes = (size_t)(p + o - (char *)w.ids);
+    w.filter = has_filter ? (uint8_t *)(p + o) : nullptr; o += has_filter ? (size_t)n + 256 : 0;
+    w.bytes = o;
+    return w;
 }
 
 // a row_filter is a statement about ONE layout of the index: the caller says which (ak_index_slots), and a mask of another
@@ -1248,78 +1305,54 @@ int filter_is_current(const Index &ix, const void *row_filter, int64_t filter_le
 
 extern "C" {
 
-// Where search_host_locked left the results on the device (the calling thread's scratch block): valid until that thread's next
-// call that reserves the block. ak_index_mmr_search reads the candidates' distances and counts from there.
-struct HostSearchDev { const double *dist = nullptr; const int *counts = nullptr; };
-
 // ak_index_search behind its lock: the caller holds ix.mu (shared) and trims the thread scratch when it is done. `who` names the
-// entry point in the filter's error message.
+// entry point in the filter's error message. The results stay in the thread's device block (host_search_layout): ak_index_mmr_search.
 static int search_host_locked(Index &ix, const float *queries, int nq, int k, int mode, const uint8_t *row_filter, int64_t filter_len,
                               uint64_t filter_epoch, int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats,
-                              const char *who, HostSearchDev *left) {
+                              const char *who) {
     if (int frc = filter_is_current(ix, row_filter, filter_len, filter_epoch, who)) return frc;
     hipStream_t st;
     if (thread_stream(&st)) return -10;
     const size_t qb = (size_t)nq * ix.dim * 4, ob = (size_t)nq * k * 8;
-    char *blk = nullptr;  // one allocation: queries | nb | out_ids | out_dist | cnt | cert | stats | filter
-    size_t off_nb = (qb + 255) & ~255ull, off_oi = off_nb + (((size_t)nq * 4 + 255) & ~255ull),
-           off_od = off_oi + ((ob + 255) & ~255ull), off_ct = off_od + ((ob + 255) & ~255ull),
-           off_ce = off_ct + (((size_t)nq * 4 + 255) & ~255ull), off_st = off_ce + (((size_t)nq * 4 + 255) & ~255ull),
-           off_fl = off_st + 256, total = off_fl + (row_filter ? (size_t)ix.n + 256 : 0);
-    if (scratch_reserve(&t_ctx.dev, &t_ctx.dev_cap, total, false)) return -10;
-    blk = t_ctx.dev;
-    // results come back in ONE device-to-host copy of [ids | dist | counts | certified | stats] into pinned memory
-    const size_t out_bytes = off_fl - off_oi, pin_q = qb <= (1u << 20) ? ((qb + 255) & ~255ull) : 0;
-    if (scratch_reserve(&t_ctx.pin, &t_ctx.pin_cap, pin_q + out_bytes, true)) return -10;
+    if (!thread_scratch(host_search_layout(nullptr, nq, k, ix.n, ix.dim, row_filter != nullptr).bytes)) return -10;
+    HostSearchWs w = host_search_layout(t_ctx.dev, nq, k, ix.n, ix.dim, row_filter != nullptr);
+    const size_t pin_q = qb <= (1u << 20) ? ((qb + 255) & ~255ull) : 0;
+    if (scratch_reserve(&t_ctx.pin, &t_ctx.pin_cap, pin_q + w.out_bytes, true)) return -10;
     char *pin_out = t_ctx.pin + pin_q;
-    float *dq = (float *)blk, *dnb = (float *)(blk + off_nb);
-    int64_t *doi = (int64_t *)(blk + off_oi);
-    double *dod = (double *)(blk + off_od);
-    int *dct = (int *)(blk + off_ct), *dce = (int *)(blk + off_ce);
-    int64_t *dst = (int64_t *)(blk + off_st);
-    uint8_t *dfl = row_filter ? (uint8_t *)(blk + off_fl) : nullptr;
+    auto pinned = [&](const void *dev) { return pin_out + ((const char *)dev - (const char *)w.ids); };
+    auto bufs = [&](size_t scan_bytes) -> const SearchBufs * { return scan_bytes && !(w.ws = thread_ws(scan_bytes)) ? nullptr : &w; };
+    auto read_flags = [&](const int **flags) -> int {
+        if (hipMemcpyAsync(pin_out, w.ids, w.out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return -10;
+        if (hipStreamSynchronize(st) != hipSuccess) { set_error(std::string("fast_search failed: ") + hipGetErrorString(hipGetLastError())); return -10; }
+        *flags = (const int *)pinned(w.cert);
+        if (out_stats) memcpy(out_stats, pinned(w.stats), 32);
+        return 0;
+    };
     int rc = 0;
     do {
         const void *qsrc = queries;
         if (pin_q) { memcpy(t_ctx.pin, queries, qb); qsrc = t_ctx.pin; }      // small batches: a truly asynchronous H2D
-        if (hipMemcpyAsync(dq, qsrc, qb, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -10; set_error("ak_index_search: H2D failed"); break; }
-        if (dfl && ix.n > 0 && hipMemcpyAsync(dfl, row_filter, (size_t)ix.n, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -10; set_error("ak_index_search: filter H2D failed"); break; }
-        const bool fast = mode != AK_SEARCH_EXACT && fast_supported(ix, nq, k);
-        if (!fast && (rc = query_norms(dq, nq, ix.dim, dnb, st))) break;      // the fast path computes them in its set-up launch
-        std::vector<int> todo;
-        int first_kprime = 0;
-        if (fast) {
-            FastPlan plan = fast_plan(ix, nq, k);
-            first_kprime = plan.i8 ? TAIL_KP : plan.kprime;      // the second chance of an int8 plan is the widest 16-bit scan
-            if (scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, plan.bytes, false)) { rc = -10; break; }
-            if ((rc = fast_search(ix, dq, dnb, false, nq, k, dfl, doi, dod, dct, dce, dst, t_ctx.ws, plan, st))) break;
-            if (hipMemcpyAsync(pin_out, blk + off_oi, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = -10; break; }
-            if (hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error(std::string("fast_search failed: ") + hipGetErrorString(hipGetLastError())); break; }
-            const int *cert = (const int *)(pin_out + (off_ce - off_oi));
-            if (out_stats) memcpy(out_stats, pin_out + (off_st - off_oi), 32);
-            for (int i = 0; i < nq; i++) if (!cert[i]) todo.push_back(i);
-            if (out_stats) { out_stats[0] = nq - (int64_t)todo.size(); out_stats[1] = (int64_t)todo.size(); }
-            if (todo.empty() || mode == AK_SEARCH_FAST_ONLY) {        // the common case ends here: one copy, one synchronisation
-                memcpy(out_ids, pin_out, ob);
-                memcpy(out_dist, pin_out + (off_od - off_oi), ob);
-                if (out_counts) memcpy(out_counts, pin_out + (off_ct - off_oi), (size_t)nq * 4);
-                break;
+        if (hipMemcpyAsync((float *)w.q, qsrc, qb, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -10; set_error("ak_index_search: H2D failed"); break; }
+        if (row_filter && ix.n > 0 && hipMemcpyAsync((uint8_t *)w.filter, row_filter, (size_t)ix.n, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -10; set_error("ak_index_search: filter H2D failed"); break; }
+        bool reran = false;      // a re-run takes the first scan's workspace: that scan's results sit in the block
+        if ((rc = search_auto(ix, nq, k, mode, st, bufs, thread_ws, read_flags, out_stats, &reran))) break;
+        if (!reran) {             // the common case ends here: one copy, one synchronisation
+            if (mode == AK_SEARCH_FAST_ONLY) {      // the driver only enqueued the scan: the same one copy, the flags only counted
+                const int *flags;
+                if ((rc = read_flags(&flags))) break;
+                if (out_stats) { out_stats[1] = std::count(flags, flags + nq, 0); out_stats[0] = nq - out_stats[1]; }
             }
-        } else {
-            for (int i = 0; i < nq; i++) todo.push_back(i);
+            memcpy(out_ids, pin_out, ob);
+            memcpy(out_dist, pinned(w.dist), ob);
+            if (out_counts) memcpy(out_counts, pinned(w.counts), (size_t)nq * 4);
+            break;
         }
-        // the first scan's workspace is no longer needed (its results sit in `blk`): the re-run takes the same thread scratch
-        RerunStats rs;
-        auto reserve = [&](size_t bytes) -> void * { return scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, bytes, false) ? nullptr : t_ctx.ws; };
-        if ((rc = rerun_uncertified(ix, dq, dnb, nq, k, dfl, doi, dod, dct, nullptr, todo, fast, first_kprime, reserve, st, &rs))) break;
-        if (out_stats && fast) { out_stats[0] += rs.second_certified; out_stats[1] = rs.exact; out_stats[3] = rs.second_certified; }
-        hipMemcpyAsync(out_ids, doi, ob, hipMemcpyDeviceToHost, st);
-        hipMemcpyAsync(out_dist, dod, ob, hipMemcpyDeviceToHost, st);
-        if (out_counts) hipMemcpyAsync(out_counts, dct, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(out_ids, w.ids, ob, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(out_dist, w.dist, ob, hipMemcpyDeviceToHost, st);
+        if (out_counts) hipMemcpyAsync(out_counts, w.counts, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
         if (hipStreamSynchronize(st) != hipSuccess) { rc = -10; set_error(std::string("ak_index_search: ") + hipGetErrorString(hipGetLastError())); }
     } while (0);
     if (rc) hipStreamSynchronize(st);      // nothing of a failed call may still be running on the cached buffers
-    if (left) { left->dist = dod; left->counts = dct; }
     return rc;
 }
 
@@ -1327,7 +1360,7 @@ static int search_host(Index &ix, const float *queries, int nq, int k, int mode,
                        uint64_t filter_epoch, int64_t *out_ids, double *out_dist, int *out_counts, int64_t *out_stats) {
     std::shared_lock<std::shared_mutex> lk(ix.mu);
     const int rc = search_host_locked(ix, queries, nq, k, mode, row_filter, filter_len, filter_epoch, out_ids, out_dist, out_counts,
-                                      out_stats, "ak_index_search", nullptr);
+                                      out_stats, "ak_index_search");
     t_ctx.trim();
     return rc;
 }
@@ -1394,12 +1427,40 @@ int ak_index_search(ak_index_t h, const float *queries, int nq, int k, int mode,
     return rc;
 }
 
+// The shared hold with the id map built. The lazy map of generated rows needs the unique lock to be built (IndexBook::slot_of), so
+// it is built BEFORE the hold; an ak_index_generate that slips in between un-builds it again and the loop goes round once more.
+static std::shared_lock<std::shared_mutex> hold_with_id_map(Index &ix) {
+    for (;;) {
+        std::shared_lock<std::shared_mutex> lk(ix.mu);
+        if (ix.map_built) return lk;
+        lk.unlock();
+        std::unique_lock<std::shared_mutex> wl(ix.mu);
+        if (!ix.map_built) (void)ix.slot_of(-1);        // a miss builds the lazy map
+    }
+}
+
+// ids [nq][width] as a search returned them -> slots [nq][width], -1 behind a query's list. The list is counts[q] long or,
+// counts == NULL, ends at the first id < 0; listed (nullable) gets its length. Caller: hold_with_id_map.
+static int resolve_slots(const IndexBook &book, const int64_t *ids, int nq, int width, const int *counts, int *slots, int *listed,
+                         const char *who, const char *noun) {
+    for (int q = 0; q < nq; q++, ids += width, slots += width) {
+        int m = counts ? counts[q] : 0;
+        if (!counts) while (m < width && ids[m] >= 0) m++;
+        for (int r = 0; r < width; r++) {
+            const auto it = r < m ? book.id2slot.find(ids[r]) : book.id2slot.end();
+            if (r < m && (it == book.id2slot.end() || it->second < 0 || it->second >= book.n)) AK_FAIL(-1, std::string(who) + ": a " + noun + " id has no row slot");
+            slots[r] = r < m ? (int)(uint32_t)it->second : -1;
+        }
+        if (listed) listed[q] = m;
+    }
+    return 0;
+}
+
 // Max-marginal-relevance search (no counterpart in the reference's store; LangChain's VectorStore contract [upstream, not in tree]):
 // the candidate search (search_host_locked, k = fetch_k), the candidates' row slots resolved on the host from the id map -- the
 // search emits ids only --, then the two kernels of mmr.hip, all under ONE hold of the shared lock: a remove or a compaction cannot
-// move a slot between the scan and the row reads. The lazy id map of generated rows needs the unique lock to be built
-// (IndexBook::slot_of), so it is built BEFORE that hold; an ak_index_generate that slips in between un-builds it again and the call
-// goes round once more. The results' distances and counts never leave the device between the two halves.
+// move a slot between the scan and the row reads (hold_with_id_map). The results' distances and counts never leave the device
+// between the two halves.
 int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int fetch_k, double lambda_mult, int mode,
                         const uint8_t *row_filter, int64_t filter_len, uint64_t filter_epoch, int64_t *out_ids, double *out_dist,
                         int *out_rank, int *out_counts, int64_t *out_stats) {
@@ -1423,39 +1484,18 @@ int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int f
     const size_t nc = (size_t)nq * fetch_k;
     cid.resize(nc); cd.resize(nc); cc.resize(nq); cs.resize(nc);
     int64_t stats[4] = {0, 0, 0, 0};
-    for (;;) {
-        std::shared_lock<std::shared_mutex> lk(ix.mu);
-        if (!ix.map_built) {                                 // generated rows not in the map yet (or a generate ran in between)
-            lk.unlock();
-            std::unique_lock<std::shared_mutex> wl(ix.mu);
-            if (!ix.map_built) (void)ix.slot_of(-1);        // a miss builds the lazy map
-            continue;
-        }
-        const IndexBook &book = ix;                          // readers: const members only
-        HostSearchDev left;
+    {
+        const std::shared_lock<std::shared_mutex> lk = hold_with_id_map(ix);
         int rc = search_host_locked(ix, queries, nq, fetch_k, mode, row_filter, filter_len, filter_epoch, cid.data(), cd.data(), cc.data(),
-                                    stats, "ak_index_mmr_search", &left);
+                                    stats, "ak_index_mmr_search");
         if (rc) { t_ctx.trim(); return rc; }
-        for (int q = 0; q < nq; q++) {
-            if (cc[q] < 0 || cc[q] > fetch_k) { t_ctx.trim(); AK_FAIL(-1, "ak_index_mmr_search: candidate count out of range"); }
-            for (int r = 0; r < fetch_k; r++) {
-                int64_t slot = -1;
-                if (r < cc[q]) {
-                    const auto it = book.id2slot.find(cid[(size_t)q * fetch_k + r]);
-                    if (it == book.id2slot.end() || it->second < 0 || it->second >= book.n) {
-                        t_ctx.trim();
-                        AK_FAIL(-1, "ak_index_mmr_search: a candidate id has no row slot");
-                    }
-                    slot = it->second;
-                }
-                cs[(size_t)q * fetch_k + r] = (int)(uint32_t)slot;
-            }
-        }
+        const HostSearchWs left = host_search_layout(t_ctx.dev, nq, fetch_k, ix.n, ix.dim, row_filter != nullptr);      // still there
+        for (int q = 0; q < nq; q++) if (cc[q] < 0 || cc[q] > fetch_k) { t_ctx.trim(); AK_FAIL(-1, "ak_index_mmr_search: candidate count out of range"); }
+        if ((rc = resolve_slots(ix, cid.data(), nq, fetch_k, cc.data(), cs.data(), nullptr, "ak_index_mmr_search", "candidate"))) { t_ctx.trim(); return rc; }
         hipStream_t st;
         if (thread_stream(&st)) return -10;
         // the candidate search's workspace is free again (its results sit in the thread's device block): the selection takes it
-        const MmrWs need = mmr_layout(nullptr, nq, k, fetch_k);
-        if (scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, need.bytes, false)) { t_ctx.trim(); return -10; }
+        if (!thread_ws(mmr_layout(nullptr, nq, k, fetch_k).bytes)) { t_ctx.trim(); return -10; }
         const MmrWs w = mmr_layout(t_ctx.ws, nq, k, fetch_k);
         rc = 0;
         do {
@@ -1470,7 +1510,6 @@ int ak_index_mmr_search(ak_index_t h, const float *queries, int nq, int k, int f
         if (rc) hipStreamSynchronize(st);
         t_ctx.trim();
         if (rc) return rc;
-        break;
     }
     memcpy(out_ids, cid.data(), (size_t)nq * k * 8);
     memcpy(out_dist, cd.data(), (size_t)nq * k * 8);
@@ -1511,44 +1550,22 @@ int ak_index_group_search(ak_index_t h, const float *queries, int nq, int k, int
     hid.resize(nf); hslot.resize(nf); hm.resize(nq); hw.resize(nq);
     rid.assign(nr, -1); rd.assign(nr, __builtin_nan("")); rg.assign(ng, -1); rs.assign(ng, 0);
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (;;) {
-        std::shared_lock<std::shared_mutex> lk(ix.mu);
-        if (!ix.map_built) {                                 // generated rows not in the map yet (or a generate ran in between)
-            lk.unlock();
-            std::unique_lock<std::shared_mutex> wl(ix.mu);
-            if (!ix.map_built) (void)ix.slot_of(-1);        // a miss builds the lazy map
-            continue;
-        }
-        const IndexBook &book = ix;                          // readers: const members only
+    do {
+        const std::shared_lock<std::shared_mutex> lk = hold_with_id_map(ix);
         // row_group is a statement about one layout, as the mask is: checked even when there is no mask
         if (int frc = filter_is_current(ix, row_group, filter_len, filter_epoch, "ak_index_group_search")) return frc;
         const int64_t n = ix.n;
         if (nq == 0 || n == 0 || ix.n_alive == 0) { std::fill(hw.begin(), hw.end(), 0); break; }      // nothing to search: padding only
         hipStream_t st;
         if (thread_stream(&st)) return -10;
-        const GroupWs need = group_layout(nullptr, nq, k, g, fetch, n, ix.dim, row_filter != nullptr);
-        if (scratch_reserve(&t_ctx.dev, &t_ctx.dev_cap, need.bytes, false)) { t_ctx.trim(); return -10; }
+        if (!thread_scratch(group_layout(nullptr, nq, k, g, fetch, n, ix.dim, row_filter != nullptr).bytes)) { t_ctx.trim(); return -10; }
         const GroupWs w = group_layout(t_ctx.dev, nq, k, g, fetch, n, ix.dim, row_filter != nullptr);
         // id -> slot of queries [q0, q0 + c): their rows of w.sids come to the host, their rows of w.slots go back
         auto resolve = [&](int q0, int c) -> int {
             AK_HIP(hipMemcpyAsync(hid.data() + (size_t)q0 * fetch, w.sids + (size_t)q0 * fetch, (size_t)c * fetch * 8, hipMemcpyDeviceToHost, st));
             AK_HIP(hipStreamSynchronize(st));
-            for (int q = q0; q < q0 + c; q++) {
-                int m = 0;
-                for (int r = 0; r < fetch; r++) {
-                    const int64_t id = hid[(size_t)q * fetch + r];
-                    int slot = -1;
-                    if (id >= 0 && m == r) {
-                        const auto it = book.id2slot.find(id);
-                        if (it == book.id2slot.end() || it->second < 0 || it->second >= n)
-                            AK_FAIL(-1, "ak_index_group_search: a returned id has no row slot");
-                        slot = (int)(uint32_t)it->second;
-                        m++;
-                    }
-                    hslot[(size_t)q * fetch + r] = slot;
-                }
-                hm[q] = m;
-            }
+            if (int rrc = resolve_slots(ix, hid.data() + (size_t)q0 * fetch, c, fetch, nullptr, hslot.data() + (size_t)q0 * fetch, hm.data() + q0,
+                                        "ak_index_group_search", "returned")) return rrc;      // a -1 id ends a list; hm[q] is its length
             AK_HIP(hipMemcpyAsync(w.slots + (size_t)q0 * fetch, hslot.data() + (size_t)q0 * fetch, (size_t)c * fetch * 4, hipMemcpyHostToDevice, st));
             return 0;
         };
@@ -1589,10 +1606,7 @@ int ak_index_group_search(ak_index_t h, const float *queries, int nq, int k, int
                 if (rounds > 1) stats[5]++;
             }
             if (rc) break;
-            if (g > 1) {
-                auto reserve = [&](size_t bytes) -> void * { return scratch_reserve(&t_ctx.ws, &t_ctx.ws_cap, bytes, false) ? nullptr : t_ctx.ws; };
-                if ((rc = group_members(ix, w, nq, k, g, n, reserve, st, &stats[6]))) break;
-            }
+            if (g > 1 && (rc = group_members(ix, w, nq, k, g, n, thread_ws, st, &stats[6]))) break;
             if (hipMemcpyAsync(rid.data(), w.rid, nr * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipMemcpyAsync(rd.data(), w.rdist, nr * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipMemcpyAsync(rg.data(), w.rgroup, ng * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1602,8 +1616,7 @@ int ak_index_group_search(ak_index_t h, const float *queries, int nq, int k, int
         if (rc) hipStreamSynchronize(st);      // nothing of a failed call may still be running on the cached buffers
         t_ctx.trim();
         if (rc) return rc;
-        break;
-    }
+    } while (0);
     if (nq > 0) {
         memcpy(out_ids, rid.data(), nr * 8);
         memcpy(out_dist, rd.data(), nr * 8);
@@ -1638,18 +1651,26 @@ int ak::search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, in
     std::lock_guard<std::mutex> wl(ix.ws_mu);
     // the previous call's kernels may still be running out of ws_dev on another stream
     if (ix.ws_pending && ix.ws_stream != st) AK_HIP(hipStreamWaitEvent(st, ix.ws_event, 0));
-    const bool fast = mode != AK_SEARCH_EXACT && fast_supported(ix, nq, k);
-    FastPlan plan;
-    size_t body = exact_scratch_bytes(ix, k);
-    if (fast) { plan = fast_plan(ix, nq, k); body = plan.bytes; }
-    const size_t a4 = ((size_t)nq * 4 + 255) & ~255ull;
-    if (ix.ws_dev.reserve(3 * a4 + 256 + body)) return -10;
-    char *p = (char *)ix.ws_dev.buf;
-    float *dnb = (float *)p; p += a4;
-    int *dct = (int *)p; p += a4;
-    int *dce = out_cert_dev ? out_cert_dev : (int *)p; p += a4;
-    int64_t *dst = (int64_t *)p; p += 256;
-    int rc = 0;
+    SearchBufs d;      // ws_dev: nb | counts | cert (unless the caller has an array for it) | stats | the first scan's workspace
+    d.q = queries_dev; d.filter = row_filter_dev; d.ids = out_ids_dev; d.dist = out_dist_dev;
+    auto bufs = [&](size_t scan_bytes) -> const SearchBufs * {
+        const size_t a4 = ((size_t)nq * 4 + 255) & ~255ull;
+        if (ix.ws_dev.reserve(3 * a4 + 256 + scan_bytes)) return nullptr;
+        char *p = (char *)ix.ws_dev.buf;
+        d.nb = (float *)p; d.counts = (int *)(p + a4); d.stats = (int64_t *)(p + 3 * a4); d.ws = p + 3 * a4 + 256;
+        d.cert = d.final_cert = out_cert_dev ? out_cert_dev : (int *)(p + 2 * a4);
+        return &d;
+    };
+    auto rerun_ws = [&](size_t bytes) -> void * { return ix.ws_fb.reserve(bytes) ? nullptr : ix.ws_fb.buf; };
+    std::vector<int> cert;
+    auto read_flags = [&](const int **flags) -> int {
+        cert.resize(nq);
+        AK_HIP(hipMemcpyAsync(cert.data(), d.cert, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+        if (stats4) AK_HIP(hipMemcpyAsync(stats4, d.stats, 32, hipMemcpyDeviceToHost, st));
+        AK_HIP(hipStreamSynchronize(st));
+        *flags = cert.data();
+        return 0;
+    };
     auto mark = [&]() -> int {
         AK_HIP(hipEventRecord(ix.ws_event, st));
         ix.ws_pending = true; ix.ws_stream = st;
@@ -1661,32 +1682,10 @@ int ak::search_dev_locked(Index &ix, const float *queries_dev, int nq, int k, in
         decltype(mark) &m; bool armed = true;
         ~Guard() { if (armed) m(); }
     } guard{mark};
-    if (!fast) {
-        // shapes the MFMA scan does not take (fewer than 4096 rows, dim % 64 != 0, k > 128) and EXACT mode: reference
-        // arithmetic over every row -- exact by construction, so every query counts as certified
-        if ((rc = query_norms(queries_dev, nq, ix.dim, dnb, st))) return rc;
-        if ((rc = exact_search(ix, queries_dev, dnb, nq, k, row_filter_dev, out_ids_dev, out_dist_dev, dct, p, st))) return rc;
-        k_fill_int<<<(nq + 255) / 256, 256, 0, st>>>(dce, nq, 1);
-        AK_HIP(hipGetLastError());
-        return 0;             // the guard records the fence
-    }
-    if ((rc = fast_search(ix, queries_dev, dnb, false, nq, k, row_filter_dev, out_ids_dev, out_dist_dev, dct, dce, dst, p, plan, st))) return rc;
-    if (mode == AK_SEARCH_FAST_ONLY) return 0;
-    // AUTO: read the certificate flags, re-run what is open
-    std::vector<int> cert(nq, 0), todo;
-    AK_HIP(hipMemcpyAsync(cert.data(), dce, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    if (stats4) AK_HIP(hipMemcpyAsync(stats4, dst, 32, hipMemcpyDeviceToHost, st));
-    AK_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < nq; i++) if (!cert[i]) todo.push_back(i);
-    if (stats4) { stats4[0] = nq - (int64_t)todo.size(); stats4[1] = (int64_t)todo.size(); }
-    if (!todo.empty()) {
-        RerunStats rs;
-        auto reserve = [&](size_t bytes) -> void * { return ix.ws_fb.reserve(bytes) ? nullptr : ix.ws_fb.buf; };
-        if ((rc = rerun_uncertified(ix, queries_dev, dnb, nq, k, row_filter_dev, out_ids_dev, out_dist_dev, dct, dce, todo, true,
-                                    plan.i8 ? TAIL_KP : plan.kprime, reserve, st, stats4 ? &rs : nullptr))) return rc;
-        AK_HIP(hipStreamSynchronize(st));
-        if (stats4) { stats4[0] += rs.second_certified; stats4[1] = rs.exact; stats4[3] = rs.second_certified; }
-    }
+    bool reran = false;
+    if (int rc = search_auto(ix, nq, k, mode, st, bufs, rerun_ws, read_flags, stats4, &reran)) return rc;
+    if (cert.empty()) return 0;      // read_flags never ran (FAST_ONLY, or no scan at all): not synchronised, the guard records the fence
+    if (reran) AK_HIP(hipStreamSynchronize(st));
     guard.armed = false;      // the stream was synchronised after the last kernel: nothing of this call is in flight
     ix.ws_pending = false;
     return 0;

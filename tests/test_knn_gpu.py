@@ -241,6 +241,96 @@ def test_device_resident_search(hip):
     ix.close()
 
 
+# Every route of the search driver -- certified by the first scan, certified by the second (widest) scan, exact re-run, no scan at
+# all -- through ak_index_search and ak_index_search_dev on the same index and queries. Pile A: 200 byte-identical rows, more equal
+# scores than k' = 64 holds and fewer than the widest plan's 512. Pile B: 700, more than any scan keeps, so only the exact path
+# settles it. Queries: A's vector, B's vector, then random unit vectors.
+def _pile_index(n, d, nq, seed=41):
+    from archi_amd.index import HipIndex
+    rng = np.random.default_rng(seed)
+    rows = _unit(rng, n, d)
+    at = rng.permutation(n)
+    a, b = at[:200], at[200:900]
+    rows[a], rows[b] = rows[a[0]], rows[b[0]]
+    ids = rng.permutation(10 * n)[:n].astype(np.int64)
+    ix = HipIndex(d, n, dtype="bf16", metric="cosine", device=0)
+    ix.add(rows, ids=ids)
+    q = np.concatenate([rows[a[0]][None], rows[b[0]][None], _unit(rng, nq - 2, d)])
+    return ix, ko.round_through(rows, "bf16"), ids, q, rng
+
+
+def _search_dev(ix, q, k, mode, flt=None):
+    import torch
+    nq = len(q)
+    tq = torch.from_numpy(np.ascontiguousarray(q)).cuda()
+    oi = torch.full((nq, k), -7, dtype=torch.int64, device="cuda")
+    od = torch.full((nq, k), -7.0, dtype=torch.float64, device="cuda")
+    oc = torch.full((nq,), -7, dtype=torch.int32, device="cuda")
+    kw = {}
+    if flt is not None:
+        tf = torch.from_numpy(flt).cuda()
+        slots, epoch = ix.layout()
+        kw = dict(row_filter_ptr=tf.data_ptr(), filter_len=slots, filter_epoch=epoch)
+    ix.search_device(tq.data_ptr(), nq, k, oi.data_ptr(), od.data_ptr(), oc.data_ptr(), torch.cuda.current_stream().cuda_stream,
+                     mode=mode, **kw)
+    torch.cuda.synchronize()
+    return oi.cpu().numpy(), od.cpu().numpy(), oc.cpu().numpy()
+
+
+def _both_entries(ix, stored, ids, q, k, mode, flt=None):
+    """ids, float64 distances and counts of both entries against the oracle; returns the host entry's stats."""
+    wi, wd, wc = ko.search(stored, q, k, "cosine", ids=ids, alive=flt)
+    hi, hd, hc, st = ix.search(q, k, mode=mode, row_filter=flt, return_stats=True)
+    di, dd, flags = _search_dev(ix, q, k, mode, flt)
+    print(f"n={len(stored)} d={stored.shape[1]} nq={len(q)} k={k} {mode} filter={flt is not None}: {st} device flags {flags.sum()}/{len(q)}")
+    sel = np.ones(len(q), dtype=bool)
+    if mode == "fast_only":                     # only what the scan proved counts, and both entries must agree on what that is
+        sel = flags == 1
+        assert st["certified"] == sel.sum(), (st, flags)
+    else:
+        assert (flags == 1).all(), flags
+    for name, gi, gd in (("host", hi, hd), ("device", di, dd)):
+        assert np.array_equal(gi[sel], wi[sel]), f"{name} entry, {mode}: ids differ in queries {np.unique(np.argwhere(gi != wi)[:, 0])[:8]}"
+        assert np.array_equal(gd[sel], wd[sel], equal_nan=True), f"{name} entry, {mode}: distances differ"
+    assert np.array_equal(hc[sel], wc[sel])
+    return st
+
+
+def test_driver_routes_through_host_and_device_entries(hip):
+    ix, stored, ids, q, rng = _pile_index(4096, 64, 8)
+    st = _both_entries(ix, stored, ids, q, 10, "auto")
+    assert st["second_chance"] >= 1 and st["exact_reruns"] >= 1, st          # pile A, pile B: not the certified route alone
+    assert st["certified"] + st["exact_reruns"] == len(q), st
+    _both_entries(ix, stored, ids, q, 10, "auto", flt=(rng.random(4096) < 0.5).astype(np.uint8))
+    _both_entries(ix, stored, ids, q, 10, "exact")
+    _both_entries(ix, stored, ids, q, 10, "fast_only")
+    _both_entries(ix, stored, ids, q, 129, "auto")                          # k > 128: no scan
+    st = _both_entries(ix, stored, ids, q[0:1], 10, "auto")                 # every query open, certified by the second scan
+    assert st["second_chance"] == 1 and st["exact_reruns"] == 0, st
+    st = _both_entries(ix, stored, ids, q[1:2], 10, "auto")                 # every query open, through the exact path
+    assert st["second_chance"] == 0 and st["exact_reruns"] == 1, st
+    ix.close()
+    ix, stored, ids, q, _ = _pile_index(1000, 64, 8)                        # fewer than 4096 rows: no scan
+    _both_entries(ix, stored, ids, q, 10, "auto")
+    ix.close()
+
+
+def test_driver_second_chance_behind_the_int8_plan(hip):
+    """The int8 plan re-ranks 512 candidates per query, but its second chance is the widest 16-bit scan: it counts as k' = 64.
+    1024 queries, because the int8 plan needs the 256-query tile, which the plan takes by itself only for a batch that large."""
+    from archi_amd import _lib
+    _lib.debug_set("AK_SCAN_I8", "2")
+    try:
+        ix, stored, ids, q, _ = _pile_index(4096, 256, 1024)
+        before = ix.i8_info()["searches"]
+        st = _both_entries(ix, stored, ids, q, 10, "auto")
+        assert ix.i8_info()["searches"] == before + 2, ix.i8_info()        # one per entry
+        assert st["second_chance"] >= 1 and st["exact_reruns"] >= 1, st    # the rule above; pile B
+        ix.close()
+    finally:
+        _lib.debug_set("AK_SCAN_I8", None)
+
+
 @pytest.fixture
 def scan_cfg():
     """Force a scan tile for the duration of a test (ak_debug_set: the library reads its environment only once)."""
